@@ -3,6 +3,7 @@
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
                   [--nodes 100000000] [--edges 1000000000]
+                  [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): sampled edges/sec, whole node, 2-hop fanout [25,10] on
 a 100M-node / 1B-edge weighted power-law graph resident in HBM.  One "step" =
@@ -12,12 +13,20 @@ one rank per GPU) the graph is hash-partitioned over the ranks (owner(id) =
 id % N) and every hop does the id / result all-to-all over RCCL; every rank
 samples its own B roots per step (weak scaling).
 
-Rank 0 prints ONE JSON line: metric/value/... plus
-  roofline      SampleNeighborPivotKernel (both launches of a step) timed with HIP
-                events on its own stream; achieved = algorithmic bytes / time
+Rank 0 prints ONE JSON line: metric/value/unit/ms_per_step/...  A plain run sets
+up, warms up, times the K steps ONCE and prints the line.  With --full it also
+reports (every --no-* option below switches one of them off again):
+  repeats       the K-step loop timed --repeats times (default 5), the median kept
+  roofline      the step's launch timed with HIP events on its own stream;
+                achieved = algorithmic bytes / time
   cpu_baseline  the reference sampler (oracle/_ref: reference sources + RNG
                 seam) timed on the host cores on a bounded sample of the same
                 workload family
+  and the oracle parity check of the last step, the one-stream and sustained
+  loops, the B = 1 024 latency leg, the secondary legs, the replicated-graph leg
+  of a sharded run.  --workload hetero / deepwalk run their whole legs either way.
+--dump-outputs DIR writes a fixed, seeded sample of the last timed step's
+outputs (ids and types as float64, weights as float32) to DIR/<name>.npy.
 """
 import argparse
 import gc
@@ -79,9 +88,17 @@ def parse():
                          "configs[3] on one GPU (random_walk length 40)")
     ap.add_argument("--tuning", default="",
                     help="A/B only: comma-separated key=value pairs for euler_gpu_set_tuning")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the K-step timed loop is repeated this many times; the line "
-                         "reports the median repetition (and lists all)")
+                         "reports the median repetition (and lists all); default 5 with "
+                         "--full, else 1")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeats, parity check, roofline, one-stream / "
+                         "sustained loops, latency, secondary and replicated-graph legs, "
+                         "cpu_baseline (a plain run times the K steps once and stops)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a seeded sample of the last step's "
+                         "outputs as DIR/<name>.npy (float32 / float64, < 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--n2v", action="store_true", help="deepwalk workload: also time node2vec")
     ap.add_argument("--unfused-aggregation", action="store_true",
@@ -127,7 +144,10 @@ def parse():
     ap.add_argument("--force-sharded", action="store_true",
                     help="run the multi-GPU sampler (unique / split / all-to-all / "
                          "merge / gather) even on one rank: measures its overhead")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 _DEFERRED = None        # a list while a process group is up: the line is printed after its teardown
@@ -194,6 +214,31 @@ def secondary_legs(args, G, p_g):
     return sec
 
 
+DUMP_ROOTS = 4096       # --dump-outputs: roots of the last step whose rows are written
+
+
+def dump_outputs(dirname, roots, out):
+    """The last timed step as its caller receives it - (neighbors [roots, hop 1, hop 2], weights,
+    types) of sample_fanout - restricted to DUMP_ROOTS roots drawn with a fixed seed (the whole
+    step is ~0.5 GB): DIR/<name>.npy, ids and types as float64 (exact below 2^53), weights float32."""
+    nbrs, wts, tps = out
+    B = roots.numel()
+    sel = np.sort(np.random.default_rng(0).choice(B, min(B, DUMP_ROOTS), replace=False))
+    sel_t = torch.as_tensor(sel, device=roots.device)
+    arrays = {"sample_root_index": sel.astype(np.float64),
+              "roots": roots[sel_t].cpu().numpy().astype(np.float64)}
+    for h in range(len(wts)):
+        def rows(x, dt):
+            return x.reshape(B, -1)[sel_t].cpu().numpy().astype(dt)
+        arrays["hop%d_ids" % (h + 1)] = rows(nbrs[h + 1], np.float64)
+        arrays["hop%d_weights" % (h + 1)] = rows(wts[h], np.float32)
+        arrays["hop%d_types" % (h + 1)] = rows(tps[h], np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` with no launcher around it: start the N ranks
     ourselves (torch.distributed.run, one process per GPU, rendezvous on
@@ -254,6 +299,8 @@ def main():
         k_, v_ = kv.split("=")
         _lib.check(L.euler_gpu_set_tuning(int(k_), int(v_)))
     if args.workload in ("hetero", "deepwalk"):
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs covers the metric / products workloads")
         (run_hetero if args.workload == "hetero" else run_deepwalk)(args)
         _teardown(sharded or world > 1)
         return
@@ -313,7 +360,8 @@ def main():
             kept = [None]                    # only the last minibatch's outputs stay alive
 
             def consume(job, value):
-                kept[0] = value
+                if job == last - first - 1:
+                    kept[0] = value
             run_interleaved(make, last - first, K,
                             enter=lambda k: torch.cuda.stream(streams[k]), on_result=consume)
             res = kept
@@ -346,7 +394,7 @@ def main():
             print("trace (step, ms since previous job started, device allocs so far):",
                   [(a[0], round((a[1] - b[1]) * 1e3, 2), a[2]) for a, b in zip(tail[1:], tail[:-1])],
                   file=sys.stderr)
-    def unsharded_run(Gx, extras=True):
+    def unsharded_run(Gx, extras=True, settle=False):
         """The K steps on the unsharded graph Gx (this rank's whole graph): --streams callers'
         streams alternating; returns (rep_secs, one_stream secs, last outputs, sustained)."""
         def step(i):
@@ -371,7 +419,9 @@ def main():
         sync()
         gc.collect(); gc.freeze(); gc.disable()      # a gen-2 collection costs ~40 ms
         one_stream_ = []
-        if side is not None and extras:       # the same K steps on ONE stream, for the record
+        # the same K steps on ONE stream, for the record (settle: run, not reported - a plain run
+        # then times the same state of the device as --full: 0.225 ms per step without, 0.199-0.210 with)
+        if side is not None and (extras or settle):
             loop(0, args.warmup, None)
             for _rep in range(3):
                 sync()
@@ -380,6 +430,8 @@ def main():
                 sync()
                 one_stream_.append(time.perf_counter() - t0)
             loop(0, 2 * n_streams, side)
+            if not extras:
+                one_stream_ = []
         rep_secs_ = []
         for _rep in range(max(1, args.repeats)):
             sync()
@@ -415,8 +467,8 @@ def main():
     replicas_leg = None
     one_stream = []
     if not sharded:
-        rep_secs, one_stream, out, sustained = unsharded_run(G)
-    elif world > 1 and not args.no_replicas_leg and args.workload == "metric":
+        rep_secs, one_stream, out, sustained = unsharded_run(G, extras=args.full, settle=True)
+    elif world > 1 and args.full and not args.no_replicas_leg and args.workload == "metric":
         # beside the hash-sharded headline: every rank with the WHOLE graph in its own HBM
         # (68.6 GB of 288), the unsharded step on its own roots - what sharding costs
         try:
@@ -448,12 +500,15 @@ def main():
     edges_per_step = B * (FANOUT[0] + FANOUT[0] * FANOUT[1]) * world
     value = edges_per_step * args.steps / elapsed
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, roots[n_steps - 1], out)
+
     # ---- parity check at full size, after the timed region: --check-roots roots of the last step
     # (default 4 096 = 1.1 M sampled edges) against the CPU oracle fed with rows exported from HBM
     # (oracle/step_check.py: all of their hop-1 samples, every hop-2 position against the first
     # position of its node, one row per distinct hop-1 child against the oracle); single GPU only
     checked = None
-    if (world == 1 or replicas) and rank == 0 and not args.no_check:
+    if (world == 1 or replicas) and rank == 0 and args.full and not args.no_check:
         from oracle import oracle as O
         from oracle.step_check import check_fanout_step
         last = n_steps - 1
@@ -493,7 +548,7 @@ def main():
     if not sharded and not fused:
         raise SystemExit("bench.py: --tuning 27=0 (hop-by-hop fanout) has no roofline leg any more; "
                          "use tools/ab_key.py for that A/B")
-    if rank == 0 and fused:
+    if rank == 0 and fused and args.full:
         # The step is ONE kernel (fanout_local.h: hop 1, the duplicate children found inside
         # the wave, hop 2 once per distinct child, the rows streamed out): the roofline object
         # is that launch.  Algorithmic bytes = SURVEY 8(d), evaluated on the roots the step
@@ -637,7 +692,7 @@ def main():
                 torch.cuda.empty_cache()
             except Exception as e:          # a side measurement must not fail the bench
                 roofline["large_batch"] = {"error": repr(e)}
-    if not fused:
+    if not fused and args.full:
         # The sharded step's own launches (every rank): the owners' pass of a hop is
         # euler_gpu_sample_neighbor_packed over the DISTINCT ids a rank is asked for - K1
         # (SampleNeighborPivotKernel, one sample per lane, wire rows written directly).  Timed
@@ -723,16 +778,17 @@ def main():
             }
 
     small = None
-    if rank == 0 and world == 1 and not sharded and not args.no_small_batch:
+    if rank == 0 and world == 1 and not sharded and args.full and not args.no_small_batch:
         try:
             small = latency_small_batch(G, L, _lib, args.nodes, default_node)
         except Exception as e:              # a side measurement must not fail the bench
             small = {"error": str(e)}
     secondary = None
-    if rank == 0 and world == 1 and not sharded and args.workload == "metric" and not args.no_secondary:
+    if rank == 0 and world == 1 and not sharded and args.workload == "metric" and args.full \
+            and not args.no_secondary:
         secondary = secondary_legs(args, G, p)
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # (N ranks: rank 0 alone, after the timed region - the other ranks wait in the closing
         # barrier; the reference's CPU sampler does not get faster with more GPUs)
         cpu = cpu_baseline(args)
@@ -780,6 +836,7 @@ def main():
                 "one_stream_ms_per_step": (round(float(np.median(one_stream)) / args.steps * 1e3, 4)
                                            if (not sharded and one_stream) else None),
                 "repeats": len(rep_secs),
+                "full": bool(args.full),
                 "repeat_ms_per_step": [round(x / args.steps * 1e3, 4) for x in rep_secs],
                 "ranks": world,
                 "transport": (None if not (sharded or world > 1) else

@@ -1,5 +1,6 @@
 #!/bin/bash
-# usage: tools/round4_profile.sh <tag>     (on the GPU box through gpurun; PMC=1 adds the counter passes)
+# usage: tools/round4_profile.sh <tag>     (on an MI355X; PMC=1 adds the counter passes;
+#        BENCH_ARGS must hold --full for the bench line's roofline)
 # Round 4's profile set: (1) kernel trace + stats of the two-stream headline loop (do two launches of
 # the step's kernel overlap?), (2) kernel stats of one-stream steps, (3) the bench line, optionally
 # (4) the counter passes of tools/pmc_fl.sh.  tools/round4_collect.py copies the summaries into profiles/.
