@@ -193,6 +193,37 @@ struct NodeSamplerView {
   float tc_sum;
 };
 
+// One ragged feature table (the layout of the node features): values of record r at
+// val[ptr[r] ...], slot f ends at idx[r * n_slots + f] (record-relative).  uniform = 1: every
+// record has the slot ends of record 0 (idx holds one row) and ptr[r] = r * stride (ptr NULL).
+struct FeatTable {
+  const int64_t* ptr;
+  const int32_t* idx;
+  const void* val;
+  int32_t n_slots;
+  int32_t uniform;
+  int64_t stride;
+};
+
+// Edge store (edge_kernels.hip).  One 32-byte slot per record; 4 slots make a 128-byte line,
+// the unit a lookup reads (8 lanes, one 16-byte load each: one request per line).
+struct EdgeSlot {
+  uint64_t src;
+  uint64_t dst;
+  int32_t type;
+  float weight;
+  int64_t ord;                        // -1 = empty slot
+};
+static_assert(sizeof(EdgeSlot) == 32, "EdgeSlot must be 32 bytes");
+
+struct EdgeStoreView {
+  const EdgeSlot* slots;              // [4 * n_lines], 128-byte aligned
+  uint64_t n_lines;                   // >= n / 2: at most half the slots are used
+  const int64_t* slot_of;             // [n] ordinal -> slot
+  int64_t n;
+  FeatTable f32, u64, bin;
+};
+
 EG_HD uint64_t Mix64(uint64_t z) {
   z ^= z >> 30; z *= 0xbf58476d1ce4e5b9ULL;
   z ^= z >> 27; z *= 0x94d049bb133111ebULL;
@@ -223,6 +254,24 @@ struct euler_gpu_graph {
   int32_t n_u64 = 0;
   bool feat_slot_aligned = false;     // uniform feature table: every slot begins at a
                                       // multiple of 4 floats (16-byte lanes allowed)
+  // edge store (edge_kernels.hip); its allocations are listed here, not in `allocations`, so
+  // that a new store can replace it.  The edge sampler's entries are alias entries whose ids are
+  // slot positions.
+  euler_gpu::EdgeStoreView edges{};
+  bool has_edges = false;
+  euler_gpu::NodeSamplerView edge_sampler{};
+  std::vector<float> edge_weight_sums;
+  std::vector<std::pair<void*, int64_t>> edge_allocs;       // (pointer, bytes)
+  std::pair<void*, int64_t> edge_sampler_alloc{nullptr, 0};
+  // binary node features of a loaded dataset: host copy until the first get_binary_feature
+  // uploads it (node_bin, counted in bytes)
+  std::vector<int64_t> bin_host_ptr;
+  std::vector<int32_t> bin_host_idx;
+  std::vector<uint8_t> bin_host_val;
+  int32_t bin_host_slots = 0;
+  mutable std::mutex bin_mu;
+  mutable euler_gpu::FeatTable node_bin{};
+  mutable bool node_bin_ready = false;
   // scratch of the sampling launcher (dedup table, unique rows), one buffer
   // per stream: calls on one stream are ordered, calls on different streams
   // never share a buffer
@@ -262,6 +311,13 @@ int BuildGraphSynthetic(const euler_gpu_synth_params* p, int device,
                         int32_t partitions, int32_t shard_index, int32_t shards,
                         euler_gpu_graph** out);
 int EnsureBlockedIndex(const euler_gpu_graph* g);   // EdgeBlocks + block pivots, on first use
+// Graph::BuildGlobalSampler's per-type alias tables + type collection (host work): the view
+// without its entries pointer, the entries, the per-type weight sums
+int BuildAliasTables(const std::vector<uint64_t>& ids, const std::vector<int32_t>& types,
+                     const std::vector<float>& weights, int32_t n_types, NodeSamplerView* view,
+                     std::vector<AliasEntry>* entries, std::vector<float>* sums,
+                     const char* noun);   // "node" / "edge": the error messages
+void DestroyEdgeStore(euler_gpu_graph* g);          // edge_kernels.hip
 // weight-bucket index, on first use; leaves view.wb == nullptr (and returns OK) for graphs it
 // does not serve
 int EnsureWbIndex(const euler_gpu_graph* g);
@@ -312,7 +368,27 @@ int N2vIdxFromLens(hipStream_t st, const int32_t* lens_dev, int64_t m, int32_t* 
 int N2vStoreColumn(hipStream_t st, const int64_t* src_dev, int64_t n, int64_t stride, int64_t col, int64_t* out_dev);
 int N2vBoundOffsets(hipStream_t st, const int32_t* idx_dev, const int64_t* bounds_dev, int32_t w, int64_t* out_dev);
 // dat_reader.cc
-struct DatGraph {
+// euler.meta's feature tables (graph_meta.h:36-39: name -> (type, idx, dim); type 0 sparse,
+// 1 dense, 2 binary)
+struct DatFeature {
+  std::string name;
+  int32_t type = 0, idx = 0;
+  int64_t dim = 0;
+};
+struct DatMeta {
+  int32_t partitions = 0, n_node_types = 0, n_edge_types = 0;
+  std::vector<DatFeature> node_features, edge_features;
+};
+// what euler_gpu_dat_open / _open_edges hand out (freed by euler_gpu_dat_close)
+struct DatOwner {
+  virtual ~DatOwner() {}
+};
+struct DatGraph : DatOwner {
+  DatMeta meta;
+  std::vector<int64_t> bfeat_ptr;     // binary features, ragged layout, bytes as values
+  std::vector<int32_t> bfeat_idx;
+  std::vector<uint8_t> bfeat_val;
+  int32_t n_binary = 0;
   std::vector<uint64_t> row_id, nbr;
   std::vector<int64_t> row_ptr, feat_ptr;
   std::vector<int32_t> type_end, node_type, feat_idx;
@@ -328,6 +404,23 @@ int LoadDatDirectory(const char* data_path, int32_t shard_index, int32_t shards,
 int VerifyEdgeFiles(const char* data_path, int32_t shard_index, int32_t shards,
                     const DatGraph& g, int64_t* edge_records, int64_t* not_in_rows,
                     int64_t* row_triples);
+// Edge records in ordinal order (file order, first of a repeated (src, dst, type) kept) with
+// their features in the ragged layout of the node features
+struct DatEdges : DatOwner {
+  DatMeta meta;
+  std::vector<uint64_t> src, dst;
+  std::vector<int32_t> type;
+  std::vector<float> weight;
+  std::vector<int64_t> feat_ptr, ufeat_ptr, bfeat_ptr;
+  std::vector<int32_t> feat_idx, ufeat_idx, bfeat_idx;
+  std::vector<float> feat_val;
+  std::vector<uint64_t> ufeat_val;
+  std::vector<uint8_t> bfeat_val;
+  int32_t n_float = 0, n_u64 = 0, n_binary = 0;
+  void Describe(euler_gpu_host_edges* e) const;
+};
+int ReadDatMeta(const char* data_path, DatMeta* out);
+int LoadDatEdges(const char* data_path, int32_t shard_index, int32_t shards, DatEdges* out);
 
 // Grid sizing for HBM-bound kernels: enough workgroups to fill 256 CUs x 8
 // resident blocks, grid-stride beyond that.

@@ -1,7 +1,8 @@
 // Reader for the on-disk graph the reference loads in Graph::Init: the
 // `euler.meta` header (core/graph/graph_builder.cc:230-307) and the
 // `Node/*_<partition>.dat` record files (graph_builder.cc:310-320; record =
-// Node::DeSerialize, core/graph/node.cc:414-526; primitives =
+// Node::DeSerialize, core/graph/node.cc:414-526), and on request the
+// `Edge/*_<partition>.dat` records (Edge::DeSerialize, core/graph/edge.cc:136-200); primitives =
 // common/bytes_io.h:28-81, common/file_io.h:113-135).  Records go straight into
 // the flat CSR arrays that are uploaded to HBM - no per-node heap objects.
 #include <dirent.h>
@@ -84,15 +85,19 @@ struct FilePart {
   std::vector<float> prefix_w, type_prefix, node_weight, feat_val;
   std::vector<int64_t> row_end, feat_end, ufeat_end;     // cumulative, per row
   std::vector<std::vector<int32_t>> f_idx_rows, u_idx_rows;
+  std::vector<uint8_t> bfeat_val;                        // binary features (bytes)
+  std::vector<int64_t> bfeat_end;
+  std::vector<std::vector<int32_t>> b_idx_rows;
   std::string error;
 };
 
 void ParseNodeFile(const std::string& path, const std::string& fn, int32_t T, FilePart* out) {
   std::string blob;
   if (!ReadFile(path, &blob)) { out->error = "graph_load: cannot read " + fn; return; }
-  std::vector<int32_t> gids, gidx, in_gids, in_gidx, u64_idx, f32_idx;
+  std::vector<int32_t> gids, gidx, in_gids, in_gidx, u64_idx, f32_idx, bin_idx;
   std::vector<float> gw, nw, in_gw, in_nw, f32_val;
   std::vector<uint64_t> nb, in_nb, u64_val;
+  std::string bin_val;
   Cursor f{blob.data(), blob.size()};
   while (f.i < f.n) {
     uint32_t len = 0;
@@ -146,8 +151,144 @@ void ParseNodeFile(const std::string& path, const std::string& fn, int32_t T, Fi
     out->u_idx_rows.push_back(u64_idx);
     out->ufeat_val.insert(out->ufeat_val.end(), u64_val.begin(), u64_val.end());
     out->ufeat_end.push_back((int64_t)out->ufeat_val.size());
+    // binary features (node.cc:515-523): an idx list and one string of all values; a record
+    // that ends before them has none
+    bin_idx.clear(); bin_val.clear();
+    if (r.i < r.n && !(r.GetVec(&bin_idx) && r.GetString(&bin_val))) {
+      out->error = "graph_load: malformed binary feature block in " + fn; return;
+    }
+    if (!bin_idx.empty() && bin_idx.back() != (int32_t)bin_val.size()) {
+      out->error = "graph_load: binary feature index does not cover values"; return;
+    }
+    out->b_idx_rows.push_back(bin_idx);
+    out->bfeat_val.insert(out->bfeat_val.end(), bin_val.begin(), bin_val.end());
+    out->bfeat_end.push_back((int64_t)out->bfeat_val.size());
   }
 }
+
+// Per-row slot ends -> the flat [rows x width] table of the ragged layout (a missing slot
+// repeats the previous end: length 0).
+void FlattenSlots(const std::vector<std::vector<int32_t>>& rows, int32_t* width,
+                  std::vector<int32_t>* out) {
+  int32_t F = 0;
+  for (const auto& v : rows) F = std::max(F, (int32_t)v.size());
+  *width = F;
+  out->assign((size_t)F * rows.size(), 0);
+  for (size_t i = 0; i < rows.size(); ++i) {
+    int32_t last = 0;
+    for (int32_t f = 0; f < F; ++f) {
+      if (f < (int32_t)rows[i].size()) last = rows[i][f];
+      (*out)[i * F + f] = last;
+    }
+  }
+}
+
+// euler.meta (graph_builder.cc:230-307): name, version, counts, partitions, the node and the
+// edge feature tables, the node type and edge type name tables.
+bool ParseMeta(const std::string& meta, DatMeta* out) {
+  Cursor m{meta.data(), meta.size()};
+  std::string name, version;
+  uint64_t node_count = 0, edge_count = 0;
+  bool ok = m.GetString(&name) && m.GetString(&version) && m.Get(&node_count) &&
+            m.Get(&edge_count) && m.Get(&out->partitions);
+  for (int pass = 0; ok && pass < 2; ++pass) {   // node features, edge features
+    uint32_t cnt = 0;
+    ok = m.Get(&cnt);
+    for (uint32_t i = 0; ok && i < cnt; ++i) {
+      DatFeature f;
+      ok = m.GetString(&f.name) && m.Get(&f.type) && m.Get(&f.idx) && m.Get(&f.dim);
+      if (ok) (pass == 0 ? out->node_features : out->edge_features).push_back(f);
+    }
+  }
+  uint32_t nt = 0, et = 0;
+  ok = ok && m.Get(&nt);
+  for (uint32_t i = 0; ok && i < nt; ++i) {
+    std::string s; uint32_t idx;
+    ok = m.GetString(&s) && m.Get(&idx);
+  }
+  ok = ok && m.Get(&et);
+  out->n_node_types = (int32_t)nt;
+  out->n_edge_types = (int32_t)et;
+  return ok;
+}
+
+// Sorted partition files of `dir` that the shard keeps.
+bool ListFiles(const std::string& dir, int32_t shard_index, int32_t shards,
+               std::vector<std::string>* files) {
+  DIR* d = opendir(dir.c_str());
+  if (!d) return false;
+  while (dirent* ent = readdir(d)) {
+    const std::string fn(ent->d_name);
+    if (KeepFile(fn, shard_index, shards)) files->push_back(fn);
+  }
+  closedir(d);
+  std::sort(files->begin(), files->end());
+  return true;
+}
+
+// Runs parse(f) for every file index f on up to 8 host threads.
+template <typename F>
+void ForEachFile(size_t n_files, F parse) {
+  const size_t hw = std::max<size_t>(1, std::thread::hardware_concurrency());
+  const size_t n_thr = std::min<size_t>(std::min<size_t>(8, hw), n_files);
+  auto work = [&](size_t first) {
+    for (size_t f = first; f < n_files; f += std::max<size_t>(n_thr, 1)) parse(f);
+  };
+  if (n_thr <= 1) {
+    if (n_files) work(0);
+    return;
+  }
+  std::vector<std::thread> pool;
+  for (size_t t = 0; t < n_thr; ++t) pool.emplace_back(work, t);
+  for (auto& th : pool) th.join();
+}
+
+// One Edge partition file (Edge::DeSerialize, core/graph/edge.cc:136-200).
+struct EdgeFilePart {
+  std::vector<uint64_t> src, dst, uval;
+  std::vector<int32_t> type;
+  std::vector<float> weight, fval;
+  std::vector<uint8_t> bval;
+  std::vector<std::vector<int32_t>> f_idx, u_idx, b_idx;
+  std::string error;
+};
+
+void ParseEdgeFile(const std::string& path, const std::string& fn, EdgeFilePart* out) {
+  std::string blob;
+  if (!ReadFile(path, &blob)) { out->error = "edge_load: cannot read " + fn; return; }
+  std::vector<int32_t> ui, fi, bi;
+  std::vector<uint64_t> uv;
+  std::vector<float> fv;
+  std::string bv;
+  Cursor f{blob.data(), blob.size()};
+  while (f.i < f.n) {
+    uint32_t len = 0;
+    if (!f.Get(&len) || f.i + len > f.n) { out->error = "edge_load: truncated record in " + fn; return; }
+    Cursor r{blob.data() + f.i, len};
+    f.i += len;
+    uint64_t src, dst; int32_t type; float weight;
+    if (!(r.Get(&src) && r.Get(&dst) && r.Get(&type) && r.Get(&weight) && r.GetVec(&ui) &&
+          r.GetVec(&uv) && r.GetVec(&fi) && r.GetVec(&fv) && r.GetVec(&bi) && r.GetString(&bv))) {
+      out->error = "edge_load: malformed edge record in " + fn; return;
+    }
+    if ((!ui.empty() && ui.back() != (int32_t)uv.size()) ||
+        (!fi.empty() && fi.back() != (int32_t)fv.size()) ||
+        (!bi.empty() && bi.back() != (int32_t)bv.size())) {
+      out->error = "edge_load: feature index does not cover values in " + fn; return;
+    }
+    out->src.push_back(src); out->dst.push_back(dst); out->type.push_back(type);
+    out->weight.push_back(weight);
+    out->u_idx.push_back(ui); out->uval.insert(out->uval.end(), uv.begin(), uv.end());
+    out->f_idx.push_back(fi); out->fval.insert(out->fval.end(), fv.begin(), fv.end());
+    out->b_idx.push_back(bi); out->bval.insert(out->bval.end(), bv.begin(), bv.end());
+  }
+}
+
+struct TripleHash {
+  size_t operator()(const std::tuple<uint64_t, uint64_t, int32_t>& k) const {
+    return (size_t)Mix64(std::get<0>(k) ^ Mix64(std::get<1>(k) ^ (uint64_t)(uint32_t)std::get<2>(k)));
+  }
+};
 
 }  // namespace
 
@@ -191,28 +332,9 @@ int LoadDatDirectory(const char* data_path, int32_t shard_index, int32_t shards,
   std::string meta;
   if (!ReadFile(root + "/euler.meta", &meta))
     return Fail(EULER_GPU_EIO, "graph_load: cannot read " + root + "/euler.meta");
-  Cursor m{meta.data(), meta.size()};
-  std::string name, version;
-  uint64_t node_count = 0, edge_count = 0;
-  int32_t parts = 0;
-  bool ok = m.GetString(&name) && m.GetString(&version) && m.Get(&node_count) &&
-            m.Get(&edge_count) && m.Get(&parts);
-  for (int pass = 0; ok && pass < 2; ++pass) {   // node features, edge features
-    uint32_t cnt = 0;
-    ok = m.Get(&cnt);
-    for (uint32_t i = 0; ok && i < cnt; ++i) {
-      std::string fname; int32_t ftype, idx; int64_t dim;
-      ok = m.GetString(&fname) && m.Get(&ftype) && m.Get(&idx) && m.Get(&dim);
-    }
-  }
-  uint32_t nt = 0, et = 0;
-  ok = ok && m.Get(&nt);
-  for (uint32_t i = 0; ok && i < nt; ++i) {
-    std::string s; uint32_t idx;
-    ok = m.GetString(&s) && m.Get(&idx);
-  }
-  ok = ok && m.Get(&et);
-  if (!ok) return Fail(EULER_GPU_EIO, "graph_load: malformed euler.meta");
+  if (!ParseMeta(meta, &out->meta)) return Fail(EULER_GPU_EIO, "graph_load: malformed euler.meta");
+  const int32_t parts = out->meta.partitions;
+  const uint32_t nt = (uint32_t)out->meta.n_node_types, et = (uint32_t)out->meta.n_edge_types;
   if (parts <= 0) return Fail(EULER_GPU_EIO, "graph_load: partitions_num must be > 0");
   *n_node_types = (int32_t)nt;
   *n_edge_types = (int32_t)et;
@@ -221,35 +343,17 @@ int LoadDatDirectory(const char* data_path, int32_t shard_index, int32_t shards,
     return Fail(EULER_GPU_EIO, "graph_load: need 1..32 edge types");
   // ---- Node/*.dat
   const std::string node_dir = root + "/Node";
-  DIR* d = opendir(node_dir.c_str());
-  if (!d) return Fail(EULER_GPU_EIO, "graph_load: no directory " + node_dir);
   std::vector<std::string> files;
-  while (dirent* ent = readdir(d)) {
-    const std::string fn(ent->d_name);
-    if (KeepFile(fn, shard_index, shards)) files.push_back(fn);
-  }
-  closedir(d);
-  std::sort(files.begin(), files.end());
+  if (!ListFiles(node_dir, shard_index, shards, &files))
+    return Fail(EULER_GPU_EIO, "graph_load: no directory " + node_dir);
   // The partition files are independent: up to 8 host threads parse them into
   // per-file parts, which are then appended in file order (the order a single
   // reader would produce).
   const int32_t T = (int32_t)et;
   std::vector<FilePart> parts_(files.size());
-  {
-    const size_t hw = std::max<size_t>(1, std::thread::hardware_concurrency());
-    const size_t n_thr = std::min<size_t>(std::min<size_t>(8, hw), files.size());
-    auto work = [&](size_t first) {
-      for (size_t f = first; f < files.size(); f += std::max<size_t>(n_thr, 1))
-        ParseNodeFile(node_dir + "/" + files[f], files[f], T, &parts_[f]);
-    };
-    if (n_thr <= 1) {
-      if (!files.empty()) work(0);
-    } else {
-      std::vector<std::thread> pool;
-      for (size_t t = 0; t < n_thr; ++t) pool.emplace_back(work, t);
-      for (auto& th : pool) th.join();
-    }
-  }
+  ForEachFile(files.size(), [&](size_t f) {
+    ParseNodeFile(node_dir + "/" + files[f], files[f], T, &parts_[f]);
+  });
   for (const FilePart& fp : parts_)
     if (!fp.error.empty()) return Fail(EULER_GPU_EIO, fp.error);
   row_id->clear(); row_ptr->assign(1, 0); type_end->clear(); nbr->clear();
@@ -259,6 +363,9 @@ int LoadDatDirectory(const char* data_path, int32_t shard_index, int32_t shards,
   out->feat_val.clear();
   out->ufeat_ptr.assign(1, 0);
   out->ufeat_val.clear();
+  std::vector<std::vector<int32_t>> b_idx_rows;
+  out->bfeat_ptr.assign(1, 0);
+  out->bfeat_val.clear();
   for (FilePart& fp : parts_) {
     const int64_t e0 = (int64_t)nbr->size();
     const int64_t f0 = (int64_t)out->feat_val.size(), u0 = (int64_t)out->ufeat_val.size();
@@ -278,6 +385,10 @@ int LoadDatDirectory(const char* data_path, int32_t shard_index, int32_t shards,
     }
     for (auto& v : fp.f_idx_rows) f_idx_rows.push_back(std::move(v));
     for (auto& v : fp.u_idx_rows) u_idx_rows.push_back(std::move(v));
+    const int64_t b0 = (int64_t)out->bfeat_val.size();
+    out->bfeat_val.insert(out->bfeat_val.end(), fp.bfeat_val.begin(), fp.bfeat_val.end());
+    for (size_t r = 0; r < fp.row_id.size(); ++r) out->bfeat_ptr.push_back(b0 + fp.bfeat_end[r]);
+    for (auto& v : fp.b_idx_rows) b_idx_rows.push_back(std::move(v));
     fp = FilePart();                       // release the part's memory as we go
   }
   int32_t F = 0;
@@ -302,6 +413,7 @@ int LoadDatDirectory(const char* data_path, int32_t shard_index, int32_t shards,
       out->ufeat_idx[i * U + f] = last;
     }
   }
+  FlattenSlots(b_idx_rows, &out->n_binary, &out->bfeat_idx);
   return EULER_GPU_OK;
 }
 
@@ -369,6 +481,84 @@ int VerifyEdgeFiles(const char* data_path, int32_t shard_index, int32_t shards,
   if (not_in_rows) *not_in_rows = missing;
   if (row_triples) *row_triples = triples;
   return EULER_GPU_OK;
+}
+
+}  // namespace euler_gpu
+
+namespace euler_gpu {
+
+int ReadDatMeta(const char* data_path, DatMeta* out) {
+  std::string meta;
+  if (!ReadFile(std::string(data_path) + "/euler.meta", &meta))
+    return Fail(EULER_GPU_EIO, std::string("dat_meta: cannot read ") + data_path + "/euler.meta");
+  if (!ParseMeta(meta, out)) return Fail(EULER_GPU_EIO, "dat_meta: malformed euler.meta");
+  return EULER_GPU_OK;
+}
+
+// Edge/*.dat: the files the shard keeps (Graph::Init's filter, graph.cc:90-98) in sorted order,
+// parsed on up to 8 threads, appended in file order.  A repeated (src, dst, type) keeps its
+// first record: the reference loads through Graph::AddEdgeFrom(vector), which inserts into an
+// unordered_map (graph.cc:197-203).  The ordinal of a record is its position after that.
+int LoadDatEdges(const char* data_path, int32_t shard_index, int32_t shards, DatEdges* out) {
+  if (shards <= 0 || shard_index < 0 || shard_index >= shards)
+    return Fail(EULER_GPU_EINVAL, "edge_load: bad shard arguments");
+  int rc = ReadDatMeta(data_path, &out->meta);
+  if (rc != EULER_GPU_OK) return rc;
+  const std::string edge_dir = std::string(data_path) + "/Edge";
+  std::vector<std::string> files;
+  if (!ListFiles(edge_dir, shard_index, shards, &files))
+    return Fail(EULER_GPU_EIO, "edge_load: no directory " + edge_dir);
+  std::vector<EdgeFilePart> parts(files.size());
+  ForEachFile(files.size(), [&](size_t f) {
+    ParseEdgeFile(edge_dir + "/" + files[f], files[f], &parts[f]);
+  });
+  for (const EdgeFilePart& p : parts)
+    if (!p.error.empty()) return Fail(EULER_GPU_EIO, p.error);
+  std::unordered_map<std::tuple<uint64_t, uint64_t, int32_t>, int64_t, TripleHash> seen;
+  std::vector<std::vector<int32_t>> f_idx, u_idx, b_idx;
+  out->feat_ptr.assign(1, 0); out->ufeat_ptr.assign(1, 0); out->bfeat_ptr.assign(1, 0);
+  for (EdgeFilePart& p : parts) {
+    int64_t fo = 0, uo = 0, bo = 0;       // value offsets of the record inside the part
+    for (size_t r = 0; r < p.src.size(); ++r) {
+      const int32_t fl = p.f_idx[r].empty() ? 0 : p.f_idx[r].back();
+      const int32_t ul = p.u_idx[r].empty() ? 0 : p.u_idx[r].back();
+      const int32_t bl = p.b_idx[r].empty() ? 0 : p.b_idx[r].back();
+      const bool first = seen.emplace(std::make_tuple(p.src[r], p.dst[r], p.type[r]),
+                                      (int64_t)out->src.size()).second;
+      if (first) {
+        out->src.push_back(p.src[r]); out->dst.push_back(p.dst[r]);
+        out->type.push_back(p.type[r]); out->weight.push_back(p.weight[r]);
+        out->feat_val.insert(out->feat_val.end(), p.fval.begin() + fo, p.fval.begin() + fo + fl);
+        out->ufeat_val.insert(out->ufeat_val.end(), p.uval.begin() + uo, p.uval.begin() + uo + ul);
+        out->bfeat_val.insert(out->bfeat_val.end(), p.bval.begin() + bo, p.bval.begin() + bo + bl);
+        out->feat_ptr.push_back((int64_t)out->feat_val.size());
+        out->ufeat_ptr.push_back((int64_t)out->ufeat_val.size());
+        out->bfeat_ptr.push_back((int64_t)out->bfeat_val.size());
+        f_idx.push_back(std::move(p.f_idx[r]));
+        u_idx.push_back(std::move(p.u_idx[r]));
+        b_idx.push_back(std::move(p.b_idx[r]));
+      }
+      fo += fl; uo += ul; bo += bl;
+    }
+    p = EdgeFilePart();
+  }
+  FlattenSlots(f_idx, &out->n_float, &out->feat_idx);
+  FlattenSlots(u_idx, &out->n_u64, &out->ufeat_idx);
+  FlattenSlots(b_idx, &out->n_binary, &out->bfeat_idx);
+  return EULER_GPU_OK;
+}
+
+void DatEdges::Describe(euler_gpu_host_edges* e) const {
+  *e = euler_gpu_host_edges{};
+  e->n = (int64_t)src.size();
+  e->n_edge_types = meta.n_edge_types;
+  e->src = src.data(); e->dst = dst.data(); e->type = type.data(); e->weight = weight.data();
+  e->n_float_features = n_float;
+  e->feat_ptr = feat_ptr.data(); e->feat_idx = feat_idx.data(); e->feat_val = feat_val.data();
+  e->n_u64_features = n_u64;
+  e->ufeat_ptr = ufeat_ptr.data(); e->ufeat_idx = ufeat_idx.data(); e->ufeat_val = ufeat_val.data();
+  e->n_binary_features = n_binary;
+  e->bfeat_ptr = bfeat_ptr.data(); e->bfeat_idx = bfeat_idx.data(); e->bfeat_val = bfeat_val.data();
 }
 
 }  // namespace euler_gpu

@@ -2,6 +2,7 @@
 // on device, global node sampler (alias tables), row export, and the graph
 // life-cycle entry points of the C ABI.
 #include <hip/hip_runtime.h>
+#include <sys/stat.h>
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -233,6 +234,7 @@ void KeepPoolMemory(int device) {
 void DestroyGraph(euler_gpu_graph* g) {
   if (!g) return;
   (void)hipSetDevice(g->device);
+  DestroyEdgeStore(g);
   for (void* p : g->allocations) (void)hipFree(p);
   for (auto& kv : g->ws) (void)hipFree(kv.second.first);
   for (auto& kv : g->flow_tables) (void)hipFree(kv.second.p);
@@ -270,16 +272,39 @@ void AliasBuild(const std::vector<float>& weights, std::vector<float>* prob,
 int BuildNodeSampler(GraphBuilder* b, const std::vector<uint64_t>& ids,
                      const std::vector<int32_t>& types,
                      const std::vector<float>& weights, int32_t n_types) {
+  NodeSamplerView s;
+  std::vector<AliasEntry> entries;
+  std::vector<float> sums;
+  const int rc = BuildAliasTables(ids, types, weights, n_types, &s, &entries, &sums, "node");
+  if (rc != EULER_GPU_OK) return rc;
+  s.entries = b->Upload(entries.data(), entries.size());
+  if (!s.entries) return b->rc;
+  b->g->sampler = s;
+  b->g->has_sampler = true;
+  b->g->n_node_types = n_types;
+  b->g->node_weight_sums = sums;
+  return EULER_GPU_OK;
+}
+
+}  // namespace
+
+// Graph::BuildGlobalSampler (core/graph/graph.cc:333-370) +
+// FastWeightedCollection::Init (common/fast_weighted_collection.h:55-75), host part.
+int BuildAliasTables(const std::vector<uint64_t>& ids, const std::vector<int32_t>& types,
+                     const std::vector<float>& weights, int32_t n_types, NodeSamplerView* view,
+                     std::vector<AliasEntry>* entries_out, std::vector<float>* sums_out,
+                     const char* noun) {
+  const std::string what = std::string(noun) + " sampler: ";
   if (n_types <= 0 || n_types > kMaxNodeTypes)
-    return Fail(EULER_GPU_EINVAL, "node sampler: 1 .. 32 node types");
+    return Fail(EULER_GPU_EINVAL, what + "1 .. 32 " + noun + " types");
   const size_t n = ids.size();
   // Everything is validated and built on the side; the graph's sampler is replaced only when the
   // new table is on the device (a failed rebuild must leave the old sampler intact).
   for (size_t i = 0; i < n; ++i) {
     if (types[i] < 0 || types[i] >= n_types)
-      return Fail(EULER_GPU_EINVAL, "node sampler: node type out of range");
+      return Fail(EULER_GPU_EINVAL, what + noun + " type out of range");
     if (!(weights[i] >= 0.f) || !std::isfinite(weights[i]))
-      return Fail(EULER_GPU_EINVAL, "node sampler: node weights must be finite and >= 0");
+      return Fail(EULER_GPU_EINVAL, what + noun + " weights must be finite and >= 0");
   }
   NodeSamplerView s;
   std::memset(&s, 0, sizeof(s));
@@ -295,7 +320,7 @@ int BuildNodeSampler(GraphBuilder* b, const std::vector<uint64_t>& ids,
   }
   for (int32_t t = 0; t < n_types; ++t)
     if (!std::isfinite(sums[t]))
-      return Fail(EULER_GPU_EINVAL, "node sampler: a node type's weights sum to infinity");
+      return Fail(EULER_GPU_EINVAL, what + "a " + noun + " type's weights sum to infinity");
   std::vector<AliasEntry> entries(n);
   size_t off = 0;
   for (int32_t t = 0; t < n_types; ++t) {
@@ -337,16 +362,11 @@ int BuildNodeSampler(GraphBuilder* b, const std::vector<uint64_t>& ids,
     s.tc_prob[t] = tprob[t];
     s.tc_alias[t] = (int32_t)talias[t];
   }
-  s.entries = b->Upload(entries.data(), entries.size());
-  if (!s.entries) return b->rc;
-  b->g->sampler = s;
-  b->g->has_sampler = true;
-  b->g->n_node_types = n_types;
-  b->g->node_weight_sums = sums;
+  *view = s;
+  entries_out->swap(entries);
+  sums_out->swap(sums);
   return EULER_GPU_OK;
 }
-
-}  // namespace
 
 // ------------------------------------------------------------------------
 // Host CSR -> device graph (optionally only the rows a shard owns).
@@ -1205,7 +1225,15 @@ int euler_gpu_graph_load(const char* data_path, int device, int32_t shard_index,
   d.Describe(&c);
   // the loader already kept only this shard's partitions
   rc = BuildGraphFromHost(&c, device, 1, 0, 1, out);
-  if (rc == EULER_GPU_OK) (*out)->partitions = d.partitions;
+  if (rc == EULER_GPU_OK) {
+    (*out)->partitions = d.partitions;
+    if (d.n_binary > 0) {                  // uploaded by the first get_binary_feature
+      (*out)->bin_host_slots = d.n_binary;
+      (*out)->bin_host_ptr.swap(d.bfeat_ptr);
+      (*out)->bin_host_idx.swap(d.bfeat_idx);
+      (*out)->bin_host_val.swap(d.bfeat_val);
+    }
+  }
   return rc;
 }
 
@@ -1219,11 +1247,49 @@ int euler_gpu_dat_open(const char* data_path, int32_t shard_index,
   if (rc != EULER_GPU_OK) return rc;
   o->Describe(csr);
   if (partitions) *partitions = o->partitions;
-  *owner = o.release();
+  *owner = static_cast<DatOwner*>(o.release());
   return EULER_GPU_OK;
 }
 
-void euler_gpu_dat_close(void* owner) { delete static_cast<DatGraph*>(owner); }
+void euler_gpu_dat_close(void* owner) { delete static_cast<DatOwner*>(owner); }
+
+int euler_gpu_dat_open_edges(const char* data_path, int32_t shard_index, int32_t shards,
+                             euler_gpu_host_edges* edges, void** owner) {
+  if (!data_path || !edges || !owner) return Fail(EULER_GPU_EINVAL, "dat_open_edges: null argument");
+  std::unique_ptr<DatEdges> o(new DatEdges());
+  const int rc = LoadDatEdges(data_path, shard_index, shards, o.get());
+  if (rc != EULER_GPU_OK) return rc;
+  o->Describe(edges);
+  *owner = static_cast<DatOwner*>(o.release());
+  return EULER_GPU_OK;
+}
+
+int euler_gpu_dat_node_binary(const void* owner, int32_t* n_slots, const int64_t** ptr,
+                              const int32_t** idx, const uint8_t** val) {
+  const DatGraph* d = dynamic_cast<const DatGraph*>(static_cast<const DatOwner*>(owner));
+  if (!d || !n_slots || !ptr || !idx || !val)
+    return Fail(EULER_GPU_EINVAL, "dat_node_binary: not a euler_gpu_dat_open owner");
+  *n_slots = d->n_binary;
+  *ptr = d->bfeat_ptr.data(); *idx = d->bfeat_idx.data(); *val = d->bfeat_val.data();
+  return EULER_GPU_OK;
+}
+
+int euler_gpu_dat_feature_info(const char* data_path, int32_t edge, const char* name,
+                               int32_t* type, int32_t* slot, int64_t* dim) {
+  if (!data_path || !name || !type || !slot || !dim)
+    return Fail(EULER_GPU_EINVAL, "dat_feature_info: null argument");
+  DatMeta m;
+  const int rc = ReadDatMeta(data_path, &m);
+  if (rc != EULER_GPU_OK) return rc;
+  for (const DatFeature& f : edge ? m.edge_features : m.node_features) {
+    if (f.name == name) {
+      *type = f.type; *slot = f.idx; *dim = f.dim;
+      return EULER_GPU_OK;
+    }
+  }
+  return Fail(EULER_GPU_EINVAL, std::string("dat_feature_info: no ") + (edge ? "edge" : "node") +
+                                " feature named " + name);
+}
 
 int euler_gpu_dat_verify_edges(const char* data_path, int32_t shard_index, int32_t shards,
                                int64_t* edge_records, int64_t* not_in_rows,
@@ -1429,6 +1495,17 @@ bool InitQueryProxy(const char* conf) {
   if (euler_gpu_graph_load(cfg["data_path"].c_str(), device, shard_idx, shard_num,
                            &g) != EULER_GPU_OK)
     return false;
+  // data_type all / edge (QueryProxy::Init, client/query_proxy.cc:145-190: the Edge records are
+  // loaded when the data type asks for them) and a dataset that has them: the edge store too
+  const std::string data_type = cfg.count("data_type") ? cfg["data_type"] : "";
+  const std::string edge_dir = cfg["data_path"] + "/Edge";
+  struct stat st_edge;
+  if ((data_type == "all" || data_type == "edge") && stat(edge_dir.c_str(), &st_edge) == 0 &&
+      S_ISDIR(st_edge.st_mode) &&
+      euler_gpu_graph_load_edges(g, cfg["data_path"].c_str(), shard_idx, shard_num) != EULER_GPU_OK) {
+    DestroyGraph(g);
+    return false;
+  }
   std::lock_guard<std::mutex> lk(g_default_mu);
   if (g_default_graph) DestroyGraph(g_default_graph);
   g_default_graph = g;

@@ -602,6 +602,44 @@ class GpuSampleNodeOp : public OpKernel {
 };
 REGISTER_OP_KERNEL("API_SAMPLE_NODE", GpuSampleNodeOp);
 
+// API_SAMPLE_EDGE (core/kernels/sample_edge_op.cc:32-78): inputs edge_type (int32[k]), count
+// (int32); output "<name>:0" [count, 3] int64 (src, dst, type) - Graph::SampleEdge over the edge
+// store (euler_gpu_sample_edge).  A failed draw logs and produces no output.
+class GpuSampleEdgeOp : public OpKernel {
+ public:
+  explicit GpuSampleEdgeOp(const std::string& name) : OpKernel(name) {}
+  void Compute(const NodeDef& nd, OpKernelContext* ctx) override {
+    if (nd.inputs.size() != 2) { LogError("Invalid input arguments for SampleEdge"); return; }
+    std::vector<int32_t> types, cnt;
+    if (!GetIntArg(nd, 0, ctx, &types)) { LogError("Retrieve edge_type input for SampleEdge failed!"); return; }
+    if (!GetIntArg(nd, 1, ctx, &cnt) || cnt.empty()) { LogError("Retrieve count input for SampleEdge failed!"); return; }
+    euler_gpu_graph* g = ctx->graph();
+    if (!g) { LogError("API_SAMPLE_EDGE: no graph initialised"); return; }
+    const int32_t count = cnt[0];
+    OpScope sc(g);
+    int64_t* d_out = sc.Alloc<int64_t>((size_t)(count > 0 ? count : 0) * 3);
+    if (!sc.ok()) OP_FAIL(sc, "API_SAMPLE_EDGE");
+    if (!sc.Call(euler_gpu_sample_edge(g, sc.stream(), ctx->seed(), ctx->NextCallId(), types.data(),
+                                       (int32_t)types.size(), count, d_out))) {
+      sc.Drain();
+      LogError("Expect sample count: " + std::to_string(count) + ", real got:0 (" + sc.error() + ")");
+      return;
+    }
+    Tensor* out = nullptr;
+    if (ctx->Allocate(OutputName(nd, 0), {(size_t)count, 3}, kInt64, &out) != 0) {
+      sc.Drain();
+      LogError("Allocate output tensor failed!");
+      return;
+    }
+    if (!sc.Download(out->Raw<int64_t>(), d_out, (size_t)count * 24) || !sc.Sync()) {
+      sc.Drain();            // a copy may still be writing into the tensor
+      ctx->Deallocate(OutputName(nd, 0));
+      OP_FAIL(sc, "API_SAMPLE_EDGE");
+    }
+  }
+};
+REGISTER_OP_KERNEL("API_SAMPLE_EDGE", GpuSampleEdgeOp);
+
 // ID_UNIQUE (core/kernels/id_unique_op.cc:35-64), node-id branch.
 class GpuIdUniqueOp : public OpKernel {
  public:

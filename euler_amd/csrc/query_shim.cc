@@ -186,6 +186,16 @@ bool QueryProxy::Execute(Query* query) {
     NodeDef nd{steps[1].args[0], "API_SAMPLE_NODE", {steps[0].args[0], steps[0].args[1]}, {}};
     return RunOp(nd, ctx);
   }
+  // sampleE(edge_type, count).as(alias)           tf_euler/kernels/sample_edge_op.cc:56
+  if (steps[0].fn == "sampleE") {
+    if (steps.size() != 2 || steps[0].args.size() != 2 || steps[1].fn != "as" ||
+        steps[1].args.size() != 1) {
+      LogError("unsupported sampleE query: " + query->gremlin_);
+      return false;
+    }
+    NodeDef nd{steps[1].args[0], "API_SAMPLE_EDGE", {steps[0].args[0], steps[0].args[1]}, {}};
+    return RunOp(nd, ctx);
+  }
   if (steps[0].fn != "v" || steps[0].args.size() != 1) {
     LogError("unsupported query: " + query->gremlin_);
     return false;

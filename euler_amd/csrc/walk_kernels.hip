@@ -11,6 +11,7 @@
 #include "k1_search.h"
 #include "fanout_local.h"     // LeanSamplePair (the walks over merged walkers)
 #include "wave_sums.h"
+#include "node_sampler.h"
 
 namespace euler_gpu {
 
@@ -19,55 +20,11 @@ namespace euler_gpu {
 // One lane per sample; draw indices follow the reference's program order
 // inside one call (domain NODE, stream 0).
 // ------------------------------------------------------------------------
-struct SampleNodeArgs {
-  NodeSamplerView s;
-  uint64_t seed;
-  uint64_t* out;
-  uint32_t call_id;
-  int32_t count;
-  int32_t mode;          // 0 fixed type, 1 all types (-1), 2 type list
-  int32_t type;          // mode 0
-  int32_t n_sub;         // mode 2
-  int32_t sub_type[kMaxNodeTypes];
-  float sub_sum[kMaxNodeTypes];
-};
-
-__device__ __forceinline__ uint64_t AliasNext(const AliasEntry* tab, int64_t n,
-                                              double u_col, double u_coin) {
-  // AliasMethod::Next (alias_method.cc:66-78)
-  const int64_t column = (int64_t)floor(__dmul_rn((double)n, u_col));
-  const AliasEntry e = tab[column];
-  return u_coin < (double)e.prob ? e.id_self : e.id_alias;
-}
-
 __global__ __launch_bounds__(256) void SampleNodeKernel(const SampleNodeArgs a) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.count;
-       i += stride) {
-    int32_t t = a.type;
-    uint64_t d = 0;   // index of the next draw of this sample
-    if (a.mode == 0) {
-      d = 2 * (uint64_t)i;
-    } else if (a.mode == 1) {
-      d = 4 * (uint64_t)i;
-      const Philox4 b = RngBlock(a.seed, a.call_id, kDomainNode, 0,
-                                 (uint32_t)(d >> 1));
-      const int64_t col = (int64_t)floor(__dmul_rn(
-          (double)a.s.n_types, UnitFromWords(b.w[0], b.w[1])));
-      t = UnitFromWords(b.w[2], b.w[3]) < (double)a.s.tc_prob[col]
-              ? (int32_t)col : a.s.tc_alias[col];
-      d += 2;
-    } else {
-      d = 3 * (uint64_t)i;
-      const double u = RngDraw(a.seed, a.call_id, kDomainNode, 0, d);
-      t = a.sub_type[RandomSelect(a.sub_sum, 0, (uint64_t)(a.n_sub - 1), u)];
-      d += 1;
-    }
-    const double u_col = RngDraw(a.seed, a.call_id, kDomainNode, 0, d);
-    const double u_coin = RngDraw(a.seed, a.call_id, kDomainNode, 0, d + 1);
-    const int64_t b = a.s.type_off[t];
-    a.out[i] = AliasNext(a.s.entries + b, a.s.type_off[t + 1] - b, u_col, u_coin);
-  }
+       i += stride)
+    a.out[i] = SampleNodeDraw(a, i);
 }
 
 // ------------------------------------------------------------------------
@@ -1634,37 +1591,8 @@ int euler_gpu_sample_node(const euler_gpu_graph* g, void* stream, uint64_t seed,
   SampleNodeArgs a{};
   a.s = g->sampler;
   a.seed = seed; a.call_id = call_id; a.count = count; a.out = out_dev;
-  const int32_t T = g->sampler.n_types;
-  if (k == 1) {                                     // api.cc:33-35
-    const int32_t type = node_types_host[0];
-    if (type == -1) {                               // graph.cc:229-236
-      if (g->sampler.tc_sum == 0.f)
-        return Fail(EULER_GPU_EEMPTY, "sample_node: total node weight is 0");
-      a.mode = 1;
-    } else {
-      if (type < 0 || type >= T)
-        return Fail(EULER_GPU_EINVAL, "sample_node: node type out of range");
-      if (g->sampler.sampler_sum[type] == 0.f ||
-          g->sampler.type_off[type + 1] == g->sampler.type_off[type])
-        return Fail(EULER_GPU_EEMPTY, "sample_node: type weight is 0");
-      a.mode = 0; a.type = type;
-    }
-  } else {                                          // graph.cc:247-275
-    a.mode = 2;
-    float acc = 0.f;
-    int32_t m = 0;
-    for (int32_t t = 0; t < T; ++t) {
-      bool in = false;
-      for (int32_t j = 0; j < k; ++j) in |= node_types_host[j] == t;
-      if (in) {
-        acc += g->sampler.type_sum[t];
-        a.sub_type[m] = t; a.sub_sum[m] = acc; ++m;
-      }
-    }
-    a.n_sub = m;
-    if (m == 0 || !(a.sub_sum[m - 1] > 0.f))
-      return Fail(EULER_GPU_EEMPTY, "sample_node: listed types have zero weight");
-  }
+  const int rc = PrepareSampleNode(g->sampler, node_types_host, k, "sample_node", "node", &a);
+  if (rc != EULER_GPU_OK) return rc;
   const int block = 256;
   hipLaunchKernelGGL(SampleNodeKernel, dim3(GridFor(count, block)), dim3(block),
                      0, (hipStream_t)stream, a);

@@ -48,6 +48,8 @@ def initialize_graph(config):
     if ok:
         h = C.c_void_p(_lib.lib().euler_gpu_default_graph())
         g = Graph(h, _lib.lib().euler_gpu_graph_device(h))
+        items = dict(kv.split('=', 1) for kv in config.decode().split(';') if '=' in kv)
+        g.data_path = items.get('data_path')
         g.close = lambda: None      # owned by the library's default slot
         set_default_graph(g)
     return ok

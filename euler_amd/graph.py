@@ -141,6 +141,58 @@ def synth_params(seed, n_nodes, n_edges, n_types=1, weighted=True, scale=None, h
     return p
 
 
+def _edge_feature_tables(e, n, dense, sparse, binary):
+    """Fill the feature tables of a HostEdges; returns the arrays it points into (keep them alive
+    for the call)."""
+    keep = []
+
+    def table(slots, vtype, vptr):
+        if all(isinstance(c, np.ndarray) and c.ndim == 2 and len(c) == n for c in slots):
+            # every record has the same slot layout: the library stores one row of ends
+            lens = np.array([c.shape[1] for c in slots], np.int64)
+            ends = np.tile(np.cumsum(lens).astype(np.int32), n)
+            ptr = np.arange(n + 1, dtype=np.int64) * int(lens.sum())
+            if len(slots) == 1:
+                val = np.ascontiguousarray(slots[0], vtype).reshape(-1)
+            else:
+                val = np.ascontiguousarray(np.concatenate([c.astype(vtype) for c in slots], 1)).reshape(-1)
+        else:
+            if vtype == np.uint8:
+                slots = [[np.frombuffer(bytes(b), np.uint8) for b in c] for c in slots]
+            lens = np.stack([np.array([len(x) for x in c], np.int64) for c in slots], 1)
+            ends = np.cumsum(lens, 1).astype(np.int32).reshape(-1)
+            ptr = np.zeros(n + 1, np.int64)
+            ptr[1:] = np.cumsum(lens.sum(1))
+            vals = [np.asarray(c[r], vtype).reshape(-1) for r in range(n) for c in slots]
+            val = np.concatenate(vals) if vals else np.zeros(0, vtype)
+        if len(val) == 0:
+            val = np.zeros(1, vtype)
+        keep.extend([ptr, ends, val])
+        return (ptr.ctypes.data_as(_lib.i64p), ends.ctypes.data_as(_lib.i32p),
+                val.ctypes.data_as(vptr))
+
+    if dense:
+        e.n_float_features = len(dense)
+        e.feat_ptr, e.feat_idx, e.feat_val = table(list(dense), np.float32, _lib.f32p)
+    if sparse:
+        e.n_u64_features = len(sparse)
+        e.ufeat_ptr, e.ufeat_idx, e.ufeat_val = table(list(sparse), np.uint64, _lib.u64p)
+    if binary:
+        e.n_binary_features = len(binary)
+        e.bfeat_ptr, e.bfeat_idx, e.bfeat_val = table(list(binary), np.uint8, _lib.u8p)
+    return keep
+
+
+
+def dat_feature_info(data_path, name, edge=False):
+    """euler.meta's (type, slot, dim) for the feature `name` exactly as written there."""
+    t, slot, dim = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    check(lib().euler_gpu_dat_feature_info(str(data_path).encode(), 1 if edge else 0,
+                                           str(name).encode(), C.byref(t), C.byref(slot),
+                                           C.byref(dim)))
+    return int(t.value), int(slot.value), int(dim.value)
+
+
 class Graph:
     """Immutable graph in HBM (CSR + row metadata + alias tables)."""
 
@@ -152,6 +204,7 @@ class Graph:
         self.seed = 0
         self._call_id = 0
         self._lock = threading.Lock()
+        self.data_path = None       # the directory of a loaded graph (feature names)
         self.node_type_names = (meta or {}).get("node_types", {})
         self.edge_type_names = (meta or {}).get("edge_types", {})
 
@@ -229,11 +282,17 @@ class Graph:
         return cls(h, device)
 
     @classmethod
-    def load(cls, data_path, device=0, shard_index=0, shards=1):
+    def load(cls, data_path, device=0, shard_index=0, shards=1, edges=False):
+        """Graph::Init over a data directory; edges=True also loads the Edge records the shard
+        keeps (edge sampling and edge features)."""
         h = C.c_void_p()
         check(lib().euler_gpu_graph_load(str(data_path).encode(), device,
                                          shard_index, shards, C.byref(h)))
-        return cls(h, device)
+        g = cls(h, device)
+        g.data_path = str(data_path)
+        if edges:
+            check(lib().euler_gpu_graph_load_edges(h, g.data_path.encode(), shard_index, shards))
+        return g
 
     def close(self):
         if self._h is not None and self._h.value:
@@ -845,6 +904,162 @@ class Graph:
                     self._h, _stream(), _ptr(nodes), n, int(fid), _ptr(idx),
                     C.byref(total), _ptr(vals)))
         return idx, vals
+
+    # ---------------------------------------------------------------- edge records
+    def set_edges(self, src, dst, types, weights, dense=None, sparse=None, binary=None):
+        """The edge store over host records in ordinal order ((src, dst, type) distinct).
+        Features, each optional, one entry per slot: an [n, d] array (every record d values;
+        binary: uint8) or a list of n per-record sequences (binary: `bytes`)."""
+        n = len(src)
+        keep = [_np(src, np.uint64), _np(dst, np.uint64), _np(types, np.int32),
+                _np(weights, np.float32)]
+        e = _lib.HostEdges()
+        e.n = n
+        e.src, e.dst = keep[0].ctypes.data_as(_lib.u64p), keep[1].ctypes.data_as(_lib.u64p)
+        e.type, e.weight = keep[2].ctypes.data_as(_lib.i32p), keep[3].ctypes.data_as(_lib.f32p)
+        keep.append(_edge_feature_tables(e, n, dense, sparse, binary))
+        with self._on_device():
+            check(lib().euler_gpu_graph_set_edges(self._h, C.byref(e)))
+
+    def set_edge_features(self, dense=None, sparse=None, binary=None):
+        """Replace the store's feature tables (rows in ordinal order, the forms of set_edges) -
+        features for the records edges_from_rows built."""
+        n = self.num_edge_records
+        e = _lib.HostEdges()
+        e.n = n
+        keep = _edge_feature_tables(e, n, dense, sparse, binary)   # noqa: F841 (alive for the call)
+        with self._on_device():
+            check(lib().euler_gpu_graph_set_edge_features(self._h, C.byref(e)))
+
+    def edges_from_rows(self):
+        """The edge store over the distinct (src, dst, type) entries of the rows, built on the
+        device (row order, then entry order; weights = the entries' own)."""
+        with self._on_device():
+            check(lib().euler_gpu_graph_edges_from_rows(self._h))
+
+    @property
+    def num_edge_records(self):
+        """Records of the edge store (-1: none)."""
+        return int(lib().euler_gpu_graph_num_edge_records(self._h))
+
+    def export_edges(self, first=0, n=None):
+        """Records [first, first + n) in ordinal order: (src, dst, type, weight) numpy arrays."""
+        if n is None:
+            n = self.num_edge_records - first
+        out = (np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.int32),
+               np.zeros(n, np.float32))
+        check(lib().euler_gpu_graph_export_edges(
+            self._h, int(first), int(n), out[0].ctypes.data_as(_lib.u64p),
+            out[1].ctypes.data_as(_lib.u64p), out[2].ctypes.data_as(_lib.i32p),
+            out[3].ctypes.data_as(_lib.f32p)))
+        return out
+
+    def set_edge_sampler(self, order=None):
+        """The edge sampler enumerating the records in `order` (ordinals; None = ordinal order)."""
+        o = None if order is None else _np(order, np.int64)
+        if o is not None and len(o) != self.num_edge_records:
+            raise ValueError("set_edge_sampler: order must list every ordinal once")
+        with self._on_device():
+            check(lib().euler_gpu_graph_set_edge_sampler(
+                self._h, None if o is None else o.ctypes.data_as(_lib.i64p)))
+
+    def sample_edge(self, count, edge_type=-1, call_id=None):
+        """tf_euler sample_edge (tf_euler/kernels/sample_edge_op.cc): [count, 3] int64
+        (src, dst, type) drawn by edge weight within the type(s)."""
+        et, et_p, k = _i32_array(np.atleast_1d(edge_type))
+        out = torch.empty((int(count), 3), dtype=torch.int64, device=self.device)
+        with self._on_device():
+            check(lib().euler_gpu_sample_edge(
+                self._h, _stream(), self.seed, self._take_call_ids(1, call_id), et_p, k,
+                int(count), _ptr(out)))
+        return out
+
+    def _edges(self, edges):
+        e = torch.as_tensor(edges)
+        if e.device != self.device or e.dtype != torch.int64:
+            e = e.to(device=self.device, dtype=torch.int64)
+        return e.reshape(-1, 3).contiguous()
+
+    def edge_ordinals(self, edges):
+        """[n, 3] (src, dst, type) -> [n] int64 ordinals, -1 where there is no record."""
+        e = self._edges(edges)
+        out = torch.empty(e.shape[0], dtype=torch.int64, device=self.device)
+        with self._on_device():
+            check(lib().euler_gpu_edge_ordinals(self._h, _stream(), _ptr(e), e.shape[0], _ptr(out)))
+        return out
+
+    def get_edge_dense_feature(self, edges, feature_ids, dimensions):
+        """tf_euler get_edge_dense_feature: list of [n, dim] float32, zeros for unknown edges."""
+        e = self._edges(edges)
+        n = e.shape[0]
+        outs = []
+        with self._on_device():
+            for fid, dim in zip(feature_ids, dimensions):
+                out = torch.empty((n, int(dim)), dtype=torch.float32, device=self.device)
+                check(lib().euler_gpu_get_edge_dense_feature(
+                    self._h, _stream(), _ptr(e), n, int(fid), int(dim), _ptr(out)))
+                outs.append(out)
+        return outs
+
+    def get_edge_sparse_feature(self, edges, feature_ids, default_values=None):
+        """tf_euler get_edge_sparse_feature: one (indices, values, dense_shape) per feature."""
+        e = self._edges(edges)
+        n = e.shape[0]
+        if default_values is None:
+            default_values = [0] * len(feature_ids)
+        outs = []
+        with self._on_device():
+            for fid, dv in zip(feature_ids, default_values):
+                row_off = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+                nnz, max_len = C.c_int64(0), C.c_int64(0)
+                check(lib().euler_gpu_get_edge_sparse_feature(
+                    self._h, _stream(), _ptr(e), n, int(fid), int(dv), _ptr(row_off),
+                    C.byref(nnz), C.byref(max_len), None, None))
+                ind = torch.empty((int(nnz.value), 2), dtype=torch.int64, device=self.device)
+                val = torch.empty(int(nnz.value), dtype=torch.int64, device=self.device)
+                if nnz.value:
+                    check(lib().euler_gpu_get_edge_sparse_feature(
+                        self._h, _stream(), _ptr(e), n, int(fid), int(dv), _ptr(row_off),
+                        C.byref(nnz), C.byref(max_len), _ptr(ind), _ptr(val)))
+                outs.append((ind, val, [n, int(max_len.value)] if n else [0, 0]))
+        return outs
+
+    def _binary(self, fn, keys, n, feature_ids):
+        outs = []
+        with self._on_device():
+            for fid in feature_ids:
+                off = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+                total = C.c_int64(0)
+                check(fn(self._h, _stream(), _ptr(keys), n, int(fid), _ptr(off), C.byref(total),
+                         None))
+                data = torch.empty(max(int(total.value), 1), dtype=torch.uint8, device=self.device)
+                if total.value:
+                    check(fn(self._h, _stream(), _ptr(keys), n, int(fid), _ptr(off),
+                             C.byref(total), _ptr(data)))
+                outs.append((off, data[:int(total.value)]))
+        return outs
+
+    def get_edge_binary_feature(self, edges, feature_ids):
+        """tf_euler get_edge_binary_feature: one (offsets [n+1] int64, bytes uint8) per feature on
+        the device; edge i's value is bytes[offsets[i]:offsets[i+1]], empty when unknown."""
+        e = self._edges(edges)
+        return self._binary(lib().euler_gpu_get_edge_binary_feature, e, e.shape[0], feature_ids)
+
+    def get_binary_feature(self, nodes, feature_ids):
+        """tf_euler get_binary_feature over node rows: (offsets, bytes) per feature."""
+        nodes = _as_i64_cuda(nodes, self.device).reshape(-1)
+        return self._binary(lib().euler_gpu_get_binary_feature, nodes, nodes.numel(), feature_ids)
+
+    def feature_info(self, name, edge=False):
+        """euler.meta's (type, slot, dim) of a feature of a loaded graph; type 0 sparse, 1 dense,
+        2 binary."""
+        if self.data_path is None:
+            raise ValueError("feature names need a graph loaded from a data directory")
+        cache = self.__dict__.setdefault("_feature_info", {})
+        key = (str(name), bool(edge))
+        if key not in cache:
+            cache[key] = dat_feature_info(self.data_path, name, edge)
+        return cache[key]
 
     _ORDER = {None: 0, "": 0, "id": 1, "weight": 2}
 

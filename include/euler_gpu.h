@@ -90,6 +90,28 @@ typedef struct euler_gpu_host_csr {
   const uint64_t* ufeat_val;   /* [ufeat_ptr[n_rows]]                           */
 } euler_gpu_host_csr;
 
+/* Host description of Edge records (core/graph/edge.h: id_ = (src, dst, type), weight_ and the
+ * uint64 / float / binary feature idx + value lists) in ORDINAL order: a record's ordinal is its
+ * position here, the order every edge entry point below uses.  Feature tables have the layout of
+ * euler_gpu_host_csr's (ptr [n+1], per-slot ends [n * slots] row-relative, values); binary
+ * values are bytes.  A table with 0 slots may have NULL arrays. */
+typedef struct euler_gpu_host_edges {
+  int64_t n;
+  int32_t n_edge_types;        /* euler.meta's edge type count (0 = not known)    */
+  int32_t pad0;
+  const uint64_t* src;         /* [n]                                             */
+  const uint64_t* dst;         /* [n]                                             */
+  const int32_t* type;         /* [n]                                             */
+  const float* weight;         /* [n]                                             */
+  int32_t n_float_features;
+  int32_t n_u64_features;
+  int32_t n_binary_features;
+  int32_t pad1;
+  const int64_t* feat_ptr;  const int32_t* feat_idx;  const float* feat_val;
+  const int64_t* ufeat_ptr; const int32_t* ufeat_idx; const uint64_t* ufeat_val;
+  const int64_t* bfeat_ptr; const int32_t* bfeat_idx; const uint8_t* bfeat_val;
+} euler_gpu_host_edges;
+
 /* Parameters of the deterministic synthetic power-law graph (benchmarks). */
 typedef struct euler_gpu_synth_params {
   uint64_t seed;
@@ -149,6 +171,24 @@ void euler_gpu_dat_close(void* owner);
 int euler_gpu_dat_verify_edges(const char* data_path, int32_t shard_index, int32_t shards,
                                int64_t* edge_records, int64_t* not_in_rows,
                                int64_t* row_triples);
+/* Host-only Edge reader (no GPU needed): Edge/<x>_<partition>.dat records (Edge::DeSerialize,
+ * core/graph/edge.cc:136-200) of the files the shard keeps (Graph::Init's filter,
+ * core/graph/graph.cc:90-98) in sorted file order; a repeated (src, dst, type) keeps its first
+ * record (Graph::AddEdgeFrom(vector) inserts, core/graph/graph.cc:197-203).  *edges describes
+ * malloc'ed arrays owned by *owner; free with euler_gpu_dat_close().  A truncated or malformed
+ * record: EULER_GPU_EIO. */
+int euler_gpu_dat_open_edges(const char* data_path, int32_t shard_index, int32_t shards,
+                             euler_gpu_host_edges* edges, void** owner);
+/* The binary node features of a euler_gpu_dat_open owner (Node::DeSerialize keeps them,
+ * core/graph/node.cc:515-523): ragged layout (ptr [n_rows+1], ends [n_rows * slots], bytes). */
+int euler_gpu_dat_node_binary(const void* owner, int32_t* n_slots, const int64_t** ptr,
+                              const int32_t** idx, const uint8_t** val);
+/* euler.meta's feature tables (GraphMeta::GetFeatureInfo / GetEdgeFeatureInfo,
+ * core/graph/graph_meta.h:97-105): `name` exactly as written there ("dense_f3"); edge = 0 the
+ * node table, 1 the edge table.  *type: 0 sparse (uint64), 1 dense (float), 2 binary;
+ * *slot: the feature's index among its type; *dim.  An unknown name: EULER_GPU_EINVAL. */
+int euler_gpu_dat_feature_info(const char* data_path, int32_t edge, const char* name,
+                               int32_t* type, int32_t* slot, int64_t* dim);
 void euler_gpu_graph_destroy(euler_gpu_graph* g);
 
 int64_t euler_gpu_graph_num_nodes(const euler_gpu_graph* g);
@@ -1006,6 +1046,74 @@ int euler_gpu_sample_fanout_with_feature(const euler_gpu_graph* g, void* stream,
                                          void* workspace_dev, const int32_t* dense_fids_host,
                                          const int32_t* dense_dims_host, int32_t n_dense,
                                          float* const* dense_out_dev);
+
+/* ---- edge records (edge_kernels.hip) ------------------------------------------
+ * The reference keeps one Edge object per record in an unordered_map<EdgeID, Edge*>
+ * (core/graph/graph.h:87-104).  Here an edge store: 32-byte slots {src, dst, type, weight,
+ * ordinal} in an open-addressing table of 128-byte lines (4 slots, at most half full, linear
+ * probing by line), an ordinal -> slot map, the per-type alias tables of the edge sampler and
+ * the edge features in the ragged layout of the node features.  No store exists until one of
+ * the three constructors runs; a constructor replaces the graph's store.  Every byte is counted
+ * in euler_gpu_graph_bytes, and a failed build returns its allocations. */
+/* The records of a dataset: Edge/<x>_<partition>.dat as euler_gpu_dat_open_edges reads them. */
+int euler_gpu_graph_load_edges(euler_gpu_graph* g, const char* data_path, int32_t shard_index,
+                               int32_t shards);
+/* Host records in ordinal order; (src, dst, type) must be distinct (EULER_GPU_EINVAL). */
+int euler_gpu_graph_set_edges(euler_gpu_graph* g, const euler_gpu_host_edges* edges);
+/* One record per distinct (src, dst, type) entry of the graph's rows, built on the device:
+ * ordinals in row order, then entry order, first occurrence kept; the weight is the entry's
+ * own (running sum minus the one before it in the row).  No features. */
+int euler_gpu_graph_edges_from_rows(euler_gpu_graph* g);
+int64_t euler_gpu_graph_num_edge_records(const euler_gpu_graph* g);   /* -1: no store */
+/* The store's feature tables replaced by those of *edges (edges->n == the record count, rows in
+ * ordinal order; the record arrays are not read) - features for a store edges_from_rows built. */
+int euler_gpu_graph_set_edge_features(euler_gpu_graph* g, const euler_gpu_host_edges* edges);
+/* Records [first, first + n) in ordinal order to host arrays (any may be NULL). */
+int euler_gpu_graph_export_edges(const euler_gpu_graph* g, int64_t first, int64_t n,
+                                 uint64_t* src_host, uint64_t* dst_host, int32_t* type_host,
+                                 float* weight_host);
+/* The edge sampler (Graph::BuildGlobalEdgeSampler, core/graph/graph.cc:372-405) rebuilt over the
+ * records in the order `order_host` lists their ordinals (a permutation of 0..n-1; NULL =
+ * ordinal order, what every constructor builds).  The reference enumerates its unordered_map. */
+int euler_gpu_graph_set_edge_sampler(euler_gpu_graph* g, const int64_t* order_host);
+/* API_SAMPLE_EDGE / Graph::SampleEdge (core/graph/graph.cc:277-326, core/kernels/
+ * sample_edge_op.cc:32-78): out_dev [count, 3] int64 (src, dst, type).  The draws are exactly
+ * euler_gpu_sample_node's (same domain, stream and draw indices).  edge_types_host[k]: one type,
+ * {-1} = all types, or a list; the reference's -1 / list path never initialises its type
+ * collection - here they draw a type by edge_weight_sums_ as SampleNode does.
+ * A zero weight sum: EULER_GPU_EEMPTY, nothing written. */
+int euler_gpu_sample_edge(const euler_gpu_graph* g, void* stream, uint64_t seed, uint32_t call_id,
+                          const int32_t* edge_types_host, int32_t k, int32_t count,
+                          int64_t* out_dev);
+/* Graph::GetEdgeByID (core/graph/graph.h:94-104): edges_dev [n, 3] int64 (src, dst, type) ->
+ * ordinals [n] int64, -1 where there is no such record. */
+int euler_gpu_edge_ordinals(const euler_gpu_graph* g, void* stream, const int64_t* edges_dev,
+                            int64_t n, int64_t* out_dev);
+/* TF GetEdgeDenseFeature (tf_euler/kernels/get_edge_dense_feature_op.cc): [n, dim] float32,
+ * zero-filled, truncated to dim; zeros for an unknown edge or slot. */
+int euler_gpu_get_edge_dense_feature(const euler_gpu_graph* g, void* stream,
+                                     const int64_t* edges_dev, int64_t n, int32_t fid,
+                                     int32_t dim, float* out_dev);
+/* TF GetEdgeSparseFeature (tf_euler/kernels/get_edge_sparse_feature_op.cc): the COO triple and
+ * two-call protocol of euler_gpu_get_sparse_feature; an empty or unknown edge contributes
+ * (row, 0) = default_value. */
+int euler_gpu_get_edge_sparse_feature(const euler_gpu_graph* g, void* stream,
+                                      const int64_t* edges_dev, int64_t n, int32_t fid,
+                                      int64_t default_value, int64_t* row_off_dev,
+                                      int64_t* nnz_host, int64_t* max_len_host,
+                                      int64_t* indices_dev, int64_t* values_dev);
+/* TF GetEdgeBinaryFeature (tf_euler/kernels/get_edge_binary_feature_op.cc:90-115): the bytes of
+ * slot fid of every edge, concatenated: call 1 (bytes_dev NULL) fills offsets_dev [n+1] int64 and
+ * *total_host; call 2 the bytes.  An unknown edge or slot is empty. */
+int euler_gpu_get_edge_binary_feature(const euler_gpu_graph* g, void* stream,
+                                      const int64_t* edges_dev, int64_t n, int32_t fid,
+                                      int64_t* offsets_dev, int64_t* total_host,
+                                      uint8_t* bytes_dev);
+/* TF GetBinaryFeature (tf_euler/kernels/get_binary_feature_op.cc) over the node rows, the same
+ * two calls.  The node binary features of a loaded dataset reach the device on the first call. */
+int euler_gpu_get_binary_feature(const euler_gpu_graph* g, void* stream, const uint64_t* nodes_dev,
+                                 int64_t n, int32_t fid, int64_t* offsets_dev, int64_t* total_host,
+                                 uint8_t* bytes_dev);
 
 /* Tuning keys, phase timers and byte counters (A/B measurements, bench.py's roofline leg) are
  * not part of the product surface: include/euler_gpu_measure.h. */

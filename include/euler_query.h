@@ -17,9 +17,11 @@
 //       v(nodes).outV(edge_types).as(nb)
 //   tf_euler/kernels/sample_node_op.cc:63,72
 //       sampleN(node_type, count).as(id)
+//   tf_euler/kernels/sample_edge_op.cc:56
+//       sampleE(edge_type, count).as(eid)
 //
 // i.e. `v(<ids>)` followed by one or more `.sampleNB(<types>, <count>, <D>).as(<alias>)`
-// steps, `v(<ids>).outV(<types>).as(<alias>)`, and `sampleN(<type>, <count>).as(<alias>)`;
+// steps, `v(<ids>).outV(<types>).as(<alias>)`, `sampleN(<type>, <count>).as(<alias>)` and `sampleE(<type>, <count>).as(<alias>)`;
 // argument names are the caller's input tensor names.  Each step runs the plugin
 // op the reference's translator would emit (API_SAMPLE_NB / API_GET_NB_NODE /
 // API_SAMPLE_NODE, include/euler_op_framework.h) with the alias as node name, so
