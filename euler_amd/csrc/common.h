@@ -299,6 +299,23 @@ struct euler_gpu_graph {
   // one left.  Guarded by ws_mu.
   struct FlowTableDense { void* p = nullptr; size_t rows = 0; uint32_t next_epoch = 1; };
   mutable std::map<void*, FlowTableDense> flow_tables;
+  int32_t shards = 1;                 // shards of the dataset this graph holds a part of
+  // Graph-label index (graph_label_kernels.hip): the nodes of every label in table order (label
+  // r owns label_nodes[label_start[r] .. label_start[r + 1]), ascending ids) and the labels'
+  // bytes; built from the node binary slot label_slot (binary_graph_label of a loaded dataset)
+  // on the first label call, or by euler_gpu_graph_set_graph_labels.  Its allocations are
+  // listed in label_allocs, not in `allocations`, so that a new index can replace it.
+  int32_t label_slot = -1;
+  mutable std::mutex label_mu;
+  mutable bool labels_ready = false;
+  mutable int64_t n_labels = 0;
+  mutable int64_t n_labelled = 0;
+  mutable const uint64_t* label_nodes = nullptr;
+  mutable const int64_t* label_start = nullptr;
+  mutable std::vector<std::pair<void*, int64_t>> label_allocs;
+  mutable std::vector<int64_t> label_off_host;       // [n_labels + 1] into label_bytes_host
+  mutable std::vector<uint8_t> label_bytes_host;
+  mutable std::map<std::string, int64_t> label_lookup;
 };
 
 namespace euler_gpu {
@@ -318,6 +335,8 @@ int BuildAliasTables(const std::vector<uint64_t>& ids, const std::vector<int32_t
                      std::vector<AliasEntry>* entries, std::vector<float>* sums,
                      const char* noun);   // "node" / "edge": the error messages
 void DestroyEdgeStore(euler_gpu_graph* g);          // edge_kernels.hip
+int EnsureNodeBinary(const euler_gpu_graph* g);     // edge_kernels.hip: node binary table, on first use
+void DestroyLabelIndex(euler_gpu_graph* g);         // graph_label_kernels.hip
 // weight-bucket index, on first use; leaves view.wb == nullptr (and returns OK) for graphs it
 // does not serve
 int EnsureWbIndex(const euler_gpu_graph* g);

@@ -576,6 +576,8 @@ int BuildFromRows(euler_gpu_graph* g) {
   return BuildStore(g, n, std::max<int32_t>(v.T, 1), src, dst, ty, w, nullptr);
 }
 
+}  // namespace
+
 int EnsureNodeBinary(const euler_gpu_graph* g) {
   std::lock_guard<std::mutex> lk(g->bin_mu);
   if (g->node_bin_ready || g->bin_host_slots == 0) return EULER_GPU_OK;
@@ -591,6 +593,8 @@ int EnsureNodeBinary(const euler_gpu_graph* g) {
   g->node_bin_ready = true;
   return EULER_GPU_OK;
 }
+
+namespace {
 
 int CheckEdgeQuery(const euler_gpu_graph* g, const char* what, int64_t n, const void* edges) {
   if (!g) return Fail(EULER_GPU_ENOGRAPH, std::string(what) + ": null graph");

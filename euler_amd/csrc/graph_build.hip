@@ -235,6 +235,7 @@ void DestroyGraph(euler_gpu_graph* g) {
   if (!g) return;
   (void)hipSetDevice(g->device);
   DestroyEdgeStore(g);
+  DestroyLabelIndex(g);
   for (void* p : g->allocations) (void)hipFree(p);
   for (auto& kv : g->ws) (void)hipFree(kv.second.first);
   for (auto& kv : g->flow_tables) (void)hipFree(kv.second.p);
@@ -587,6 +588,7 @@ int BuildGraphFromHost(const euler_gpu_host_csr* c, int device,
     b.g->node_type_dev = b.Upload(row_type.data(), row_type.size());
     if (b.rc != EULER_GPU_OK) { DestroyGraph(b.g.release()); return b.rc; }
   }
+  b.g->shards = shards;
   *out = b.g.release();
   return EULER_GPU_OK;
 }
@@ -840,6 +842,7 @@ int BuildGraphSynthetic(const euler_gpu_synth_params* sp, int device,
   }
   b.g->has_sampler = false;   // uniform roots are drawn by the caller
   b.g->n_node_types = 1;
+  b.g->shards = shards;
   *out = b.g.release();
   return EULER_GPU_OK;
 }
@@ -1227,6 +1230,11 @@ int euler_gpu_graph_load(const char* data_path, int device, int32_t shard_index,
   rc = BuildGraphFromHost(&c, device, 1, 0, 1, out);
   if (rc == EULER_GPU_OK) {
     (*out)->partitions = d.partitions;
+    (*out)->shards = shards;
+    // graph labels: the node binary feature binary_graph_label (Graph::GetGraphLabel reads it
+    // through GetNodeFeatureId, core/graph/graph.cc:439-457)
+    for (const DatFeature& f : d.meta.node_features)
+      if (f.name == "binary_graph_label" && f.type == 2) (*out)->label_slot = f.idx;
     if (d.n_binary > 0) {                  // uploaded by the first get_binary_feature
       (*out)->bin_host_slots = d.n_binary;
       (*out)->bin_host_ptr.swap(d.bfeat_ptr);

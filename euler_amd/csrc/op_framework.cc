@@ -211,7 +211,8 @@ void OpKernelContext::SetProcessSeed(uint64_t seed) {
 
 size_t SizeOfType(DataType t) {
   switch (t) {
-    case kInt8: case kUInt8: case kBool: case kString: return 1;
+    case kInt8: case kUInt8: case kBool: return 1;
+    case kString: return sizeof(std::string*);    // an owned std::string* per element (tensor.cc:45-75)
     case kInt16: case kUInt16: return 2;
     case kInt32: case kUInt32: case kFloat: return 4;
     default: return 8;
@@ -300,10 +301,23 @@ void HostFree(void* p) {
 }
 }  // namespace
 
+// kString (core/framework/tensor.cc:45-75): every element is a std::string* the tensor owns,
+// created empty with it and deleted with it.
 Tensor::Tensor(const TensorShape& shape, DataType type)
     : shape_(shape), type_(type),
-      data_(HostAlloc(shape.NumElements() * SizeOfType(type) + 16)) {}
-Tensor::~Tensor() { HostFree(data_); }
+      data_(HostAlloc(shape.NumElements() * SizeOfType(type) + 16)) {
+  if (type_ == kString) {
+    std::string** p = Raw<std::string*>();
+    for (size_t i = 0; i < shape_.NumElements(); ++i) p[i] = new std::string;
+  }
+}
+Tensor::~Tensor() {
+  if (type_ == kString) {
+    std::string** p = Raw<std::string*>();
+    for (size_t i = 0; i < shape_.NumElements(); ++i) delete p[i];
+  }
+  HostFree(data_);
+}
 
 std::string OutputName(const NodeDef& node_def, int i) {
   return node_def.name + ":" + std::to_string(i);
@@ -415,6 +429,9 @@ OpStatus CreateOpKernel(const std::string& name, OpKernel** kernel) {
 // ---------------------------------------------------------------- kernels
 #define OP_FAIL(scope, what)                                                   \
   do { LogError(std::string(what) + ": " + (scope).error()); return; } while (0)
+// a failed C ABI call made outside an OpScope (nothing enqueued)
+#define OP_FAIL_MSG(what)                                                      \
+  do { LogError(std::string(what) + ": " + euler_gpu_last_error()); return; } while (0)
 
 // API_SAMPLE_NB (core/kernels/sample_neighbor_op.cc:37-147, no-condition
 // path): inputs node_ids (uint64), edge_types (int32), count (int32[1]),
@@ -639,6 +656,130 @@ class GpuSampleEdgeOp : public OpKernel {
   }
 };
 REGISTER_OP_KERNEL("API_SAMPLE_EDGE", GpuSampleEdgeOp);
+
+// API_SAMPLE_GRAPH_LABEL (core/kernels/sample_graph_label_op.cc:32-66): input count (int32[1]);
+// output "<name>:0" int8, the drawn labels joined by ",".  The draws are label ids on the device
+// (euler_gpu_sample_graph_label, RNG domain 7); the strings come from the label table.  A graph
+// without labels (EEMPTY; the reference aborts) logs and produces no output.
+class GpuSampleGraphLabelOp : public OpKernel {
+ public:
+  explicit GpuSampleGraphLabelOp(const std::string& name) : OpKernel(name) {}
+  void Compute(const NodeDef& nd, OpKernelContext* ctx) override {
+    std::vector<int32_t> cnt;
+    if (nd.inputs.size() != 1 || !GetIntArg(nd, 0, ctx, &cnt) || cnt.empty() || cnt[0] < 0) {
+      LogError("API_SAMPLE_GRAPH_LABEL: bad count input");
+      return;
+    }
+    euler_gpu_graph* g = ctx->graph();
+    if (!g) { LogError("API_SAMPLE_GRAPH_LABEL: no graph initialised"); return; }
+    const int32_t count = cnt[0];
+    const int64_t L = euler_gpu_graph_num_graph_labels(g);
+    if (L <= 0) {
+      LogError("API_SAMPLE_GRAPH_LABEL: graph label set is empty (" +
+               std::string(L < 0 ? euler_gpu_last_error() : "no labels") + ")");
+      return;
+    }
+    std::vector<int64_t> off((size_t)L + 1);
+    if (euler_gpu_graph_export_graph_labels(g, off.data(), nullptr) != 0) OP_FAIL_MSG("API_SAMPLE_GRAPH_LABEL");
+    std::vector<uint8_t> bytes((size_t)off[L] + 1);
+    if (euler_gpu_graph_export_graph_labels(g, off.data(), bytes.data()) != 0) OP_FAIL_MSG("API_SAMPLE_GRAPH_LABEL");
+    std::vector<int64_t> ids((size_t)count);
+    {
+      OpScope sc(g);
+      int64_t* d_out = sc.Alloc<int64_t>((size_t)(count > 0 ? count : 1));
+      if (!sc.ok()) OP_FAIL(sc, "API_SAMPLE_GRAPH_LABEL");
+      if (!sc.Call(euler_gpu_sample_graph_label(g, sc.stream(), ctx->seed(), ctx->NextCallId(), count,
+                                                d_out))) {
+        sc.Drain();
+        OP_FAIL(sc, "API_SAMPLE_GRAPH_LABEL");
+      }
+      if (!sc.Download(ids.data(), d_out, (size_t)count * 8) || !sc.Sync()) {
+        sc.Drain();
+        OP_FAIL(sc, "API_SAMPLE_GRAPH_LABEL");
+      }
+    }
+    std::string joined;
+    for (int32_t i = 0; i < count; ++i) {
+      if (i) joined.push_back(',');
+      const int64_t r = ids[i];
+      joined.append(reinterpret_cast<const char*>(bytes.data()) + off[r], (size_t)(off[r + 1] - off[r]));
+    }
+    Tensor* out = nullptr;
+    if (ctx->Allocate(OutputName(nd, 0), {joined.size()}, kInt8, &out) != 0) {
+      LogError("Allocate output tensor failed!");
+      return;
+    }
+    std::copy(joined.begin(), joined.end(), out->Raw<char>());
+  }
+};
+REGISTER_OP_KERNEL("API_SAMPLE_GRAPH_LABEL", GpuSampleGraphLabelOp);
+
+// API_GET_GRAPH_BY_LABEL (core/kernels/get_graph_by_label_op.cc:32-75): input a kString tensor of
+// labels; outputs "<name>:0" int32 [B, 2] (start, end) and "<name>:1" uint64 node ids.  An unknown
+// label is an empty range.  Any failure drains the stream and leaves no output.
+class GpuGetGraphByLabelOp : public OpKernel {
+ public:
+  explicit GpuGetGraphByLabelOp(const std::string& name) : OpKernel(name) {}
+  void Compute(const NodeDef& nd, OpKernelContext* ctx) override {
+    Tensor* labels_t = nullptr;
+    if (nd.inputs.size() != 1 || ctx->tensor(nd.inputs[0], &labels_t) != 0 ||
+        labels_t->Type() != kString) {
+      LogError("API_GET_GRAPH_BY_LABEL: graph label input error");
+      return;
+    }
+    euler_gpu_graph* g = ctx->graph();
+    if (!g) { LogError("API_GET_GRAPH_BY_LABEL: no graph initialised"); return; }
+    const int64_t B = labels_t->NumElements();
+    std::vector<int64_t> off((size_t)B + 1, 0);
+    std::string bytes;
+    for (int64_t i = 0; i < B; ++i) {
+      bytes += *(labels_t->Raw<std::string*>()[i]);
+      off[i + 1] = (int64_t)bytes.size();
+    }
+    std::vector<int64_t> ids((size_t)B);
+    if (euler_gpu_graph_label_ids(g, B, off.data(), reinterpret_cast<const uint8_t*>(bytes.data()),
+                                  ids.data()) != 0)
+      OP_FAIL_MSG("API_GET_GRAPH_BY_LABEL");
+    std::vector<int32_t> idx((size_t)B * 2);
+    std::vector<uint64_t> vals;
+    if (B > 0) {
+      OpScope sc(g);
+      int64_t* d_ids = sc.Alloc<int64_t>((size_t)B);
+      int32_t* d_idx = sc.Alloc<int32_t>((size_t)B * 2);
+      int64_t total = 0;
+      if (!sc.Upload(d_ids, ids.data(), (size_t)B * 8) ||
+          !sc.Call(euler_gpu_get_graph_by_label(g, sc.stream(), d_ids, B, d_idx, &total, nullptr))) {
+        sc.Drain();
+        OP_FAIL(sc, "API_GET_GRAPH_BY_LABEL");
+      }
+      uint64_t* d_v = sc.Alloc<uint64_t>((size_t)(total > 0 ? total : 1));
+      if (!sc.ok() || (total > 0 && !sc.Call(euler_gpu_get_graph_by_label(g, sc.stream(), d_ids, B, d_idx,
+                                                                         &total, d_v)))) {
+        sc.Drain();
+        OP_FAIL(sc, "API_GET_GRAPH_BY_LABEL");
+      }
+      vals.resize((size_t)total);
+      if (!sc.Download(idx.data(), d_idx, (size_t)B * 8) ||
+          (total > 0 && !sc.Download(vals.data(), d_v, (size_t)total * 8)) || !sc.Sync()) {
+        sc.Drain();
+        OP_FAIL(sc, "API_GET_GRAPH_BY_LABEL");
+      }
+    }
+    Tensor *o_idx = nullptr, *o_data = nullptr;
+    if (ctx->Allocate(OutputName(nd, 0), {(size_t)B, 2}, kInt32, &o_idx) != 0) {
+      LogError("Allocate output tensor failed!");
+      return;
+    }
+    if (ctx->Allocate(OutputName(nd, 1), {vals.size()}, kUInt64, &o_data) != 0) {
+      ctx->Deallocate(OutputName(nd, 0));
+      LogError("Allocate output tensor failed!");
+      return;
+    }
+    std::copy(idx.begin(), idx.end(), o_idx->Raw<int32_t>());
+    std::copy(vals.begin(), vals.end(), o_data->Raw<uint64_t>());
+  }
+};
+REGISTER_OP_KERNEL("API_GET_GRAPH_BY_LABEL", GpuGetGraphByLabelOp);
 
 // ID_UNIQUE (core/kernels/id_unique_op.cc:35-64), node-id branch.
 class GpuIdUniqueOp : public OpKernel {

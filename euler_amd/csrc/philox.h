@@ -35,7 +35,8 @@ enum RngDomain : uint32_t {
   kDomainLayer = 5,     // API_SAMPLE_L: stream = POSITION in the root list (the
                         // same node drawn twice samples twice), draws of one
                         // Node::SampleNeighbor(count = 1)
-  kDomainLocalLayer = 6 // API_LOCAL_SAMPLE_L: stream = batch row, draw j = sample j
+  kDomainLocalLayer = 6, // API_LOCAL_SAMPLE_L: stream = batch row, draw j = sample j
+  kDomainGraphLabel = 7  // API_SAMPLE_GRAPH_LABEL: stream = 0, draw j = sample j
 };
 
 EG_HD uint32_t DomainSalt(uint32_t domain) {
@@ -45,7 +46,8 @@ EG_HD uint32_t DomainSalt(uint32_t domain) {
        : domain == 3 ? 0xF39CC060u
        : domain == 4 ? 0x6A09E667u
        : domain == 5 ? 0xB5C0FBCFu
-                     : 0x3C6EF372u;
+       : domain == 6 ? 0x3C6EF372u
+                     : 0xA54FF53Au;
 }
 
 struct Philox4 {

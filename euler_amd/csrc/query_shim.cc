@@ -114,6 +114,14 @@ euler_gpu_graph* g_proxy_graph = nullptr;
 
 Query::Query(const std::string& gremlin)
     : ctx_(std::make_shared<OpKernelContext>()), gremlin_(gremlin) {}
+
+Query::Query(const std::string& op_name, const std::string& alias, int32_t output_num,
+             const std::vector<std::string>& input_tensor_names,
+             const std::vector<std::string>& norm_attr_names)
+    : ctx_(std::make_shared<OpKernelContext>()), gremlin_(op_name), single_op_(true),
+      op_name_(op_name), alias_(alias), output_num_(output_num), op_inputs_(input_tensor_names) {
+  op_inputs_.insert(op_inputs_.end(), norm_attr_names.begin(), norm_attr_names.end());
+}
 Query::~Query() {}
 
 Tensor* Query::AllocInput(const std::string& name, const TensorShape& shape,
@@ -163,6 +171,20 @@ bool QueryProxy::Execute(Query* query) {
   {
     std::lock_guard<std::mutex> lk(g_proxy_mu);
     if (g_proxy_graph != nullptr) ctx->SetGraph(g_proxy_graph);
+  }
+  // Query(op_name, alias, output_num, inputs, attrs): the op node of Compiler::Op2DAGDef, its
+  // outputs named by the alias (the AS node), nothing else
+  if (query->single_op_) {
+    NodeDef nd{query->alias_, query->op_name_, query->op_inputs_, {}};
+    if (!RunOp(nd, ctx)) return false;
+    for (int32_t i = 1; i < query->output_num_; ++i) {
+      Tensor* t = nullptr;
+      if (ctx->tensor(OutputName(nd, i), &t) != 0) {
+        LogError(query->op_name_ + ": output " + OutputName(nd, i) + " missing");
+        return false;
+      }
+    }
+    return true;
   }
   std::vector<Step> steps;
   if (!Tokenise(query->gremlin_, &steps)) {
@@ -253,6 +275,11 @@ void QueryProxy::RunAsyncGremlin(Query* query, DoneCallback callback) {
 }  // namespace gpu_abi
 }  // namespace euler
 
+namespace {
+int64_t RunAndCopy(euler::QueryProxy* proxy, euler::Query* query, const char* result_name,
+                   void* out, int64_t capacity);
+}  // namespace
+
 extern "C" {
 
 void euler_query_set_seed(uint64_t seed) { euler::QueryProxy::SetSeed(seed); }
@@ -273,6 +300,40 @@ int64_t euler_query_run(const char* gremlin, int32_t n_inputs, const char* const
     if (t == nullptr) { delete query; return -1; }
     memcpy(t->Raw<char>(), data[i], t->TotalBytes());
   }
+  return RunAndCopy(proxy, query, result_name, out, capacity);
+}
+
+int64_t euler_query_run_op(const char* op_name, const char* alias, int32_t output_num,
+                           int32_t n_inputs, int32_t n_attrs, const char* const* names,
+                           const int32_t* dtypes, const int64_t* counts, const void* const* data,
+                           const char* result_name, void* out, int64_t capacity) {
+  using namespace euler;
+  QueryProxy* proxy = QueryProxy::GetInstance();
+  if (proxy == nullptr || n_inputs < 0 || n_attrs < 0) return -1;
+  std::vector<std::string> in(names, names + n_inputs), attrs(names + n_inputs, names + n_inputs + n_attrs);
+  Query* query = new Query(op_name, alias, output_num, in, attrs);
+  for (int32_t i = 0; i < n_inputs + n_attrs; ++i) {
+    Tensor* t = counts[i] < 0
+        ? query->AllocInput(names[i], {}, (DataType)dtypes[i])
+        : query->AllocInput(names[i], {(size_t)counts[i]}, (DataType)dtypes[i]);
+    if (t == nullptr) { delete query; return -1; }
+    if (dtypes[i] == kString) {
+      const char* const* strs = static_cast<const char* const*>(data[i]);
+      for (int j = 0; j < t->NumElements(); ++j) *(t->Raw<std::string*>()[j]) = strs[j];
+    } else {
+      memcpy(t->Raw<char>(), data[i], t->TotalBytes());
+    }
+  }
+  return RunAndCopy(proxy, query, result_name, out, capacity);
+}
+
+}  // extern "C"
+
+namespace {
+
+int64_t RunAndCopy(euler::QueryProxy* proxy, euler::Query* query, const char* result_name,
+                   void* out, int64_t capacity) {
+  using namespace euler;
   std::mutex mu;
   std::condition_variable cv;
   bool done = false;
@@ -296,4 +357,4 @@ int64_t euler_query_run(const char* gremlin, int32_t n_inputs, const char* const
   return rc;
 }
 
-}  // extern "C"
+}  // namespace

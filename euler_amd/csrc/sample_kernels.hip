@@ -20,6 +20,7 @@ namespace euler_gpu { extern thread_local int g_walk_collapse, g_walk_grid, g_wa
 namespace euler_gpu { extern std::atomic<int> g_sharded_self_exchange, g_sharded_walk_enqueued, g_sharded_walk_tail, g_sharded_walk_split; }   // sharded.cc (process-wide)
 namespace euler_gpu { extern std::atomic<int> g_flow_fused; extern std::atomic<int> g_flow_rowpos; }              // dataflow_kernels.hip (key 60)
 namespace euler_gpu { extern std::atomic<int> g_blk_fail_next; }           // graph_build.hip (test hook)
+namespace euler_gpu { extern thread_local int g_label_hash_bits; }     // graph_label_kernels.hip (key 74)
 namespace euler_gpu { extern thread_local int g_root_host_batch, g_adj_scan, g_adj_long_row, g_sum_scalar; }   // layer_kernels.hip
 
 namespace euler_gpu {
@@ -1818,6 +1819,7 @@ int euler_gpu_set_debug_buffer(void* dev) {
 }
 
 int euler_gpu_set_tuning(int32_t key, int32_t value) {
+  if (key == 74 && value >= 1 && value <= 64) { g_label_hash_bits = value; return EULER_GPU_OK; }
   if (key == 0 && (value == 0 || value == 5 || value == 6)) { g_k1_variant = value; return EULER_GPU_OK; }
   if (key == 3) { g_k1_grid_cap = value; return EULER_GPU_OK; }
   if (key == 9) { g_k1_fuse_mark = value != 0; return EULER_GPU_OK; }

@@ -418,3 +418,34 @@ class WholeDataFlow(NeighborDataFlow):
         for _ in range(self.num_hops):
             data_flow.append(n_id, inv, None, edge_index)
         return data_flow
+
+
+class WholeGraphDataFlow(object):
+    """WholeDataFlow with the intended reading of its adjacency (DESIGN Q16): every hop is the same
+    block - every listed-type edge between two nodes of the batch (Graph.whole_graph_block: (j, c)
+    with n_id[c] an out-neighbour of n_id[j]), then the self loops - built in O(N + listed edges).
+    WholeDataFlow above keeps the reference's literal reading (every source batch row 0).  The
+    metapath must list one neighbour type throughout, as whole_dataflow.py requires."""
+
+    def __init__(self, graph, metapath, add_self_loops=True):
+        self.graph = graph
+        self.num_hops = len(metapath)
+        self.add_self_loops = add_self_loops
+        self.neighbor_type = metapath[0]
+        for n_type in metapath:
+            if not n_type == self.neighbor_type:
+                raise ValueError('Metapath should be the same in whole graph sampler.')
+
+    def __call__(self, n_id):
+        return self.produce_subgraph(n_id)
+
+    def produce_subgraph(self, n_id):
+        n_id = torch.as_tensor(n_id).reshape(-1)
+        if n_id.device != self.graph.device:
+            n_id = n_id.to(self.graph.device)
+        edge_index = self.graph.whole_graph_block(n_id, self.neighbor_type, self.add_self_loops)
+        res_n_id = torch.arange(n_id.numel(), dtype=torch.int64, device=n_id.device)
+        data_flow = DataFlow(n_id)
+        for _ in range(self.num_hops):
+            data_flow.append(n_id, res_n_id, None, edge_index)
+        return data_flow

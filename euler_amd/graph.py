@@ -193,6 +193,30 @@ def dat_feature_info(data_path, name, edge=False):
     return int(t.value), int(slot.value), int(dim.value)
 
 
+def _label_triple(idx, ids):
+    """SparseTensorBuilder's triple of a get_graph_by_label result
+    (tf_euler/kernels/get_graph_by_label_op.cc): a label with no nodes emits (i, 0) = 0."""
+    dev = ids.device
+    b = idx.shape[0]
+    if b == 0:
+        return (torch.zeros((0, 2), dtype=torch.int64, device=dev),
+                torch.zeros(0, dtype=torch.int64, device=dev), [0, 0])
+    lens = (idx[:, 1] - idx[:, 0]).to(torch.int64)
+    slots = torch.clamp(lens, min=1)
+    nnz = int(slots.sum().item())
+    row = torch.repeat_interleave(torch.arange(b, device=dev), slots, output_size=nnz)
+    first = torch.cumsum(slots, 0) - slots
+    col = torch.arange(nnz, device=dev) - first[row]
+    # values: the nodes where a label has them, 0 at the fill entry
+    src = idx[:, 0].to(torch.int64)[row] + col
+    has = lens[row] > 0
+    vals = torch.zeros(nnz, dtype=torch.int64, device=dev)
+    if ids.numel():
+        vals[has] = ids[src[has]]
+    width = max(int(lens.max().item()), 1)
+    return torch.stack([row, col], 1), vals, [b, width]
+
+
 class Graph:
     """Immutable graph in HBM (CSR + row metadata + alias tables)."""
 
@@ -1060,6 +1084,147 @@ class Graph:
         if key not in cache:
             cache[key] = dat_feature_info(self.data_path, name, edge)
         return cache[key]
+
+    # ------------------------------------------------------------ graph labels
+    @staticmethod
+    def _label_bytes(labels):
+        """(offsets int64 [n + 1], bytes uint8) of a list of str / bytes labels."""
+        enc = [x.encode() if isinstance(x, str) else bytes(x) for x in labels]
+        off = np.zeros(len(enc) + 1, np.int64)
+        off[1:] = np.cumsum([len(x) for x in enc], dtype=np.int64)
+        data = np.frombuffer(b"".join(enc) or b"\0", np.uint8).copy()
+        return off, data
+
+    def set_graph_labels(self, ids, labels):
+        """Graph labels by node id (a str / bytes each; "" = no label) for a graph not read from
+        .dat; replaces the index.  An id without a row or listed twice raises, and the old index
+        stays."""
+        ids = _np(np.asarray(ids).reshape(-1), np.uint64)
+        if len(labels) != ids.size:
+            raise ValueError("set_graph_labels: one label per id")
+        off, data = self._label_bytes(labels)
+        with self._on_device():
+            check(lib().euler_gpu_graph_set_graph_labels(
+                self._h, ids.ctypes.data_as(_lib.u64p), ids.size, off.ctypes.data_as(_lib.i64p),
+                data.ctypes.data_as(_lib.u8p)))
+
+    @property
+    def num_graph_labels(self):
+        """Number of distinct graph labels (0 when the graph has none)."""
+        with self._on_device():
+            n = int(lib().euler_gpu_graph_num_graph_labels(self._h))
+        if n < 0:
+            check(n)
+        return n
+
+    def graph_labels(self):
+        """The label table in table order (by each label's smallest node id, DESIGN Q14)."""
+        n = self.num_graph_labels
+        if n == 0:
+            return []
+        off = np.zeros(n + 1, np.int64)
+        check(lib().euler_gpu_graph_export_graph_labels(self._h, off.ctypes.data_as(_lib.i64p), None))
+        data = np.zeros(max(int(off[-1]), 1), np.uint8)
+        check(lib().euler_gpu_graph_export_graph_labels(self._h, off.ctypes.data_as(_lib.i64p),
+                                                        data.ctypes.data_as(_lib.u8p)))
+        b = data.tobytes()
+        return [b[off[i]:off[i + 1]].decode("utf-8", "surrogateescape") for i in range(n)]
+
+    def graph_label_ids(self, labels):
+        """Table ids of labels (str / bytes) as int64 numpy, -1 for an unknown label."""
+        off, data = self._label_bytes(labels)
+        out = np.zeros(len(labels), np.int64)
+        with self._on_device():
+            check(lib().euler_gpu_graph_label_ids(
+                self._h, len(labels), off.ctypes.data_as(_lib.i64p), data.ctypes.data_as(_lib.u8p),
+                out.ctypes.data_as(_lib.i64p)))
+        return out
+
+    def label_index_info(self):
+        """(labelled nodes, device bytes of the label index)."""
+        n, b = C.c_int64(0), C.c_int64(0)
+        with self._on_device():
+            check(lib().euler_gpu_graph_label_index_info(self._h, C.byref(n), C.byref(b)))
+        return int(n.value), int(b.value)
+
+    def sample_graph_label(self, count, call_id=None):
+        """tf_euler sample_graph_label as table ids: [count] int64 on the device, uniform with
+        replacement (RNG domain 7)."""
+        out = torch.empty(int(count), dtype=torch.int64, device=self.device)
+        with self._on_device():
+            check(lib().euler_gpu_sample_graph_label(
+                self._h, _stream(), self.seed, self._take_call_ids(1, call_id), int(count),
+                _ptr(out)))
+        return out
+
+    def _label_id_tensor(self, labels):
+        if torch.is_tensor(labels):
+            return _as_i64_cuda(labels, self.device).reshape(-1)
+        labels = list(labels)
+        if all(isinstance(x, (str, bytes)) for x in labels):
+            return torch.as_tensor(self.graph_label_ids(labels)).to(self.device)
+        return _as_i64_cuda(np.asarray(labels, np.int64), self.device).reshape(-1)
+
+    def get_graph_by_label_core(self, labels):
+        """(idx [B, 2] int32 (start, end), node ids int64) of API_GET_GRAPH_BY_LABEL."""
+        ids = self._label_id_tensor(labels)
+        n = ids.numel()
+        idx = torch.empty((n, 2), dtype=torch.int32, device=self.device)
+        total = C.c_int64(0)
+        with self._on_device():
+            check(lib().euler_gpu_get_graph_by_label(self._h, _stream(), _ptr(ids), n, _ptr(idx),
+                                                     C.byref(total), None))
+            out = torch.empty(int(total.value), dtype=torch.int64, device=self.device)
+            if total.value:
+                check(lib().euler_gpu_get_graph_by_label(self._h, _stream(), _ptr(ids), n, _ptr(idx),
+                                                         C.byref(total), _ptr(out)))
+        return idx, out
+
+    def get_graph_by_label(self, labels):
+        """tf_euler get_graph_by_label (tf_euler/kernels/get_graph_by_label_op.cc): the
+        SparseTensor triple (indices [nnz, 2] (i, j), values int64, dense_shape) of labels (str /
+        bytes, or table ids).  A label with no nodes gives the single entry (i, 0) = 0; dense_shape
+        is [B, max(len, 1)], [0, 0] for B = 0."""
+        idx, ids = self.get_graph_by_label_core(labels)
+        return _label_triple(idx, ids)
+
+    def whole_graph_block(self, n_id, edge_types, add_self_loops=True):
+        """edge_index [2, E (+ N)] int64 of WholeDataFlow (whole_dataflow.py:37-63, DESIGN Q16):
+        (j, c) for every listed-type edge n_id[j] -> n_id[c], sorted by j then c, then the self
+        loops (i, i).  One library call when the capacity suffices, a second with room when not."""
+        n_id = _as_i64_cuda(n_id, self.device).reshape(-1)
+        n = n_id.numel()
+        et, et_p, k = _i32_array(edge_types)
+        cap = self.__dict__.get("_block_cap", 0)
+        cap = max(cap, 8 * n + 64)
+        total = C.c_int64(0)
+        with self._on_device():
+            for _ in range(2):
+                out = torch.empty((2, cap), dtype=torch.int64, device=self.device)
+                check(lib().euler_gpu_whole_graph_block(
+                    self._h, _stream(), _ptr(n_id), n, et_p, k, 1 if add_self_loops else 0, cap,
+                    C.byref(total), _ptr(out)))
+                if total.value <= cap:
+                    break
+                cap = int(total.value)
+            self._block_cap = max(self.__dict__.get("_block_cap", 0), int(total.value))
+        return out[:, :int(total.value)]
+
+    def graph_batch(self, count_or_labels, edge_types, add_self_loops=True, call_id=None):
+        """One minibatch of whole-graph classification (graph_estimator.get_train_from_input +
+        the whole-graph block): (label ids int64, n_id int64, node_graph_idx int64,
+        edge_index [2, E (+ N)] int64).  n_id and node_graph_idx are the get_graph_by_label
+        triple's values and indices[:, 0], as the reference reads them: a label without nodes
+        contributes its fill entry (node 0, its own row).  An int draws that many labels
+        (sample_graph_label); otherwise the labels (str / bytes or table ids) are used as given."""
+        if isinstance(count_or_labels, (int, np.integer)):
+            label_ids = self.sample_graph_label(int(count_or_labels), call_id)
+        else:
+            label_ids = self._label_id_tensor(count_or_labels)
+        ind, n_id, _shape = self.get_graph_by_label(label_ids)
+        node_graph_idx = ind[:, 0]
+        edge_index = self.whole_graph_block(n_id, edge_types, add_self_loops)
+        return label_ids, n_id, node_graph_idx, edge_index
 
     _ORDER = {None: 0, "": 0, "id": 1, "weight": 2}
 

@@ -1115,6 +1115,55 @@ int euler_gpu_get_binary_feature(const euler_gpu_graph* g, void* stream, const u
                                  int64_t n, int32_t fid, int64_t* offsets_dev, int64_t* total_host,
                                  uint8_t* bytes_dev);
 
+/* ---- graph labels --------------------------------------------
+ * Graph::GetGraphLabel's index (core/graph/graph.cc:439-457): label -> the nodes that carry it.
+ * A loaded dataset's labels are the node binary feature binary_graph_label (euler.meta); the
+ * index is built on the device on the first label call.  Table order: by the smallest node id
+ * of a label; nodes of a label: ascending ids (Q14).  An empty value is no label (Q15).  A graph
+ * without labels answers EULER_GPU_EEMPTY; a sharded graph (shards > 1) EULER_GPU_EINVAL.
+ *
+ * Labels by node id for a graph not read from .dat (replaces the binary_graph_label feature the
+ * reference's converter writes, tf_euler/python/dataset/multigraph_util.py:68-90): label i is
+ * bytes_host[offsets_host[i] .. offsets_host[i + 1]).  An id without a row, or an id listed
+ * twice, is EULER_GPU_EINVAL and the old index stays intact. */
+int euler_gpu_graph_set_graph_labels(euler_gpu_graph* g, const uint64_t* ids_host, int64_t n,
+                                     const int64_t* offsets_host, const uint8_t* bytes_host);
+/* The number of labels (0 when the graph has none, < 0 an error code). */
+int64_t euler_gpu_graph_num_graph_labels(const euler_gpu_graph* g);
+/* The label table in table order: offsets_host [labels + 1]; bytes_host [offsets_host[labels]]
+ * (NULL: offsets only - the usual two calls). */
+int euler_gpu_graph_export_graph_labels(const euler_gpu_graph* g, int64_t* offsets_host,
+                                        uint8_t* bytes_host);
+/* Label strings -> table ids (-1 for an unknown label), on the host. */
+int euler_gpu_graph_label_ids(const euler_gpu_graph* g, int64_t n, const int64_t* offsets_host,
+                              const uint8_t* bytes_host, int64_t* out_host);
+/* The index's size: labelled nodes and the device bytes it holds. */
+int euler_gpu_graph_label_index_info(const euler_gpu_graph* g, int64_t* n_labelled_host,
+                                     int64_t* index_bytes_host);
+/* API_SAMPLE_GRAPH_LABEL (core/kernels/sample_graph_label_op.cc:32-66): `count` label ids drawn
+ * uniformly with replacement, RNG domain 7, stream 0: draw j is sample j, label =
+ * min(floor(u * L), L - 1).  out_dev [count] int64. */
+int euler_gpu_sample_graph_label(const euler_gpu_graph* g, void* stream, uint64_t seed,
+                                 uint32_t call_id, int32_t count, int64_t* out_dev);
+/* API_GET_GRAPH_BY_LABEL (core/kernels/get_graph_by_label_op.cc:32-75) on label ids: two calls
+ * like euler_gpu_get_full_neighbor - out_dev NULL fills idx_dev [n, 2] int32 (start, end) and
+ * *total_host (synchronises the stream); the second call writes the node ids.  A negative or
+ * unknown id gives an empty range. */
+int euler_gpu_get_graph_by_label(const euler_gpu_graph* g, void* stream, const int64_t* label_ids_dev,
+                                 int64_t n, int32_t* idx_dev, int64_t* total_host, uint64_t* out_dev);
+/* The whole-graph block of WholeDataFlow (tf_euler/python/dataflow/whole_dataflow.py:37-63): for
+ * nodes_dev [n] (any order, duplicates and unknown ids allowed), every (j, c) such that nodes[c]
+ * is an out-neighbour of nodes[j] by one of the k listed edge types, sorted by j then c; then the
+ * self loops (i, i) when add_self_loops.  out_dev is int64 [2, cap]: sources in row 0, targets in
+ * row 1.  *total_host = edges + loops; when that exceeds cap nothing is written and the caller
+ * asks again with room (one call when the capacity suffices).  A neighbour listed twice (two
+ * edge types, a repeated edge) gives one pair.  Costs O(n + listed edges); reads three sizes on
+ * the host per call (listed edges, hits, block edges).  Synchronises the stream. */
+int euler_gpu_whole_graph_block(const euler_gpu_graph* g, void* stream, const uint64_t* nodes_dev,
+                                int64_t n, const int32_t* edge_types_host, int32_t k,
+                                int32_t add_self_loops, int64_t cap, int64_t* total_host,
+                                int64_t* out_dev);
+
 /* Tuning keys, phase timers and byte counters (A/B measurements, bench.py's roofline leg) are
  * not part of the product surface: include/euler_gpu_measure.h. */
 

@@ -153,6 +153,8 @@ extern "C" {
  *        long rows are done), 0 = two launches.  key 73: PROCESS-WIDE: 1 (default) = the node2vec
  *        walk of more than 16 384 walkers (one launch, a wave per walker) hands the walkers out by
  *        ticket, 0 = every 16 384th walker to a wave (100 000 x 10 on the metric graph: 17.2 / 19.1 ms).
+ * key 74: hash bits of the graph-label index (1 .. 64, default 64): fewer bits make different
+ *        labels share a hash, which the build must still tell apart (tests force collisions).
  * All settings produce identical results; the knobs exist for A/B measurements
  * and tests.  They are THREAD-LOCAL: a call changes the launches the calling host
  * thread enqueues afterwards and nobody else's (new threads start from the

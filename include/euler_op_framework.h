@@ -9,7 +9,7 @@
 // (API_SAMPLE_NB, API_SAMPLE_NODE, ID_UNIQUE, IDX_GATHER, DATA_GATHER,
 // API_GET_NB_NODE and the layerwise chain API_GET_EDGE_SUM_WEIGHT,
 // API_SAMPLE_ROOT, API_SAMPLE_L, API_SPARSE_GEN_ADJ, API_SPARSE_GET_ADJ,
-// API_GATHER_RESULT), so a build of the reference that links this
+// API_GATHER_RESULT, and API_SAMPLE_EDGE, API_SAMPLE_GRAPH_LABEL, API_GET_GRAPH_BY_LABEL), so a build of the reference that links this
 // library INSTEAD of the corresponding core/kernels/*.cc files dispatches the
 // same DAG nodes to the MI355X.  Tensors are host buffers (malloc, uninitialised
 // like the reference's, op_kernel.cc:92-105); device memory stays behind the

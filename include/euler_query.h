@@ -49,6 +49,14 @@ inline namespace gpu_abi {
 class Query {
  public:
   explicit Query(const std::string& gremlin);
+  // The single-op form (euler/client/query.h:36-41): ONE plugin op, its inputs named by
+  // input_tensor_names then norm_attr_names (the node_def Compiler::Op2DAGDef builds,
+  // euler/parser/compiler.h:69-110), outputs "<alias>:0" .. "<alias>:<output_num - 1>".  What
+  // tf_euler/kernels/sample_graph_label_op.cc:47, get_graph_by_label_op.cc:43 and
+  // sparse_get_adj_op.cc:58 construct.
+  Query(const std::string& op_name, const std::string& alias, int32_t output_num,
+        const std::vector<std::string>& input_tensor_names,
+        const std::vector<std::string>& norm_attr_names);
   ~Query();
   Query(const Query&) = delete;
   Query& operator=(const Query&) = delete;
@@ -61,12 +69,16 @@ class Query {
   std::unordered_map<std::string, Tensor*> GetResult(
       const std::vector<std::string>& result_names);
   Tensor* GetResult(const std::string& result_name);
-  bool SingleOpQuery() { return false; }
+  bool SingleOpQuery() { return single_op_; }
   const std::string& gremlin() const { return gremlin_; }
 
  private:
   std::shared_ptr<OpKernelContext> ctx_;
   std::string gremlin_;
+  bool single_op_ = false;
+  std::string op_name_, alias_;
+  int32_t output_num_ = 0;
+  std::vector<std::string> op_inputs_;      // input_tensor_names, then norm_attr_names
   friend class QueryProxy;
 };
 
@@ -114,6 +126,15 @@ int64_t euler_query_run(const char* gremlin, int32_t n_inputs, const char* const
                         const int32_t* dtypes, const int64_t* counts,
                         const void* const* data, const char* result_name, void* out,
                         int64_t capacity);
+/* The same through the single-op Query constructor: op_name, alias, output_num, the first
+ * n_inputs names as input_tensor_names and the next n_attrs as norm_attr_names; one dtype / count
+ * / data per name.  A kString (11) tensor's data is an array of `count` NUL-terminated strings,
+ * written into the tensor's std::string elements as tf_euler/kernels/get_graph_by_label_op.cc:46-50
+ * does. */
+int64_t euler_query_run_op(const char* op_name, const char* alias, int32_t output_num,
+                           int32_t n_inputs, int32_t n_attrs, const char* const* names,
+                           const int32_t* dtypes, const int64_t* counts, const void* const* data,
+                           const char* result_name, void* out, int64_t capacity);
 void euler_query_set_seed(uint64_t seed);
 /* QueryProxy::Init(graph): the proxy serves this (borrowed) graph instead of the
  * process default; NULL returns to the default graph. */
