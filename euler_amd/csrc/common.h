@@ -243,7 +243,7 @@ struct euler_gpu_graph {
   int64_t bytes = 0;
   uint64_t max_id = 0;          // largest node id of this graph (shard)
   int32_t partitions = 0;       // euler.meta's partitions_num for a loaded dataset, else 0
-  std::vector<void*> allocations;     // every hipMalloc owned by the graph
+  std::vector<std::pair<void*, int64_t>> allocations;   // every hipMalloc owned by the graph: (pointer, bytes)
   std::vector<float> node_weight_sums;
   const int32_t* node_type_dev = nullptr;   // [n_rows] node types; nullptr = all 0
   // sparse (uint64) features in the layout of the float ones: values of row r at
@@ -337,6 +337,8 @@ int BuildAliasTables(const std::vector<uint64_t>& ids, const std::vector<int32_t
 void DestroyEdgeStore(euler_gpu_graph* g);          // edge_kernels.hip
 int EnsureNodeBinary(const euler_gpu_graph* g);     // edge_kernels.hip: node binary table, on first use
 void DestroyLabelIndex(euler_gpu_graph* g);         // graph_label_kernels.hip
+// mp_kernels.hip: out[i] = in[0] + ... + in[i - 1] on `stream` (its scratch is stream-ordered)
+int ExclusiveScanI64(hipStream_t stream, const int64_t* in, int64_t* out, int64_t n);
 // weight-bucket index, on first use; leaves view.wb == nullptr (and returns OK) for graphs it
 // does not serve
 int EnsureWbIndex(const euler_gpu_graph* g);

@@ -19,12 +19,10 @@
 #include <numeric>
 #include <vector>
 
+#include "device_mem.h"
 #include "node_sampler.h"
 
 namespace euler_gpu {
-
-int ExclusiveScanI64(hipStream_t stream, const int64_t* in, int64_t* out,
-                     int64_t n);   // mp_kernels.hip
 
 namespace {
 
@@ -315,59 +313,13 @@ __global__ void GatherRecordsKernel(const EdgeStoreView s, int64_t first, int64_
 }
 
 // ---- host side
-// Allocations of one store build: returned on failure, handed to the graph on success.
-struct StoreAllocs {
-  std::vector<std::pair<void*, int64_t>> list;
-  int rc = EULER_GPU_OK;
-  template <typename T>
-  T* Alloc(size_t count) {
-    void* p = nullptr;
-    const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
-    const hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-      rc = Fail(EULER_GPU_ENOMEM, std::string("edge store: hipMalloc(") + std::to_string(bytes) +
-                                      "): " + hipGetErrorString(e));
-      return nullptr;
-    }
-    list.emplace_back(p, (int64_t)bytes);
-    return (T*)p;
-  }
-  template <typename T>
-  T* Upload(const T* host, size_t count) {
-    T* d = Alloc<T>(count);
-    if (d && count > 0) {
-      const hipError_t e = hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        rc = Fail(EULER_GPU_EHIP, std::string("edge store: hipMemcpy H2D: ") + hipGetErrorString(e));
-        return nullptr;
-      }
-    }
-    return d;
-  }
-  void Release() {
-    for (auto& p : list) (void)hipFree(p.first);
-    list.clear();
-  }
-};
-
-// Temporary device buffer of a build (not part of the store).
-struct Scratch {
-  void* p = nullptr;
-  ~Scratch() { if (p) (void)hipFree(p); }
-};
-
-int CheckLaunch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return Fail(EULER_GPU_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  const hipError_t s = hipDeviceSynchronize();
-  if (s != hipSuccess) return Fail(EULER_GPU_EHIP, std::string(what) + ": " + hipGetErrorString(s));
-  return EULER_GPU_OK;
-}
+// (the allocations of one store build are an AllocList: returned on failure, handed to the graph
+// on success; temporaries of a build, not part of the store, are DevBufs)
 
 // A host feature table -> device.  uniform: every record has record 0's slot ends and its
 // values start at r * (record 0's length): one row of ends, no offsets.
 template <typename V>
-FeatTable UploadTable(StoreAllocs* a, int64_t n, int32_t slots, const int64_t* ptr,
+FeatTable UploadTable(AllocList* a, int64_t n, int32_t slots, const int64_t* ptr,
                       const int32_t* idx, const V* val) {
   FeatTable t{};
   if (slots <= 0 || n <= 0 || !ptr || !idx) return t;
@@ -388,15 +340,15 @@ FeatTable UploadTable(StoreAllocs* a, int64_t n, int32_t slots, const int64_t* p
 
 // The edge sampler over the store's records, enumerated in `order` (null = ordinal order).
 int BuildEdgeSampler(const EdgeStoreView& s, int32_t n_types, const int64_t* order,
-                     StoreAllocs* a, NodeSamplerView* view, std::vector<float>* sums) {
+                     AllocList* a, NodeSamplerView* view, std::vector<float>* sums) {
   const int64_t n = s.n;
   std::vector<uint64_t> ids((size_t)n);
   std::vector<int32_t> types((size_t)n);
   std::vector<float> weights((size_t)n);
   {
-    Scratch tmp;
-    EG_HIP(hipMalloc(&tmp.p, (size_t)std::max<int64_t>(n, 1) * 16));
-    int64_t* slot = static_cast<int64_t*>(tmp.p);
+    DevBuf tmp;
+    EG_HIP(tmp.alloc((size_t)std::max<int64_t>(n, 1) * 16));
+    int64_t* slot = tmp.as<int64_t>();
     int32_t* ty = reinterpret_cast<int32_t*>(slot + n);
     float* w = reinterpret_cast<float*>(ty + n);
     hipLaunchKernelGGL(GatherRecordsKernel, dim3(GridFor(n, 256)), dim3(256), 0, 0, s, 0, n,
@@ -430,7 +382,7 @@ int BuildEdgeSampler(const EdgeStoreView& s, int32_t n_types, const int64_t* ord
 }
 
 // Installs a built store (its allocations and sampler) in place of the graph's.
-void InstallStore(euler_gpu_graph* g, const EdgeStoreView& s, StoreAllocs* a,
+void InstallStore(euler_gpu_graph* g, const EdgeStoreView& s, AllocList* a,
                   const NodeSamplerView& sampler, std::vector<float>* sums) {
   DestroyEdgeStore(g);
   g->edges = s;
@@ -446,12 +398,6 @@ void InstallStore(euler_gpu_graph* g, const EdgeStoreView& s, StoreAllocs* a,
   g->edge_weight_sums.swap(*sums);
 }
 
-struct DeviceGuard {
-  int prev = 0;
-  explicit DeviceGuard(int dev) { (void)hipGetDevice(&prev); (void)hipSetDevice(dev); }
-  ~DeviceGuard() { (void)hipSetDevice(prev); }
-};
-
 int NumTypes(const std::vector<int32_t>& type, int32_t declared, int32_t* out) {
   int32_t T = std::max<int32_t>(declared, 1);
   for (int32_t t : type) {
@@ -466,7 +412,7 @@ int NumTypes(const std::vector<int32_t>& type, int32_t declared, int32_t* out) {
 // description `e` (may be null: none).
 int BuildStore(euler_gpu_graph* g, int64_t n, int32_t T, const uint64_t* src, const uint64_t* dst,
                const int32_t* ty, const float* w, const euler_gpu_host_edges* e) {
-  StoreAllocs a;
+  AllocList a("edge store: ");
   EdgeStoreView s{};
   s.n = n;
   s.n_lines = (uint64_t)std::max<int64_t>((n + 1) / 2, 1);
@@ -474,14 +420,14 @@ int BuildStore(euler_gpu_graph* g, int64_t n, int32_t T, const uint64_t* src, co
   int64_t* slot_of = slots ? a.Alloc<int64_t>((size_t)n) : nullptr;
   if (slot_of) {
     s.slots = slots; s.slot_of = slot_of;
-    Scratch tmp;
+    DevBuf tmp;
     hipError_t he = hipMemset(slots, 0xff, (size_t)(4 * s.n_lines) * sizeof(EdgeSlot));
-    if (he == hipSuccess) he = hipMalloc(&tmp.p, 16);
-    if (he == hipSuccess) he = hipMemset(tmp.p, 0, 16);
+    if (he == hipSuccess) he = tmp.alloc(16);
+    if (he == hipSuccess) he = hipMemset(tmp.as(), 0, 16);
     if (he != hipSuccess) {
       a.rc = Fail(EULER_GPU_EHIP, std::string("edge store: ") + hipGetErrorString(he));
     } else {
-      int32_t* repeats = static_cast<int32_t*>(tmp.p);
+      int32_t* repeats = tmp.as<int32_t>();
       hipLaunchKernelGGL(InsertRecordsKernel, dim3(GridFor(n, 256)), dim3(256), 0, 0, slots,
                          s.n_lines, src, dst, ty, w, n, slot_of);
       a.rc = CheckLaunch("edge store: insert");
@@ -524,9 +470,9 @@ int BuildFromHost(euler_gpu_graph* g, const euler_gpu_host_edges* e) {
   int rc = NumTypes(std::vector<int32_t>(e->type, e->type + n), e->n_edge_types, &T);
   if (rc != EULER_GPU_OK) return rc;
   DeviceGuard dg(g->device);
-  Scratch tmp;
-  EG_HIP(hipMalloc(&tmp.p, (size_t)n * 24));
-  uint64_t* src = static_cast<uint64_t*>(tmp.p);
+  DevBuf tmp;
+  EG_HIP(tmp.alloc((size_t)n * 24));
+  uint64_t* src = tmp.as<uint64_t>();
   uint64_t* dst = src + n;
   int32_t* ty = reinterpret_cast<int32_t*>(dst + n);
   float* w = reinterpret_cast<float*>(ty + n);
@@ -546,12 +492,12 @@ int BuildFromRows(euler_gpu_graph* g) {
   if (v.T > kMaxNodeTypes) return Fail(EULER_GPU_EINVAL, "edges_from_rows: more than 32 edge types");
   DeviceGuard dg(g->device);
   const uint64_t n_lines = (uint64_t)std::max<int64_t>((E + 1) / 2, 1);
-  Scratch table, flags;
-  EG_HIP(hipMalloc(&table.p, (size_t)(4 * n_lines) * sizeof(EdgeSlot)));
-  EG_HIP(hipMemset(table.p, 0xff, (size_t)(4 * n_lines) * sizeof(EdgeSlot)));
-  EG_HIP(hipMalloc(&flags.p, (size_t)(2 * E + 2) * 8));
-  EdgeSlot* slots = static_cast<EdgeSlot*>(table.p);
-  int64_t* first = static_cast<int64_t*>(flags.p);
+  DevBuf table, flags;
+  EG_HIP(table.alloc((size_t)(4 * n_lines) * sizeof(EdgeSlot)));
+  EG_HIP(hipMemset(table.as(), 0xff, (size_t)(4 * n_lines) * sizeof(EdgeSlot)));
+  EG_HIP(flags.alloc((size_t)(2 * E + 2) * 8));
+  EdgeSlot* slots = table.as<EdgeSlot>();
+  int64_t* first = flags.as<int64_t>();
   int64_t* ord = first + E + 1;
   EG_HIP(hipMemset(first + E, 0, 8));
   hipLaunchKernelGGL(RowsInsertKernel, dim3(GridFor(v.n_rows, 64)), dim3(64), 0, 0, v, slots,
@@ -561,9 +507,9 @@ int BuildFromRows(euler_gpu_graph* g) {
   if (rc != EULER_GPU_OK) return rc;
   int64_t n = 0;
   EG_HIP(hipMemcpy(&n, ord + E, 8, hipMemcpyDeviceToHost));
-  Scratch recs;
-  EG_HIP(hipMalloc(&recs.p, (size_t)n * 24 + 16));
-  uint64_t* src = static_cast<uint64_t*>(recs.p);
+  DevBuf recs;
+  EG_HIP(recs.alloc((size_t)n * 24 + 16));
+  uint64_t* src = recs.as<uint64_t>();
   uint64_t* dst = src + n;
   int32_t* ty = reinterpret_cast<int32_t*>(dst + n);
   float* w = reinterpret_cast<float*>(ty + n);
@@ -571,8 +517,8 @@ int BuildFromRows(euler_gpu_graph* g) {
                      slots, 4 * n_lines, ord, src, dst, ty, w);
   rc = CheckLaunch("edges_from_rows: records");
   if (rc != EULER_GPU_OK) return rc;
-  (void)hipFree(table.p); table.p = nullptr;
-  (void)hipFree(flags.p); flags.p = nullptr;
+  table.reset();     // (returned before the store takes its own blocks)
+  flags.reset();
   return BuildStore(g, n, std::max<int32_t>(v.T, 1), src, dst, ty, w, nullptr);
 }
 
@@ -582,13 +528,13 @@ int EnsureNodeBinary(const euler_gpu_graph* g) {
   std::lock_guard<std::mutex> lk(g->bin_mu);
   if (g->node_bin_ready || g->bin_host_slots == 0) return EULER_GPU_OK;
   DeviceGuard dg(g->device);
-  StoreAllocs a;
+  AllocList a("edge store: ");
   const int64_t n = (int64_t)g->bin_host_ptr.size() - 1;
   const FeatTable t = UploadTable(&a, n, g->bin_host_slots, g->bin_host_ptr.data(),
                                   g->bin_host_idx.data(), g->bin_host_val.data());
   if (a.rc != EULER_GPU_OK) { a.Release(); return a.rc; }
   euler_gpu_graph* mg = const_cast<euler_gpu_graph*>(g);   // the upload is the graph's from now on
-  for (auto& p : a.list) { mg->allocations.push_back(p.first); mg->bytes += p.second; }
+  mg->bytes += a.HandOver(&mg->allocations);
   g->node_bin = t;
   g->node_bin_ready = true;
   return EULER_GPU_OK;
@@ -609,19 +555,12 @@ int CheckEdgeQuery(const euler_gpu_graph* g, const char* what, int64_t n, const 
 // The two calls of a ragged result: (1) counts -> offsets [n+1] (+ total, max) on the host,
 // (2) the fill.  `count` launches the count kernel into counts [n] (max into counts[n + 1]).
 // Stream-ordered scratch freed on every exit.
-struct AsyncScratch {
-  void* p = nullptr;
-  hipStream_t st;
-  explicit AsyncScratch(hipStream_t s) : st(s) {}
-  ~AsyncScratch() { if (p) (void)hipFreeAsync(p, st); }
-};
-
 template <typename CountFn>
 int RaggedOffsets(hipStream_t st, int64_t n, CountFn count, int64_t* off_dev, int64_t* total_host,
                   int64_t* max_host) {
-  AsyncScratch scratch(st);
-  EG_HIP(hipMallocAsync(&scratch.p, (size_t)(n + 2) * sizeof(int64_t), st));
-  int64_t* counts = static_cast<int64_t*>(scratch.p);
+  StreamBuf scratch(st);
+  EG_HIP(scratch.alloc((size_t)(n + 2) * sizeof(int64_t)));
+  int64_t* counts = scratch.as<int64_t>();
   EG_HIP(hipMemsetAsync(counts + n, 0, 2 * sizeof(int64_t), st));
   count(counts, reinterpret_cast<unsigned long long*>(counts + n + 1));
   const int rc = ExclusiveScanI64(st, counts, off_dev, n + 1);
@@ -645,10 +584,9 @@ EdgeQuery MakeQuery(const euler_gpu_graph* g, const int64_t* edges, int64_t n, i
 }  // namespace
 
 void DestroyEdgeStore(euler_gpu_graph* g) {
-  for (auto& p : g->edge_allocs) { (void)hipFree(p.first); g->bytes -= p.second; }
-  g->edge_allocs.clear();
+  g->bytes -= FreeBlocks(&g->edge_allocs);
   if (g->edge_sampler_alloc.first) {
-    (void)hipFree(g->edge_sampler_alloc.first);
+    (void)hipFree(g->edge_sampler_alloc.first);   // owned by the graph, kept apart from the list
     g->bytes -= g->edge_sampler_alloc.second;
   }
   g->edge_sampler_alloc = {nullptr, 0};
@@ -700,7 +638,7 @@ int euler_gpu_graph_set_edge_features(euler_gpu_graph* g, const euler_gpu_host_e
       e->n_binary_features < 0)
     return Fail(EULER_GPU_EINVAL, "set_edge_features: need the store's record count of feature rows");
   DeviceGuard dg(g->device);
-  StoreAllocs a;
+  AllocList a("edge store: ");
   const int64_t n = e->n;
   const FeatTable f32 = UploadTable(&a, n, e->n_float_features, e->feat_ptr, e->feat_idx, e->feat_val);
   const FeatTable u64 = a.rc == EULER_GPU_OK
@@ -714,12 +652,12 @@ int euler_gpu_graph_set_edge_features(euler_gpu_graph* g, const euler_gpu_host_e
       auto it = std::find_if(g->edge_allocs.begin(), g->edge_allocs.end(),
                              [p](const std::pair<void*, int64_t>& x) { return p && x.first == p; });
       if (it == g->edge_allocs.end()) continue;
-      (void)hipFree(it->first);
+      (void)hipFree(it->first);            // a replaced table leaves the store's list
       g->bytes -= it->second;
       g->edge_allocs.erase(it);
     }
   }
-  for (auto& p : a.list) { g->edge_allocs.push_back(p); g->bytes += p.second; }
+  g->bytes += a.HandOver(&g->edge_allocs);
   g->edges.f32 = f32; g->edges.u64 = u64; g->edges.bin = bin;
   return EULER_GPU_OK;
 }
@@ -733,9 +671,9 @@ int euler_gpu_graph_export_edges(const euler_gpu_graph* g, int64_t first, int64_
     return Fail(EULER_GPU_EINVAL, "export_edges: range outside the records");
   if (n == 0) return EULER_GPU_OK;
   DeviceGuard dg(g->device);
-  Scratch tmp;
-  EG_HIP(hipMalloc(&tmp.p, (size_t)n * 24));
-  uint64_t* src = static_cast<uint64_t*>(tmp.p);
+  DevBuf tmp;
+  EG_HIP(tmp.alloc((size_t)n * 24));
+  uint64_t* src = tmp.as<uint64_t>();
   uint64_t* dst = src + n;
   int32_t* ty = reinterpret_cast<int32_t*>(dst + n);
   float* w = reinterpret_cast<float*>(ty + n);
@@ -754,13 +692,13 @@ int euler_gpu_graph_set_edge_sampler(euler_gpu_graph* g, const int64_t* order_ho
   int rc = CheckEdgeQuery(g, "set_edge_sampler", 0, nullptr);
   if (rc != EULER_GPU_OK) return rc;
   DeviceGuard dg(g->device);
-  StoreAllocs a;
+  AllocList a("edge store: ");
   NodeSamplerView sampler{};
   std::vector<float> sums;
   rc = BuildEdgeSampler(g->edges, g->edge_sampler.n_types, order_host, &a, &sampler, &sums);
   if (rc != EULER_GPU_OK) { a.Release(); return rc; }
   (void)hipDeviceSynchronize();          // (no launch may still read the old table)
-  (void)hipFree(g->edge_sampler_alloc.first);
+  (void)hipFree(g->edge_sampler_alloc.first);   // the replaced table; the new one is handed over below
   g->bytes -= g->edge_sampler_alloc.second;
   g->edge_sampler_alloc = a.list.back();
   g->bytes += g->edge_sampler_alloc.second;

@@ -5,11 +5,9 @@
 #include <hip/hip_runtime.h>
 
 #include "device_fns.h"
+#include "device_mem.h"
 
 namespace euler_gpu {
-
-int ExclusiveScanI64(hipStream_t stream, const int64_t* in, int64_t* out,
-                     int64_t n);   // mp_kernels.hip
 
 namespace {
 
@@ -150,20 +148,20 @@ int euler_gpu_get_sparse_feature(const euler_gpu_graph* g, void* stream,
   a.nodes = nodes_dev; a.n = n; a.n_u64 = g->n_u64; a.fid = fid;
   const int block = 256;
   if (indices_dev == nullptr) {
-    int64_t* counts = nullptr;
-    EG_HIP(hipMallocAsync((void**)&counts, (size_t)(n + 2) * sizeof(int64_t), st));
+    StreamBuf counts_buf(st);
+    EG_HIP(counts_buf.alloc((size_t)(n + 2) * sizeof(int64_t)));
+    int64_t* counts = counts_buf.as<int64_t>();
     unsigned long long* max_len = reinterpret_cast<unsigned long long*>(counts + n + 1);
     EG_HIP(hipMemsetAsync(counts + n, 0, 2 * sizeof(int64_t), st));
     hipLaunchKernelGGL(SparseFeatCountKernel, dim3(GridFor(n, block)), dim3(block), 0, st, a,
                        counts, max_len);
     int rc = ExclusiveScanI64(st, counts, row_off_dev, n + 1);
-    if (rc != EULER_GPU_OK) { (void)hipFreeAsync(counts, st); return rc; }
+    if (rc != EULER_GPU_OK) return rc;
     int64_t total = 0;
     unsigned long long ml = 0;
     EG_HIP(hipMemcpyAsync(&total, row_off_dev + n, 8, hipMemcpyDeviceToHost, st));
     EG_HIP(hipMemcpyAsync(&ml, max_len, 8, hipMemcpyDeviceToHost, st));
     EG_HIP(hipStreamSynchronize(st));
-    EG_HIP(hipFreeAsync(counts, st));
     if (nnz_host) *nnz_host = total;
     if (max_len_host) *max_len_host = (int64_t)ml;
     return EULER_GPU_OK;
@@ -191,20 +189,20 @@ int euler_gpu_get_sparse_feature_core(const euler_gpu_graph* g, void* stream,
   a.nodes = nodes_dev; a.n = n; a.n_u64 = g->n_u64; a.fid = fid;
   const int block = 256;
   if (values_dev == nullptr) {
-    int64_t* counts = nullptr;
-    EG_HIP(hipMallocAsync((void**)&counts, (size_t)(2 * n + 2) * sizeof(int64_t), st));
+    StreamBuf counts_buf(st);
+    EG_HIP(counts_buf.alloc((size_t)(2 * n + 2) * sizeof(int64_t)));
+    int64_t* counts = counts_buf.as<int64_t>();
     int64_t* off = counts + n + 1;
     EG_HIP(hipMemsetAsync(counts + n, 0, sizeof(int64_t), st));
     hipLaunchKernelGGL(SparseFeatCoreCountKernel, dim3(GridFor(n, block)), dim3(block), 0, st,
                        a, counts);
     int rc = ExclusiveScanI64(st, counts, off, n + 1);
-    if (rc != EULER_GPU_OK) { (void)hipFreeAsync(counts, st); return rc; }
+    if (rc != EULER_GPU_OK) return rc;
     hipLaunchKernelGGL(SparseFeatOffsetsToIdxKernel, dim3((unsigned)((n + block - 1) / block)),
                        dim3(block), 0, st, off, n, idx_dev);
     int64_t total = 0;
     EG_HIP(hipMemcpyAsync(&total, off + n, 8, hipMemcpyDeviceToHost, st));
     EG_HIP(hipStreamSynchronize(st));
-    EG_HIP(hipFreeAsync(counts, st));
     if (total_host) *total_host = total;
     return EULER_GPU_OK;
   }

@@ -16,6 +16,7 @@
 #include <sstream>
 
 #include "device_fns.h"
+#include "device_mem.h"
 #include "wb_index.h"
 
 namespace euler_gpu {
@@ -35,40 +36,13 @@ int Fail(int code, const std::string& msg) {
 
 namespace {
 
-struct GraphBuilder {
+// A build: the graph under construction and the blocks allocated for it, which become the
+// graph's with Commit() and are returned if the build ends without it.
+struct GraphBuilder : AllocList {
   std::unique_ptr<euler_gpu_graph> g{new euler_gpu_graph()};
-  int rc = EULER_GPU_OK;
-
-  template <typename T>
-  T* Alloc(size_t count) {
-    void* p = nullptr;
-    const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-      rc = Fail(EULER_GPU_ENOMEM, std::string("hipMalloc(") +
-                                      std::to_string(bytes) +
-                                      "): " + hipGetErrorString(e));
-      return nullptr;
-    }
-    g->allocations.push_back(p);
-    g->bytes += (int64_t)bytes;
-    return (T*)p;
-  }
-
-  template <typename T>
-  T* Upload(const T* host, size_t count) {
-    T* d = Alloc<T>(count);
-    if (!d) return nullptr;
-    if (count > 0) {
-      hipError_t e = hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        rc = Fail(EULER_GPU_EHIP, std::string("hipMemcpy H2D: ") +
-                                      hipGetErrorString(e));
-        return nullptr;
-      }
-    }
-    return d;
-  }
+  GraphBuilder() : AllocList("") {}
+  ~GraphBuilder() { Release(); }
+  void Commit() { g->bytes += HandOver(&g->allocations); }
 };
 
 // ---- sampling index (EdgeBlock + skip levels), built from the flat arrays --
@@ -149,15 +123,15 @@ int VerifyTotals(GraphBuilder* b) {
   GraphView& v = b->g->view;
   v.total_in_meta = 0;
   if (v.T != 1 || v.n_rows == 0) return EULER_GPU_OK;
-  int32_t* flag = nullptr;
-  EG_HIP(hipMalloc((void**)&flag, 16));
+  DevBuf flag_buf;
+  EG_HIP(flag_buf.alloc(16));
+  int32_t* flag = flag_buf.as<int32_t>();
   const int32_t one = 1;
   EG_HIP(hipMemcpy(flag, &one, 4, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(VerifyTotalsKernel, dim3((v.n_rows + 255) / 256), dim3(256), 0, 0, v,
                      flag);
   int32_t res = 0;
   EG_HIP(hipMemcpy(&res, flag, 4, hipMemcpyDeviceToHost));
-  EG_HIP(hipFree(flag));
   v.total_in_meta = res;
   return EULER_GPU_OK;
 }
@@ -236,9 +210,9 @@ void DestroyGraph(euler_gpu_graph* g) {
   (void)hipSetDevice(g->device);
   DestroyEdgeStore(g);
   DestroyLabelIndex(g);
-  for (void* p : g->allocations) (void)hipFree(p);
-  for (auto& kv : g->ws) (void)hipFree(kv.second.first);
-  for (auto& kv : g->flow_tables) (void)hipFree(kv.second.p);
+  (void)FreeBlocks(&g->allocations);
+  for (auto& kv : g->ws) (void)hipFree(kv.second.first);           // persistent workspaces,
+  for (auto& kv : g->flow_tables) (void)hipFree(kv.second.p);      // one per stream
   delete g;
 }
 
@@ -589,6 +563,7 @@ int BuildGraphFromHost(const euler_gpu_host_csr* c, int device,
     if (b.rc != EULER_GPU_OK) { DestroyGraph(b.g.release()); return b.rc; }
   }
   b.g->shards = shards;
+  b.Commit();
   *out = b.g.release();
   return EULER_GPU_OK;
 }
@@ -781,33 +756,28 @@ int BuildGraphSynthetic(const euler_gpu_synth_params* sp, int device,
   std::memcpy(p.deg_table, sp->deg_table, sizeof(p.deg_table));
   const int block = 256;
   // degrees -> row_ptr (temporary, dropped after row_meta is built)
-  int64_t* deg = nullptr;
-  int64_t* row_ptr = nullptr;
-  EG_HIP(hipMalloc((void**)&deg, (size_t)(n_rows + 1) * 8 + 16));
-  EG_HIP(hipMalloc((void**)&row_ptr, (size_t)(n_rows + 1) * 8 + 16));
+  DevBuf deg_buf, row_ptr_buf;
+  EG_HIP(deg_buf.alloc((size_t)(n_rows + 1) * 8 + 16));
+  EG_HIP(row_ptr_buf.alloc((size_t)(n_rows + 1) * 8 + 16));
+  int64_t* deg = deg_buf.as<int64_t>();
+  int64_t* row_ptr = row_ptr_buf.as<int64_t>();
   EG_HIP(hipMemset(deg, 0, (size_t)(n_rows + 1) * 8));
   if (n_rows > 0)
     hipLaunchKernelGGL(SynthDegreeKernel, dim3((n_rows + block - 1) / block),
                        dim3(block), 0, 0, p, base, stride, n_rows, deg);
   {
-    size_t tmp_bytes = 0;
-    EG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, deg, row_ptr,
-                                            n_rows + 1));
-    void* tmp = nullptr;
-    EG_HIP(hipMalloc(&tmp, tmp_bytes + 16));
-    EG_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, deg, row_ptr,
-                                            n_rows + 1));
+    const int rc = ExclusiveScanI64(0, deg, row_ptr, n_rows + 1);
+    if (rc != EULER_GPU_OK) return rc;
     EG_HIP(hipDeviceSynchronize());
-    EG_HIP(hipFree(tmp));
   }
   int64_t E = 0;
   EG_HIP(hipMemcpy(&E, row_ptr + n_rows, 8, hipMemcpyDeviceToHost));
-  EG_HIP(hipFree(deg));
+  deg_buf.reset();        // (returned before the edge arrays are taken)
   v.n_edges = E;
   uint64_t* nbr = b.Alloc<uint64_t>((size_t)E);
   float* pw = b.Alloc<float>((size_t)E);
   uint8_t* meta = b.Alloc<uint8_t>((size_t)n_rows * v.meta_stride + 16);
-  if (b.rc != EULER_GPU_OK) { (void)hipFree(row_ptr); DestroyGraph(b.g.release()); return b.rc; }
+  if (b.rc != EULER_GPU_OK) { DestroyGraph(b.g.release()); return b.rc; }
   if (E > 0)
     hipLaunchKernelGGL(SynthEdgeKernel, dim3(GridFor(E, block)), dim3(block), 0, 0,
                        p, base, stride, n_rows, row_ptr, E, nbr, pw);
@@ -817,7 +787,7 @@ int BuildGraphSynthetic(const euler_gpu_synth_params* sp, int device,
                        meta);
   EG_HIP(hipGetLastError());
   EG_HIP(hipDeviceSynchronize());
-  EG_HIP(hipFree(row_ptr));
+  row_ptr_buf.reset();
   v.nbr = nbr; v.prefix_w = pw; v.row_meta = meta;
   if (p.hashed_ids && n_rows > 0) {
     uint64_t cap = 16;
@@ -843,6 +813,7 @@ int BuildGraphSynthetic(const euler_gpu_synth_params* sp, int device,
   b.g->has_sampler = false;   // uniform roots are drawn by the caller
   b.g->n_node_types = 1;
   b.g->shards = shards;
+  b.Commit();
   *out = b.g.release();
   return EULER_GPU_OK;
 }
@@ -1021,28 +992,20 @@ int BuildWbIndex(GraphBuilder* b) {
   const bool plain = v.T == 1 && v.total_in_meta != 0 && v.map_mode == 0;
   const int block = 256;
   // temporaries, released on every way out (EG_HIP returns early)
-  struct Temps {
-    uint32_t* nbk = nullptr; uint32_t* wb_lo = nullptr; void* scan = nullptr; unsigned long long* ovf = nullptr;
-    ~Temps() {
-      if (nbk) (void)hipFree(nbk);
-      if (wb_lo) (void)hipFree(wb_lo);
-      if (scan) (void)hipFree(scan);
-      if (ovf) (void)hipFree(ovf);
-    }
-  } tmp;
-  if (hipMalloc((void**)&tmp.nbk, ((size_t)v.n_rows + 1) * 4 + 16) != hipSuccess ||
-      hipMalloc((void**)&tmp.wb_lo, ((size_t)v.n_rows + 1) * 4 + 16) != hipSuccess) {
+  DevBuf nbk_buf, wb_lo_buf, scan_buf, ovf_buf;
+  if (nbk_buf.alloc(((size_t)v.n_rows + 1) * 4 + 16) != hipSuccess ||
+      wb_lo_buf.alloc(((size_t)v.n_rows + 1) * 4 + 16) != hipSuccess) {
     (void)hipGetLastError();
     return EULER_GPU_OK;          // no room: the pivot-level search stays
   }
-  uint32_t* nbk = tmp.nbk;
-  uint32_t* wb_lo = tmp.wb_lo;
+  uint32_t* nbk = nbk_buf.as<uint32_t>();
+  uint32_t* wb_lo = wb_lo_buf.as<uint32_t>();
   hipLaunchKernelGGL(WbCountKernel, dim3((v.n_rows + 1 + block - 1) / block), dim3(block), 0, 0, v, nbk);
   {
     size_t tmp_bytes = 0;
     EG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, nbk, wb_lo, v.n_rows + 1));
-    EG_HIP(hipMalloc(&tmp.scan, tmp_bytes + 16));
-    EG_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.scan, tmp_bytes, nbk, wb_lo, v.n_rows + 1));
+    EG_HIP(scan_buf.alloc(tmp_bytes + 16));
+    EG_HIP(hipcub::DeviceScan::ExclusiveSum(scan_buf.as(), tmp_bytes, nbk, wb_lo, v.n_rows + 1));
     EG_HIP(hipDeviceSynchronize());
   }
   uint32_t n_wb32 = 0;
@@ -1059,8 +1022,8 @@ int BuildWbIndex(GraphBuilder* b) {
   if (b->rc != EULER_GPU_OK) return b->rc;
   hipLaunchKernelGGL(WbRecKernel, dim3((v.n_rows + block - 1) / block), dim3(block), 0, 0, v, wb_lo,
                      wbg, stride);
-  EG_HIP(hipMalloc((void**)&tmp.ovf, 16 + 4 * kWbOverflowKeep));
-  unsigned long long* ovf = tmp.ovf;
+  EG_HIP(ovf_buf.alloc(16 + 4 * kWbOverflowKeep));
+  unsigned long long* ovf = ovf_buf.as<unsigned long long>();
   EG_HIP(hipMemset(ovf, 0, 16 + 4 * kWbOverflowKeep));
   if (n_wb > 0)
     hipLaunchKernelGGL(WbFillKernel, dim3(GridFor(n_wb, block)), dim3(block), 0, 0, v, wb_lo, n_wb, wb, ovf);
@@ -1085,14 +1048,11 @@ int EnsureWbIndex(const euler_gpu_graph* cg) {
   if (g->wb_tried.load(std::memory_order_acquire) != 0) return EULER_GPU_OK;
   std::lock_guard<std::mutex> lk(g_blocked_mu);
   if (g->wb_tried.load(std::memory_order_acquire) != 0) return EULER_GPU_OK;
-  int prev = 0;
-  EG_HIP(hipGetDevice(&prev));
-  EG_HIP(hipSetDevice(g->device));
+  DeviceGuard dg(g->device);
   GraphBuilder b;
-  b.g.reset(g);                 // borrow the graph: allocations land in its list
-  const size_t n_alloc = g->allocations.size();
-  const int64_t bytes0 = g->bytes;
+  b.g.reset(g);                 // borrow the graph: the index's blocks become its own on success
   const int rc = BuildWbIndex(&b);
+  if (rc == EULER_GPU_OK) b.Commit();
   b.g.release();
   if (rc != EULER_GPU_OK) {
     // The index is an optimisation: a failure while building it (no memory for a temporary, a
@@ -1101,13 +1061,11 @@ int EnsureWbIndex(const euler_gpu_graph* cg) {
     (void)hipGetLastError();
     (void)hipDeviceSynchronize();
     (void)hipGetLastError();
-    while (g->allocations.size() > n_alloc) { (void)hipFree(g->allocations.back()); g->allocations.pop_back(); }
-    g->bytes = bytes0;
+    b.Release();
     GraphView& v = g->view;
     v.wb = nullptr; v.wbg = nullptr; v.wrec = nullptr; v.n_wb = 0; v.wb_lean_ok = 0;
     v.trec = nullptr; v.trec_stride = 0; v.fat = nullptr;
   }
-  (void)hipSetDevice(prev);
   g->wb_tried.store(1, std::memory_order_release);
   return EULER_GPU_OK;
 }
@@ -1126,13 +1084,9 @@ int EnsureBlockedIndex(const euler_gpu_graph* cg) {
   if (g->blk_ready.load(std::memory_order_acquire) != 0) return EULER_GPU_OK;
   std::lock_guard<std::mutex> lk(g_blocked_mu);
   if (g->blk_ready.load(std::memory_order_acquire) != 0) return EULER_GPU_OK;
-  int prev = 0;
-  EG_HIP(hipGetDevice(&prev));
-  EG_HIP(hipSetDevice(g->device));
+  DeviceGuard dg(g->device);
   GraphBuilder b;
-  b.g.reset(g);                 // borrow the graph: allocations land in its list
-  const size_t n_alloc = g->allocations.size();
-  const int64_t bytes0 = g->bytes;
+  b.g.reset(g);                 // borrow the graph: the index's blocks become its own on success
   int rc;
   if (g_blk_fail_next.load() > 0) {
     g_blk_fail_next.fetch_sub(1);
@@ -1141,17 +1095,16 @@ int EnsureBlockedIndex(const euler_gpu_graph* cg) {
   } else {
     rc = BuildBlockedIndex(&b);
   }
+  if (rc == EULER_GPU_OK) b.Commit();
   b.g.release();
   if (rc != EULER_GPU_OK) {
     (void)hipGetLastError();
     (void)hipDeviceSynchronize();
     (void)hipGetLastError();
-    while (g->allocations.size() > n_alloc) { (void)hipFree(g->allocations.back()); g->allocations.pop_back(); }
-    g->bytes = bytes0;
+    b.Release();
     GraphView& v = g->view;
     v.blk = nullptr; v.skip1 = nullptr; v.bpiv = nullptr; v.n_blk = 0;
   }
-  (void)hipSetDevice(prev);
   // 1 = built, 2 = declined: either way this graph is not asked again
   g->blk_ready.store(rc == EULER_GPU_OK ? 1 : 2, std::memory_order_release);
   return EULER_GPU_OK;
@@ -1355,33 +1308,25 @@ int euler_gpu_graph_set_node_sampler(euler_gpu_graph* g, int64_t n, const uint64
     ids[(size_t)i] = ids_host ? ids_host[i] : v.id_base + v.id_stride * (uint64_t)i;
   if (types_host) std::memcpy(types.data(), types_host, (size_t)n * sizeof(int32_t));
   if (weights_host) std::memcpy(weights.data(), weights_host, (size_t)n * sizeof(float));
-  int prev = 0;
-  EG_HIP(hipGetDevice(&prev));
-  EG_HIP(hipSetDevice(g->device));
+  DeviceGuard dg(g->device);
   const AliasEntry* old = g->has_sampler ? g->sampler.entries : nullptr;
-  const int64_t old_bytes = g->has_sampler
-      ? (int64_t)std::max<size_t>((size_t)g->sampler.type_off[g->sampler.n_types] * sizeof(AliasEntry), 16) : 0;
-  const size_t n_alloc = g->allocations.size();
-  const int64_t bytes0 = g->bytes;
   GraphBuilder b;
-  b.g.reset(g);                 // borrow the graph: the table lands in its allocation list
+  b.g.reset(g);                 // borrow the graph: the table becomes its own on success
   const int rc = BuildNodeSampler(&b, ids, types, weights, n_node_types);
   b.g.release();
-  if (rc != EULER_GPU_OK) {
-    // nothing of the graph was touched except, possibly, an allocation whose upload failed
-    while (g->allocations.size() > n_alloc) { (void)hipFree(g->allocations.back()); g->allocations.pop_back(); }
-    g->bytes = bytes0;
-  } else if (old != nullptr) {
-    auto it = std::find(g->allocations.begin(), g->allocations.end(), (void*)old);
-    if (it != g->allocations.end()) {
-      (void)hipDeviceSynchronize();      // (no launch may still read the old table)
-      (void)hipFree(*it);
-      g->allocations.erase(it);
-      g->bytes -= old_bytes;
-    }
+  // (on failure nothing of the graph was touched; an allocation whose upload failed goes back
+  // with the builder)
+  if (rc != EULER_GPU_OK) return rc;
+  auto it = std::find_if(g->allocations.begin(), g->allocations.end(),
+                         [old](const std::pair<void*, int64_t>& x) { return old && x.first == old; });
+  if (it != g->allocations.end()) {
+    (void)hipDeviceSynchronize();      // (no launch may still read the old table)
+    (void)hipFree(it->first);          // the replaced table leaves the graph's list
+    g->bytes -= it->second;
+    g->allocations.erase(it);
   }
-  (void)hipSetDevice(prev);
-  return rc;
+  g->bytes += b.HandOver(&g->allocations);
+  return EULER_GPU_OK;
 }
 
 int euler_gpu_graph_index_overflow_rows(const euler_gpu_graph* g, uint64_t* ids_host, int64_t cap,
@@ -1419,10 +1364,11 @@ int euler_gpu_graph_export_rows(const euler_gpu_graph* g, const uint64_t* ids_ho
   row_ptr_host[0] = 0;
   if (n == 0) return EULER_GPU_OK;
   const int32_t T = g->view.T;
-  uint64_t* ids_dev = nullptr;
-  int64_t* deg_dev = nullptr;
-  EG_HIP(hipMalloc((void**)&ids_dev, n * 8));
-  EG_HIP(hipMalloc((void**)&deg_dev, n * 16 + (size_t)n * T * 8));
+  DevBuf ids_buf, deg_buf;
+  EG_HIP(ids_buf.alloc(n * 8));
+  EG_HIP(deg_buf.alloc(n * 16 + (size_t)n * T * 8));
+  uint64_t* ids_dev = ids_buf.as<uint64_t>();
+  int64_t* deg_dev = deg_buf.as<int64_t>();
   int64_t* off_dev = deg_dev + n;
   int32_t* te_dev = (int32_t*)(off_dev + n);
   float* tp_dev = (float*)(te_dev + n * T);
@@ -1444,8 +1390,6 @@ int euler_gpu_graph_export_rows(const euler_gpu_graph* g, const uint64_t* ids_ho
                        (size_t)deg[i] * 4, hipMemcpyDeviceToHost));
     }
   }
-  EG_HIP(hipFree(ids_dev));
-  EG_HIP(hipFree(deg_dev));
   return EULER_GPU_OK;
 }
 

@@ -22,42 +22,14 @@
 #include <vector>
 
 #include "common.h"
+#include "device_mem.h"
 #include "device_fns.h"
 
 namespace euler_gpu {
 
-int ExclusiveScanI64(hipStream_t stream, const int64_t* in, int64_t* out,
-                     int64_t n);   // mp_kernels.hip
-
 thread_local int g_label_hash_bits = 64;   // euler_gpu_set_tuning key 74
 
 namespace {
-
-struct Scratch {
-  void* p = nullptr;
-  ~Scratch() { if (p) (void)hipFree(p); }
-};
-
-struct DeviceGuard {
-  int prev = 0;
-  explicit DeviceGuard(int dev) { (void)hipGetDevice(&prev); (void)hipSetDevice(dev); }
-  ~DeviceGuard() { (void)hipSetDevice(prev); }
-};
-
-struct AsyncScratch {
-  void* p = nullptr;
-  hipStream_t st;
-  explicit AsyncScratch(hipStream_t s) : st(s) {}
-  ~AsyncScratch() { if (p) (void)hipFreeAsync(p, st); }
-};
-
-int CheckLaunch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return Fail(EULER_GPU_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  const hipError_t s = hipDeviceSynchronize();
-  if (s != hipSuccess) return Fail(EULER_GPU_EHIP, std::string(what) + ": " + hipGetErrorString(s));
-  return EULER_GPU_OK;
-}
 
 constexpr uint64_t kNoLabel = ~0ULL;     // hash key of an entry without a label (sorts last)
 
@@ -228,9 +200,9 @@ int SortPairs(const K* kin, K* kout, const V* vin, V* vout, int64_t n, int end_b
   size_t tmp_bytes = 0;
   EG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kin, kout, vin, vout, (int)n, 0,
                                             end_bit, (hipStream_t)0));
-  Scratch tmp;
-  EG_HIP(hipMalloc(&tmp.p, tmp_bytes + 16));
-  EG_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, kin, kout, vin, vout, (int)n, 0,
+  DevBuf tmp;
+  EG_HIP(tmp.alloc(tmp_bytes + 16));
+  EG_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.as(), tmp_bytes, kin, kout, vin, vout, (int)n, 0,
                                             end_bit, (hipStream_t)0));
   return EULER_GPU_OK;
 }
@@ -282,27 +254,6 @@ int SplitCollisions(int64_t m, int64_t nv, const uint64_t* hs_d, int64_t* perm_d
   return EULER_GPU_OK;
 }
 
-struct LabelAllocs {
-  std::vector<std::pair<void*, int64_t>> list;
-  template <typename T>
-  T* Alloc(size_t count, int* rc) {
-    void* p = nullptr;
-    const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
-    const hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-      *rc = Fail(EULER_GPU_ENOMEM, std::string("graph labels: hipMalloc(") + std::to_string(bytes) +
-                                       "): " + hipGetErrorString(e));
-      return nullptr;
-    }
-    list.emplace_back(p, (int64_t)bytes);
-    return (T*)p;
-  }
-  void Release() {
-    for (auto& p : list) (void)hipFree(p.first);
-    list.clear();
-  }
-};
-
 // The index over m entries (id_d, beg_d, len_d) whose bytes live in val_d [val_bytes].  On
 // success the graph's old index (if any) is replaced; on failure it is left as it was and every
 // allocation of this build is returned.
@@ -311,10 +262,10 @@ int BuildIndex(const euler_gpu_graph* g, int64_t m, const uint64_t* id_d, const 
   if (m >= ((int64_t)1 << 31)) return Fail(EULER_GPU_EINVAL, "graph labels: more than 2^31 nodes");
   const int bits = g_label_hash_bits;
   // scratch: 12 arrays of m (+ 1) words and the counters
-  Scratch ws;
+  DevBuf ws;
   const size_t per = (size_t)(std::max<int64_t>(m, 1) * 8 + 32);
-  EG_HIP(hipMalloc(&ws.p, per * 13 + 64));
-  uint8_t* at = static_cast<uint8_t*>(ws.p);
+  EG_HIP(ws.alloc(per * 13 + 64));
+  uint8_t* at = ws.as<uint8_t>();
   uint64_t* key = Carve<uint64_t>(at, m);
   uint64_t* key2 = Carve<uint64_t>(at, m + 1);
   int64_t* iota = Carve<int64_t>(at, m);
@@ -373,17 +324,17 @@ int BuildIndex(const euler_gpu_graph* g, int64_t m, const uint64_t* id_d, const 
     return EULER_GPU_OK;
   }
   // the index itself
-  LabelAllocs a;
-  uint64_t* nodes = a.Alloc<uint64_t>((size_t)nv, &rc);
-  int64_t* start = nodes ? a.Alloc<int64_t>((size_t)L + 1, &rc) : nullptr;
-  if (!start) { a.Release(); return rc; }
+  AllocList a("graph labels: ");
+  uint64_t* nodes = a.Alloc<uint64_t>((size_t)nv);
+  int64_t* start = nodes ? a.Alloc<int64_t>((size_t)L + 1) : nullptr;
+  if (!start) { a.Release(); return a.rc; }
   // the labels' bytes pass through the device once, in scratch: export and lookup are host work
-  Scratch boff_s, bytes_s;
-  if (hipMalloc(&boff_s.p, ((size_t)L + 1) * 8) != hipSuccess) {
+  DevBuf boff_s, bytes_s;
+  if (boff_s.alloc(((size_t)L + 1) * 8) != hipSuccess) {
     a.Release();
     return Fail(EULER_GPU_ENOMEM, "graph labels: byte offsets");
   }
-  int64_t* boff = static_cast<int64_t*>(boff_s.p);
+  int64_t* boff = boff_s.as<int64_t>();
   std::vector<int64_t> boff_h;
   std::vector<uint8_t> bytes_h;
   if (nv > 0) {
@@ -416,7 +367,7 @@ int BuildIndex(const euler_gpu_graph* g, int64_t m, const uint64_t* id_d, const 
     if (rc == EULER_GPU_OK) rc = Download(&boff_h, (const int64_t*)boff, L + 1);
     uint8_t* lbytes = nullptr;
     if (rc == EULER_GPU_OK) {
-      if (hipMalloc(&bytes_s.p, (size_t)boff_h[L] + 16) == hipSuccess) lbytes = static_cast<uint8_t*>(bytes_s.p);
+      if (bytes_s.alloc((size_t)boff_h[L] + 16) == hipSuccess) lbytes = bytes_s.as<uint8_t>();
       else rc = Fail(EULER_GPU_ENOMEM, "graph labels: label bytes");
     }
     if (lbytes) {
@@ -439,7 +390,7 @@ int BuildIndex(const euler_gpu_graph* g, int64_t m, const uint64_t* id_d, const 
   euler_gpu_graph* mg = const_cast<euler_gpu_graph*>(g);
   (void)hipDeviceSynchronize();          // (no launch may still read the old index)
   DestroyLabelIndex(mg);
-  for (auto& p : a.list) { mg->label_allocs.push_back(p); mg->bytes += p.second; }
+  mg->bytes += a.HandOver(&mg->label_allocs);
   g->label_nodes = nodes;
   g->label_start = start;
   g->n_labels = L;
@@ -464,9 +415,9 @@ int EnsureLabelIndexLocked(const euler_gpu_graph* g, const char* what) {
   int rc = EnsureNodeBinary(g);
   if (rc != EULER_GPU_OK) return rc;
   DeviceGuard dg(g->device);
-  Scratch ent;
-  EG_HIP(hipMalloc(&ent.p, (size_t)n * 20 + 64));
-  uint64_t* id = static_cast<uint64_t*>(ent.p);
+  DevBuf ent;
+  EG_HIP(ent.alloc((size_t)n * 20 + 64));
+  uint64_t* id = ent.as<uint64_t>();
   int64_t* beg = reinterpret_cast<int64_t*>(id + n);
   int32_t* len = reinterpret_cast<int32_t*>(beg + n);
   hipLaunchKernelGGL(EntriesFromSlotKernel, dim3(GridFor(n, 256)), dim3(256), 0, 0, g->view,
@@ -685,9 +636,9 @@ int SortPairsAsync(hipStream_t st, const K* kin, K* kout, const V* vin, V* vout,
   size_t tmp_bytes = 0;
   EG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kin, kout, vin, vout, (int)n, 0,
                                             end_bit, st));
-  AsyncScratch tmp(st);
-  EG_HIP(hipMallocAsync(&tmp.p, tmp_bytes + 16, st));
-  EG_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, kin, kout, vin, vout, (int)n, 0,
+  StreamBuf tmp(st);
+  EG_HIP(tmp.alloc(tmp_bytes + 16));
+  EG_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.as(), tmp_bytes, kin, kout, vin, vout, (int)n, 0,
                                             end_bit, st));
   return EULER_GPU_OK;
 }
@@ -695,8 +646,7 @@ int SortPairsAsync(hipStream_t st, const K* kin, K* kout, const V* vin, V* vout,
 }  // namespace
 
 void DestroyLabelIndex(euler_gpu_graph* g) {
-  for (auto& p : g->label_allocs) { (void)hipFree(p.first); g->bytes -= p.second; }
-  g->label_allocs.clear();
+  g->bytes -= FreeBlocks(&g->label_allocs);
   g->label_nodes = nullptr;
   g->label_start = nullptr;
   g->n_labels = 0;
@@ -731,13 +681,13 @@ int euler_gpu_graph_set_graph_labels(euler_gpu_graph* g, const uint64_t* ids_hos
   std::vector<int64_t> beg(offsets_host, offsets_host + n);
   std::vector<int32_t> len((size_t)n);
   for (int64_t i = 0; i < n; ++i) len[i] = (int32_t)(offsets_host[i + 1] - offsets_host[i]);
-  Scratch ent;
+  DevBuf ent;
   const size_t bad_at = ((size_t)n * 20 + 15) & ~(size_t)15;     // 8-byte aligned counter
-  EG_HIP(hipMalloc(&ent.p, bad_at + 16 + (size_t)nb + 64));
-  uint64_t* id = static_cast<uint64_t*>(ent.p);
+  EG_HIP(ent.alloc(bad_at + 16 + (size_t)nb + 64));
+  uint64_t* id = ent.as<uint64_t>();
   int64_t* bg = reinterpret_cast<int64_t*>(id + n);
   int32_t* ln = reinterpret_cast<int32_t*>(bg + n);
-  unsigned long long* bad = reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(ent.p) + bad_at);
+  unsigned long long* bad = reinterpret_cast<unsigned long long*>(ent.as<uint8_t>() + bad_at);
   uint8_t* val = reinterpret_cast<uint8_t*>(bad) + 16;
   EG_HIP(hipMemset(bad, 0, 8));
   if (n > 0) {
@@ -830,9 +780,9 @@ int euler_gpu_get_graph_by_label(const euler_gpu_graph* g, void* stream, const i
   hipStream_t st = (hipStream_t)stream;
   if (out_dev == nullptr) {
     if (n == 0) { if (total_host) *total_host = 0; return EULER_GPU_OK; }
-    AsyncScratch scratch(st);
-    EG_HIP(hipMallocAsync(&scratch.p, (size_t)(2 * n + 2) * 8, st));
-    int64_t* counts = static_cast<int64_t*>(scratch.p);
+    StreamBuf scratch(st);
+    EG_HIP(scratch.alloc((size_t)(2 * n + 2) * 8));
+    int64_t* counts = scratch.as<int64_t>();
     int64_t* off = counts + n + 1;
     EG_HIP(hipMemsetAsync(counts + n, 0, 8, st));
     hipLaunchKernelGGL(LabelCountKernel, dim3(GridFor(n, 256)), dim3(256), 0, st, label_ids_dev, n,
@@ -874,10 +824,10 @@ int euler_gpu_whole_graph_block(const euler_gpu_graph* g, void* stream, const ui
   // positions by id and their table
   uint64_t tcap = 16;
   while (tcap < 2 * (uint64_t)n) tcap <<= 1;
-  AsyncScratch ws(st);
+  StreamBuf ws(st);
   const size_t bytes = (size_t)n * 8 * 6 + 256 + tcap * sizeof(PosSlot);   // (Carve pads each array)
-  EG_HIP(hipMallocAsync(&ws.p, bytes, st));
-  uint8_t* at = static_cast<uint8_t*>(ws.p);
+  EG_HIP(ws.alloc(bytes));
+  uint8_t* at = ws.as<uint8_t>();
   uint64_t* sid = Carve<uint64_t>(at, n);
   int64_t* iota = Carve<int64_t>(at, n);
   int64_t* spos = Carve<int64_t>(at, n);
@@ -900,10 +850,10 @@ int euler_gpu_whole_graph_block(const euler_gpu_graph* g, void* stream, const ui
   EG_HIP(hipStreamSynchronize(st));                         // host read 1: listed edges
   if (lam >= ((int64_t)1 << 31)) return Fail(EULER_GPU_EINVAL, "whole_graph_block: more than 2^31 listed edges");
   int64_t E = 0;
-  AsyncScratch ws2(st);
+  StreamBuf ws2(st);
   if (lam > 0) {
-    EG_HIP(hipMallocAsync(&ws2.p, (size_t)(lam + 1) * 16 + 64, st));
-    int64_t* hits = static_cast<int64_t*>(ws2.p);
+    EG_HIP(ws2.alloc((size_t)(lam + 1) * 16 + 64));
+    int64_t* hits = ws2.as<int64_t>();
     int64_t* hoff = hits + lam + 1;
     EG_HIP(hipMemsetAsync(hits + lam, 0, 8, st));
     hipLaunchKernelGGL(BlockHitsKernel, dim3(GridFor(lam, 256)), dim3(256), 0, st, a, eoff, n, row, lam,
@@ -916,9 +866,9 @@ int euler_gpu_whole_graph_block(const euler_gpu_graph* g, void* stream, const ui
     if (E > 0) {
       // (j, c) keys, sorted; a neighbour listed twice in a row (two edge types, or a repeated
       // edge) is one pair, as in SparseGetAdj's mask
-      AsyncScratch ks(st);
-      EG_HIP(hipMallocAsync(&ks.p, (size_t)E * 16 + 64, st));
-      uint64_t* keys = static_cast<uint64_t*>(ks.p);
+      StreamBuf ks(st);
+      EG_HIP(ks.alloc((size_t)E * 16 + 64));
+      uint64_t* keys = ks.as<uint64_t>();
       uint64_t* skeys = keys + E;
       int64_t* n_sel = reinterpret_cast<int64_t*>(skeys + E);
       hipLaunchKernelGGL(BlockFillKernel, dim3(GridFor(lam, 256)), dim3(256), 0, st, a, eoff, n, row, lam,
@@ -927,10 +877,10 @@ int euler_gpu_whole_graph_block(const euler_gpu_graph* g, void* stream, const ui
       const int end_bit = 32 + BitsFor(n);
       EG_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, keys, skeys, (int)E, 0, end_bit, st));
       EG_HIP(hipcub::DeviceSelect::Unique(nullptr, uniq_bytes, skeys, keys, n_sel, (int)E, st));
-      AsyncScratch tmp(st);
-      EG_HIP(hipMallocAsync(&tmp.p, std::max(sort_bytes, uniq_bytes) + 16, st));
-      EG_HIP(hipcub::DeviceRadixSort::SortKeys(tmp.p, sort_bytes, keys, skeys, (int)E, 0, end_bit, st));
-      EG_HIP(hipcub::DeviceSelect::Unique(tmp.p, uniq_bytes, skeys, keys, n_sel, (int)E, st));
+      StreamBuf tmp(st);
+      EG_HIP(tmp.alloc(std::max(sort_bytes, uniq_bytes) + 16));
+      EG_HIP(hipcub::DeviceRadixSort::SortKeys(tmp.as(), sort_bytes, keys, skeys, (int)E, 0, end_bit, st));
+      EG_HIP(hipcub::DeviceSelect::Unique(tmp.as(), uniq_bytes, skeys, keys, n_sel, (int)E, st));
       EG_HIP(hipMemcpyAsync(&E, n_sel, 8, hipMemcpyDeviceToHost, st));
       EG_HIP(hipStreamSynchronize(st));                     // host read 3: block edges
       *total_host = E + loops;

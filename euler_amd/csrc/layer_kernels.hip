@@ -18,6 +18,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "device_mem.h"
 #include "layer_fns.h"
 #include "local_layer_host.h"
 #include "wave_sums.h"
@@ -52,9 +53,6 @@ thread_local int g_adj_long_row = 16384;
 // 1 = scalar loads + a wave-uniform add chain (measured 2x slower: 11.9 vs 5.6 ms on
 // the 4096 heaviest rows - the s_loads are not overlapped with the chain).
 thread_local int g_sum_scalar = 0;
-
-int ExclusiveScanI64(hipStream_t stream, const int64_t* in, int64_t* out,
-                     int64_t n);   // mp_kernels.hip
 
 namespace {
 
@@ -802,8 +800,9 @@ int BuildAdjMaskOnly(const euler_gpu_graph* g, hipStream_t st, AdjArgs a, uint64
       const int64_t wgs = a.batch * (int64_t)a.wgs_per_row;
       const size_t lds = (size_t)mc * 8 + (size_t)cap * 4 + (size_t)4 * ((mc + 31) / 32) * 4;
       // queue of the hub sources: [R] indices + a counter
-      uint8_t* q = nullptr;
-      EG_HIP(hipMallocAsync((void**)&q, (size_t)R * 8 + 8, st));
+      StreamBuf q_buf(st);
+      EG_HIP(q_buf.alloc((size_t)R * 8 + 8));
+      uint8_t* q = q_buf.as<uint8_t>();
       a.long_src = reinterpret_cast<int64_t*>(q);
       a.n_long = reinterpret_cast<unsigned long long*>(q + (size_t)R * 8);
       a.long_row = g_adj_long_row;
@@ -812,8 +811,7 @@ int BuildAdjMaskOnly(const euler_gpu_graph* g, hipStream_t st, AdjArgs a, uint64
                          dim3(block), lds, st, a);
       hipLaunchKernelGGL(AdjLongRowsKernel, dim3(2048), dim3(block), lds, st, a);
       hipError_t e1 = hipGetLastError();
-      hipError_t e2 = hipFreeAsync(q, st);
-      EG_HIP(e0); EG_HIP(e1); EG_HIP(e2);
+      EG_HIP(e0); EG_HIP(e1);
     }
     EG_HIP(hipGetLastError());
   }
@@ -824,16 +822,13 @@ int BuildAdjMaskOnly(const euler_gpu_graph* g, hipStream_t st, AdjArgs a, uint64
 int AdjMaskOffsets(hipStream_t st, const uint64_t* mask, int64_t R, int32_t n, int32_t m,
                    int32_t words, int32_t tf, int64_t* off) {
   const int block = 256;
-  int64_t* counts = nullptr;
-  EG_HIP(hipMallocAsync((void**)&counts, (size_t)(R + 1) * sizeof(int64_t), st));
+  StreamBuf counts_buf(st);
+  EG_HIP(counts_buf.alloc((size_t)(R + 1) * sizeof(int64_t)));
+  int64_t* counts = counts_buf.as<int64_t>();
   EG_HIP(hipMemsetAsync(counts + R, 0, sizeof(int64_t), st));
   hipLaunchKernelGGL(AdjCountKernel, dim3(GridFor(R, block)), dim3(block), 0, st, mask, R, n, m,
                      words, tf, counts);
-  int rc = ExclusiveScanI64(st, counts, off, R + 1);
-  hipError_t f = hipFreeAsync(counts, st);
-  if (rc != EULER_GPU_OK) return rc;
-  EG_HIP(f);
-  return EULER_GPU_OK;
+  return ExclusiveScanI64(st, counts, off, R + 1);
 }
 
 // mask -> counts -> offsets, all on the stream
@@ -867,8 +862,9 @@ int euler_gpu_get_edge_sum_weight(const euler_gpu_graph* g, void* stream,
   const int block = 256;
   hipStream_t st = (hipStream_t)stream;
   // queue of the long rows: [n] rows, [n] positions, one counter
-  uint8_t* q = nullptr;
-  EG_HIP(hipMallocAsync((void**)&q, (size_t)n * 12 + 16, st));
+  StreamBuf q_buf(st);
+  EG_HIP(q_buf.alloc((size_t)n * 12 + 16));
+  uint8_t* q = q_buf.as<uint8_t>();
   int64_t* long_rows = reinterpret_cast<int64_t*>(q);
   int32_t* long_pos = reinterpret_cast<int32_t*>(long_rows + n);
   unsigned long long* n_long =
@@ -879,8 +875,7 @@ int euler_gpu_get_edge_sum_weight(const euler_gpu_graph* g, void* stream,
   hipLaunchKernelGGL(EdgeSumLongRowsKernel, dim3(GridFor(n * 64, block)), dim3(block), 0, st,
                      g->view, tl, long_rows, long_pos, n_long, out_w_dev, g_sum_scalar);
   hipError_t l = hipGetLastError();
-  hipError_t f = hipFreeAsync(q, st);
-  EG_HIP(e); EG_HIP(l); EG_HIP(f);
+  EG_HIP(e); EG_HIP(l);
   return EULER_GPU_OK;
 }
 
@@ -895,8 +890,9 @@ int euler_gpu_sample_root(void* stream, uint64_t seed, uint32_t call_id,
     return Fail(EULER_GPU_EINVAL, "sample_root: null buffer");
   hipStream_t st = (hipStream_t)stream;
   const int64_t cells = batch * n;
-  uint8_t* buf = nullptr;
-  EG_HIP(hipMallocAsync((void**)&buf, (size_t)(cells * 16 + batch * 4), st));
+  StreamBuf buf_buf(st);
+  EG_HIP(buf_buf.alloc((size_t)(cells * 16 + batch * 4)));
+  uint8_t* buf = buf_buf.as<uint8_t>();
   RootScratch s;
   s.wn = reinterpret_cast<float*>(buf);
   s.prob = s.wn + cells;
@@ -913,7 +909,7 @@ int euler_gpu_sample_root(void* stream, uint64_t seed, uint32_t call_id,
     hipError_t c = hipMemcpyAsync(h_w.data(), weights_dev, (size_t)cells * 4,
                                   hipMemcpyDeviceToHost, st);
     if (c == hipSuccess) c = hipStreamSynchronize(st);
-    if (c != hipSuccess) { (void)hipFreeAsync(buf, st); EG_HIP(c); }
+    EG_HIP(c);
     auto build = [&](int64_t b0, int64_t b1) {
       for (int64_t b = b0; b < b1; ++b)
         h_sum[b] = AliasBuildRow(h_w.data() + b * n, n, batch, h_wn.data() + b,
@@ -936,7 +932,7 @@ int euler_gpu_sample_root(void* stream, uint64_t seed, uint32_t call_id,
       c = hipMemcpyAsync(s.alias, h_alias.data(), (size_t)cells * 4, hipMemcpyHostToDevice, st);
     if (c == hipSuccess)
       c = hipMemcpyAsync(s.sum, h_sum.data(), (size_t)batch * 4, hipMemcpyHostToDevice, st);
-    if (c != hipSuccess) { (void)hipFreeAsync(buf, st); EG_HIP(c); }
+    EG_HIP(c);
   } else {
     hipLaunchKernelGGL(SampleRootBuildKernel, dim3(GridFor(batch, block)), dim3(block), 0,
                        st, weights_dev, batch, n, s);
@@ -945,12 +941,11 @@ int euler_gpu_sample_root(void* stream, uint64_t seed, uint32_t call_id,
                      0, st, roots_dev, batch, n, m, seed, call_id, default_node, s,
                      out_dev);
   hipError_t e = hipGetLastError();
-  // the host vectors feed asynchronous copies: they must outlive them
+  // the host vectors feed asynchronous copies: they must outlive them (and the scratch is
+  // returned after this wait: its guard is declared before them)
   hipError_t y = on_host ? hipStreamSynchronize(st) : hipSuccess;
-  hipError_t f = hipFreeAsync(buf, st);
   EG_HIP(e);
   EG_HIP(y);
-  EG_HIP(f);
   return EULER_GPU_OK;
 }
 
@@ -1000,9 +995,10 @@ int euler_gpu_sample_neighbor_layerwise(const euler_gpu_graph* g, void* stream,
   if (!nodes_dev || !out_dev)
     return Fail(EULER_GPU_EINVAL, "sample_neighbor_layerwise: null buffer");
   hipStream_t st = (hipStream_t)stream;
-  uint8_t* buf = nullptr;
   const int64_t cells = batch * n, draws = batch * (int64_t)count;
-  EG_HIP(hipMallocAsync((void**)&buf, (size_t)(draws * 8 + cells * 4), st));
+  StreamBuf buf_buf(st);
+  EG_HIP(buf_buf.alloc((size_t)(draws * 8 + cells * 4)));
+  uint8_t* buf = buf_buf.as<uint8_t>();
   uint64_t* l_root = reinterpret_cast<uint64_t*>(buf);
   float* weights = reinterpret_cast<float*>(l_root + draws);
   int rc = euler_gpu_get_edge_sum_weight(g, stream, nodes_dev, cells, edge_types_host,
@@ -1014,10 +1010,7 @@ int euler_gpu_sample_neighbor_layerwise(const euler_gpu_graph* g, void* stream,
     rc = euler_gpu_sample_layer(g, stream, seed, call_id, l_root, draws,
                                 edge_types_host, k, default_node, out_dev, nullptr,
                                 nullptr);
-  hipError_t f = hipFreeAsync(buf, st);
-  if (rc != EULER_GPU_OK) return rc;
-  EG_HIP(f);
-  return EULER_GPU_OK;
+  return rc;
 }
 
 int euler_gpu_local_sample_layer(void* stream, uint64_t seed, uint32_t call_id,
@@ -1058,9 +1051,10 @@ int euler_gpu_local_sample_layer(void* stream, uint64_t seed, uint32_t call_id,
   std::vector<float>&u_w = tb.u_w, &sum_w = tb.sum_w;
   std::vector<int32_t>& u_t = tb.u_t;
   const size_t U = u_id.size();
-  uint8_t* buf = nullptr;
   const size_t bytes = (size_t)(batch + 1) * 8 + U * 8 + U * 12 + 64;
-  EG_HIP(hipMallocAsync((void**)&buf, bytes, st));
+  StreamBuf buf_buf(st);
+  EG_HIP(buf_buf.alloc(bytes));
+  uint8_t* buf = buf_buf.as<uint8_t>();
   LocalLayerArgs a{};
   int64_t* d_seg = reinterpret_cast<int64_t*>(buf);
   uint64_t* d_id = reinterpret_cast<uint64_t*>(d_seg + batch + 1);
@@ -1086,8 +1080,7 @@ int euler_gpu_local_sample_layer(void* stream, uint64_t seed, uint32_t call_id,
     c = hipGetLastError();
   }
   hipError_t y = hipStreamSynchronize(st);      // the host vectors feed async copies
-  hipError_t f = hipFreeAsync(buf, st);
-  EG_HIP(c); EG_HIP(y); EG_HIP(f);
+  EG_HIP(c); EG_HIP(y);
   return EULER_GPU_OK;
 }
 
@@ -1115,8 +1108,9 @@ int euler_gpu_sample_n_with_types(const euler_gpu_graph* g, void* stream, uint64
   if (!types_dev || !out_dev)
     return Fail(EULER_GPU_EINVAL, "sample_n_with_types: null buffer");
   hipStream_t st = (hipStream_t)stream;
-  int32_t* bad = nullptr;
-  EG_HIP(hipMallocAsync((void**)&bad, sizeof(int32_t), st));
+  StreamBuf bad_buf(st);
+  EG_HIP(bad_buf.alloc(sizeof(int32_t)));
+  int32_t* bad = bad_buf.as<int32_t>();
   EG_HIP(hipMemsetAsync(bad, 0, sizeof(int32_t), st));
   const int block = 256;
   hipLaunchKernelGGL(SampleNWithTypesKernel, dim3(GridFor(n * count, block)), dim3(block),
@@ -1125,8 +1119,7 @@ int euler_gpu_sample_n_with_types(const euler_gpu_graph* g, void* stream, uint64
   int32_t bad_host = 0;
   hipError_t c = hipMemcpyAsync(&bad_host, bad, sizeof(int32_t), hipMemcpyDeviceToHost, st);
   hipError_t y = hipStreamSynchronize(st);
-  hipError_t f = hipFreeAsync(bad, st);
-  EG_HIP(e); EG_HIP(c); EG_HIP(y); EG_HIP(f);
+  EG_HIP(e); EG_HIP(c); EG_HIP(y);
   if (bad_host)
     return Fail(EULER_GPU_EEMPTY,
                 "sample_n_with_types: a listed type is unknown or has zero weight");

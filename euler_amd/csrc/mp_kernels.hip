@@ -13,6 +13,7 @@
 #include <utility>
 
 #include "device_fns.h"
+#include "device_mem.h"
 
 struct euler_gpu_front {
   int64_t* stage = nullptr;      // pinned + mapped: [kMaxShards + 1] bucket starts, then the sequence word
@@ -30,11 +31,10 @@ int ExclusiveScanI64(hipStream_t stream, const int64_t* in, int64_t* out,
   size_t tmp_bytes = 0;
   EG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, in, out, (int)n,
                                           stream));
-  void* tmp = nullptr;
-  EG_HIP(hipMallocAsync(&tmp, tmp_bytes + 16, stream));
-  EG_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, in, out, (int)n,
+  StreamBuf tmp(stream);
+  EG_HIP(tmp.alloc(tmp_bytes + 16));
+  EG_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.as(), tmp_bytes, in, out, (int)n,
                                           stream));
-  EG_HIP(hipFreeAsync(tmp, stream));
   return EULER_GPU_OK;
 }
 
@@ -280,29 +280,23 @@ static int ScatterImpl(hipStream_t st, const float* upd, const int32_t* idx,
   const int32_t* keys = idx;
   const uint32_t* perm = nullptr;
   // stream-ordered scratch of the unsorted path, released on every exit
-  struct Scratch {
-    hipStream_t st;
-    void* p = nullptr;
-    explicit Scratch(hipStream_t s) : st(s) {}
-    ~Scratch() { if (p) (void)hipFreeAsync(p, st); }
-  } sc(st);
-  void*& scratch = sc.p;
+  StreamBuf scratch(st);
   if (e > 1) {
-    int32_t* flag = nullptr;
-    EG_HIP(hipMallocAsync((void**)&flag, 16, st));
+    StreamBuf flag_buf(st);
+    EG_HIP(flag_buf.alloc(16));
+    int32_t* flag = flag_buf.as<int32_t>();
     int32_t one = 1, sorted = 1;
     EG_HIP(hipMemcpyAsync(flag, &one, 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(IsSortedKernel, dim3((e + 255) / 256), dim3(256), 0, st, idx,
                        e, flag);
     EG_HIP(hipMemcpyAsync(&sorted, flag, 4, hipMemcpyDeviceToHost, st));
     EG_HIP(hipStreamSynchronize(st));
-    EG_HIP(hipFreeAsync(flag, st));
     if (!sorted) {
       // stable sort of (destination, original position)
       const size_t n = (size_t)e;
       const size_t bytes = n * (4 + 4 + 4 + 4) + 64;
-      EG_HIP(hipMallocAsync(&scratch, bytes, st));
-      int32_t* keys_out = (int32_t*)scratch;
+      EG_HIP(scratch.alloc(bytes));
+      int32_t* keys_out = scratch.as<int32_t>();
       uint32_t* vals_in = (uint32_t*)(keys_out + n);
       uint32_t* vals_out = vals_in + n;
       hipLaunchKernelGGL(IotaKernel, dim3((e + 255) / 256), dim3(256), 0, st,
@@ -311,12 +305,11 @@ static int ScatterImpl(hipStream_t st, const float* upd, const int32_t* idx,
       EG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, idx, keys_out,
                                                 vals_in, vals_out, (int)e, 0, 32,
                                                 st));
-      void* tmp = nullptr;
-      EG_HIP(hipMallocAsync(&tmp, tmp_bytes + 16, st));
-      EG_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, idx, keys_out,
+      StreamBuf tmp(st);        // (the library's scratch goes back before the reduction runs)
+      EG_HIP(tmp.alloc(tmp_bytes + 16));
+      EG_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.as(), tmp_bytes, idx, keys_out,
                                                 vals_in, vals_out, (int)e, 0, 32,
                                                 st));
-      EG_HIP(hipFreeAsync(tmp, st));
       keys = keys_out;
       perm = vals_out;
     }
@@ -857,8 +850,9 @@ int euler_gpu_neighbor_post_process(void* stream, int64_t n, int32_t* idx_dev,
   const size_t o_key = o_pout + al((size_t)total * 4);
   const size_t o_len = o_key + al((size_t)total * 8), o_off = o_len + al((size_t)(n + 1) * 8);
   const size_t bytes = o_off + al((size_t)(n + 1) * 8);
-  uint8_t* buf = nullptr;
-  EG_HIP(hipMallocAsync((void**)&buf, bytes, st));
+  StreamBuf buf_buf(st);
+  EG_HIP(buf_buf.alloc(bytes));
+  uint8_t* buf = buf_buf.as<uint8_t>();
   uint64_t* c_id = (uint64_t*)(buf + o_id);
   float* c_w = (float*)(buf + o_w);
   int32_t* c_t = (int32_t*)(buf + o_t);
@@ -878,7 +872,7 @@ int euler_gpu_neighbor_post_process(void* stream, int64_t n, int32_t* idx_dev,
                                    hipcub::CountingInputIterator<int32_t>>
         seg_b(row_it, IdxEdgeLong{idx_dev, 0}), seg_e(row_it, IdxEdgeLong{idx_dev, 1});
     size_t tmp_bytes = 0;
-    void* tmp = nullptr;
+    StreamBuf tmp(st);
     // the library pass is only needed when some row is longer than a wave ranks
     int32_t max_len = 0;
     {
@@ -897,10 +891,10 @@ int euler_gpu_neighbor_post_process(void* stream, int64_t n, int32_t* idx_dev,
                                                   keys_out, p_in, p_out, (int)total, \
                                                   (int)n, seg_b, seg_e, 0,           \
                                                   (int)sizeof(KEY_T) * 8, st));      \
-      EG_HIP(hipMallocAsync(&tmp, tmp_bytes + 16, st));                              \
-      EG_HIP(hipcub::DeviceSegmentedRadixSort::FN(tmp, tmp_bytes, KEYS_IN, keys_out, \
-                                                  p_in, p_out, (int)total, (int)n,   \
-                                                  seg_b, seg_e, 0,                   \
+      EG_HIP(tmp.alloc(tmp_bytes + 16));                                             \
+      EG_HIP(hipcub::DeviceSegmentedRadixSort::FN(tmp.as(), tmp_bytes, KEYS_IN,      \
+                                                  keys_out, p_in, p_out, (int)total, \
+                                                  (int)n, seg_b, seg_e, 0,           \
                                                   (int)sizeof(KEY_T) * 8, st));      \
     } }
     if (order_by == 1) {
@@ -911,7 +905,7 @@ int euler_gpu_neighbor_post_process(void* stream, int64_t n, int32_t* idx_dev,
       else EG_SEGSORT(float, c_w, SortPairs)
     }
 #undef EG_SEGSORT
-    if (tmp) EG_HIP(hipFreeAsync(tmp, st));
+    tmp.reset();       // (the library's scratch goes back before the rest of the call)
     // short rows: ranked in a wave, written into the same permutation array
     {
       const int gridw = GridFor(n * 64, block);
@@ -943,7 +937,6 @@ int euler_gpu_neighbor_post_process(void* stream, int64_t n, int32_t* idx_dev,
   int32_t last[2];
   EG_HIP(hipMemcpyAsync(last, idx_dev + 2 * (n - 1), 8, hipMemcpyDeviceToHost, st));
   EG_HIP(hipStreamSynchronize(st));
-  EG_HIP(hipFreeAsync(buf, st));
   if (total_host) *total_host = last[1];
   return EULER_GPU_OK;
 }
@@ -1034,8 +1027,9 @@ int euler_gpu_id_unique(void* stream, const uint64_t* ids_dev, int64_t n,
   while (cap < (uint64_t)n * 2) cap <<= 1;
   const size_t slots = cap + 1;
   const size_t bytes = slots * (8 + 4 + 4) + (size_t)n * (4 + 8 + 8) + 256;
-  uint8_t* buf = nullptr;
-  EG_HIP(hipMallocAsync((void**)&buf, bytes, st));
+  StreamBuf buf_buf(st);
+  EG_HIP(buf_buf.alloc(bytes));
+  uint8_t* buf = buf_buf.as<uint8_t>();
   UniqueTable t;
   t.keys = (unsigned long long*)buf;
   int64_t* is_first = (int64_t*)(t.keys + slots);
@@ -1063,7 +1057,6 @@ int euler_gpu_id_unique(void* stream, const uint64_t* ids_dev, int64_t n,
   EG_HIP(hipMemcpyAsync(&tail[0], rank + (n - 1), 8, hipMemcpyDeviceToHost, st));
   EG_HIP(hipMemcpyAsync(&tail[1], is_first + (n - 1), 8, hipMemcpyDeviceToHost, st));
   EG_HIP(hipStreamSynchronize(st));
-  EG_HIP(hipFreeAsync(buf, st));
   if (n_unique_host) *n_unique_host = tail[0] + tail[1];
   return EULER_GPU_OK;
 }
@@ -1074,8 +1067,9 @@ int euler_gpu_idx_gather(void* stream, const int32_t* idx_dev,
   if (n < 0) return Fail(EULER_GPU_EINVAL, "idx_gather: bad n");
   if (n == 0) { if (total_host) *total_host = 0; return EULER_GPU_OK; }
   hipStream_t st = (hipStream_t)stream;
-  int64_t* len = nullptr;
-  EG_HIP(hipMallocAsync((void**)&len, (2 * n + 2) * 8, st));
+  StreamBuf len_buf(st);
+  EG_HIP(len_buf.alloc((2 * n + 2) * 8));
+  int64_t* len = len_buf.as<int64_t>();
   int64_t* off = len + n + 1;
   const int block = 256;
   const dim3 grid((unsigned)((n + block - 1) / block));
@@ -1088,7 +1082,6 @@ int euler_gpu_idx_gather(void* stream, const int32_t* idx_dev,
   int32_t last[2];
   EG_HIP(hipMemcpyAsync(last, out_idx_dev + 2 * (n - 1), 8, hipMemcpyDeviceToHost, st));
   EG_HIP(hipStreamSynchronize(st));
-  EG_HIP(hipFreeAsync(len, st));
   if (total_host) *total_host = last[1];
   return EULER_GPU_OK;
 }
@@ -1133,8 +1126,9 @@ int euler_gpu_id_split(void* stream, const uint64_t* ids_dev, int64_t n,
   hipStream_t st = (hipStream_t)stream;
   const int64_t n_blocks = (n + kSplitBlock - 1) / kSplitBlock;
   const int64_t cells = n_blocks * shards;
-  int64_t* hist = nullptr;
-  EG_HIP(hipMallocAsync((void**)&hist, (2 * cells + 2) * 8, st));
+  StreamBuf hist_buf(st);
+  EG_HIP(hist_buf.alloc((2 * cells + 2) * 8));
+  int64_t* hist = hist_buf.as<int64_t>();
   int64_t* off = hist + cells + 1;
   hipLaunchKernelGGL(SplitHistKernel, dim3((unsigned)n_blocks), dim3(kSplitBlock), 0,
                      st, ids_dev, n, partitions, shards, hist);
@@ -1150,7 +1144,6 @@ int euler_gpu_id_split(void* stream, const uint64_t* ids_dev, int64_t n,
     EG_HIP(hipMemcpyAsync(&starts[s], off + (int64_t)s * n_blocks, 8,
                           hipMemcpyDeviceToHost, st));
   EG_HIP(hipStreamSynchronize(st));
-  EG_HIP(hipFreeAsync(hist, st));
   for (int s = 0; s < shards; ++s) shard_off_host[s] = starts[s];
   shard_off_host[shards] = n;
   return EULER_GPU_OK;
@@ -1194,8 +1187,9 @@ int euler_gpu_inflate_idx(void* stream, const int32_t* idx_dev, int64_t n, int32
                                             (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n,
                                             0, 32, st));
   const size_t head = (un * 12 + 16 + 255) & ~(size_t)255;     // sorted keys, positions in / out, stat
-  char* buf = nullptr;
-  EG_HIP(hipMallocAsync((void**)&buf, head + tmp_bytes + 16, st));
+  StreamBuf buf_buf(st);
+  EG_HIP(buf_buf.alloc(head + tmp_bytes + 16));
+  char* buf = buf_buf.as<char>();
   int32_t* keys_out = (int32_t*)buf;
   uint32_t* vals_in = (uint32_t*)(keys_out + un);
   uint32_t* vals_out = vals_in + un;
@@ -1217,7 +1211,6 @@ int euler_gpu_inflate_idx(void* stream, const int32_t* idx_dev, int64_t n, int32
         hipStreamSynchronize(st) != hipSuccess)
       rc = EULER_GPU_EHIP;
   } while (false);
-  (void)hipFreeAsync(buf, st);
   if (rc != EULER_GPU_OK) return Fail(rc, "inflate_idx: HIP call failed");
   // h[0] + 1 distinct values, all of them >= h[1] and <= h[2]
   if (h[1] < 0 || (int64_t)h[2] > (int64_t)h[0])
@@ -1562,7 +1555,7 @@ static int ScratchReserve(StreamScratch* e, hipStream_t stream, size_t bytes, vo
   if (e->bytes < bytes) {
     if (e->ptr != nullptr) {
       EG_HIP(hipStreamSynchronize(stream));
-      EG_HIP(hipFree(e->ptr));
+      EG_HIP(hipFree(e->ptr));              // persistent per-stream scratch: outlives the call
       e->ptr = nullptr; e->bytes = 0;
     }
     const size_t want = bytes + bytes / 4;

@@ -10,6 +10,7 @@
 #include <cmath>
 #include <vector>
 
+#include "device_mem.h"
 #include "k1_args.h"
 #include "k1_search.h"
 #include "fanout_local.h"
@@ -834,7 +835,7 @@ static int GetWorkspace(const euler_gpu_graph* g, hipStream_t stream, size_t byt
   if (slot.second < bytes) {
     if (slot.first != nullptr) {
       EG_HIP(hipStreamSynchronize(stream));   // earlier calls may still use it
-      EG_HIP(hipFree(slot.first));
+      EG_HIP(hipFree(slot.first));            // persistent workspace: outlives the call
       slot.first = nullptr; slot.second = 0;
     }
     const size_t want = bytes + bytes / 4;
@@ -2033,8 +2034,9 @@ int euler_gpu_sample_neighbor_packed(const euler_gpu_graph* g, void* stream,
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t total = (size_t)n * (size_t)count;
   const size_t o_w = al(total * 8), o_t = o_w + al(total * 4), o_m = o_t + al(total * 4);
-  uint8_t* buf = nullptr;
-  EG_HIP(hipMallocAsync((void**)&buf, o_m + al((size_t)n), st));
+  StreamBuf scratch(st);
+  EG_HIP(scratch.alloc(o_m + al((size_t)n)));
+  uint8_t* buf = scratch.as<uint8_t>();
   int rc = LaunchSampleNeighbor(g, st, seed, call_id, roots_dev, n, nullptr, 1,
                                 edge_types_host, k, count, EULER_GPU_LAYOUT_TF, default_node,
                                 (uint64_t*)buf, (float*)(buf + o_w), (int32_t*)(buf + o_t),
@@ -2043,7 +2045,6 @@ int euler_gpu_sample_neighbor_packed(const euler_gpu_graph* g, void* stream,
     rc = euler_gpu_pack_rows(stream, (const uint64_t*)buf, (const float*)(buf + o_w),
                              (const int32_t*)(buf + o_t), buf + o_m, n, count, single_type,
                              packed_dev);
-  (void)hipFreeAsync(buf, st);
   return rc;
 }
 
@@ -2324,8 +2325,9 @@ int euler_gpu_expand_rows(void* stream, const int32_t* pos_dev, int64_t n,
   hipStream_t st = (hipStream_t)stream;
   // DedupExpandKernel gates on a device-side counter: give it one that says
   // "expand" (0 distinct roots * 4 <= n * 3)
-  uint32_t* zero = nullptr;
-  EG_HIP(hipMallocAsync((void**)&zero, 16, st));
+  StreamBuf zero_buf(st);
+  EG_HIP(zero_buf.alloc(16));
+  uint32_t* zero = zero_buf.as<uint32_t>();
   EG_HIP(hipMemsetAsync(zero, 0, 16, st));
   ExpandArgs x{};
   x.counter = zero;
@@ -2349,7 +2351,6 @@ int euler_gpu_expand_rows(void* stream, const int32_t* pos_dev, int64_t n,
   LaunchExpand(U, g_expand_steps, false, (int)blocks, block, st, x, stride_rows,
                stride_slots);
   EG_HIP(hipGetLastError());
-  EG_HIP(hipFreeAsync(zero, st));
   return EULER_GPU_OK;
 }
 

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <vector>
 
+#include "device_mem.h"
 #include "k1_args.h"
 #include "k1_search.h"
 #include "fanout_local.h"     // LeanSamplePair (the walks over merged walkers)
@@ -1018,7 +1019,7 @@ int WalkEdgeTypes(hipStream_t st, const int32_t* edge_types_host, int32_t k, int
                   int32_t** et_dev) {
   *et_dev = nullptr;
   const size_t et_bytes = (size_t)walk_len * (k > 0 ? k : 1) * sizeof(int32_t) + 16;
-  EG_HIP(hipMallocAsync((void**)et_dev, et_bytes, st));
+  EG_HIP(hipMallocAsync((void**)et_dev, et_bytes, st));     // handed out: the caller frees it (common.h)
   if (k > 0 && walk_len > 0)
     EG_HIP(hipMemcpyAsync(*et_dev, edge_types_host, (size_t)walk_len * k * sizeof(int32_t),
                           hipMemcpyHostToDevice, st));
@@ -1087,7 +1088,7 @@ static int LaunchShPath(hipStream_t st, const int64_t* starts_dev, int64_t n, in
   a.row_stride = row_stride; a.live_lens = live_lens; a.live_stride = live_stride;
   a.map0 = map0 ? 1 : 0; a.p_out = p_out;
   const int32_t n_next = len + (p_out != nullptr ? 1 : 0);      // next tables the kernel reads
-  void* tab = nullptr;
+  StreamBuf tab_buf(st);
   if (n_next <= kShPathLevels) {
     for (int32_t s = 0; s <= len; ++s) a.ids_arg[s] = level_ids_host[s];
     for (int32_t s = 0; s < n_next; ++s) a.next_arg[s] = level_next_host[s];
@@ -1095,12 +1096,13 @@ static int LaunchShPath(hipStream_t st, const int64_t* starts_dev, int64_t n, in
     // a long walk: the tables through device memory (the copies are waited for - their
     // sources are the caller's host arrays)
     const size_t tb = ((size_t)len + 1) * 8, tn = (size_t)n_next * 8;
-    EG_HIP(hipMallocAsync(&tab, tb + tn, st));
+    EG_HIP(tab_buf.alloc(tb + tn));
+    uint8_t* tab = tab_buf.as<uint8_t>();
     EG_HIP(hipMemcpyAsync(tab, level_ids_host, tb, hipMemcpyHostToDevice, st));
-    EG_HIP(hipMemcpyAsync((uint8_t*)tab + tb, level_next_host, tn, hipMemcpyHostToDevice, st));
+    EG_HIP(hipMemcpyAsync(tab + tb, level_next_host, tn, hipMemcpyHostToDevice, st));
     EG_HIP(hipStreamSynchronize(st));
     a.ids = (const uint64_t* const*)tab;
-    a.next = (const int32_t* const*)((uint8_t*)tab + tb);
+    a.next = (const int32_t* const*)(tab + tb);
   }
   // The kernel is a chain of walk_len dependent 4-byte loads per walker: it wants WAVES in flight,
   // not a wide tile.  16 columns at a time (128-byte runs of a walker's row, 8.7 KB of LDS a wave:
@@ -1115,7 +1117,6 @@ static int LaunchShPath(hipStream_t st, const int64_t* starts_dev, int64_t n, in
   const int64_t tiles = (n + 63) / 64, wgs = (tiles + waves - 1) / waves;
   hipLaunchKernelGGL(ShWalkPathKernel, dim3((unsigned)(wgs < 65536 ? wgs : 65536)), dim3(64 * waves),
                      wave_bytes * waves, st, a);
-  if (tab != nullptr) (void)hipFreeAsync(tab, st);
   EG_HIP(hipGetLastError());
   return EULER_GPU_OK;
 }
@@ -1197,11 +1198,9 @@ int N2vIdxFromLens(hipStream_t st, const int32_t* lens_dev, int64_t m, int32_t* 
   if (m <= 0) return EULER_GPU_OK;
   size_t bytes = 0;
   EG_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, bytes, lens_dev, tmp_ends_dev, (int)m, st));
-  void* tmp = nullptr;
-  EG_HIP(hipMallocAsync(&tmp, bytes + 16, st));
-  const hipError_t e = hipcub::DeviceScan::InclusiveSum(tmp, bytes, lens_dev, tmp_ends_dev, (int)m, st);
-  (void)hipFreeAsync(tmp, st);
-  EG_HIP(e);
+  StreamBuf tmp(st);
+  EG_HIP(tmp.alloc(bytes + 16));
+  EG_HIP(hipcub::DeviceScan::InclusiveSum(tmp.as(), bytes, lens_dev, tmp_ends_dev, (int)m, st));
   hipLaunchKernelGGL(N2vIdxKernel, dim3(GridFor(m, 256)), dim3(256), 0, st, lens_dev, tmp_ends_dev, m, idx_dev);
   EG_HIP(hipGetLastError());
   return EULER_GPU_OK;
@@ -1602,12 +1601,6 @@ int euler_gpu_sample_node(const euler_gpu_graph* g, void* stream, uint64_t seed,
 
 }  // extern "C"
 
-// exclusive scan helper (mp_kernels.hip)
-namespace euler_gpu {
-int ExclusiveScanI64(hipStream_t stream, const int64_t* in, int64_t* out,
-                     int64_t n);
-}
-
 extern "C" {
 
 int euler_gpu_get_full_neighbor(const euler_gpu_graph* g, void* stream,
@@ -1628,8 +1621,9 @@ int euler_gpu_get_full_neighbor(const euler_gpu_graph* g, void* stream,
   for (int i = 0; i < k; ++i) a.et[i] = edge_types_host[i];
   const int block = 256;
   if (out_id_dev == nullptr) {
-    int64_t* counts = nullptr;
-    EG_HIP(hipMallocAsync((void**)&counts, (2 * n + 2) * sizeof(int64_t), st));
+    StreamBuf counts_buf(st);
+    EG_HIP(counts_buf.alloc((2 * n + 2) * sizeof(int64_t)));
+    int64_t* counts = counts_buf.as<int64_t>();
     int64_t* offsets = counts + n + 1;
     hipLaunchKernelGGL(FullNbCountKernel, dim3((n + block - 1) / block),
                        dim3(block), 0, st, a, counts);
@@ -1640,7 +1634,6 @@ int euler_gpu_get_full_neighbor(const euler_gpu_graph* g, void* stream,
     int32_t last[2];
     EG_HIP(hipMemcpyAsync(last, idx_dev + 2 * (n - 1), 8, hipMemcpyDeviceToHost, st));
     EG_HIP(hipStreamSynchronize(st));
-    EG_HIP(hipFreeAsync(counts, st));
     if (total_host) *total_host = last[1];
     return EULER_GPU_OK;
   }
@@ -1725,22 +1718,23 @@ int euler_gpu_node2vec_step(void* stream, uint64_t seed, uint32_t call_id, int64
     }
     // are the running sums of a step monotone (no negative weight among the fetched ones)?
     // The whole-wave path then re-runs only the chunks after a checkpoint (n2v_kernels.h).
-    int32_t* flag = nullptr;
-    EG_HIP(hipMallocAsync((void**)&flag, 16, (hipStream_t)stream));
+    StreamBuf flag_buf((hipStream_t)stream);
+    EG_HIP(flag_buf.alloc(16));
+    int32_t* flag = flag_buf.as<int32_t>();
     EG_HIP(hipMemsetD32Async((hipDeviceptr_t)flag, 1, 1, (hipStream_t)stream));
     if (c_entries > 0)
       hipLaunchKernelGGL(N2vNonNegKernel, dim3(GridFor(c_entries, 256)), dim3(256), 0, (hipStream_t)stream,
                          c_w_dev, c_entries, flag);
     w.nonneg_flag = flag;
     // long rows by a workgroup each (key 69: the threshold, 0 = none)
-    int32_t* q = nullptr;
+    StreamBuf q_buf((hipStream_t)stream);
     const int32_t big_at = g_n2v_list_big.load();
     const bool big = big_at > 0 && n <= (1ll << 30);
     if (big) {
       const size_t q_bytes = ((size_t)n * 4 + 15) & ~(size_t)15;
-      EG_HIP(hipMallocAsync((void**)&q, q_bytes + 16, (hipStream_t)stream));
-      w.big_queue = q;
-      w.big_count = (int32_t*)((uint8_t*)q + q_bytes);
+      EG_HIP(q_buf.alloc(q_bytes + 16));
+      w.big_queue = q_buf.as<int32_t>();
+      w.big_count = (int32_t*)(q_buf.as<uint8_t>() + q_bytes);
       w.big_threshold = big_at;
       w.big_parent = g_n2v_list_big_parent.load();
       w.ticket_batch = c_entries < 32 * n ? 8 : c_entries < 256 * n ? 2 : 1;
@@ -1753,8 +1747,6 @@ int euler_gpu_node2vec_step(void* stream, uint64_t seed, uint32_t call_id, int64
       if (wgs > 512) wgs = 512;
       hipLaunchKernelGGL(N2vListMergedKernel, dim3((unsigned)wgs), dim3(64 * kN2vBigWaves), 0, (hipStream_t)stream, w, a);
       EG_HIP(hipGetLastError());
-      EG_HIP(hipFreeAsync(flag, (hipStream_t)stream));
-      EG_HIP(hipFreeAsync(q, (hipStream_t)stream));
       return EULER_GPU_OK;
     }
     hipLaunchKernelGGL(Node2VecListWaveKernel<true>, dim3(GridFor(n * 64, 256)), dim3(256), 0,
@@ -1765,8 +1757,6 @@ int euler_gpu_node2vec_step(void* stream, uint64_t seed, uint32_t call_id, int64
     if (big)
       hipLaunchKernelGGL(N2vBigStepListKernel, dim3(512), dim3(64 * kN2vBigWaves), 0, (hipStream_t)stream, w, a);
     EG_HIP(hipGetLastError());
-    EG_HIP(hipFreeAsync(flag, (hipStream_t)stream));
-    if (q != nullptr) EG_HIP(hipFreeAsync(q, (hipStream_t)stream));
     return EULER_GPU_OK;
   } else {
     hipLaunchKernelGGL(Node2VecListStepKernel, dim3(GridFor(n, 256)), dim3(256), 0,
@@ -1788,9 +1778,11 @@ int euler_gpu_random_walk(const euler_gpu_graph* g, void* stream, uint64_t seed,
   if (!nodes_dev || !out_dev || (k > 0 && walk_len > 0 && !edge_types_host))
     return Fail(EULER_GPU_EINVAL, "random_walk: null buffer");
   hipStream_t st = (hipStream_t)stream;
-  int32_t* et_dev = nullptr;
   const size_t et_bytes = (size_t)walk_len * (k > 0 ? k : 1) * sizeof(int32_t) + 16;
-  EG_HIP(hipMallocAsync((void**)&et_dev, et_bytes, st));
+  // the edge-type table must outlive the kernel: stream-ordered free
+  StreamBuf et_dev_buf(st);
+  EG_HIP(et_dev_buf.alloc(et_bytes));
+  int32_t* et_dev = et_dev_buf.as<int32_t>();
   if (k > 0 && walk_len > 0)
     EG_HIP(hipMemcpyAsync(et_dev, edge_types_host,
                           (size_t)walk_len * k * sizeof(int32_t),
@@ -1798,7 +1790,7 @@ int euler_gpu_random_walk(const euler_gpu_graph* g, void* stream, uint64_t seed,
   WalkArgs a{};
   {
     const int rcv = SamplingView(g, &a.g);
-    if (rcv != EULER_GPU_OK) { (void)hipFreeAsync(et_dev, st); return rcv; }
+    if (rcv != EULER_GPU_OK) return rcv;
   }
   a.seed = seed; a.call_id = call_id; a.nodes = nodes_dev;
   a.edge_types = et_dev; a.out = out_dev; a.n = n; a.default_node = default_node;
@@ -1827,7 +1819,7 @@ int euler_gpu_random_walk(const euler_gpu_graph* g, void* stream, uint64_t seed,
     // through to the per-walker kernel, which needs none.
     bool merged = g_walk_collapse != 0 && walk_len >= 4 && n >= g_walk_collapse && n < ((int64_t)1 << 31) &&
                   g->view.n_rows < ((int64_t)1 << 31) - 2 && k > 0;
-    uint8_t* buf = nullptr;
+    StreamBuf walk_buf(st);
     size_t o_rec = 0, o_tid = 0, o_tsl = 0, o_own = 0, o_tr = 0, total = 0;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     // first step of the tail (walk_len: none)
@@ -1846,22 +1838,14 @@ int euler_gpu_random_walk(const euler_gpu_graph* g, void* stream, uint64_t seed,
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || total > free_b / 3) merged = false;
       }
-      if (merged && hipMallocAsync((void**)&buf, total, st) != hipSuccess) {
+      if (merged && walk_buf.alloc(total) != hipSuccess) {
         (void)hipGetLastError();          // clear the sticky allocation error
-        buf = nullptr;
         merged = false;
       }
     }
     if (merged) {
       // (CwSampleKernel ...; every error return below releases the scratch first)
-      struct Release {
-        uint8_t* p; hipStream_t s;
-        ~Release() { if (p != nullptr) (void)hipFreeAsync(p, s); }
-      } release{buf, st};
-      struct ReleaseEt {
-        int32_t* p; hipStream_t s; bool armed;
-        ~ReleaseEt() { if (armed) (void)hipFreeAsync(p, s); }
-      } release_et{et_dev, st, true};
+      uint8_t* buf = walk_buf.as<uint8_t>();
       CwArgs c{};
       c.g = a.g; c.seed = seed; c.call_id = call_id; c.edge_types = et_dev; c.k = k;
       c.walk_len = walk_len; c.cap = n; c.default_node = default_node; c.fast = fast ? 1 : 0;
@@ -1921,7 +1905,6 @@ int euler_gpu_random_walk(const euler_gpu_graph* g, void* stream, uint64_t seed,
                            lds, st, tr, out_dev, n, L, ch);
       }
       EG_HIP(hipGetLastError());
-      release_et.armed = false;       // the common exit below frees the edge-type table
     } else if (fast) {
       hipLaunchKernelGGL(RandomWalkKernel<true>, dim3(GridFor(n, block)), dim3(block), 0,
                          st, a);
@@ -1933,9 +1916,10 @@ int euler_gpu_random_walk(const euler_gpu_graph* g, void* stream, uint64_t seed,
     if (g_n2v_wave >= 3 && walk_len > 0 && n < (1ll << 31)) {
       // step by step: classify, the short lists one wave per walker, the long ones one
       // workgroup per walker from a queue handed out by an atomic counter
-      int32_t* q = nullptr;
       const size_t q_bytes = ((size_t)n * 4 + 15) & ~(size_t)15;
-      EG_HIP(hipMallocAsync((void**)&q, q_bytes + (size_t)walk_len * 8, st));
+      StreamBuf q_buf(st);
+      EG_HIP(q_buf.alloc(q_bytes + (size_t)walk_len * 8));
+      int32_t* q = q_buf.as<int32_t>();
       int32_t* counters = (int32_t*)((uint8_t*)q + q_bytes);
       EG_HIP(hipMemsetAsync(counters, 0, (size_t)walk_len * 8, st));
       a.big_threshold = g_n2v_big > 0 ? g_n2v_big : (1 << 30);
@@ -1952,17 +1936,15 @@ int euler_gpu_random_walk(const euler_gpu_graph* g, void* stream, uint64_t seed,
           hipLaunchKernelGGL(N2vBigStepKernel, dim3(512), dim3(64 * kN2vBigWaves), 0, st, a);
       }
       EG_HIP(hipGetLastError());
-      EG_HIP(hipFreeAsync(q, st));
     } else if (g_n2v_wave >= 2) {
-      unsigned long long* ticket = nullptr;
+      StreamBuf ticket(st);
       if (g_n2v_walk_tickets.load() != 0 && n > 16384) {      // (fewer walkers than waves: one each)
-        EG_HIP(hipMallocAsync((void**)&ticket, 8, st));
-        EG_HIP(hipMemsetAsync(ticket, 0, 8, st));
-        a.walk_ticket = ticket;
+        EG_HIP(ticket.alloc(8));
+        EG_HIP(hipMemsetAsync(ticket.as(), 0, 8, st));
+        a.walk_ticket = ticket.as<unsigned long long>();
       }
       hipLaunchKernelGGL(Node2VecWaveKernel<true>, dim3(GridFor(n * 64, block)), dim3(block), 0,
                          st, a);
-      if (ticket != nullptr) EG_HIP(hipFreeAsync(ticket, st));
     } else if (g_n2v_wave != 0) {
       hipLaunchKernelGGL(Node2VecWaveKernel<false>, dim3(GridFor(n * 64, block)), dim3(block), 0,
                          st, a);
@@ -1971,8 +1953,6 @@ int euler_gpu_random_walk(const euler_gpu_graph* g, void* stream, uint64_t seed,
     }
   }
   EG_HIP(hipGetLastError());
-  // the edge-type table must outlive the kernel: stream-ordered free
-  EG_HIP(hipFreeAsync(et_dev, st));
   return EULER_GPU_OK;
 }
 
@@ -2002,9 +1982,10 @@ int euler_gpu_random_walk_algo_bytes(const euler_gpu_graph* g, void* stream,
   if (!walks_dev || (k > 0 && !edge_types_host))
     return Fail(EULER_GPU_EINVAL, "random_walk_algo_bytes: null buffer");
   hipStream_t st = (hipStream_t)stream;
-  uint8_t* buf = nullptr;
   const size_t et_bytes = ((size_t)walk_len * (k > 0 ? k : 1) * sizeof(int32_t) + 15) & ~(size_t)15;
-  EG_HIP(hipMallocAsync((void**)&buf, et_bytes + 16, st));
+  StreamBuf buf_buf(st);
+  EG_HIP(buf_buf.alloc(et_bytes + 16));
+  uint8_t* buf = buf_buf.as<uint8_t>();
   double* acc = (double*)(buf + et_bytes);
   EG_HIP(hipMemsetAsync(acc, 0, 8, st));
   if (k > 0)
@@ -2022,7 +2003,6 @@ int euler_gpu_random_walk_algo_bytes(const euler_gpu_graph* g, void* stream,
   EG_HIP(hipGetLastError());
   EG_HIP(hipMemcpyAsync(bytes_host, acc, 8, hipMemcpyDeviceToHost, st));
   EG_HIP(hipStreamSynchronize(st));
-  EG_HIP(hipFreeAsync(buf, st));
   return EULER_GPU_OK;
 }
 
@@ -2061,8 +2041,9 @@ int euler_gpu_sample_neighbor_algo_bytes(const euler_gpu_graph* g, void* stream,
   if (n < 0 || k < 0 || k > kMaxListedTypes || !bytes_host)
     return Fail(EULER_GPU_EINVAL, "algo_bytes: bad arguments");
   hipStream_t st = (hipStream_t)stream;
-  double* acc = nullptr;
-  EG_HIP(hipMallocAsync((void**)&acc, sizeof(double), st));
+  StreamBuf acc_buf(st);
+  EG_HIP(acc_buf.alloc(sizeof(double)));
+  double* acc = acc_buf.as<double>();
   EG_HIP(hipMemsetAsync(acc, 0, sizeof(double), st));
   FullNbArgs a{};
   a.g = g->view; a.ids = roots_dev; a.n = n; a.k = k;
@@ -2073,7 +2054,6 @@ int euler_gpu_sample_neighbor_algo_bytes(const euler_gpu_graph* g, void* stream,
                        0, st, a, count, acc);
   EG_HIP(hipMemcpyAsync(bytes_host, acc, sizeof(double), hipMemcpyDeviceToHost, st));
   EG_HIP(hipStreamSynchronize(st));
-  EG_HIP(hipFreeAsync(acc, st));
   return EULER_GPU_OK;
 }
 

@@ -518,7 +518,13 @@ def test_python_deepwalk_example(EA, O, torch_cuda, capsys, monkeypatch):
     rng = np.random.default_rng(3)
     w = (0.25 + rng.random(N)).astype(np.float32)
     ty = rng.integers(0, 3, N).astype(np.int32)
+    # a replaced table takes its bytes with it: N entries, N // 2 (explicit ids), N again
     G.set_node_sampler(None, ty, w, 3)
+    bytes_n = G.device_bytes
+    G.set_node_sampler(np.arange(1, N // 2 + 1, dtype=np.uint64), ty[:N // 2], w[:N // 2], 3)
+    bytes_half = G.device_bytes
+    G.set_node_sampler(None, ty, w, 3)
+    assert bytes_half != bytes_n and G.device_bytes == bytes_n
     G.set_seed(77, 10)
     EA.euler_ops.set_default_graph(G)
     po = O.SynthParams()
