@@ -254,6 +254,13 @@ struct euler_gpu_graph {
   int32_t n_u64 = 0;
   bool feat_slot_aligned = false;     // uniform feature table: every slot begins at a
                                       // multiple of 4 floats (16-byte lanes allowed)
+  // dense features stored in 16 bits (euler_gpu_graph_set_dense_feature_dtype, mp_half_kernels.hip):
+  // the value array of view.feat_val converted element by element - every offset of the view
+  // still holds, in elements - and view.feat_val nulled.  Kept here, not in the view: the
+  // sampling kernels take the view by value.
+  const void* feat16 = nullptr;
+  int32_t feat_dtype = 0;             // EULER_GPU_F32 / _BF16 / _F16
+  bool feat_slot_aligned8 = false;    // uniform table: stride and every slot begin % 8 == 0
   // edge store (edge_kernels.hip); its allocations are listed here, not in `allocations`, so
   // that a new store can replace it.  The edge sampler's entries are alias entries whose ids are
   // slot positions.

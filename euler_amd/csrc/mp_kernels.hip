@@ -14,6 +14,7 @@
 
 #include "device_fns.h"
 #include "device_mem.h"
+#include "mp_segments.h"
 
 struct euler_gpu_front {
   int64_t* stage = nullptr;      // pinned + mapped: [kMaxShards + 1] bucket starts, then the sequence word
@@ -76,55 +77,6 @@ __global__ void IsSortedKernel(const int32_t* idx, int64_t e, int32_t* flag) {
 __global__ void IotaKernel(uint32_t* v, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) v[i] = (uint32_t)i;
-}
-
-__device__ __forceinline__ int64_t LowerBound(const int32_t* a, int64_t n,
-                                              int32_t key) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (a[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-// Segment [b, en) of destination r in the grouped key array.  Sampled blocks
-// scatter `count` updates to every destination in order (keys = 0,0,..,1,1,..): the
-// proportional guess r * e / size is then exact and costs two loads; anything else
-// falls back to the bisection.
-__device__ __forceinline__ int64_t SegStart(const int32_t* keys, int64_t e, int32_t size,
-                                            int64_t r) {
-  // r == size: the end of the LAST destination's segment - the first key >= size, not e:
-  // out-of-range scatter indices (undefined behaviour in the reference,
-  // tf_euler/kernels/scatter_op.cc:27-105) are left out instead of being folded into
-  // row size - 1
-  if (r >= size) return (e > 0 && keys[e - 1] >= size) ? LowerBound(keys, e, size) : e;
-  const int64_t g = r * e / size;
-  if ((g == 0 || keys[g - 1] < (int32_t)r) && (g == e || keys[g] >= (int32_t)r)) return g;
-  return LowerBound(keys, e, (int32_t)r);
-}
-
-// Where destination r's updates are: a grouped key array (scatter: bisected / guessed),
-// explicit offsets (segment reduce), or `count` updates per destination.
-struct SegSpec {
-  const int32_t* keys;
-  const int64_t* ptr;      // [size + 1] when keys == nullptr (nullptr: uniform `count`)
-  int64_t count;
-  int64_t e;
-  int32_t size;
-};
-
-__device__ __forceinline__ void SegBounds(const SegSpec& s, int64_t r, int64_t* b, int64_t* en) {
-  if (s.keys != nullptr) {
-    *b = SegStart(s.keys, s.e, s.size, r);
-    *en = SegStart(s.keys, s.e, s.size, r + 1);
-  } else if (s.ptr != nullptr) {
-    *b = s.ptr[r];
-    *en = s.ptr[r + 1];
-  } else {
-    *b = r * s.count;
-    *en = *b + s.count;
-  }
 }
 
 // One wave-slot per output row: blockDim = (64, 4): 4 rows per block,
@@ -268,19 +220,10 @@ __global__ __launch_bounds__(256) void SegmentReduceVec4Kernel(
   }
 }
 
-template <int MODE>
-static int ScatterImpl(hipStream_t st, const float* upd, const int32_t* idx,
-                       int64_t e, int64_t d, int32_t size, float* out,
-                       const int32_t* gsrc = nullptr) {
-  if (e < 0 || d < 0 || size < 0) return Fail(EULER_GPU_EINVAL, "scatter: bad shape");
-  if (size == 0 || d == 0) return EULER_GPU_OK;
-  if (!out || (e > 0 && (!upd || !idx)))
-    return Fail(EULER_GPU_EINVAL, "scatter: null buffer");
-  if (e >= (1LL << 31)) return Fail(EULER_GPU_EINVAL, "scatter: e >= 2^31");
-  const int32_t* keys = idx;
-  const uint32_t* perm = nullptr;
-  // stream-ordered scratch of the unsorted path, released on every exit
-  StreamBuf scratch(st);
+int GroupScatterKeys(hipStream_t st, const int32_t* idx, int64_t e, StreamBuf* scratch,
+                     const int32_t** keys, const uint32_t** perm) {
+  *keys = idx;
+  *perm = nullptr;
   if (e > 1) {
     StreamBuf flag_buf(st);
     EG_HIP(flag_buf.alloc(16));
@@ -295,8 +238,8 @@ static int ScatterImpl(hipStream_t st, const float* upd, const int32_t* idx,
       // stable sort of (destination, original position)
       const size_t n = (size_t)e;
       const size_t bytes = n * (4 + 4 + 4 + 4) + 64;
-      EG_HIP(scratch.alloc(bytes));
-      int32_t* keys_out = scratch.as<int32_t>();
+      EG_HIP(scratch->alloc(bytes));
+      int32_t* keys_out = scratch->as<int32_t>();
       uint32_t* vals_in = (uint32_t*)(keys_out + n);
       uint32_t* vals_out = vals_in + n;
       hipLaunchKernelGGL(IotaKernel, dim3((e + 255) / 256), dim3(256), 0, st,
@@ -310,9 +253,29 @@ static int ScatterImpl(hipStream_t st, const float* upd, const int32_t* idx,
       EG_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.as(), tmp_bytes, idx, keys_out,
                                                 vals_in, vals_out, (int)e, 0, 32,
                                                 st));
-      keys = keys_out;
-      perm = vals_out;
+      *keys = keys_out;
+      *perm = vals_out;
     }
+  }
+  return EULER_GPU_OK;
+}
+
+template <int MODE>
+static int ScatterImpl(hipStream_t st, const float* upd, const int32_t* idx,
+                       int64_t e, int64_t d, int32_t size, float* out,
+                       const int32_t* gsrc = nullptr) {
+  if (e < 0 || d < 0 || size < 0) return Fail(EULER_GPU_EINVAL, "scatter: bad shape");
+  if (size == 0 || d == 0) return EULER_GPU_OK;
+  if (!out || (e > 0 && (!upd || !idx)))
+    return Fail(EULER_GPU_EINVAL, "scatter: null buffer");
+  if (e >= (1LL << 31)) return Fail(EULER_GPU_EINVAL, "scatter: e >= 2^31");
+  const int32_t* keys = idx;
+  const uint32_t* perm = nullptr;
+  // stream-ordered scratch of the unsorted path, released on every exit
+  StreamBuf scratch(st);
+  {
+    const int rc = GroupScatterKeys(st, idx, e, &scratch, &keys, &perm);
+    if (rc != EULER_GPU_OK) return rc;
   }
   const dim3 block(64, 4);
   const int64_t d4 = d / 4;
@@ -996,6 +959,9 @@ int euler_gpu_get_dense_feature(const euler_gpu_graph* g, void* stream,
   if (n == 0 || dim == 0) return EULER_GPU_OK;
   if (!nodes_dev || !out_dev)
     return Fail(EULER_GPU_EINVAL, "get_dense_feature: null buffer");
+  // a table converted to bf16 / fp16 (mp_half_kernels.hip): fp32 rows of the rounded values
+  if (g->feat_dtype != EULER_GPU_F32)
+    return euler_gpu_get_dense_feature_t(g, stream, nodes_dev, n, fid, dim, out_dev, EULER_GPU_F32);
   const int block = 256;
   const GraphView& v = g->view;
   const bool vec4 = g_feature_vec4 != 0 && v.feat_uniform && fid >= 0 && fid < v.n_float && dim % 4 == 0 &&

@@ -979,7 +979,9 @@ def gpu_sharded_sampler(graph, partitions=None, group=None, dedup=True, dense_id
             S.local_sample_packed = graph.sample_neighbor_packed
             S.local_sample_sets_packed = graph.sample_neighbor_sets_packed
     S.device = graph.device
-    S.local_feature = graph.get_dense_feature
+    # (the exchange moves fp32 rows: a 16-bit table - possible on an unsharded graph only - is widened)
+    S.local_feature = lambda ids, fids, dims: graph.get_dense_feature(ids, fids, dims,
+                                                                      out_dtype=torch.float32)
     S.row_gather_fn = lambda rows, pos: ops.gather(rows, pos.to(torch.int32))
     S.local_sample_node = lambda count, node_type, call_id: graph.sample_node(
         count, node_type, call_id=call_id)

@@ -85,7 +85,7 @@ def to_sparse(idx, values):
 
 def sample_fanout_with_feature(nodes, edge_types, count, default_node,
                                dense_feature_names, dense_dimensions,
-                               sparse_feature_names=(), sparse_default_values=()):
+                               sparse_feature_names=(), sparse_default_values=(), out_dtype=None):
     """sample_fanout + the dense features of every layer's nodes in one call
     (neighbor_ops.py:49-70 over tf_euler/kernels/sample_fanout_with_feature_op.cc):
     returns (neighbors, weights, types, dense_features, sparse_features) with
@@ -93,7 +93,8 @@ def sample_fanout_with_feature(nodes, edge_types, count, default_node,
     (layer 0 = the roots), as the op lays its outputs out (:135-178,233).
     sparse_features[layer * len(sparse names) + j] likewise, each a
     SparseTensor triple (indices, values, dense_shape) with the per-feature
-    default values (tf_euler/kernels/sample_fanout_with_feature_op.cc:180-232)."""
+    default values (tf_euler/kernels/sample_fanout_with_feature_op.cc:180-232).  out_dtype: the
+    dtype of the dense rows, as Graph.get_dense_feature."""
     g = base.get_default_graph()
     ets = [type_ops.get_edge_type_id(et) for et in edge_types]
     fids = [int(str(f)) for f in dense_feature_names]
@@ -103,7 +104,7 @@ def sample_fanout_with_feature(nodes, edge_types, count, default_node,
     # (euler_gpu_sample_fanout_with_feature); the sparse features need their sizes on the
     # host, one query per layer
     neighbors, weights, types, dense = g.sample_fanout_with_feature(
-        nodes, ets, count, default_node, fids, list(dense_dimensions))
+        nodes, ets, count, default_node, fids, list(dense_dimensions), out_dtype=out_dtype)
     sparse = []
     for layer_nodes in neighbors:
         if sfids:

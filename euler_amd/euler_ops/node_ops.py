@@ -82,13 +82,14 @@ def random_walk(nodes, edge_types, p=1.0, q=1.0, default_node=-1):
 
 
 # ---- features (feature_ops.py)
-def get_dense_feature(nodes, feature_names, dimensions, thread_num=1):
-    """Fetch dense (float) features of nodes: a list of [n, dim] float32
-    tensors, one per feature id in `feature_names` (ints, or their string
+def get_dense_feature(nodes, feature_names, dimensions, thread_num=1, out_dtype=None):
+    """Fetch dense (float) features of nodes: a list of [n, dim] tensors (float32, or the
+    dtype Graph.set_dense_feature_dtype stored the table in; out_dtype as
+    Graph.get_dense_feature), one per feature id in `feature_names` (ints, or their string
     forms as tf_euler passes them).  thread_num is accepted for signature
     compatibility; the fetch is one kernel per feature."""
     fids = [int(str(f)) for f in feature_names]
-    return base.get_default_graph().get_dense_feature(nodes, fids, list(dimensions))
+    return base.get_default_graph().get_dense_feature(nodes, fids, list(dimensions), out_dtype=out_dtype)
 
 
 def get_sparse_feature(nodes, feature_names, default_values=None, thread_num=1):

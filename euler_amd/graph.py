@@ -639,12 +639,14 @@ class Graph:
         return id1, w1, t1, idx.to(torch.int64) & 0xFFFFFFFF, rid, rw, rt
 
     def sample_fanout_with_feature(self, nodes, edge_types, counts, default_node,
-                                   feature_ids, dimensions, call_id=None):
+                                   feature_ids, dimensions, call_id=None, out_dtype=None):
         """tf_euler sample_fanout_with_feature, dense part (euler_ops/neighbor_ops.py:49-70
         over tf_euler/kernels/sample_fanout_with_feature_op.cc:135-233) as ONE enqueue
         (euler_gpu_sample_fanout_with_feature): returns (neighbors_list, weights_list,
         types_list, dense_features) with dense_features[layer * len(feature_ids) + j] =
-        [m_layer, dimensions[j]] float32, layer 0 = the roots."""
+        [m_layer, dimensions[j]], layer 0 = the roots.  out_dtype as get_dense_feature (16-bit
+        rows are fetched per layer after the fanout's enqueue)."""
+        od = self._feature_out_dtype(out_dtype)
         nodes = _as_i64_cuda(nodes, self.device).reshape(-1)
         layers = len(counts)
         et = np.asarray(edge_types, dtype=np.int32).reshape(layers, -1)
@@ -664,8 +666,10 @@ class Graph:
             outs_n.append(torch.empty(m, dtype=torch.int64, device=self.device))
             outs_w.append(torch.empty(m, dtype=torch.float32, device=self.device))
             outs_t.append(torch.empty(m, dtype=torch.int32, device=self.device))
+        if od != torch.float32:
+            nd = 0              # the entry writes fp32 rows: the typed fetch follows the fanout
         for ml in sizes:
-            for d in dimensions:
+            for d in (dimensions if nd else ()):
                 dense.append(torch.empty((ml, int(d)), dtype=torch.float32, device=self.device))
         ws_bytes = lib().euler_gpu_sample_fanout_workspace(n, cnt_p, layers)
         ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=self.device)
@@ -678,6 +682,9 @@ class Graph:
                 self._h, _stream(), self.seed, self._take_call_ids(layers, call_id),
                 _ptr(nodes), n, et_p, k, cnt_p, layers, int(default_node), pn, pw, pt, _ptr(ws),
                 fid_p, dim_p, nd, pd))
+        if od != torch.float32:
+            for layer_nodes in [nodes] + outs_n:
+                dense.extend(self.get_dense_feature(layer_nodes, feature_ids, dimensions, out_dtype=od))
         return [nodes] + outs_n, outs_w, outs_t, dense
 
     def sage_blocks(self, nodes, edge_types, fanouts, default_node=-1, add_self_loops=True,
@@ -864,19 +871,67 @@ class Graph:
     def num_float_features(self):
         return lib().euler_gpu_graph_num_float_features(self._h)
 
-    def get_dense_feature(self, nodes, feature_ids, dimensions):
+    _FEAT_DT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
+    _FEAT_TORCH = {v: k for k, v in _FEAT_DT.items()}
+
+    @property
+    def dense_feature_dtype(self):
+        """storage dtype of the dense feature table: torch.float32 until
+        set_dense_feature_dtype converts it"""
+        return self._FEAT_TORCH[lib().euler_gpu_graph_dense_feature_dtype(self._h)]
+
+    def set_dense_feature_dtype(self, dtype):
+        """Store the dense feature table as torch.bfloat16 or torch.float16
+        (euler_gpu_graph_set_dense_feature_dtype): every value rounded once, to nearest even,
+        on the device; the fp32 table is freed (device_bytes drops by half the table).  The
+        same dtype again is a no-op; a 16-bit table cannot be converted again (ValueError),
+        nor can a shard of a sharded graph.  Waits for the device."""
+        if dtype not in self._FEAT_DT:
+            raise TypeError("set_dense_feature_dtype: float32, bfloat16 or float16, not %s" % (dtype,))
+        with self._on_device():
+            try:
+                check(lib().euler_gpu_graph_set_dense_feature_dtype(self._h, _stream(),
+                                                                    self._FEAT_DT[dtype]))
+            except _lib.EulerGpuError as err:
+                if err.code == _lib.EINVAL:
+                    raise ValueError(str(err)) from None
+                raise
+        return self
+
+    def _feature_out_dtype(self, out_dtype):
+        """None = the table's dtype; else fp32 or - for an fp32 table - either 16-bit type"""
+        table = self.dense_feature_dtype
+        if out_dtype is None:
+            return table
+        if out_dtype not in self._FEAT_DT:
+            raise TypeError("get_dense_feature: out_dtype is float32, bfloat16 or float16, not %s"
+                            % (out_dtype,))
+        if table != torch.float32 and out_dtype not in (torch.float32, table):
+            raise TypeError("get_dense_feature: out_dtype is float32 or the table's dtype (%s), not %s"
+                            % (table, out_dtype))
+        return out_dtype
+
+    def get_dense_feature(self, nodes, feature_ids, dimensions, out_dtype=None):
         """tf_euler get_dense_feature (euler_ops/feature_ops.py:108-122 over
         tf_euler/kernels/get_dense_feature_op.cc): nodes [n] int64 -> list of
-        [n, dim] float32 tensors, one per feature id; unknown nodes and missing
-        features are zero rows."""
+        [n, dim] tensors, one per feature id; unknown nodes and missing
+        features are zero rows.  out_dtype: None = the table's dtype (float32 unless
+        set_dense_feature_dtype changed it); torch.float32 widens a 16-bit table's rows;
+        a 16-bit type on an fp32 table rounds the rows once at the store."""
+        od = self._feature_out_dtype(out_dtype)
         nodes = _as_i64_cuda(nodes, self.device).reshape(-1)
         n = nodes.numel()
         outs = []
         with self._on_device():
             for fid, dim in zip(feature_ids, dimensions):
-                out = torch.empty((n, int(dim)), dtype=torch.float32, device=self.device)
-                check(lib().euler_gpu_get_dense_feature(
-                    self._h, _stream(), _ptr(nodes), n, int(fid), int(dim), _ptr(out)))
+                out = torch.empty((n, int(dim)), dtype=od, device=self.device)
+                if od == torch.float32:
+                    check(lib().euler_gpu_get_dense_feature(
+                        self._h, _stream(), _ptr(nodes), n, int(fid), int(dim), _ptr(out)))
+                else:
+                    check(lib().euler_gpu_get_dense_feature_t(
+                        self._h, _stream(), _ptr(nodes), n, int(fid), int(dim), _ptr(out),
+                        self._FEAT_DT[od]))
                 outs.append(out)
         return outs
 

@@ -45,59 +45,119 @@ def _need_cuda(*ts):
                                "(no CPU fallback)")
 
 
-def _gather_raw(params, indices):
+_DT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
+_F32 = torch.float32
+
+
+def _dt(name, t):
+    """dtype code of a data tensor; anything but fp32 / bf16 / fp16 is an error, never a
+    reinterpretation of its bytes"""
+    try:
+        return _DT[t.dtype]
+    except KeyError:
+        raise TypeError("%s: data must be float32, bfloat16 or float16, not %s" % (name, t.dtype))
+
+
+def _out_dt(name, t, out_dtype):
+    """out_dtype None = the input's dtype; else fp32 or the input's dtype"""
+    if out_dtype is None or out_dtype == t.dtype:
+        return t.dtype
+    if out_dtype != _F32:
+        raise TypeError("%s: out_dtype is float32 or the input's dtype (%s), not %s"
+                        % (name, t.dtype, out_dtype))
+    return _F32
+
+
+def _gather_raw(params, indices, out_dtype=None):
+    code = _dt("gather", params)
+    od = _out_dt("gather", params, out_dtype)
     params = params.contiguous()
     indices = indices.to(torch.int32).contiguous()
     _need_cuda(params, indices)
     e, d = indices.numel(), params.shape[1]
-    out = torch.empty((e, d), dtype=torch.float32, device=params.device)
+    out = torch.empty((e, d), dtype=od, device=params.device)
     with _on(params.device):
-        check(lib().euler_gpu_gather(_stream(), _ptr(params), _ptr(indices), e, d,
-                                     params.shape[0], _ptr(out)))
+        if code == _lib.F32:
+            check(lib().euler_gpu_gather(_stream(), _ptr(params), _ptr(indices), e, d,
+                                         params.shape[0], _ptr(out)))
+        else:
+            check(lib().euler_gpu_gather_t(_stream(), _ptr(params), code, _ptr(indices), e, d,
+                                           params.shape[0], _ptr(out), _DT[od]))
     return out
 
 
-def _scatter_raw(fn, updates, indices, size):
+_SCATTER_F32 = ("euler_gpu_scatter_add", "euler_gpu_scatter_max", "euler_gpu_scatter_mean")
+
+
+def _scatter_raw(mode, updates, indices, size, out_dtype=None):
+    """mode: 0 add, 1 max, 2 mean"""
+    code = _dt("scatter", updates)
+    od = _out_dt("scatter", updates, out_dtype)
     updates = updates.contiguous()
     indices = indices.to(torch.int32).contiguous()
     _need_cuda(updates, indices)
     e, d = updates.shape
-    out = torch.empty((int(size), d), dtype=torch.float32, device=updates.device)
+    out = torch.empty((int(size), d), dtype=od, device=updates.device)
     with _on(updates.device):
-        check(fn(_stream(), _ptr(updates), _ptr(indices), e, d, int(size), _ptr(out)))
+        if code == _lib.F32:
+            check(getattr(lib(), _SCATTER_F32[mode])(_stream(), _ptr(updates), _ptr(indices), e, d,
+                                                     int(size), _ptr(out)))
+        else:
+            check(lib().euler_gpu_scatter_t(_stream(), mode, _ptr(updates), code, _ptr(indices), e, d,
+                                            int(size), _ptr(out), _DT[od]))
     return out
 
 
-# Gradients as registered in tf_euler/python/euler_ops/mp_ops.py:39-62.
+_ADD, _MAX, _MEAN = 0, 1, 2
+
+
+def _count(indices, size, device):
+    """scatter_add(ones) + 1e-7, fp32: the denominator of the mean's gradient"""
+    ones = torch.ones((indices.numel(), 1), dtype=_F32, device=device)
+    return _scatter_raw(_ADD, ones, indices, size) + 1e-7
+
+
+def _max_per_edge(updates32, out, si, size, grad):
+    """the per-edge gradient of a max reduce (mp_ops.py:39-62), all fp32"""
+    indicators = (updates32 == _gather_raw(out, si, _F32)).to(_F32)
+    num_selected = _scatter_raw(_ADD, indicators, si, size)
+    return indicators / _gather_raw(num_selected, si) * _gather_raw(grad, si, _F32)
+
+
+# Gradients as registered in tf_euler/python/euler_ops/mp_ops.py:39-62.  With 16-bit data the
+# formulas are the same and run in fp32: every intermediate of a backward pass is taken with
+# out_dtype = fp32 (the widening is exact), and the gradient is rounded once, to the dtype of the
+# input it belongs to.  `grad` may arrive as fp32 or in 16 bits.
 class _Gather(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, params, indices):
+    def forward(ctx, params, indices, out_dtype):
         ctx.save_for_backward(indices)
-        ctx.n = params.shape[0]
-        return _gather_raw(params, indices)
+        ctx.n, ctx.dt = params.shape[0], params.dtype
+        return _gather_raw(params, indices, out_dtype)
 
     @staticmethod
     def backward(ctx, grad):
         (indices,) = ctx.saved_tensors
-        return _scatter_raw(lib().euler_gpu_scatter_add, grad, indices, ctx.n), None
+        return _scatter_raw(_ADD, grad, indices, ctx.n, _F32).to(ctx.dt), None, None
 
 
 class _ScatterAdd(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, updates, indices, size):
+    def forward(ctx, updates, indices, size, out_dtype):
         ctx.save_for_backward(indices)
-        return _scatter_raw(lib().euler_gpu_scatter_add, updates, indices, size)
+        ctx.dt = updates.dtype
+        return _scatter_raw(_ADD, updates, indices, size, out_dtype)
 
     @staticmethod
     def backward(ctx, grad):
         (indices,) = ctx.saved_tensors
-        return _gather_raw(grad, indices), None, None
+        return _gather_raw(grad, indices, _F32).to(ctx.dt), None, None, None
 
 
 class _ScatterMax(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, updates, indices, size):
-        out = _scatter_raw(lib().euler_gpu_scatter_max, updates, indices, size)
+    def forward(ctx, updates, indices, size, out_dtype):
+        out = _scatter_raw(_MAX, updates, indices, size, out_dtype)
         ctx.save_for_backward(updates, indices, out)
         ctx.size = size
         return out
@@ -105,26 +165,29 @@ class _ScatterMax(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad):
         updates, indices, out = ctx.saved_tensors
-        indicators = (updates == _gather_raw(out, indices)).to(updates.dtype)
-        num_selected = _scatter_raw(lib().euler_gpu_scatter_add, indicators,
-                                    indices, ctx.size)
-        indicators = indicators / _gather_raw(num_selected, indices)
-        return indicators * _gather_raw(grad, indices), None, None
+        per_edge = _max_per_edge(updates.to(_F32), out, indices, ctx.size, grad)
+        return per_edge.to(updates.dtype), None, None, None
 
 
-def gather(params, indices):
-    """MPGather: out[i,:] = params[indices[i],:] (fp32, int32 indices)."""
-    return _Gather.apply(params, indices)
+def gather(params, indices, out_dtype=None):
+    """MPGather: out[i,:] = params[indices[i],:] (fp32, bf16 or fp16 rows, int32 indices).
+    out_dtype: None = the dtype of params, or torch.float32 for 16-bit params (the rows widened,
+    which is exact)."""
+    return _Gather.apply(params, indices, out_dtype)
 
 
-def scatter_add(updates, indices, size):
-    """MPScatterAdd: out[indices[i],:] += updates[i,:], zero init, [size,D]."""
-    return _ScatterAdd.apply(updates, indices, int(size))
+def scatter_add(updates, indices, size, out_dtype=None):
+    """MPScatterAdd: out[indices[i],:] += updates[i,:], zero init, [size,D].  16-bit updates are
+    added in fp32, in input order - the bits of the fp32 op on updates.float() - and the sums
+    are returned as fp32 (out_dtype=torch.float32) or rounded once to the updates' dtype
+    (out_dtype=None)."""
+    return _ScatterAdd.apply(updates, indices, int(size), out_dtype)
 
 
-def scatter_max(updates, indices, size):
-    """MPScatterMax: element-wise max per destination, -1e9 for empty rows."""
-    return _ScatterMax.apply(updates, indices, int(size))
+def scatter_max(updates, indices, size, out_dtype=None):
+    """MPScatterMax: element-wise max per destination, -1e9 for empty rows (rounded to the
+    output's dtype).  out_dtype as scatter_add."""
+    return _ScatterMax.apply(updates, indices, int(size), out_dtype)
 
 
 class _ScatterMean(torch.autograd.Function):
@@ -132,29 +195,29 @@ class _ScatterMean(torch.autograd.Function):
     the gradient of the composition: grad / (count + 1e-7) gathered back."""
 
     @staticmethod
-    def forward(ctx, updates, indices, size):
+    def forward(ctx, updates, indices, size, out_dtype):
         ctx.save_for_backward(indices)
-        ctx.size = size
-        return _scatter_raw(lib().euler_gpu_scatter_mean, updates, indices, size)
+        ctx.size, ctx.dt = size, updates.dtype
+        return _scatter_raw(_MEAN, updates, indices, size, out_dtype)
 
     @staticmethod
     def backward(ctx, grad):
         (indices,) = ctx.saved_tensors
-        ones = torch.ones((indices.numel(), 1), dtype=torch.float32, device=grad.device)
-        count = _scatter_raw(lib().euler_gpu_scatter_add, ones, indices, ctx.size) + 1e-7
-        return _gather_raw(grad / count, indices), None, None
+        count = _count(indices, ctx.size, grad.device)
+        return _gather_raw(grad / count, indices).to(ctx.dt), None, None, None
 
 
-def scatter_mean(updates, indices, size):
-    """mp_ops.py:65-69."""
+def scatter_mean(updates, indices, size, out_dtype=None):
+    """mp_ops.py:65-69.  out_dtype as scatter_add."""
     if updates.shape[0] < (1 << 24):
-        return _ScatterMean.apply(updates, indices, int(size))
-    out = scatter_add(updates, indices, size)
+        return _ScatterMean.apply(updates, indices, int(size), out_dtype)
+    od = _out_dt("scatter_mean", updates, out_dtype)
+    out = scatter_add(updates, indices, size, out_dtype=_F32)
     ep = 1e-7
     ones = torch.ones((updates.shape[0], 1), dtype=torch.float32,
                       device=updates.device)
     count = scatter_add(ones, indices, size) + ep
-    return out / count
+    return (out / count).to(od)
 
 
 _GS_MODE = {"add": 0, "max": 1, "mean": 2}
@@ -166,7 +229,10 @@ def _check_rows(name, gi, n_rows):
         raise IndexError("%s: gather index out of range" % name)
 
 
-def _gather_scatter_raw(mode, params, gather_indices, scatter_indices, size, validate=False):
+def _gather_scatter_raw(mode, params, gather_indices, scatter_indices, size, validate=False,
+                        out_dtype=None):
+    code = _dt("gather_scatter", params)
+    od = _out_dt("gather_scatter", params, out_dtype)
     params = params.contiguous()
     gi = gather_indices.to(torch.int32).contiguous()
     si = scatter_indices.to(torch.int32).contiguous()
@@ -177,11 +243,24 @@ def _gather_scatter_raw(mode, params, gather_indices, scatter_indices, size, val
     if validate:
         _check_rows("gather_scatter", gi, params.shape[0])
     e, d = gi.numel(), params.shape[1]
-    out = torch.empty((int(size), d), dtype=torch.float32, device=params.device)
+    out = torch.empty((int(size), d), dtype=od, device=params.device)
     with _on(params.device):
-        check(lib().euler_gpu_gather_scatter(_stream(), mode, _ptr(params), _ptr(gi), _ptr(si), e, d,
-                                             int(size), _ptr(out)))
+        if code == _lib.F32:
+            check(lib().euler_gpu_gather_scatter(_stream(), mode, _ptr(params), _ptr(gi), _ptr(si), e, d,
+                                                 int(size), _ptr(out)))
+        else:
+            check(lib().euler_gpu_gather_scatter_t(_stream(), mode, _ptr(params), code, _ptr(gi), _ptr(si),
+                                                   e, d, int(size), _ptr(out), _DT[od]))
     return out
+
+
+def _edge_grad(op, params, gi, si, out, size, grad):
+    """fp32 gradient of reduce(op, gather(params, gi), si, size) per edge (mp_ops.py:39-62)"""
+    if op == "add":
+        return _gather_raw(grad, si, _F32)
+    if op == "mean":
+        return _gather_raw(grad / _count(si, size, grad.device), si)
+    return _max_per_edge(_gather_raw(params, gi, _F32), out, si, size, grad)
 
 
 class _GatherScatter(torch.autograd.Function):
@@ -190,9 +269,9 @@ class _GatherScatter(torch.autograd.Function):
     scatter-added into the rows of params the edges read."""
 
     @staticmethod
-    def forward(ctx, params, gather_indices, scatter_indices, size, op, validate):
+    def forward(ctx, params, gather_indices, scatter_indices, size, op, validate, out_dtype):
         out = _gather_scatter_raw(_GS_MODE[op], params, gather_indices, scatter_indices, size,
-                                  validate)
+                                  validate, out_dtype)
         ctx.save_for_backward(params, gather_indices, scatter_indices, out)
         ctx.size, ctx.op = size, op
         return out
@@ -200,33 +279,24 @@ class _GatherScatter(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad):
         params, gi, si, out = ctx.saved_tensors
-        if ctx.op == "add":
-            per_edge = _gather_raw(grad, si)
-        elif ctx.op == "mean":
-            ones = torch.ones((si.numel(), 1), dtype=torch.float32, device=grad.device)
-            count = _scatter_raw(lib().euler_gpu_scatter_add, ones, si, ctx.size) + 1e-7
-            per_edge = _gather_raw(grad / count, si)
-        else:
-            updates = _gather_raw(params, gi)
-            indicators = (updates == _gather_raw(out, si)).to(updates.dtype)
-            num_selected = _scatter_raw(lib().euler_gpu_scatter_add, indicators, si, ctx.size)
-            per_edge = indicators / _gather_raw(num_selected, si) * _gather_raw(grad, si)
-        return (_scatter_raw(lib().euler_gpu_scatter_add, per_edge, gi, params.shape[0]),
-                None, None, None, None, None)
+        per_edge = _edge_grad(ctx.op, params, gi, si, out, ctx.size, grad)
+        return (_scatter_raw(_ADD, per_edge, gi, params.shape[0]).to(params.dtype),
+                None, None, None, None, None, None)
 
 
-def gather_scatter(op, params, gather_indices, scatter_indices, size, validate=False):
+def gather_scatter(op, params, gather_indices, scatter_indices, size, validate=False, out_dtype=None):
     """scatter_(op, gather(params, gather_indices), scatter_indices, size) for op in
     "add" / "max" / "mean" - the aggregation of a message-passing step whose message is
     the neighbour's row (SAGE mean / max, GCN after its normalisation) - without
     materialising the gathered [E, D] block: same bits, a third of the HBM traffic.
     Like `gather`, the kernel trusts the gather indices; validate=True checks them first
-    (one device round trip)."""
+    (one device round trip).  out_dtype as scatter_add."""
     if op not in _GS_MODE:
         raise ValueError("gather_scatter: op is add, max or mean")
     if op == "mean" and gather_indices.numel() >= (1 << 24):
-        return scatter_mean(gather(params, gather_indices), scatter_indices, size)
-    return _GatherScatter.apply(params, gather_indices, scatter_indices, int(size), op, bool(validate))
+        return scatter_mean(gather(params, gather_indices), scatter_indices, size, out_dtype=out_dtype)
+    return _GatherScatter.apply(params, gather_indices, scatter_indices, int(size), op, bool(validate),
+                                out_dtype)
 
 
 def _segment_dst(seg_ptr, count, size, device):
@@ -239,7 +309,9 @@ def _segment_dst(seg_ptr, count, size, device):
 
 class _GatherSegmentReduce(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, params, gather_indices, seg_ptr, count, size, op, validate):
+    def forward(ctx, params, gather_indices, seg_ptr, count, size, op, validate, out_dtype):
+        code = _dt("gather_segment_reduce", params)
+        od = _out_dt("gather_segment_reduce", params, out_dtype)
         params = params.contiguous()
         # int64 ids (what the samplers return) are read in place: index = low word of the id,
         # the int32 a cast would give, without the cast's pass (euler_gpu_gather_segment_reduce_ids)
@@ -256,16 +328,26 @@ class _GatherSegmentReduce(torch.autograd.Function):
             raise ValueError("gather_segment_reduce: size * count gather indices")
         if validate:
             _check_rows("gather_segment_reduce", gi, params.shape[0])
-        out = torch.empty((int(size), params.shape[1]), dtype=torch.float32, device=params.device)
+        out = torch.empty((int(size), params.shape[1]), dtype=od, device=params.device)
+        sp_p = _ptr(sp) if sp is not None else None
         with _on(params.device):
-            if as_ids:      # (ids past the table read its last row: euler_gpu.h)
-                check(lib().euler_gpu_gather_segment_reduce_ids(
-                    _stream(), _GS_MODE[op], _ptr(params), int(params.shape[0]), _ptr(gi),
-                    _ptr(sp) if sp is not None else None, int(count), params.shape[1], int(size), _ptr(out)))
+            if code == _lib.F32:
+                if as_ids:      # (ids past the table read its last row: euler_gpu.h)
+                    check(lib().euler_gpu_gather_segment_reduce_ids(
+                        _stream(), _GS_MODE[op], _ptr(params), int(params.shape[0]), _ptr(gi),
+                        sp_p, int(count), params.shape[1], int(size), _ptr(out)))
+                else:
+                    check(lib().euler_gpu_gather_segment_reduce(
+                        _stream(), _GS_MODE[op], _ptr(params), _ptr(gi), sp_p,
+                        int(count), params.shape[1], int(size), _ptr(out)))
+            elif as_ids:
+                check(lib().euler_gpu_gather_segment_reduce_ids_t(
+                    _stream(), _GS_MODE[op], _ptr(params), code, int(params.shape[0]), _ptr(gi),
+                    sp_p, int(count), params.shape[1], int(size), _ptr(out), _DT[od]))
             else:
-                check(lib().euler_gpu_gather_segment_reduce(
-                    _stream(), _GS_MODE[op], _ptr(params), _ptr(gi), _ptr(sp) if sp is not None else None,
-                    int(count), params.shape[1], int(size), _ptr(out)))
+                check(lib().euler_gpu_gather_segment_reduce_t(
+                    _stream(), _GS_MODE[op], _ptr(params), code, _ptr(gi), sp_p,
+                    int(count), params.shape[1], int(size), _ptr(out), _DT[od]))
         if as_ids and ctx.needs_input_grad[0]:
             # the gradient kernels take int32 indices.  The forward kernel reads an id past the
             # table - or a negative one, e.g. default_node = -1: unsigned there - from the table's
@@ -282,48 +364,45 @@ class _GatherSegmentReduce(torch.autograd.Function):
     def backward(ctx, grad):
         params, gi, sp, out = ctx.saved_tensors
         si = _segment_dst(sp if ctx.has_ptr else None, ctx.count, ctx.size, grad.device)
-        if ctx.op == "add":
-            per_edge = _gather_raw(grad, si)
-        elif ctx.op == "mean":
-            ones = torch.ones((si.numel(), 1), dtype=torch.float32, device=grad.device)
-            cnt = _scatter_raw(lib().euler_gpu_scatter_add, ones, si, ctx.size) + 1e-7
-            per_edge = _gather_raw(grad / cnt, si)
-        else:
-            updates = _gather_raw(params, gi)
-            indicators = (updates == _gather_raw(out, si)).to(updates.dtype)
-            num_selected = _scatter_raw(lib().euler_gpu_scatter_add, indicators, si, ctx.size)
-            per_edge = indicators / _gather_raw(num_selected, si) * _gather_raw(grad, si)
-        return (_scatter_raw(lib().euler_gpu_scatter_add, per_edge, gi, params.shape[0]),
-                None, None, None, None, None, None)
+        per_edge = _edge_grad(ctx.op, params, gi, si, out, ctx.size, grad)
+        return (_scatter_raw(_ADD, per_edge, gi, params.shape[0]).to(params.dtype),
+                None, None, None, None, None, None, None)
 
 
-def gather_segment_reduce(op, params, gather_indices, size, seg_ptr=None, count=None, validate=False):
+def gather_segment_reduce(op, params, gather_indices, size, seg_ptr=None, count=None, validate=False,
+                          out_dtype=None):
     """The aggregation of a sampled block: destination r reduces (op = "add" / "max" /
     "mean") the rows params[gather_indices[p]] for p in [seg_ptr[r], seg_ptr[r + 1]) - or
     its `count` consecutive indices when seg_ptr is None (SampleNeighbor's fixed fan-out)
     - in that order.  The bits of scatter_(op, gather(params, gather_indices), dst, size)
     with dst = the destination of every index, in one pass and without the scatter's
     look at its key column (no host wait; validate=True checks the gather indices first,
-    which is one)."""
+    which is one).  out_dtype as scatter_add."""
     if op not in _GS_MODE:
         raise ValueError("gather_segment_reduce: op is add, max or mean")
     if (seg_ptr is None) == (count is None):
         raise ValueError("gather_segment_reduce: pass seg_ptr or count")
     return _GatherSegmentReduce.apply(params, gather_indices, seg_ptr, 0 if count is None else int(count),
-                                      int(size), op, bool(validate))
+                                      int(size), op, bool(validate), out_dtype)
 
 
-def scatter_softmax(updates, indices, size):
-    """mp_ops.py:76-79."""
-    updates = updates - gather(scatter_max(updates, indices, size), indices)
-    updates = torch.exp(updates)
-    return updates / gather(scatter_add(updates, indices, size), indices)
+def scatter_softmax(updates, indices, size, out_dtype=None):
+    """mp_ops.py:76-79.  16-bit updates: the fp32 softmax of updates.float(), rounded once at the end
+    unless out_dtype is torch.float32 (and its gradient once on the way back)."""
+    if updates.dtype == _F32:
+        _out_dt("scatter_softmax", updates, out_dtype)
+        updates = updates - gather(scatter_max(updates, indices, size), indices)
+        updates = torch.exp(updates)
+        return updates / gather(scatter_add(updates, indices, size), indices)
+    _dt("scatter_softmax", updates)
+    od = _out_dt("scatter_softmax", updates, out_dtype)
+    return scatter_softmax(updates.float(), indices, size).to(od)
 
 
-def scatter_(op, updates, indices, size):
+def scatter_(op, updates, indices, size, out_dtype=None):
     """mp_ops.py:72-73."""
     return {"add": scatter_add, "max": scatter_max, "mean": scatter_mean,
-            "softmax": scatter_softmax}[op](updates, indices, size)
+            "softmax": scatter_softmax}[op](updates, indices, size, out_dtype=out_dtype)
 
 
 def gen_pair(paths, left_win_size, right_win_size):

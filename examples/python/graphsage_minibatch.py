@@ -9,9 +9,13 @@ function names (euler_amd.euler_ops mirrors tf_euler.python.euler_ops; tensors a
 tensors in HBM).  Nothing returns to the host between the ops except the layer sizes.
 
     python examples/python/graphsage_minibatch.py [--data DIR] [--batch 1024] [--steps 50]
+                                                  [--feature-dtype {fp32,bf16,fp16}]
 
 --data: a directory written by euler/tools (euler.meta + Node/*.dat, float feature 0 = the
 input features); without it a synthetic power-law graph with a random feature table is used.
+--feature-dtype: store the feature table in 16 bits (Graph.set_dense_feature_dtype, or the
+synthetic table's dtype) and run the same pipeline on 16-bit rows: the aggregations add in
+fp32 and round once per block, and every row moves half the bytes.
 """
 import argparse
 import os
@@ -35,17 +39,20 @@ def main():
     ap.add_argument("--fanouts", type=int, nargs=2, default=[10, 5])      # run_graphsage.py:41-42
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--nodes", type=int, default=2_000_000)
+    ap.add_argument("--feature-dtype", choices=["fp32", "bf16", "fp16"], default="fp32")
     a = ap.parse_args()
+    fdt = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[a.feature_dtype]
     if a.data:
         euler_ops.initialize_graph({"mode": "local", "data_path": a.data})       # euler_ops/base.py
         G = euler_ops.get_default_graph()
         max_id = int(G.id_range()[0])
         feat = None
+        G.set_dense_feature_dtype(fdt)
     else:
         G = euler_amd.Graph.synthetic(euler_amd.synth_params(1, a.nodes, 10 * a.nodes, weighted=True))
         euler_ops.set_default_graph(G)
         max_id = a.nodes
-        feat = torch.randn(a.nodes + 2, a.dim, device="cuda")                   # row = node id
+        feat = torch.randn(a.nodes + 2, a.dim, device="cuda").to(fdt)           # row = node id
     G.set_seed(42)
     flow = SageDataFlow(G, a.fanouts, [[0], [0]], add_self_loops=True, max_id=max_id)
 
@@ -65,8 +72,8 @@ def main():
         out = step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
-    print("batch %d, fanouts %s: %.3f ms per training-step input (%d x %d aggregated rows), %.0f steps/s"
-          % (a.batch, a.fanouts, dt * 1e3, out.shape[0], out.shape[1], 1.0 / dt))
+    print("batch %d, fanouts %s, %s features: %.3f ms per training-step input (%d x %d aggregated rows), %.0f steps/s"
+          % (a.batch, a.fanouts, a.feature_dtype, dt * 1e3, out.shape[0], out.shape[1], 1.0 / dt))
 
 
 if __name__ == "__main__":

@@ -581,6 +581,24 @@ int euler_gpu_get_dense_feature(const euler_gpu_graph* g, void* stream,
                                 const uint64_t* nodes_dev, int64_t n, int32_t fid,
                                 int32_t dim, float* out_dev);
 
+/* The dense feature table in 16 bits.  euler_gpu_graph_set_dense_feature_dtype converts the
+ * value array on the device, element by element (round to nearest even; every offset is in
+ * elements and stays), frees the fp32 array and lowers euler_gpu_graph_bytes by the half it
+ * saves.  The same dtype again is a no-op; a 16-bit table cannot go back to fp32 or to the
+ * other 16-bit type (the bits are gone): EULER_GPU_EINVAL, as for an unknown dtype, a graph
+ * without dense features and a shard of a sharded graph (shards > 1: the sharded feature
+ * exchange moves fp32 rows).  It waits for the device: no other call may run on the graph
+ * meanwhile.  Afterwards euler_gpu_get_dense_feature and euler_gpu_sample_fanout_with_feature
+ * return fp32 rows of the rounded values.
+ * euler_gpu_get_dense_feature_t writes rows of out_dtype: fp32, or the table's dtype (the stored
+ * bits); an fp32 table serves all three (values rounded once at the store).  Anything else:
+ * EULER_GPU_EINVAL. */
+int euler_gpu_graph_set_dense_feature_dtype(euler_gpu_graph* g, void* stream, int32_t dtype);
+int32_t euler_gpu_graph_dense_feature_dtype(const euler_gpu_graph* g);
+int euler_gpu_get_dense_feature_t(const euler_gpu_graph* g, void* stream,
+                                  const uint64_t* nodes_dev, int64_t n, int32_t fid,
+                                  int32_t dim, void* out_dev, int32_t out_dtype);
+
 /* ---- sparse (uint64) features ----------------------------------------------
  * TF GetSparseFeature (tf_euler/kernels/get_sparse_feature_op.cc:52-131) over
  * Node::GetUint64Feature (core/graph/node.cc:330-372), one feature slot per
@@ -786,6 +804,38 @@ int euler_gpu_gather_segment_reduce_ids(void* stream, int32_t mode, const float*
 int euler_gpu_gather(void* stream, const float* params_dev,
                      const int32_t* indices_dev, int64_t e, int64_t d,
                      int64_t n_params, float* out_dev);
+
+/* ---- message passing over 16-bit storage ---------------------------------------
+ * The entries above with the storage type of the data as an argument: EULER_GPU_F32 (what the
+ * untyped entries take; a typed call with it forwards to them), EULER_GPU_BF16 or
+ * EULER_GPU_F16 (IEEE half).  out_dtype is EULER_GPU_F32 or in_dtype.  For 16-bit input x the
+ * result has the bits of the fp32 entry on the widened x (widening is exact: the same fp32
+ * adds in input order, max over the widened values, mean = sum / (length + 1e-7f), -1e9 for
+ * an empty max row), stored as fp32 unchanged or rounded once, to nearest even, to in_dtype.
+ * Nothing is summed in 16 bits.  16-bit buffers must be 2-byte aligned; 16-byte aligned
+ * ones with d % 8 == 0, d <= 512, d / 8 a divisor of 64 take the 16-byte-lane kernels.
+ * Unknown dtype, or out_dtype neither fp32 nor in_dtype: EULER_GPU_EINVAL.
+ * euler_gpu_scatter_t: mode 0 add, 1 max, 2 mean (e < 2^24). */
+enum { EULER_GPU_F32 = 0, EULER_GPU_BF16 = 1, EULER_GPU_F16 = 2 };
+int euler_gpu_gather_t(void* stream, const void* params_dev, int32_t in_dtype,
+                       const int32_t* indices_dev, int64_t e, int64_t d, int64_t n_params,
+                       void* out_dev, int32_t out_dtype);
+int euler_gpu_scatter_t(void* stream, int32_t mode, const void* updates_dev, int32_t in_dtype,
+                        const int32_t* indices_dev, int64_t e, int64_t d, int32_t size,
+                        void* out_dev, int32_t out_dtype);
+int euler_gpu_gather_scatter_t(void* stream, int32_t mode, const void* params_dev, int32_t in_dtype,
+                               const int32_t* gather_indices_dev,
+                               const int32_t* scatter_indices_dev, int64_t e, int64_t d,
+                               int32_t size, void* out_dev, int32_t out_dtype);
+int euler_gpu_gather_segment_reduce_t(void* stream, int32_t mode, const void* params_dev,
+                                      int32_t in_dtype, const int32_t* gather_indices_dev,
+                                      const int64_t* seg_ptr_dev, int64_t count, int64_t d,
+                                      int32_t size, void* out_dev, int32_t out_dtype);
+int euler_gpu_gather_segment_reduce_ids_t(void* stream, int32_t mode, const void* params_dev,
+                                          int32_t in_dtype, int64_t params_rows,
+                                          const int64_t* gather_ids_dev,
+                                          const int64_t* seg_ptr_dev, int64_t count, int64_t d,
+                                          int32_t size, void* out_dev, int32_t out_dtype);
 
 /* ---- shard ops (multi-GPU) --------------------------------------------------
  * ID_SPLIT (core/kernels/id_split_op.cc:46-99): stable bucket of ids by
