@@ -17,6 +17,7 @@
 #include "device_mem.h"
 #include "half_cvt.h"
 #include "mp_segments.h"
+#include "mp_weighted.h"
 
 namespace euler_gpu {
 namespace {
@@ -243,6 +244,134 @@ int ScatterHalf(hipStream_t st, int32_t mode, const void* upd, int32_t in_dtype,
   if (rc != EULER_GPU_OK) return rc;
   return DispatchReduce(st, mode, in_dtype, out_dtype, upd, SegSpec{keys, nullptr, 0, e, size}, perm,
                         gsrc, d, out, 1, 0xFFFFFFFFu);
+}
+
+// ---- edge-weighted reduces (the weighted kernels of mp_kernels.hip over 16-bit rows) -----------
+// params in bf16 / fp16, w [E, heads] in fp32 or in the dtype of params: both widened exactly,
+// the product and the sum in fp32 (WeightedReduceRow of mp_weighted.h), one rounding at the store.
+template <int DT>
+__device__ __forceinline__ float LoadWeight(const void* w, bool w16, int64_t i) {
+  return w16 ? HalfCvt<DT>::Widen(static_cast<const uint16_t*>(w)[i]) : static_cast<const float*>(w)[i];
+}
+
+template <int DT>
+struct WeightedHalfOps1 {
+  using Raw = uint16_t;
+  MpwIndex ix;
+  const uint16_t* upd; int64_t d; int64_t c;
+  const void* w; bool w16; int32_t heads; int32_t head;
+  __device__ __forceinline__ int64_t Pos(int64_t p) const { return ix.Pos(p); }
+  __device__ __forceinline__ int64_t Row(int64_t pos) const { return ix.Row(pos); }
+  __device__ __forceinline__ float Weight(int64_t pos) const { return LoadWeight<DT>(w, w16, pos * heads + head); }
+  __device__ __forceinline__ uint16_t Load(int64_t row) const { return upd[row * d + c]; }
+  __device__ __forceinline__ void Widen(uint16_t v, float f[1]) const { f[0] = HalfCvt<DT>::Widen(v); }
+};
+
+template <int DT>
+struct WeightedHalfOps8 {
+  using Raw = uint4;
+  MpwIndex ix;
+  const uint4* u8; int64_t d8; int64_t cl;
+  const void* w; bool w16; int32_t heads; int32_t head;
+  __device__ __forceinline__ int64_t Pos(int64_t p) const { return ix.Pos(p); }
+  __device__ __forceinline__ int64_t Row(int64_t pos) const { return ix.Row(pos); }
+  __device__ __forceinline__ float Weight(int64_t pos) const { return LoadWeight<DT>(w, w16, pos * heads + head); }
+  __device__ __forceinline__ uint4 Load(int64_t row) const { return u8[row * d8 + cl]; }
+  __device__ __forceinline__ void Widen(const uint4& v, float f[8]) const { Widen8V<DT>(v, f); }
+};
+
+template <int MODE, int DT, bool OUT16>
+__global__ __launch_bounds__(256) void WeightedSegmentReduceHalfKernel(
+    const uint16_t* __restrict__ upd, const SegSpec seg, const MpwIndex ix, int64_t d,
+    void* __restrict__ out, const void* __restrict__ w, const bool w16, const int32_t heads,
+    const int32_t dh) {
+  const int lane = threadIdx.x;
+  const int32_t size = seg.size;
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.y + threadIdx.y; r < size;
+       r += (int64_t)gridDim.x * blockDim.y) {
+    int64_t b, en;
+    SegBounds(seg, r, &b, &en);
+    for (int64_t c = lane; c < d; c += 64) {
+      const WeightedHalfOps1<DT> ops{ix, upd, d, c, w, w16, heads, (int32_t)(c / dh)};
+      float acc[1];
+      WeightedReduceRow<MODE, 1>(ops, b, en, acc);
+      StoreElem<OUT16 ? DT : kF32>(out, r * d + c, acc[0]);
+    }
+  }
+}
+
+// the 16-byte-lane form: d8 = d / 8 lanes a row, and dh % 8 == 0 so that a lane's eight columns
+// lie in one head
+template <int MODE, int DT, bool OUT16>
+__global__ __launch_bounds__(256) void WeightedSegmentReduceVec8Kernel(
+    const uint4* __restrict__ u8, const SegSpec seg, const MpwIndex ix, int32_t d8,
+    void* __restrict__ out, const void* __restrict__ w, const bool w16, const int32_t heads,
+    const int32_t dh) {
+  const int32_t size = seg.size;
+  const int32_t rows_per_wave = 64 / d8;
+  const int32_t sub = threadIdx.x / d8, cl = threadIdx.x - sub * d8;
+  const int64_t rows_per_block = (int64_t)blockDim.y * rows_per_wave;
+  const WeightedHalfOps8<DT> ops{ix, u8, d8, cl, w, w16, heads, (cl * 8) / dh};
+  for (int64_t r = (int64_t)blockIdx.x * rows_per_block + threadIdx.y * rows_per_wave + sub;
+       r < size; r += (int64_t)gridDim.x * rows_per_block) {
+    int64_t b, en;
+    SegBounds(seg, r, &b, &en);
+    float acc[8];
+    WeightedReduceRow<MODE, 8>(ops, b, en, acc);
+    Store8<DT, OUT16>(out, r * d8 + cl, acc);
+  }
+}
+
+template <int MODE, int DT, bool OUT16>
+int LaunchWeightedReduce(hipStream_t st, const void* upd, const SegSpec& seg, const MpwIndex& ix,
+                         int64_t d, void* out, const void* w, bool w16, int32_t heads) {
+  const dim3 block(64, 4);
+  const int64_t d8 = d / 8;
+  const int32_t dh = (int32_t)(d / heads);
+  const int32_t size = seg.size;
+  if (d % 8 == 0 && d8 <= 64 && 64 % d8 == 0 && dh % 8 == 0 && ((uintptr_t)upd % 16 == 0) &&
+      ((uintptr_t)out % 16 == 0)) {
+    const int64_t rows_per_block = 4 * (64 / d8);
+    int64_t blocks = ((int64_t)size + rows_per_block - 1) / rows_per_block;
+    if (blocks > 256 * 32) blocks = 256 * 32;
+    hipLaunchKernelGGL((WeightedSegmentReduceVec8Kernel<MODE, DT, OUT16>), dim3((unsigned)blocks), block,
+                       0, st, static_cast<const uint4*>(upd), seg, ix, (int32_t)d8, out, w, w16, heads, dh);
+  } else {
+    int64_t blocks = ((int64_t)size + 3) / 4;
+    if (blocks > 256 * 32) blocks = 256 * 32;
+    hipLaunchKernelGGL((WeightedSegmentReduceHalfKernel<MODE, DT, OUT16>), dim3((unsigned)blocks), block,
+                       0, st, static_cast<const uint16_t*>(upd), seg, ix, d, out, w, w16, heads, dh);
+  }
+  EG_HIP(hipGetLastError());
+  return EULER_GPU_OK;
+}
+
+int DispatchWeightedReduce(hipStream_t st, int32_t mode, int32_t in_dtype, int32_t out_dtype,
+                           const void* upd, const SegSpec& seg, const MpwIndex& ix, int64_t d,
+                           void* out, const void* w, bool w16, int32_t heads) {
+#define EG_WREDUCE(M, DT)                                                                        \
+  return out_dtype == EULER_GPU_F32                                                              \
+             ? LaunchWeightedReduce<M, DT, false>(st, upd, seg, ix, d, out, w, w16, heads)       \
+             : LaunchWeightedReduce<M, DT, true>(st, upd, seg, ix, d, out, w, w16, heads)
+  if (in_dtype == EULER_GPU_BF16) {
+    if (mode == 0) { EG_WREDUCE(0, kBF16); }
+    if (mode == 1) { EG_WREDUCE(1, kBF16); }
+    EG_WREDUCE(2, kBF16);
+  }
+  if (mode == 0) { EG_WREDUCE(0, kF16); }
+  if (mode == 1) { EG_WREDUCE(1, kF16); }
+  EG_WREDUCE(2, kF16);
+#undef EG_WREDUCE
+}
+
+// w_dtype is fp32 or the dtype of the rows
+int CheckWeightDtype(const char* what, int32_t in_dtype, int32_t w_dtype, const void* w) {
+  if (w_dtype != EULER_GPU_F32 && w_dtype != in_dtype)
+    return Fail(EULER_GPU_EINVAL, std::string(what) + ": w_dtype " + std::to_string(w_dtype) +
+                                      " is neither fp32 nor the input's dtype");
+  if ((uintptr_t)w % (w_dtype == EULER_GPU_F32 ? 4 : 2) != 0)
+    return Fail(EULER_GPU_EINVAL, std::string(what) + ": the weights are not aligned to their type");
+  return EULER_GPU_OK;
 }
 
 // ---- MPGather ------------------------------------------------------------------------------
@@ -486,6 +615,106 @@ int euler_gpu_gather_segment_reduce_ids_t(void* stream, int32_t mode, const void
   const int32_t* lo = reinterpret_cast<const int32_t*>(gather_ids_dev);     // little endian: word 0 of every id
   return DispatchReduce((hipStream_t)stream, mode, in_dtype, out_dtype, params_dev,
                         SegSpec{nullptr, seg_ptr_dev, count, 0, size}, nullptr, lo, d, out_dev, 2, row_max);
+}
+
+int euler_gpu_gather_scatter_w_t(void* stream, int32_t mode, const void* params_dev, int32_t in_dtype,
+                                 const int32_t* gather_indices_dev, const int32_t* scatter_indices_dev,
+                                 int64_t e, int64_t d, int32_t size, void* out_dev, int32_t out_dtype,
+                                 const void* w_dev, int32_t w_dtype, int32_t heads) {
+  int rc = CheckDtypes("gather_scatter_w", in_dtype, out_dtype);
+  if (rc == EULER_GPU_OK) rc = CheckWeightDtype("gather_scatter_w", in_dtype, w_dtype, w_dev);
+  if (rc != EULER_GPU_OK) return rc;
+  if (in_dtype == EULER_GPU_F32)
+    return euler_gpu_gather_scatter_w(stream, mode, static_cast<const float*>(params_dev),
+                                      gather_indices_dev, scatter_indices_dev, e, d, size,
+                                      static_cast<float*>(out_dev), static_cast<const float*>(w_dev), heads);
+  rc = CheckWeightedShape("gather_scatter_w", mode, d, heads);
+  if (rc != EULER_GPU_OK) return rc;
+  if (e < 0 || size < 0) return Fail(EULER_GPU_EINVAL, "gather_scatter_w: bad shape");
+  if (size == 0 || d == 0) return EULER_GPU_OK;
+  if (!out_dev || (e > 0 && (!params_dev || !scatter_indices_dev || !w_dev)))
+    return Fail(EULER_GPU_EINVAL, "gather_scatter_w: null buffer");
+  if (e >= (1LL << 31)) return Fail(EULER_GPU_EINVAL, "gather_scatter_w: e >= 2^31");
+  if (mode == 2 && e >= (1LL << 24)) return Fail(EULER_GPU_EINVAL, "gather_scatter_w: mean needs e < 2^24");
+  if ((uintptr_t)params_dev % 2 != 0 || (uintptr_t)out_dev % 2 != 0)
+    return Fail(EULER_GPU_EINVAL, "gather_scatter_w: 16-bit data must be 2-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const int32_t* keys = scatter_indices_dev;
+  const uint32_t* perm = nullptr;
+  StreamBuf scratch(st);
+  rc = GroupScatterKeys(st, scatter_indices_dev, e, &scratch, &keys, &perm);
+  if (rc != EULER_GPU_OK) return rc;
+  return DispatchWeightedReduce(st, mode, in_dtype, out_dtype, params_dev, SegSpec{keys, nullptr, 0, e, size},
+                                MpwIndex{perm, gather_indices_dev, 1, 0xFFFFFFFFu}, d, out_dev, w_dev,
+                                w_dtype != EULER_GPU_F32, heads);
+}
+
+int euler_gpu_gather_segment_reduce_w_t(void* stream, int32_t mode, const void* params_dev, int32_t in_dtype,
+                                        const int32_t* gather_indices_dev, const int64_t* seg_ptr_dev,
+                                        int64_t count, int64_t d, int32_t size, void* out_dev,
+                                        int32_t out_dtype, const void* w_dev, int32_t w_dtype,
+                                        int32_t heads) {
+  int rc = CheckDtypes("gather_segment_reduce_w", in_dtype, out_dtype);
+  if (rc == EULER_GPU_OK) rc = CheckWeightDtype("gather_segment_reduce_w", in_dtype, w_dtype, w_dev);
+  if (rc != EULER_GPU_OK) return rc;
+  if (in_dtype == EULER_GPU_F32)
+    return euler_gpu_gather_segment_reduce_w(stream, mode, static_cast<const float*>(params_dev),
+                                             gather_indices_dev, seg_ptr_dev, count, d, size,
+                                             static_cast<float*>(out_dev), static_cast<const float*>(w_dev),
+                                             heads);
+  rc = CheckWeightedShape("gather_segment_reduce_w", mode, d, heads);
+  if (rc != EULER_GPU_OK) return rc;
+  if (size < 0 || (!seg_ptr_dev && count < 0))
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_w: bad shape");
+  if (size == 0 || d == 0) return EULER_GPU_OK;
+  if (!out_dev || !params_dev || !w_dev)
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_w: null buffer");
+  if (!seg_ptr_dev && (int64_t)size * count >= (1LL << 31))
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_w: e >= 2^31");
+  if (!seg_ptr_dev && mode == 2 && count >= (1LL << 24))
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_w: mean needs segments shorter than 2^24");
+  if ((uintptr_t)params_dev % 2 != 0 || (uintptr_t)out_dev % 2 != 0)
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_w: 16-bit data must be 2-byte aligned");
+  return DispatchWeightedReduce((hipStream_t)stream, mode, in_dtype, out_dtype, params_dev,
+                                SegSpec{nullptr, seg_ptr_dev, count, 0, size},
+                                MpwIndex{nullptr, gather_indices_dev, 1, 0xFFFFFFFFu}, d, out_dev, w_dev,
+                                w_dtype != EULER_GPU_F32, heads);
+}
+
+int euler_gpu_gather_segment_reduce_ids_w_t(void* stream, int32_t mode, const void* params_dev,
+                                            int32_t in_dtype, int64_t params_rows,
+                                            const int64_t* gather_ids_dev, const int64_t* seg_ptr_dev,
+                                            int64_t count, int64_t d, int32_t size, void* out_dev,
+                                            int32_t out_dtype, const void* w_dev, int32_t w_dtype,
+                                            int32_t heads) {
+  int rc = CheckDtypes("gather_segment_reduce_ids_w", in_dtype, out_dtype);
+  if (rc == EULER_GPU_OK) rc = CheckWeightDtype("gather_segment_reduce_ids_w", in_dtype, w_dtype, w_dev);
+  if (rc != EULER_GPU_OK) return rc;
+  if (in_dtype == EULER_GPU_F32)
+    return euler_gpu_gather_segment_reduce_ids_w(stream, mode, static_cast<const float*>(params_dev),
+                                                 params_rows, gather_ids_dev, seg_ptr_dev, count, d, size,
+                                                 static_cast<float*>(out_dev),
+                                                 static_cast<const float*>(w_dev), heads);
+  rc = CheckWeightedShape("gather_segment_reduce_ids_w", mode, d, heads);
+  if (rc != EULER_GPU_OK) return rc;
+  if (size < 0 || (!seg_ptr_dev && count < 0))
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: bad shape");
+  if (size == 0 || d == 0) return EULER_GPU_OK;
+  if (!out_dev || !params_dev || !gather_ids_dev || !w_dev)
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: null buffer");
+  if (!seg_ptr_dev && (int64_t)size * count >= (1LL << 31))
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: e >= 2^31");
+  if (!seg_ptr_dev && mode == 2 && count >= (1LL << 24))
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: mean needs segments shorter than 2^24");
+  if (params_rows < 0 || params_rows >= ((int64_t)1 << 31))
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: the table must have fewer than 2^31 rows");
+  if ((uintptr_t)params_dev % 2 != 0 || (uintptr_t)out_dev % 2 != 0)
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: 16-bit data must be 2-byte aligned");
+  const uint32_t row_max = params_rows > 0 ? (uint32_t)(params_rows - 1) : 0xFFFFFFFFu;
+  const int32_t* lo = reinterpret_cast<const int32_t*>(gather_ids_dev);     // little endian: word 0 of every id
+  return DispatchWeightedReduce((hipStream_t)stream, mode, in_dtype, out_dtype, params_dev,
+                                SegSpec{nullptr, seg_ptr_dev, count, 0, size}, MpwIndex{nullptr, lo, 2, row_max},
+                                d, out_dev, w_dev, w_dtype != EULER_GPU_F32, heads);
 }
 
 int32_t euler_gpu_graph_dense_feature_dtype(const euler_gpu_graph* g) {

@@ -15,6 +15,7 @@
 #include "device_fns.h"
 #include "device_mem.h"
 #include "mp_segments.h"
+#include "mp_weighted.h"
 
 struct euler_gpu_front {
   int64_t* stage = nullptr;      // pinned + mapped: [kMaxShards + 1] bucket starts, then the sequence word
@@ -317,6 +318,125 @@ static int SegmentReduceImpl(hipStream_t st, const float* params, const int32_t*
                        nullptr, gsrc, d, out, gstride, row_max);
   }
   EG_HIP(hipGetLastError());
+  return EULER_GPU_OK;
+}
+
+// ------------------------------------------------------------------------
+// The edge-weighted reduces: update p contributes fl(params[g(p)][c] * w[p][c / dh]) - the message
+// of GCN / APPNP (gcn_conv.py:50-51, appnp_conv.py:54-55: norm_i * norm_j * x_j) and of GAT /
+// AGNN (gat_conv.py:71, agnn_conv.py:54: x_j * alpha, one alpha per head) - folded into the
+// segment reduce like the gather.  w is [E, heads] fp32, indexed by the update's ORIGINAL
+// position; dh = d / heads columns share a weight.  The arithmetic of a destination is
+// WeightedReduceRow of mp_weighted.h (a rounded product, then the rounded add / compare, in
+// input order: the bits of scatter_(op, gather(params, g) * w, dst)); the kernels below only
+// assign lanes, exactly as SegmentReduceKernel / SegmentReduceVec4Kernel do.
+// ------------------------------------------------------------------------
+struct WeightedOps1 {
+  using Raw = float;
+  MpwIndex ix;
+  const float* upd; int64_t d; int64_t c;
+  const float* w; int32_t heads; int32_t head;
+  __device__ __forceinline__ int64_t Pos(int64_t p) const { return ix.Pos(p); }
+  __device__ __forceinline__ int64_t Row(int64_t pos) const { return ix.Row(pos); }
+  __device__ __forceinline__ float Weight(int64_t pos) const { return w[pos * heads + head]; }
+  __device__ __forceinline__ float Load(int64_t row) const { return upd[row * d + c]; }
+  __device__ __forceinline__ void Widen(float v, float f[1]) const { f[0] = v; }
+};
+
+struct WeightedOps4 {
+  using Raw = float4;
+  MpwIndex ix;
+  const float4* u4; int64_t d4; int64_t cl;
+  const float* w; int32_t heads; int32_t head;
+  __device__ __forceinline__ int64_t Pos(int64_t p) const { return ix.Pos(p); }
+  __device__ __forceinline__ int64_t Row(int64_t pos) const { return ix.Row(pos); }
+  __device__ __forceinline__ float Weight(int64_t pos) const { return w[pos * heads + head]; }
+  __device__ __forceinline__ float4 Load(int64_t row) const { return u4[row * d4 + cl]; }
+  __device__ __forceinline__ void Widen(const float4& v, float f[4]) const {
+    f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
+  }
+};
+
+// blockDim = (64, 4): a wave-slot per output row, one column per lane (any d, any dh)
+template <int MODE>
+__global__ __launch_bounds__(256) void WeightedSegmentReduceKernel(
+    const float* __restrict__ upd, const SegSpec seg, const MpwIndex ix, int64_t d,
+    float* __restrict__ out, const float* __restrict__ w, const int32_t heads, const int32_t dh) {
+  const int lane = threadIdx.x;
+  const int32_t size = seg.size;
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.y + threadIdx.y; r < size;
+       r += (int64_t)gridDim.x * blockDim.y) {
+    int64_t b, en;
+    SegBounds(seg, r, &b, &en);
+    for (int64_t c = lane; c < d; c += 64) {
+      const WeightedOps1 ops{ix, upd, d, c, w, heads, (int32_t)(c / dh)};
+      float acc[1];
+      WeightedReduceRow<MODE, 1>(ops, b, en, acc);
+      out[r * d + c] = acc[0];
+    }
+  }
+}
+
+// d % 4 == 0 with d / 4 a divisor of 64, and dh % 4 == 0 so that the four columns of a lane lie
+// in one head: d / 4 lanes a row, 256 / d rows a wave, 16-byte loads and stores.
+template <int MODE>
+__global__ __launch_bounds__(256) void WeightedSegmentReduceVec4Kernel(
+    const float* __restrict__ upd, const SegSpec seg, const MpwIndex ix, int32_t d4,
+    float* __restrict__ out, const float* __restrict__ w, const int32_t heads, const int32_t dh) {
+  const int32_t size = seg.size;
+  const int32_t rows_per_wave = 64 / d4;
+  const int32_t sub = threadIdx.x / d4, cl = threadIdx.x - sub * d4;
+  const int64_t rows_per_block = (int64_t)blockDim.y * rows_per_wave;
+  const WeightedOps4 ops{ix, reinterpret_cast<const float4*>(upd), d4, cl, w, heads, (cl * 4) / dh};
+  for (int64_t r = (int64_t)blockIdx.x * rows_per_block + threadIdx.y * rows_per_wave + sub;
+       r < size; r += (int64_t)gridDim.x * rows_per_block) {
+    int64_t b, en;
+    SegBounds(seg, r, &b, &en);
+    float acc[4];
+    WeightedReduceRow<MODE, 4>(ops, b, en, acc);
+    reinterpret_cast<float4*>(out)[r * d4 + cl] = make_float4(acc[0], acc[1], acc[2], acc[3]);
+  }
+}
+
+template <int MODE>
+static int LaunchWeightedReduce(hipStream_t st, const float* params, const SegSpec& seg,
+                                const MpwIndex& ix, int64_t d, float* out, const float* w,
+                                int32_t heads) {
+  const dim3 block(64, 4);
+  const int64_t d4 = d / 4;
+  const int32_t dh = (int32_t)(d / heads);
+  const int32_t size = seg.size;
+  if (d % 4 == 0 && d4 <= 64 && 64 % d4 == 0 && dh % 4 == 0 && ((uintptr_t)params % 16 == 0) &&
+      ((uintptr_t)out % 16 == 0)) {
+    const int64_t rows_per_block = 4 * (64 / d4);
+    int64_t blocks = ((int64_t)size + rows_per_block - 1) / rows_per_block;
+    if (blocks > 256 * 32) blocks = 256 * 32;
+    hipLaunchKernelGGL(WeightedSegmentReduceVec4Kernel<MODE>, dim3((unsigned)blocks), block, 0, st,
+                       params, seg, ix, (int32_t)d4, out, w, heads, dh);
+  } else {
+    int64_t blocks = ((int64_t)size + 3) / 4;
+    if (blocks > 256 * 32) blocks = 256 * 32;
+    hipLaunchKernelGGL(WeightedSegmentReduceKernel<MODE>, dim3((unsigned)blocks), block, 0, st,
+                       params, seg, ix, d, out, w, heads, dh);
+  }
+  EG_HIP(hipGetLastError());
+  return EULER_GPU_OK;
+}
+
+static int DispatchWeightedReduce(hipStream_t st, int32_t mode, const float* params,
+                                  const SegSpec& seg, const MpwIndex& ix, int64_t d, float* out,
+                                  const float* w, int32_t heads) {
+  if (mode == 0) return LaunchWeightedReduce<0>(st, params, seg, ix, d, out, w, heads);
+  if (mode == 1) return LaunchWeightedReduce<1>(st, params, seg, ix, d, out, w, heads);
+  return LaunchWeightedReduce<2>(st, params, seg, ix, d, out, w, heads);
+}
+
+int CheckWeightedShape(const char* what, int32_t mode, int64_t d, int32_t heads) {
+  if (mode < 0 || mode > 2)
+    return Fail(EULER_GPU_EINVAL, std::string(what) + ": mode is 0 add, 1 max, 2 mean");
+  if (heads < 1) return Fail(EULER_GPU_EINVAL, std::string(what) + ": heads < 1");
+  if (d < 0 || d % heads != 0)
+    return Fail(EULER_GPU_EINVAL, std::string(what) + ": heads must divide d");
   return EULER_GPU_OK;
 }
 
@@ -791,6 +911,79 @@ int euler_gpu_gather_scatter(void* stream, int32_t mode, const float* params_dev
   if (mode == 1)
     return ScatterImpl<1>(st, params_dev, scatter_indices_dev, e, d, size, out_dev, gather_indices_dev);
   return ScatterImpl<2>(st, params_dev, scatter_indices_dev, e, d, size, out_dev, gather_indices_dev);
+}
+
+int euler_gpu_gather_scatter_w(void* stream, int32_t mode, const float* params_dev,
+                               const int32_t* gather_indices_dev,
+                               const int32_t* scatter_indices_dev, int64_t e, int64_t d,
+                               int32_t size, float* out_dev, const float* w_dev, int32_t heads) {
+  const int rc = CheckWeightedShape("gather_scatter_w", mode, d, heads);
+  if (rc != EULER_GPU_OK) return rc;
+  if (e < 0 || size < 0) return Fail(EULER_GPU_EINVAL, "gather_scatter_w: bad shape");
+  if (size == 0 || d == 0) return EULER_GPU_OK;
+  if (!out_dev || (e > 0 && (!params_dev || !scatter_indices_dev || !w_dev)))
+    return Fail(EULER_GPU_EINVAL, "gather_scatter_w: null buffer");
+  if (e >= (1LL << 31)) return Fail(EULER_GPU_EINVAL, "gather_scatter_w: e >= 2^31");
+  if (mode == 2 && e >= (1LL << 24))
+    return Fail(EULER_GPU_EINVAL, "gather_scatter_w: mean needs e < 2^24");
+  hipStream_t st = (hipStream_t)stream;
+  const int32_t* keys = scatter_indices_dev;
+  const uint32_t* perm = nullptr;
+  StreamBuf scratch(st);
+  {
+    const int rg = GroupScatterKeys(st, scatter_indices_dev, e, &scratch, &keys, &perm);
+    if (rg != EULER_GPU_OK) return rg;
+  }
+  return DispatchWeightedReduce(st, mode, params_dev, SegSpec{keys, nullptr, 0, e, size},
+                                MpwIndex{perm, gather_indices_dev, 1, 0xFFFFFFFFu}, d, out_dev, w_dev,
+                                heads);
+}
+
+int euler_gpu_gather_segment_reduce_w(void* stream, int32_t mode, const float* params_dev,
+                                      const int32_t* gather_indices_dev,
+                                      const int64_t* seg_ptr_dev, int64_t count, int64_t d,
+                                      int32_t size, float* out_dev, const float* w_dev,
+                                      int32_t heads) {
+  const int rc = CheckWeightedShape("gather_segment_reduce_w", mode, d, heads);
+  if (rc != EULER_GPU_OK) return rc;
+  if (size < 0 || (!seg_ptr_dev && count < 0))
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_w: bad shape");
+  if (size == 0 || d == 0) return EULER_GPU_OK;
+  if (!out_dev || !params_dev || !w_dev)
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_w: null buffer");
+  if (!seg_ptr_dev && (int64_t)size * count >= (1LL << 31))
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_w: e >= 2^31");
+  if (!seg_ptr_dev && mode == 2 && count >= (1LL << 24))
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_w: mean needs segments shorter than 2^24");
+  return DispatchWeightedReduce((hipStream_t)stream, mode, params_dev,
+                                SegSpec{nullptr, seg_ptr_dev, count, 0, size},
+                                MpwIndex{nullptr, gather_indices_dev, 1, 0xFFFFFFFFu}, d, out_dev,
+                                w_dev, heads);
+}
+
+int euler_gpu_gather_segment_reduce_ids_w(void* stream, int32_t mode, const float* params_dev,
+                                          int64_t params_rows, const int64_t* gather_ids_dev,
+                                          const int64_t* seg_ptr_dev, int64_t count, int64_t d,
+                                          int32_t size, float* out_dev, const float* w_dev,
+                                          int32_t heads) {
+  const int rc = CheckWeightedShape("gather_segment_reduce_ids_w", mode, d, heads);
+  if (rc != EULER_GPU_OK) return rc;
+  if (size < 0 || (!seg_ptr_dev && count < 0))
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: bad shape");
+  if (size == 0 || d == 0) return EULER_GPU_OK;
+  if (!out_dev || !params_dev || !gather_ids_dev || !w_dev)
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: null buffer");
+  if (!seg_ptr_dev && (int64_t)size * count >= (1LL << 31))
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: e >= 2^31");
+  if (!seg_ptr_dev && mode == 2 && count >= (1LL << 24))
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: mean needs segments shorter than 2^24");
+  if (params_rows < 0 || params_rows >= ((int64_t)1 << 31))
+    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: the table must have fewer than 2^31 rows");
+  const uint32_t row_max = params_rows > 0 ? (uint32_t)(params_rows - 1) : 0xFFFFFFFFu;
+  const int32_t* lo = reinterpret_cast<const int32_t*>(gather_ids_dev);     // little endian: word 0 of every id
+  return DispatchWeightedReduce((hipStream_t)stream, mode, params_dev,
+                                SegSpec{nullptr, seg_ptr_dev, count, 0, size},
+                                MpwIndex{nullptr, lo, 2, row_max}, d, out_dev, w_dev, heads);
 }
 
 int euler_gpu_neighbor_post_process(void* stream, int64_t n, int32_t* idx_dev,

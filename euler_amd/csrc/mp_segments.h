@@ -65,6 +65,8 @@ __device__ __forceinline__ void SegBounds(const SegSpec& s, int64_t r, int64_t* 
 // the original position of the p-th grouped update.
 int GroupScatterKeys(hipStream_t st, const int32_t* idx, int64_t e, StreamBuf* scratch,
                      const int32_t** keys, const uint32_t** perm);
+// mp_kernels.hip: the argument checks every weighted entry shares (mode 0..2, heads >= 1, heads | d)
+int CheckWeightedShape(const char* what, int32_t mode, int64_t d, int32_t heads);
 #pragma GCC visibility pop
 
 }  // namespace euler_gpu

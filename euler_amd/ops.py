@@ -284,15 +284,27 @@ class _GatherScatter(torch.autograd.Function):
                 None, None, None, None, None, None)
 
 
-def gather_scatter(op, params, gather_indices, scatter_indices, size, validate=False, out_dtype=None):
+def gather_scatter(op, params, gather_indices, scatter_indices, size, validate=False, out_dtype=None,
+                   edge_weight=None):
     """scatter_(op, gather(params, gather_indices), scatter_indices, size) for op in
     "add" / "max" / "mean" - the aggregation of a message-passing step whose message is
     the neighbour's row (SAGE mean / max, GCN after its normalisation) - without
     materialising the gathered [E, D] block: same bits, a third of the HBM traffic.
     Like `gather`, the kernel trusts the gather indices; validate=True checks them first
-    (one device round trip).  out_dtype as scatter_add."""
+    (one device round trip).  out_dtype as scatter_add.
+    edge_weight ([E], [E, 1] or [E, H] with H dividing D; fp32 or the dtype of params): the
+    message is the row times its edge's weight - column c takes weight c // (D // H) - as in
+    GCN / APPNP (norm_i * norm_j * x_j) and GAT / AGNN (x_j * alpha): the bits of
+    scatter_(op, gather(params, gi) * w_expanded, si, size) with the multiply in fp32, still one
+    pass.  Gradients flow to params and to edge_weight (the latter through `edge_dot`)."""
     if op not in _GS_MODE:
         raise ValueError("gather_scatter: op is add, max or mean")
+    if edge_weight is not None:
+        _edge_weight("gather_scatter", edge_weight, gather_indices.numel(), params)
+        if op == "mean" and gather_indices.numel() >= (1 << 24):
+            raise ValueError("gather_scatter: a weighted mean needs fewer than 2^24 edges")
+        return _GatherScatterW.apply(params, gather_indices, scatter_indices, int(size), op, bool(validate),
+                                     out_dtype, edge_weight)
     if op == "mean" and gather_indices.numel() >= (1 << 24):
         return scatter_mean(gather(params, gather_indices), scatter_indices, size, out_dtype=out_dtype)
     return _GatherScatter.apply(params, gather_indices, scatter_indices, int(size), op, bool(validate),
@@ -370,20 +382,274 @@ class _GatherSegmentReduce(torch.autograd.Function):
 
 
 def gather_segment_reduce(op, params, gather_indices, size, seg_ptr=None, count=None, validate=False,
-                          out_dtype=None):
+                          out_dtype=None, edge_weight=None):
     """The aggregation of a sampled block: destination r reduces (op = "add" / "max" /
     "mean") the rows params[gather_indices[p]] for p in [seg_ptr[r], seg_ptr[r + 1]) - or
     its `count` consecutive indices when seg_ptr is None (SampleNeighbor's fixed fan-out)
     - in that order.  The bits of scatter_(op, gather(params, gather_indices), dst, size)
     with dst = the destination of every index, in one pass and without the scatter's
     look at its key column (no host wait; validate=True checks the gather indices first,
-    which is one).  out_dtype as scatter_add."""
+    which is one).  out_dtype as scatter_add.  edge_weight as gather_scatter - e.g. the weights
+    sample_neighbor returns next to the ids."""
     if op not in _GS_MODE:
         raise ValueError("gather_segment_reduce: op is add, max or mean")
     if (seg_ptr is None) == (count is None):
         raise ValueError("gather_segment_reduce: pass seg_ptr or count")
+    if edge_weight is not None:
+        _edge_weight("gather_segment_reduce", edge_weight, gather_indices.numel(), params)
+        return _GatherSegmentReduceW.apply(params, gather_indices, seg_ptr, 0 if count is None else int(count),
+                                           int(size), op, bool(validate), out_dtype, edge_weight)
     return _GatherSegmentReduce.apply(params, gather_indices, seg_ptr, 0 if count is None else int(count),
                                       int(size), op, bool(validate), out_dtype)
+
+
+# ---- edge-weighted aggregation ---------------------------------------------------------------
+def _edge_weight(name, w, e, params):
+    """checks an edge_weight argument; -> (the weights as a contiguous [E, H] tensor, H)"""
+    _dt(name, params)
+    if w.dtype != _F32 and (w.dtype != params.dtype or w.dtype not in _DT):
+        raise TypeError("%s: edge_weight is float32 or the dtype of params (%s), not %s"
+                        % (name, params.dtype, w.dtype))
+    _need_cuda(w)
+    if w.dim() == 1:
+        w2 = w.reshape(-1, 1)
+    elif w.dim() == 2:
+        w2 = w
+    else:
+        raise ValueError("%s: edge_weight is [E], [E, 1] or [E, H]" % name)
+    if w2.shape[0] != e:
+        raise ValueError("%s: one weight row per edge (%d), not %d" % (name, e, w2.shape[0]))
+    heads, d = int(w2.shape[1]), int(params.shape[1])
+    if heads < 1 or d % heads != 0:
+        raise ValueError("%s: the %d weights of an edge do not divide the %d columns" % (name, heads, d))
+    return w2.contiguous(), heads
+
+
+def _gather_scatter_w_raw(mode, params, gi, si, size, w2, heads, out_dtype=None, validate=False):
+    """the weighted fused reduce; gi None: update p is row p of params"""
+    code = _dt("gather_scatter", params)
+    od = _out_dt("gather_scatter", params, out_dtype)
+    params = params.contiguous()
+    si = si.to(torch.int32).contiguous()
+    _need_cuda(params, si, w2)
+    if gi is not None:
+        gi = gi.to(torch.int32).contiguous()
+        _need_cuda(gi)
+        if gi.numel() != si.numel():
+            raise ValueError("gather_scatter: one gather index and one scatter index per edge")
+        if validate:
+            _check_rows("gather_scatter", gi, params.shape[0])
+    e, d = si.numel(), params.shape[1]
+    out = torch.empty((int(size), d), dtype=od, device=params.device)
+    with _on(params.device):
+        if code == _lib.F32:
+            check(lib().euler_gpu_gather_scatter_w(_stream(), mode, _ptr(params), _ptr(gi), _ptr(si), e, d,
+                                                   int(size), _ptr(out), _ptr(w2), heads))
+        else:
+            check(lib().euler_gpu_gather_scatter_w_t(_stream(), mode, _ptr(params), code, _ptr(gi), _ptr(si),
+                                                     e, d, int(size), _ptr(out), _DT[od], _ptr(w2),
+                                                     _DT[w2.dtype], heads))
+    return out
+
+
+def _edge_dot_raw(a, ai, b, bi, heads, od):
+    """[E, heads] per-edge dot products (euler_gpu_edge_dot_t); ai / bi None: row p"""
+    ca, cb = _dt("edge_dot", a), _dt("edge_dot", b)
+    a, b = a.contiguous(), b.contiguous()
+    _need_cuda(a, b)
+    if ai is not None:
+        ai = ai.to(torch.int32).contiguous()
+        _need_cuda(ai)
+    if bi is not None:
+        bi = bi.to(torch.int32).contiguous()
+        _need_cuda(bi)
+    e = ai.numel() if ai is not None else bi.numel() if bi is not None else a.shape[0]
+    d = a.shape[1]
+    if d == 0:
+        return torch.zeros((e, heads), dtype=od, device=a.device)
+    out = torch.empty((e, heads), dtype=od, device=a.device)
+    with _on(a.device):
+        check(lib().euler_gpu_edge_dot_t(_stream(), _ptr(a), ca, _ptr(ai), _ptr(b), cb, _ptr(bi), e, d,
+                                         heads, _ptr(out), _DT[od]))
+    return out
+
+
+def _weighted_backward(op, params, gi, si, w, out, size, grad, refwd):
+    """(grad_params, grad_edge_weight) of reduce(op, gather(params, gi) * w, si, size): the
+    gradients of the composition under autograd.  add / mean: with G = grad (add) or
+    grad / (count + 1e-7) (mean) in fp32, grad_params is the weighted fused op itself with the
+    roles swapped - rows of G gathered by si, scattered by gi, the same w: the same operand pairs
+    and the same stable grouping as the composition - and grad_edge_weight the per-edge dot
+    product of G[si] and params[gi]; neither builds an [E, D] block.  max needs the values of the
+    messages for the tie rule of mp_ops.py:53-62 and materialises them."""
+    e = si.numel()
+    w2 = w.reshape(e, -1)
+    heads = w2.shape[1]
+    w32 = w2.float().contiguous()
+    n = params.shape[0]
+    if op == "max":
+        if out.dtype != _F32:       # the maxima as fp32: a rounded one equals no message
+            out = refwd()
+        x = _gather_raw(params, gi, _F32)
+        wexp = w32.repeat_interleave(params.shape[1] // heads, dim=1)
+        per_edge = _max_per_edge(x * wexp, out, si, size, grad)
+        grad_params = _scatter_raw(_ADD, per_edge * wexp, gi, n)
+        grad_w = per_edge * x             # (dh = 1: the product itself)
+        if params.shape[1] != heads:
+            grad_w = grad_w.view(e, heads, -1).sum(-1)
+    else:
+        g = grad.float() if op == "add" else grad / _count(si, size, grad.device)
+        g = g.contiguous()
+        grad_params = _gather_scatter_w_raw(_ADD, g, si, gi, n, w32, heads)
+        grad_w = _edge_dot_raw(g, si, params, gi, heads, _F32)
+    return grad_params.to(params.dtype), grad_w.to(w.dtype).reshape(w.shape)
+
+
+class _GatherScatterW(torch.autograd.Function):
+    """gather_scatter with edge_weight (euler_gpu_gather_scatter_w)"""
+
+    @staticmethod
+    def forward(ctx, params, gather_indices, scatter_indices, size, op, validate, out_dtype, w):
+        w2, heads = _edge_weight("gather_scatter", w, gather_indices.numel(), params)
+        out = _gather_scatter_w_raw(_GS_MODE[op], params, gather_indices, scatter_indices, size, w2, heads,
+                                    out_dtype, validate)
+        ctx.save_for_backward(params, gather_indices, scatter_indices, w, out)
+        ctx.size, ctx.op = size, op
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        params, gi, si, w, out = ctx.saved_tensors
+        w2 = w.reshape(gi.numel(), -1).contiguous()
+        refwd = lambda: _gather_scatter_w_raw(_MAX, params, gi, si, ctx.size, w2, w2.shape[1], _F32)
+        gp, gw = _weighted_backward(ctx.op, params, gi, si, w, out, ctx.size, grad, refwd)
+        return gp, None, None, None, None, None, None, gw
+
+
+class _GatherSegmentReduceW(torch.autograd.Function):
+    """gather_segment_reduce with edge_weight (euler_gpu_gather_segment_reduce_w / _ids_w)"""
+
+    @staticmethod
+    def _raw(mode, params, gi, as_ids, sp, count, size, w2, heads, od):
+        code = _lib.F32 if params.dtype == _F32 else _DT[params.dtype]
+        out = torch.empty((int(size), params.shape[1]), dtype=od, device=params.device)
+        sp_p = _ptr(sp) if sp is not None else None
+        d = params.shape[1]
+        with _on(params.device):
+            if code == _lib.F32:
+                if as_ids:
+                    check(lib().euler_gpu_gather_segment_reduce_ids_w(
+                        _stream(), mode, _ptr(params), int(params.shape[0]), _ptr(gi), sp_p, int(count), d,
+                        int(size), _ptr(out), _ptr(w2), heads))
+                else:
+                    check(lib().euler_gpu_gather_segment_reduce_w(
+                        _stream(), mode, _ptr(params), _ptr(gi), sp_p, int(count), d, int(size), _ptr(out),
+                        _ptr(w2), heads))
+            elif as_ids:
+                check(lib().euler_gpu_gather_segment_reduce_ids_w_t(
+                    _stream(), mode, _ptr(params), code, int(params.shape[0]), _ptr(gi), sp_p, int(count), d,
+                    int(size), _ptr(out), _DT[od], _ptr(w2), _DT[w2.dtype], heads))
+            else:
+                check(lib().euler_gpu_gather_segment_reduce_w_t(
+                    _stream(), mode, _ptr(params), code, _ptr(gi), sp_p, int(count), d, int(size), _ptr(out),
+                    _DT[od], _ptr(w2), _DT[w2.dtype], heads))
+        return out
+
+    @staticmethod
+    def forward(ctx, params, gather_indices, seg_ptr, count, size, op, validate, out_dtype, w):
+        _dt("gather_segment_reduce", params)
+        od = _out_dt("gather_segment_reduce", params, out_dtype)
+        w2, heads = _edge_weight("gather_segment_reduce", w, gather_indices.numel(), params)
+        params = params.contiguous()
+        as_ids = gather_indices.dtype == torch.int64 and not validate
+        gi = gather_indices.contiguous() if as_ids else gather_indices.to(torch.int32).contiguous()
+        _need_cuda(params, gi)
+        sp = None
+        if seg_ptr is not None:
+            sp = seg_ptr.to(torch.int64).contiguous()
+            _need_cuda(params, sp)
+            if sp.numel() != size + 1:
+                raise ValueError("gather_segment_reduce: seg_ptr has size + 1 entries")
+        elif gi.numel() != size * count:
+            raise ValueError("gather_segment_reduce: size * count gather indices")
+        if validate:
+            _check_rows("gather_segment_reduce", gi, params.shape[0])
+        out = _GatherSegmentReduceW._raw(_GS_MODE[op], params, gi, as_ids, sp, count, size, w2, heads, od)
+        if as_ids and (ctx.needs_input_grad[0] or ctx.needs_input_grad[8]):
+            # the clamp-to-last-row rule of the forward kernel for the saved indices
+            # (_GatherSegmentReduce.forward)
+            last = int(params.shape[0]) - 1
+            gi = torch.clamp(gi & 0xFFFFFFFF, max=last).to(torch.int32)
+        ctx.save_for_backward(params, gi, sp if sp is not None else torch.empty(0), w, out)
+        ctx.has_ptr, ctx.count, ctx.size, ctx.op = sp is not None, int(count), int(size), op
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        params, gi, sp, w, out = ctx.saved_tensors
+        si = _segment_dst(sp if ctx.has_ptr else None, ctx.count, ctx.size, grad.device)
+        w2 = w.reshape(gi.numel(), -1).contiguous()
+        refwd = lambda: _gather_scatter_w_raw(_MAX, params, gi, si, ctx.size, w2, w2.shape[1], _F32)
+        gp, gw = _weighted_backward(ctx.op, params, gi, si, w, out, ctx.size, grad, refwd)
+        return gp, None, None, None, None, None, None, None, gw
+
+
+class _EdgeDot(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, a_index, b, b_index, heads, od):
+        ctx.save_for_backward(a, b, *[t for t in (a_index, b_index) if t is not None])
+        ctx.has = (a_index is not None, b_index is not None)
+        ctx.heads = heads
+        return _edge_dot_raw(a, a_index, b, b_index, heads, od)
+
+    @staticmethod
+    def backward(ctx, grad):
+        a, b = ctx.saved_tensors[:2]
+        rest = list(ctx.saved_tensors[2:])
+        ai = rest.pop(0) if ctx.has[0] else None
+        bi = rest.pop(0) if ctx.has[1] else None
+        g = grad.float().contiguous()
+        e = g.shape[0]
+        every = None
+        if ai is None or bi is None:
+            every = torch.arange(e, device=g.device, dtype=torch.int32)
+        ga = gb = None
+        if ctx.needs_input_grad[0]:       # d out[p, h] / d a[ai[p]] = grad[p, h] * b[bi[p]]
+            ga = _gather_scatter_w_raw(_ADD, b, bi, ai if ai is not None else every, a.shape[0], g,
+                                       ctx.heads, _F32).to(a.dtype)
+        if ctx.needs_input_grad[2]:
+            gb = _gather_scatter_w_raw(_ADD, a, ai, bi if bi is not None else every, b.shape[0], g,
+                                       ctx.heads, _F32).to(b.dtype)
+        return ga, None, gb, None, None, None
+
+
+def edge_dot(a, a_index, b, b_index, heads=1, out_dtype=None):
+    """out[p, h] = sum_c a[a_index[p], h * dh + c] * b[b_index[p], h * dh + c] with dh = D // heads:
+    the dot product of two gathered rows per edge (and per head) - AGNN's attention logit, the
+    gradient of an edge-weighted aggregation with respect to its weights - without either [E, D]
+    block (euler_gpu_edge_dot).  a and b are [*, D] tables in fp32, bf16 or fp16 (each its own),
+    the indices int32 [E] (None: row p).  fp32 products and sums in a fixed order; out_dtype:
+    torch.float32, or a 16-bit dtype (rounded once); None = the dtype of a and b when they agree,
+    else float32.  Returns [E, heads].
+    grad_a = gather_scatter("add", b, b_index, a_index, rows_a, edge_weight=grad_out), grad_b the
+    same with the roles swapped."""
+    _dt("edge_dot", a)
+    _dt("edge_dot", b)
+    _need_cuda(a, b)
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError("edge_dot: a and b are [rows, D] tables of one D")
+    heads = int(heads)
+    if heads < 1 or a.shape[1] % heads != 0:
+        raise ValueError("edge_dot: heads must divide D")
+    if out_dtype is None:
+        out_dtype = a.dtype if a.dtype == b.dtype else _F32
+    if out_dtype not in _DT:
+        raise TypeError("edge_dot: out_dtype is float32, bfloat16 or float16, not %s" % out_dtype)
+    e = a_index.numel() if a_index is not None else b_index.numel() if b_index is not None else a.shape[0]
+    if (b_index is not None and b_index.numel() != e) or (a_index is None and a.shape[0] != e) or \
+            (b_index is None and b.shape[0] != e):
+        raise ValueError("edge_dot: one row of a and one of b per edge")
+    return _EdgeDot.apply(a, a_index, b, b_index, heads, out_dtype)
 
 
 def scatter_softmax(updates, indices, size, out_dtype=None):

@@ -837,6 +837,71 @@ int euler_gpu_gather_segment_reduce_ids_t(void* stream, int32_t mode, const void
                                           const int64_t* seg_ptr_dev, int64_t count, int64_t d,
                                           int32_t size, void* out_dev, int32_t out_dtype);
 
+/* ---- edge-weighted message passing -----------------------------------------------
+ * The fused reduces above with a per-edge multiplier folded in: update p contributes
+ * fl(params[g(p)][c] * w[p][c / dh]), dh = d / heads - the message of GCN and APPNP
+ * (tf_euler/python/convolution/gcn_conv.py:50-51, appnp_conv.py:54-55: norm_i * norm_j * x_j;
+ * heads = 1) and of GAT and AGNN (gat_conv.py:71, agnn_conv.py:54: x_j * alpha, one alpha per
+ * head), or a sampled neighbour's weight (sample_neighbor returns them next to the ids).
+ * w_dev is [e, heads], indexed by the update's position in the INPUT.  The product and the add
+ * are two correctly rounded fp32 operations, in input order: the bits of
+ * scatter_(op, gather(params, g) * w, dst, size) with the multiply done elementwise in fp32,
+ * without any [e, d] intermediate.  mean divides by (segment length + 1e-7f); the weights do not
+ * enter the denominator.  Arguments as the unweighted sibling, then w_dev and heads (and, for the
+ * _t forms, w_dtype: EULER_GPU_F32 or in_dtype - widened exactly, products and sums in fp32, one
+ * rounding at the store).  gather_indices_dev of euler_gpu_gather_scatter_w may be NULL: update p
+ * is row p.  16-byte-aligned buffers with the unweighted vector shapes and dh % 4 == 0 (fp32) /
+ * dh % 8 == 0 (16-bit) take the 16-byte-lane kernels.  EULER_GPU_EINVAL: heads < 1, heads not
+ * dividing d, a null buffer, e >= 2^31, mean with e (or count) >= 2^24.  size == 0 or d == 0
+ * returns EULER_GPU_OK and touches nothing. */
+int euler_gpu_gather_scatter_w(void* stream, int32_t mode, const float* params_dev,
+                               const int32_t* gather_indices_dev,
+                               const int32_t* scatter_indices_dev, int64_t e, int64_t d,
+                               int32_t size, float* out_dev, const float* w_dev, int32_t heads);
+int euler_gpu_gather_segment_reduce_w(void* stream, int32_t mode, const float* params_dev,
+                                      const int32_t* gather_indices_dev,
+                                      const int64_t* seg_ptr_dev, int64_t count, int64_t d,
+                                      int32_t size, float* out_dev, const float* w_dev,
+                                      int32_t heads);
+int euler_gpu_gather_segment_reduce_ids_w(void* stream, int32_t mode, const float* params_dev,
+                                          int64_t params_rows, const int64_t* gather_ids_dev,
+                                          const int64_t* seg_ptr_dev, int64_t count, int64_t d,
+                                          int32_t size, float* out_dev, const float* w_dev,
+                                          int32_t heads);
+int euler_gpu_gather_scatter_w_t(void* stream, int32_t mode, const void* params_dev, int32_t in_dtype,
+                                 const int32_t* gather_indices_dev,
+                                 const int32_t* scatter_indices_dev, int64_t e, int64_t d,
+                                 int32_t size, void* out_dev, int32_t out_dtype, const void* w_dev,
+                                 int32_t w_dtype, int32_t heads);
+int euler_gpu_gather_segment_reduce_w_t(void* stream, int32_t mode, const void* params_dev,
+                                        int32_t in_dtype, const int32_t* gather_indices_dev,
+                                        const int64_t* seg_ptr_dev, int64_t count, int64_t d,
+                                        int32_t size, void* out_dev, int32_t out_dtype,
+                                        const void* w_dev, int32_t w_dtype, int32_t heads);
+int euler_gpu_gather_segment_reduce_ids_w_t(void* stream, int32_t mode, const void* params_dev,
+                                            int32_t in_dtype, int64_t params_rows,
+                                            const int64_t* gather_ids_dev,
+                                            const int64_t* seg_ptr_dev, int64_t count, int64_t d,
+                                            int32_t size, void* out_dev, int32_t out_dtype,
+                                            const void* w_dev, int32_t w_dtype, int32_t heads);
+/* out[p][h] = sum over c < dh of a[a_index[p]][h * dh + c] * b[b_index[p]][h * dh + c], dh =
+ * d / heads: the per-edge dot product of two gathered rows - the gradient of the entries above
+ * with respect to w, and AGNN's attention logit (agnn_conv.py:43-47) - without either [e, d]
+ * block of gathered rows.  An index array may be NULL (row p); indices must be valid rows.  fp32
+ * products and fp32 sums in a fixed order that depends on dh, the types and the 16-byte alignment
+ * of the tables, never on e or the launch (stated in euler_amd/csrc/edge_dot_kernels.hip): the
+ * same call returns the same bits; dh = 1 returns the fp32 product.  out_dev is [e, heads].
+ * The _t form: each table has its own storage type, out_dtype is any of the three (one
+ * rounding).  EULER_GPU_EINVAL: heads < 1, heads not dividing d, a null buffer, e >= 2^31, an
+ * unknown dtype.  e == 0 or d == 0 returns EULER_GPU_OK and touches nothing. */
+int euler_gpu_edge_dot(void* stream, const float* a_dev, const int32_t* a_index_dev,
+                       const float* b_dev, const int32_t* b_index_dev, int64_t e, int64_t d,
+                       int32_t heads, float* out_dev);
+int euler_gpu_edge_dot_t(void* stream, const void* a_dev, int32_t a_dtype,
+                         const int32_t* a_index_dev, const void* b_dev, int32_t b_dtype,
+                         const int32_t* b_index_dev, int64_t e, int64_t d, int32_t heads,
+                         void* out_dev, int32_t out_dtype);
+
 /* ---- shard ops (multi-GPU) --------------------------------------------------
  * ID_SPLIT (core/kernels/id_split_op.cc:46-99): stable bucket of ids by
  * owner(id) = (id % partitions) % shards.  shard_off_host [shards+1] is
