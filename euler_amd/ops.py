@@ -652,6 +652,103 @@ def edge_dot(a, a_index, b, b_index, heads=1, out_dtype=None):
     return _EdgeDot.apply(a, a_index, b, b_index, heads, out_dtype)
 
 
+# ---- fused softmax over the updates of a destination ------------------------------------------
+def _edge_softmax_raw(x2, grad2, si, sp, count, size, od):
+    """euler_gpu_edge_softmax (grad2 None) / euler_gpu_edge_softmax_grad (x2 = the forward's
+    output) on contiguous [E, H] tensors; -> [E, H] of dtype od"""
+    e, heads = x2.shape
+    out = torch.empty((e, heads), dtype=od, device=x2.device)
+    if e == 0:
+        return out
+    if heads == 0:
+        raise ValueError("edge_softmax: heads < 1")
+    with _on(x2.device):
+        if grad2 is None:
+            check(lib().euler_gpu_edge_softmax(_stream(), _ptr(x2), _DT[x2.dtype], _ptr(si), _ptr(sp),
+                                               int(count), e, heads, int(size), _ptr(out), _DT[od]))
+        else:
+            check(lib().euler_gpu_edge_softmax_grad(_stream(), _ptr(x2), _DT[x2.dtype], _ptr(grad2),
+                                                    _DT[grad2.dtype], _ptr(si), _ptr(sp), int(count), e,
+                                                    heads, int(size), _ptr(out), _DT[od]))
+    return out
+
+
+class _EdgeSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, si, sp, count, size, od):
+        x2 = logits.reshape(logits.shape[0], 1 if logits.dim() == 1 else logits.shape[1]).contiguous()
+        # the backward reads the forward's fp32 output; a 16-bit visible one is its rounding
+        keep = ctx.needs_input_grad[0] and od != _F32
+        y = _edge_softmax_raw(x2, None, si, sp, count, size, _F32 if keep else od)
+        ctx.save_for_backward(y, *[t for t in (si, sp) if t is not None])
+        ctx.has, ctx.count, ctx.size, ctx.in_dtype = (si is not None, sp is not None), count, size, logits.dtype
+        return (y.to(od) if keep else y).reshape(logits.shape)
+
+    @staticmethod
+    def backward(ctx, grad):
+        y = ctx.saved_tensors[0]
+        rest = list(ctx.saved_tensors[1:])
+        si = rest.pop(0) if ctx.has[0] else None
+        sp = rest.pop(0) if ctx.has[1] else None
+        g2 = grad.reshape(y.shape).contiguous()
+        if g2.dtype not in _DT:
+            g2 = g2.float()
+        gx = _edge_softmax_raw(y, g2, si, sp, ctx.count, ctx.size, ctx.in_dtype)
+        return gx.reshape(grad.shape), None, None, None, None, None
+
+
+def edge_softmax(logits, indices=None, size=None, seg_ptr=None, count=None, out_dtype=None):
+    """The softmax of the logits over the updates of every destination, in one read and one write
+    (euler_gpu_edge_softmax): what GATConv / AGNNConv run between `edge_dot` and an aggregation
+    with edge_weight.  logits is [E], [E, 1] or [E, H] (one column per head) in fp32, bf16 or fp16;
+    the output has its shape.  The destinations come in exactly one form: `indices` (int32 [E]
+    scatter keys in any order, with `size`), `seg_ptr` (int64 [size + 1] offsets) or `count`
+    (updates per destination, with `size`) - the forms of gather_scatter and
+    gather_segment_reduce.  Arithmetic in fp32 with the library's own exp and a fixed summation
+    order: the same segment gives the same bits through every form - not the bits of
+    `scatter_softmax`, which stays the reference's composition.  out_dtype: torch.float32 or the
+    input's dtype (None), rounded once.  Updates that belong to no destination (a key outside
+    [0, size), a position outside [seg_ptr[0], seg_ptr[size])) get 0.
+    Differentiable: grad = y * (g - sum_q y_q g_q) per destination (euler_gpu_edge_softmax_grad),
+    on the fp32 output."""
+    _dt("edge_softmax", logits)
+    od = _out_dt("edge_softmax", logits, out_dtype)
+    _need_cuda(logits)
+    if logits.dim() not in (1, 2):
+        raise ValueError("edge_softmax: logits is [E], [E, 1] or [E, H]")
+    if logits.dim() == 2 and logits.shape[1] < 1:
+        raise ValueError("edge_softmax: logits needs at least one head")
+    if (indices is not None) + (seg_ptr is not None) + (count is not None) != 1:
+        raise ValueError("edge_softmax: pass exactly one of indices, seg_ptr and count")
+    e = int(logits.shape[0])
+    si = sp = None
+    if indices is not None:
+        if size is None:
+            raise ValueError("edge_softmax: indices need size")
+        si = indices.to(torch.int32).contiguous()
+        _need_cuda(si)
+        if si.numel() != e:
+            raise ValueError("edge_softmax: one index per edge (%d), not %d" % (e, si.numel()))
+    elif seg_ptr is not None:
+        sp = seg_ptr.to(torch.int64).contiguous()
+        _need_cuda(sp)
+        if size is None:
+            size = sp.numel() - 1
+        if sp.numel() != int(size) + 1:
+            raise ValueError("edge_softmax: seg_ptr has size + 1 entries")
+    else:
+        count = int(count)
+        if count < 1:
+            raise ValueError("edge_softmax: count >= 1")
+        if size is None:
+            size = e // count
+        if int(size) * count != e:
+            raise ValueError("edge_softmax: size * count logit rows")
+    if int(size) < 0:
+        raise ValueError("edge_softmax: size >= 0")
+    return _EdgeSoftmax.apply(logits, si, sp, 0 if count is None else count, int(size), od)
+
+
 def scatter_softmax(updates, indices, size, out_dtype=None):
     """mp_ops.py:76-79.  16-bit updates: the fp32 softmax of updates.float(), rounded once at the end
     unless out_dtype is torch.float32 (and its gradient once on the way back)."""

@@ -901,6 +901,38 @@ int euler_gpu_edge_dot_t(void* stream, const void* a_dev, int32_t a_dtype,
                          const int32_t* a_index_dev, const void* b_dev, int32_t b_dtype,
                          const int32_t* b_index_dev, int64_t e, int64_t d, int32_t heads,
                          void* out_dev, int32_t out_dtype);
+/* edge_softmax: the softmax of the [e, heads] logits over the updates of every destination -
+ * what GATConv and AGNNConv run between the logit and the aggregate (gat_conv.py:66-72), the
+ * reference's scatter_softmax (tf_euler/python/euler_ops/mp_ops.py:76-79) - in one read and one
+ * write, and its gradient gx_p = y_p * (g_p - sum_q y_q g_q) on the forward's output y.
+ * What differs from the composition scatter_max / gather / exp / scatter_add / gather / divide:
+ * the exponential is the library's own (ExpNonPositive of euler_amd/csrc/mp_softmax.h: correctly
+ * rounded fp32 operations only, +0 below -86, error bound in DESIGN 4.11), and the sum runs in the
+ * order that header states - a function of the segment length and of heads, never of e, size or
+ * the launch.  So the bits are NOT those of the composition; they are the same for the same
+ * segment through every form, on every call, and on the host build of the header.
+ * The destinations are given in exactly ONE of three forms: indices_dev (int32 scatter keys, e of
+ * them, any order; grouped by one stable sort a call when they are not non-decreasing, values are
+ * read and written at their input position), seg_ptr_dev (int64, size + 1 non-decreasing offsets
+ * into the e updates; those outside [seg_ptr[0], seg_ptr[size]) have no destination), or count > 0
+ * (destination r owns updates [r * count, (r + 1) * count); e == size * count).  An empty segment
+ * writes nothing; updates that belong to no destination (a key outside [0, size), a position
+ * outside the span of seg_ptr) get 0 (output and gradient); a -inf
+ * logit beside a finite maximum gets exactly 0.  A segment whose maximum is not finite (all -inf,
+ * a +inf) returns NaN for all of it; a NaN logit is left out of the maximum and gets 0.
+ * Storage: logits fp32 / bf16 / fp16, out_dtype fp32 or in_dtype (one rounding); in the gradient
+ * y, grad and the output are each any of the three; all arithmetic is fp32.
+ * EULER_GPU_EINVAL: heads < 1, a null buffer, an unknown dtype, e >= 2^31, not exactly one
+ * segment form, count with e != size * count.  e == 0 returns EULER_GPU_OK and touches nothing. */
+int euler_gpu_edge_softmax(void* stream, const void* logits_dev, int32_t in_dtype,
+                           const int32_t* indices_dev, const int64_t* seg_ptr_dev, int64_t count,
+                           int64_t e, int32_t heads, int32_t size, void* out_dev,
+                           int32_t out_dtype);
+int euler_gpu_edge_softmax_grad(void* stream, const void* y_dev, int32_t y_dtype,
+                                const void* grad_dev, int32_t grad_dtype,
+                                const int32_t* indices_dev, const int64_t* seg_ptr_dev,
+                                int64_t count, int64_t e, int32_t heads, int32_t size,
+                                void* out_dev, int32_t out_dtype);
 
 /* ---- shard ops (multi-GPU) --------------------------------------------------
  * ID_SPLIT (core/kernels/id_split_op.cc:46-99): stable bucket of ids by
