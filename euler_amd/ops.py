@@ -117,11 +117,35 @@ def _count(indices, size, device):
     return _scatter_raw(_ADD, ones, indices, size) + 1e-7
 
 
+# An update whose scatter key lies outside [0, size) belongs to no destination: the reduces leave
+# it out (mp_segments.h), so its gradient is exactly 0 and no backward pass may read a row of
+# grad, out or a count with its key - `gather` trusts its indices.  The keys are made safe and the
+# rows of such updates zeroed on the device, without a host wait; in-range updates keep their bits.
+def _keys_in_range(si, size):
+    """-> (valid [E, 1] bool, the keys as int32 with every key outside [0, size) replaced by 0)"""
+    si = si.to(torch.int32)
+    valid = (si >= 0) & (si < size)
+    return valid.reshape(-1, 1), torch.where(valid, si, torch.zeros_like(si))
+
+
+def _gather_by_key(t, si, out_dtype=None):
+    """rows of t ([size, D]: grad, or grad / count) by scatter key; 0 where the key names no row"""
+    size = t.shape[0]
+    if size == 0:
+        return torch.zeros((si.numel(), t.shape[1]), dtype=_out_dt("gather", t, out_dtype), device=t.device)
+    valid, safe = _keys_in_range(si, size)
+    return _gather_raw(t, safe, out_dtype).masked_fill_(~valid, 0)
+
+
 def _max_per_edge(updates32, out, si, size, grad):
     """the per-edge gradient of a max reduce (mp_ops.py:39-62), all fp32"""
-    indicators = (updates32 == _gather_raw(out, si, _F32)).to(_F32)
-    num_selected = _scatter_raw(_ADD, indicators, si, size)
-    return indicators / _gather_raw(num_selected, si) * _gather_raw(grad, si, _F32)
+    if size == 0:
+        return torch.zeros_like(updates32)
+    valid, safe = _keys_in_range(si, size)
+    indicators = (updates32 == _gather_raw(out, safe, _F32)).to(_F32)
+    num_selected = _scatter_raw(_ADD, indicators, si, size)      # (leaves the same updates out)
+    per_edge = indicators / _gather_raw(num_selected, safe) * _gather_raw(grad, safe, _F32)
+    return per_edge.masked_fill_(~valid, 0)
 
 
 # Gradients as registered in tf_euler/python/euler_ops/mp_ops.py:39-62.  With 16-bit data the
@@ -151,7 +175,7 @@ class _ScatterAdd(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad):
         (indices,) = ctx.saved_tensors
-        return _gather_raw(grad, indices, _F32).to(ctx.dt), None, None, None
+        return _gather_by_key(grad, indices, _F32).to(ctx.dt), None, None, None
 
 
 class _ScatterMax(torch.autograd.Function):
@@ -180,7 +204,12 @@ def scatter_add(updates, indices, size, out_dtype=None):
     """MPScatterAdd: out[indices[i],:] += updates[i,:], zero init, [size,D].  16-bit updates are
     added in fp32, in input order - the bits of the fp32 op on updates.float() - and the sums
     are returned as fp32 (out_dtype=torch.float32) or rounded once to the updates' dtype
-    (out_dtype=None)."""
+    (out_dtype=None).
+    An update whose index is < 0 or >= size belongs to no destination: it is left out of `out`
+    and its gradient is exactly 0.  The rule holds for every op with a scatter key column -
+    scatter_add / scatter_max / scatter_mean and gather_scatter, with or without edge_weight (there
+    for grad_edge_weight too) - as it does for edge_softmax; no backward pass reads a row of
+    grad with such a key."""
     return _ScatterAdd.apply(updates, indices, int(size), out_dtype)
 
 
@@ -204,7 +233,7 @@ class _ScatterMean(torch.autograd.Function):
     def backward(ctx, grad):
         (indices,) = ctx.saved_tensors
         count = _count(indices, ctx.size, grad.device)
-        return _gather_raw(grad / count, indices).to(ctx.dt), None, None, None
+        return _gather_by_key(grad / count, indices).to(ctx.dt), None, None, None
 
 
 def scatter_mean(updates, indices, size, out_dtype=None):
@@ -257,9 +286,9 @@ def _gather_scatter_raw(mode, params, gather_indices, scatter_indices, size, val
 def _edge_grad(op, params, gi, si, out, size, grad):
     """fp32 gradient of reduce(op, gather(params, gi), si, size) per edge (mp_ops.py:39-62)"""
     if op == "add":
-        return _gather_raw(grad, si, _F32)
+        return _gather_by_key(grad, si, _F32)
     if op == "mean":
-        return _gather_raw(grad / _count(si, size, grad.device), si)
+        return _gather_by_key(grad / _count(si, size, grad.device), si)
     return _max_per_edge(_gather_raw(params, gi, _F32), out, si, size, grad)
 
 
@@ -499,9 +528,14 @@ def _weighted_backward(op, params, gi, si, w, out, size, grad, refwd):
             grad_w = grad_w.view(e, heads, -1).sum(-1)
     else:
         g = grad.float() if op == "add" else grad / _count(si, size, grad.device)
-        g = g.contiguous()
-        grad_params = _gather_scatter_w_raw(_ADD, g, si, gi, n, w32, heads)
-        grad_w = _edge_dot_raw(g, si, params, gi, heads, _F32)
+        # here the scatter keys are GATHER indices, and the products with G's rows are formed
+        # inside the kernels, where nothing can be zeroed afterwards: an update with a key
+        # outside [0, size) (_keys_in_range) reads a row of zeros appended to G, with a weight of 0
+        valid, key = _keys_in_range(si, size)
+        key = torch.where(valid.reshape(-1), key, torch.full_like(key, size))
+        g = torch.cat([g, g.new_zeros((1, g.shape[1]))])
+        grad_params = _gather_scatter_w_raw(_ADD, g, key, gi, n, w32.masked_fill(~valid, 0), heads)
+        grad_w = _edge_dot_raw(g, key, params, gi, heads, _F32).masked_fill_(~valid, 0)
     return grad_params.to(params.dtype), grad_w.to(w.dtype).reshape(w.shape)
 
 

@@ -756,7 +756,13 @@ int euler_gpu_data_gather(void* stream, const void* data_dev, int32_t elem_size,
  * MPScatterAdd / MPScatterMax / MPGather (tf_euler/kernels/scatter_op.cc:27-105,
  * gather_op.cc:26-59).  fp32 data, int32 indices.  Scatter results are
  * order-faithful: each output element adds its updates in input order, so
- * they are bit-identical to the reference's sequential loop. */
+ * they are bit-identical to the reference's sequential loop.
+ * An update whose scatter index is < 0 or >= size belongs to no destination (undefined behaviour
+ * in the reference): every entry with a key column - scatter_add / _max / _mean, gather_scatter and
+ * their _w and _t forms - leaves it out, an empty destination is 0 (add, mean) or -1e9 (max), and
+ * the gradients the Python layer builds from these entries give such an update exactly 0 (output
+ * and gradient, as euler_gpu_edge_softmax below) without reading grad, out or a count by its key.
+ * euler_gpu_gather trusts its indices. */
 int euler_gpu_scatter_add(void* stream, const float* updates_dev,
                           const int32_t* indices_dev, int64_t e, int64_t d,
                           int32_t size, float* out_dev);
