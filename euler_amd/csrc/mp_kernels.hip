@@ -1130,16 +1130,10 @@ __global__ __launch_bounds__(256) void DenseFeatureVec4Kernel(
     const int32_t c = (int32_t)(s - j * (uint32_t)dv) * 4;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     const int64_t row = FindRow(g, nodes[j]);
-    if (row >= 0 && c < len) {
-      const float* src = g.feat_val + row * g.feat_stride + pre + c;
-      if (c + 3 < len) {
-        v = *reinterpret_cast<const float4*>(src);
-      } else {
-        v.x = src[0];
-        if (c + 1 < len) v.y = src[1];
-        if (c + 2 < len) v.z = src[2];
-      }
-    }
+    // every slot end of such a table is a multiple of 4 (the slot begins and the stride are),
+    // and so is c: c < len means the whole 16 bytes are the slot's
+    if (row >= 0 && c < len)
+      v = *reinterpret_cast<const float4*>(g.feat_val + row * g.feat_stride + pre + c);
     out[s] = v;
   }
 }
