@@ -41,6 +41,7 @@
 
 #include "k1_search.h"
 #include "wb_index.h"
+#include "wb_hw.h"
 
 namespace euler_gpu {
 
@@ -682,6 +683,57 @@ __device__ __forceinline__ void WbSamplePair(const GraphView& g, const WbRec rec
   }
 }
 
+// Hop 2 of the plain-graph fanout through the header + window lines (wb_hw.h): hop 2 needs
+// neither the drawn edge's number nor ten keys in registers, so a draw asks for its line's
+// 16-byte header and then, in ONE dependent trip, for the window the header names and the 12
+// bytes before it (the entry a guess that is one too high wants) - three requests in two trips
+// where a block costs four.  Both headers are issued before either window, all four window
+// loads before any is examined; Q3 draws and everything the two entries do not settle replay
+// RandomSelect, exactly as WbSamplePair's cold draws do.  No branch encloses a load or a check:
+// the compiler would sink a window's words into the branches and fetch them one trip at a time,
+// and a wave-wide second trip for the few lanes whose guess is off costs more than it saves
+// (measured: DESIGN 4.2).
+__device__ __forceinline__ void HwSamplePair(const HwLine* hw, const float* prefix_w, const uint64_t* nbr,
+                                             const WbRec rec, const bool live, const double u0,
+                                             const double u1, uint64_t id[2], float w[2]) {
+  const double r0 = __dmul_rn(u0, (double)rec.total), r1 = __dmul_rn(u1, (double)rec.total);
+  const bool t0 = live && (double)rec.total > r0, t1 = live && (double)rec.total > r1;
+  const float f0 = WbFloorToFloat(r0), f1 = WbFloorToFloat(r1);
+  const uint32_t nbk = WbBuckets(rec.deg);
+  uint32_t j0 = 0u, j1 = 0u;
+  if (nbk > 1u) {
+    const float scale = WbScale(nbk, rec.total);
+    j0 = WbBucketOf(f0, nbk, scale);
+    j1 = WbBucketOf(f1, nbk, scale);
+  }
+  // (a dead lane's record is all zeros: line 0, a valid line nobody uses)
+  const HwLine* l0 = hw + rec.wb_lo + j0;
+  const HwLine* l1 = hw + rec.wb_lo + j1;
+  const HwHead h0 = HwLoadHead(l0), h1 = HwLoadHead(l1);
+  const uint32_t i0 = HwGuess(h0, f0), i1 = HwGuess(h1, f1);
+  const HwPre p0 = HwLoadPre(l0, i0), p1 = HwLoadPre(l1, i1);
+  const HwWin x0 = HwLoadWin(l0, i0), x1 = HwLoadWin(l1, i1);
+  id[0] = 0; id[1] = 0; w[0] = 0.f; w[1] = 0.f;
+  const int32_t d0 = HwPick(p0, x0, i0, f0, &id[0], &w[0]), d1 = HwPick(p1, x1, i1, f1, &id[1], &w[1]);
+  const bool hot0 = t0 && d0 == 0, hot1 = t1 && d1 == 0;
+  if (!hot0) { id[0] = 0; w[0] = 0.f; }
+  if (!hot1) { id[1] = 0; w[1] = 0.f; }
+  const bool cold0 = live && !hot0, cold1 = live && !hot1;
+  if (__ballot(cold0 || cold1) != 0ull) {
+#pragma nounroll
+    for (int s = 0; s < 2; ++s) {
+      if (s == 0 ? cold0 : cold1) {
+        const float* nw = prefix_w + rec.lo;
+        const uint32_t mid = (uint32_t)RandomSelect(nw, 0, (uint64_t)(rec.deg - 1u), s == 0 ? u0 : u1);
+        const uint64_t ci = nbr[rec.lo + mid];
+        const float cw = __fsub_rn(nw[mid], mid == 0u ? 0.f : nw[mid - 1]);
+        if (s == 0) { id[0] = ci; w[0] = cw; }
+        else { id[1] = ci; w[1] = cw; }
+      }
+    }
+  }
+}
+
 // The same pair of draws on ANY graph the weight-bucket index serves - several edge-type
 // groups per node, hashed ids - for one listed type: the segment's limits and the row's first
 // block come out of the row's weight-bucket record (common.h: GraphView::wbg) alone.
@@ -1104,7 +1156,8 @@ __host__ __device__ inline FanoutLeanLds FanoutLeanLayout(int32_t gr, int32_t c1
 // sample, WbSampleTypedPair; at most 127 types); 4 = 3 with the row record in registers (at most 4
 // type groups); 5 = 4 on a graph of uniform weights (the neighbour draw is an index computation);
 // 6 = 2 on a graph of uniform weights.
-template <bool WIDE, int WPS, bool UNIFORM = false, int WB = 0>
+// HW (with WB = 1): hop 2 draws through the header + window side index (HwSamplePair, g.hw).
+template <bool WIDE, int WPS, bool UNIFORM = false, int WB = 0, bool HW = false>
 __global__ __launch_bounds__(256, WPS) void SampleFanoutLeanKernel(
     const FanoutLocalArgs a) {
   extern __shared__ __align__(16) uint8_t fl_smem[];
@@ -1353,6 +1406,8 @@ __global__ __launch_bounds__(256, WPS) void SampleFanoutLeanKernel(
                                               UnitFromWords(pb.w[2], pb.w[3]), id, w, m);
         else if (WB == 2) WbSamplePairG(g, ws, a.t2, live, UnitFromWords(pb.w[0], pb.w[1]),
                                    UnitFromWords(pb.w[2], pb.w[3]), id, w, m);
+        else if (WB == 1 && HW) HwSamplePair(g.hw, g.prefix_w, g.nbr, wr, live, UnitFromWords(pb.w[0], pb.w[1]),
+                                             UnitFromWords(pb.w[2], pb.w[3]), id, w);
         else if (WB) WbSamplePair(g, wr, live, UnitFromWords(pb.w[0], pb.w[1]),
                                   UnitFromWords(pb.w[2], pb.w[3]), id, w, m);
         else if (UNIFORM) LeanSamplePairUniform(g, lo, deg, total, live, UnitFromWords(pb.w[0], pb.w[1]),

@@ -47,6 +47,7 @@ namespace euler_gpu {
 struct FanoutPlainArgs {
   const WbRec* wrec;
   const EdgeBlock* wb;
+  const HwLine* hw;             // HW builds: hop 2's header + window lines (wb_hw.h), same buckets
   const float* prefix_w;        // cold draws only (Q3, a bucket that overflows its block)
   const uint64_t* nbr;
   const uint64_t* roots;
@@ -355,7 +356,9 @@ __device__ __forceinline__ WbRec PlainLoadRec(const FanoutPlainArgs& a, const ui
   return wr;
 }
 
-template <int WPS, bool COOP, bool LITE2 = false>
+// HW = true (tuning key 75, the default where the graph has the side index; not with COOP /
+// LITE2): hop 2 draws through the header + window lines - two requests per draw (HwSamplePair).
+template <int WPS, bool COOP, bool LITE2 = false, bool HW = false>
 __global__ __launch_bounds__(256, WPS) void SampleFanoutPlainKernel(const FanoutPlainArgs a) {
   extern __shared__ __align__(16) uint8_t fp_smem[];
   const uint32_t lane = threadIdx.x & 63u;
@@ -517,6 +520,9 @@ __global__ __launch_bounds__(256, WPS) void SampleFanoutPlainKernel(const Fanout
           const uint32_t left = ns - sb < RPI ? ns - sb : RPI;        // slots of this step
           WaveSamplePairs(a, lane, __umul24(left, hp2), s_stage, s_blk, cr, lv, lv, UnitFromWords(pb.w[0], pb.w[1]),
                           UnitFromWords(pb.w[2], pb.w[3]), i2, w2, m2);
+        } else if (HW) {
+          HwSamplePair(a.hw, a.prefix_w, a.nbr, cr, lv, UnitFromWords(pb.w[0], pb.w[1]),
+                       UnitFromWords(pb.w[2], pb.w[3]), i2, w2);
         } else if (LITE2) {
           PlainSamplePairLite(a, cr, lv, lv, UnitFromWords(pb.w[0], pb.w[1]), UnitFromWords(pb.w[2], pb.w[3]), i2, w2);
         } else {

@@ -18,6 +18,7 @@
 #include "device_fns.h"
 #include "device_mem.h"
 #include "wb_index.h"
+#include "wb_hw.h"
 
 namespace euler_gpu {
 
@@ -881,6 +882,28 @@ __global__ __launch_bounds__(256) void WbFillKernel(GraphView g, const uint32_t*
   if (mine != 0) atomicAdd(overflows, mine);
 }
 
+// the header + window lines of the same buckets (wb_hw.h), one lane per line
+__global__ __launch_bounds__(256) void HwFillKernel(GraphView g, const uint32_t* wb_lo, int64_t n_wb,
+                                                    HwLine* hw, unsigned long long* overflows) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  unsigned long long mine = 0;
+  for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < n_wb; b += stride) {
+    int64_t lo = 0, hi = g.n_rows;            // wb_lo[lo] <= b < wb_lo[hi]
+    while (hi - lo > 1) {
+      const int64_t mid = (lo + hi) >> 1;
+      if ((int64_t)wb_lo[mid] <= b) lo = mid; else hi = mid;
+    }
+    const RowMeta m = LoadRowMeta(g, lo);
+    const uint32_t deg = (uint32_t)m.type_end[g.T - 1];
+    HwLine e;
+    if (HwBuildLine(g.prefix_w, g.nbr, (uint32_t)m.row_ptr, deg, g.prefix_w[m.row_ptr + deg - 1],
+                    (uint32_t)(b - (int64_t)wb_lo[lo]), &e))
+      ++mine;
+    hw[b] = e;
+  }
+  if (mine != 0) atomicAdd(overflows, mine);
+}
+
 // 64-byte hash slots carrying the row record (common.h: GraphView::fat)
 __global__ __launch_bounds__(256) void FatFillKernel(GraphView g, const uint8_t* trec, int32_t trec_stride,
                                                      uint8_t* fat) {
@@ -963,6 +986,51 @@ bool WbFits(size_t need) {
   return need + ((size_t)1 << 30) <= free_b;
 }
 
+// The side index of wb_hw.h, for the graphs whose hop 2 the plain fanout kernels serve.  An
+// optimisation on top of an optimisation: whatever goes wrong DECLINES it (said once per
+// process), gives its memory back and leaves the weight-bucket index as it is.
+void BuildHwSide(GraphBuilder* b, const uint32_t* wb_lo, int64_t n_wb) {
+  static std::atomic<int> said{0};
+  GraphView& v = b->g->view;
+  auto decline = [&](const char* why) {
+    (void)hipGetLastError();
+    if (said.exchange(1) == 0)
+      fprintf(stderr, "euler_gpu: header + window side index declined (%s); hop 2 of the fanout step keeps "
+                      "the weight-bucket blocks\n", why);
+  };
+  const size_t bytes = (size_t)n_wb * sizeof(HwLine);
+  if (!WbFits(bytes)) { decline("over the index budget"); return; }
+  DevBuf cnt;
+  AllocList side("");
+  HwLine* hw = side.Alloc<HwLine>((size_t)n_wb);
+  if (hw == nullptr || cnt.alloc(16) != hipSuccess || hipMemset(cnt.as(), 0, 16) != hipSuccess) {
+    side.Release();
+    decline("no memory");
+    return;
+  }
+  hipLaunchKernelGGL(HwFillKernel, dim3(GridFor(n_wb, 256)), dim3(256), 0, 0, v, wb_lo, n_wb, hw,
+                     cnt.as<unsigned long long>());
+  unsigned long long n_ovf = 0;
+  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpy(&n_ovf, cnt.as(), 8, hipMemcpyDeviceToHost) != hipSuccess) {
+    side.Release();
+    decline("build failed");
+    return;
+  }
+  // nine entries per line where a block has ten: counted again, same bound
+  if ((double)n_ovf > 0.002 * (double)n_wb) {
+    side.Release();
+    decline("more than 2 lines in a thousand overflow");
+    return;
+  }
+  for (auto& blk : side.list) b->list.push_back(blk);
+  side.list.clear();
+  v.hw = hw;
+  b->g->hw_bytes = (int64_t)std::max<size_t>(bytes, 16);
+  b->g->hw_lines = n_wb;
+  b->g->hw_overflows = (int64_t)n_ovf;
+}
+
 int BuildWbIndex(GraphBuilder* b) {
   GraphView& v = b->g->view;
   // uniform weights, several edge-type groups: the row records alone (a draw there is an index
@@ -1040,6 +1108,7 @@ int BuildWbIndex(GraphBuilder* b) {
   v.trec = wbg; v.trec_stride = stride;
   // (i.i.d. uniform weights: 1e-4; lognormal sigma 2, Pareto alpha 0.7: ~5e-2)
   v.wb_lean_ok = (double)n_ovf <= 0.002 * (double)n_wb ? 1 : 0;
+  if (plain && v.has_zero_nbr == 0 && v.wb_lean_ok != 0 && n_wb > 0) BuildHwSide(b, wb_lo, n_wb);
   return BuildFatSlots(b);
 }
 
@@ -1065,6 +1134,7 @@ int EnsureWbIndex(const euler_gpu_graph* cg) {
     GraphView& v = g->view;
     v.wb = nullptr; v.wbg = nullptr; v.wrec = nullptr; v.n_wb = 0; v.wb_lean_ok = 0;
     v.trec = nullptr; v.trec_stride = 0; v.fat = nullptr;
+    v.hw = nullptr; g->hw_bytes = 0; g->hw_lines = 0; g->hw_overflows = 0;
   }
   g->wb_tried.store(1, std::memory_order_release);
   return EULER_GPU_OK;
@@ -1344,6 +1414,16 @@ int euler_gpu_graph_index_overflow_rows(const euler_gpu_graph* g, uint64_t* ids_
     ids_host[n++] = v.id_base + v.id_stride * (uint64_t)row;
   }
   *n_host = n;
+  return EULER_GPU_OK;
+}
+
+int euler_gpu_graph_side_index(const euler_gpu_graph* g, int64_t* bytes_host, int64_t* lines_host,
+                               int64_t* overflows_host) {
+  if (!g || !bytes_host || !lines_host || !overflows_host)
+    return Fail(EULER_GPU_EINVAL, "graph_side_index: null argument");
+  const int rc = EnsureWbIndex(g);
+  if (rc != EULER_GPU_OK) return rc;
+  *bytes_host = g->hw_bytes; *lines_host = g->hw_lines; *overflows_host = g->hw_overflows;
   return EULER_GPU_OK;
 }
 

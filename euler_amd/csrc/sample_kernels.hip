@@ -583,6 +583,9 @@ thread_local int g_fp_coop = 0;       // key 54: ... a block's keys fetched by t
                                       // staged in LDS (1); 0 = three 16-byte loads per lane and line (round 5's pattern)
 thread_local int g_fp_lite2 = 0;      // key 57: ... hop 2 asks for two key chunks per draw and for the third only at
                                       // the ends of its block (1); 0 = all three
+thread_local int g_fp_hw = 1;         // key 75: hop 2 of the plain-graph 2-hop fanout (both kernels) draws through the header +
+                                      // window side index (wb_hw.h: two requests per draw) when the graph has it (1);
+                                      // 0 = through the weight-bucket blocks (four)
 thread_local int g_fp_wps = 5;        // key 55: ... its register budget, waves per SIMD (4 .. 8)
 thread_local int g_fl_wb = 1;         // key 45: the lean kernel draws through the weight-bucket index (wb_index.h:
                                       // one line per draw); 0 = the pivot-level search of rounds 2-3
@@ -618,7 +621,7 @@ int SamplingView(const euler_gpu_graph* g, GraphView* out) {
   }
   *out = g->view;
   if (!wb) { out->wb = nullptr; out->wbg = nullptr; out->wrec = nullptr; out->n_wb = 0; out->wb_lean_ok = 0;
-             out->trec = nullptr; out->trec_stride = 0; out->fat = nullptr; }
+             out->hw = nullptr; out->trec = nullptr; out->trec_stride = 0; out->fat = nullptr; }
   if (g_fl_fat == 0) out->fat = nullptr;
   return EULER_GPU_OK;
 }
@@ -1570,7 +1573,8 @@ static int RunFanout(const euler_gpu_graph* g, hipStream_t stream, uint64_t seed
           if (pgr * ((c1 + 1) / 2) <= 64 && pgr * c1 <= 255 && pgr * c1 % 4 == 0 && tp % 4 == 0 && c2 <= 64 &&
               c1 <= 128 && (int64_t)pcap * c2 < 4096 && (size_t)pl.bytes * (pblock / 64) <= 64 * 1024) {
             FanoutPlainArgs pa{};
-            pa.wrec = f.g.wrec; pa.wb = f.g.wb; pa.prefix_w = f.g.prefix_w; pa.nbr = f.g.nbr;
+            const bool hw2 = g_fp_hw != 0 && f.g.hw != nullptr && !coop && g_fp_lite2 == 0;
+            pa.wrec = f.g.wrec; pa.wb = f.g.wb; pa.hw = f.g.hw; pa.prefix_w = f.g.prefix_w; pa.nbr = f.g.nbr;
             pa.roots = roots_dev;
             pa.id1 = f.id1; pa.w1 = f.w1; pa.ty1 = f.ty1; pa.id2 = f.id2; pa.w2 = f.w2; pa.ty2 = f.ty2;
             pa.row_index = t_fl_row_index;
@@ -1585,7 +1589,7 @@ static int RunFanout(const euler_gpu_graph* g, hipStream_t stream, uint64_t seed
             if (pwaves > 0 && pblocks > (pwaves + pwpb - 1) / pwpb) pblocks = (pwaves + pwpb - 1) / pwpb;
             void (*pk)(const FanoutPlainArgs) = nullptr;
 #define EG_FP(W) (coop ? SampleFanoutPlainKernel<W, true, false> : g_fp_lite2 != 0 ? SampleFanoutPlainKernel<W, false, true> \
-                       : SampleFanoutPlainKernel<W, false, false>)
+                       : hw2 ? SampleFanoutPlainKernel<W, false, false, true> : SampleFanoutPlainKernel<W, false, false>)
             pk = g_fp_wps >= 8 ? EG_FP(8) : g_fp_wps == 7 ? EG_FP(7) : g_fp_wps == 6 ? EG_FP(6)
                  : g_fp_wps == 5 ? EG_FP(5) : EG_FP(4);
 #undef EG_FP
@@ -1623,6 +1627,13 @@ static int RunFanout(const euler_gpu_graph* g, hipStream_t stream, uint64_t seed
           } else if (v.uniform_w != 0) {
             lk = g_fl_wps == 8 ? (f.wide ? SampleFanoutLeanKernel<true, 8, true> : SampleFanoutLeanKernel<false, 8, true>)
                                : (f.wide ? SampleFanoutLeanKernel<true, 5, true> : SampleFanoutLeanKernel<false, 5, true>);
+          } else if (use_wb && plain && g_fp_hw != 0 && f.g.hw != nullptr) {      // hop 2 through the side index
+            lk = f.wide ? (g_fl_wps == 8 ? SampleFanoutLeanKernel<true, 8, false, 1, true>
+                                         : g_fl_wps == 5 ? SampleFanoutLeanKernel<true, 5, false, 1, true>
+                                                         : SampleFanoutLeanKernel<true, 6, false, 1, true>)
+                        : (g_fl_wps == 8 ? SampleFanoutLeanKernel<false, 8, false, 1, true>
+                                         : g_fl_wps == 5 ? SampleFanoutLeanKernel<false, 5, false, 1, true>
+                                                         : SampleFanoutLeanKernel<false, 6, false, 1, true>);
           } else if (use_wb) {
             lk = f.wide ? (g_fl_wps == 8 ? SampleFanoutLeanKernel<true, 8, false, 1>
                                          : g_fl_wps == 5 ? SampleFanoutLeanKernel<true, 5, false, 1>
@@ -1881,6 +1892,7 @@ int euler_gpu_set_tuning(int32_t key, int32_t value) {
   if (key == 64 && value >= 1 && value <= 64) { g_walk_path_ch.store(value); return EULER_GPU_OK; }
   if (key == 63 && (value == 0 || value == 1)) { g_sharded_walk_enqueued.store(value); return EULER_GPU_OK; }
   if (key == 55 && value >= 4 && value <= 8) { g_fp_wps = value; return EULER_GPU_OK; }
+  if (key == 75 && (value == 0 || value == 1)) { g_fp_hw = value; return EULER_GPU_OK; }
   if (key == 56 && value >= 0) { g_blk_fail_next.store(value); return EULER_GPU_OK; }
   return Fail(EULER_GPU_EINVAL, "set_tuning: unknown key");
 }

@@ -383,6 +383,15 @@ class Graph:
             tp.ctypes.data_as(_lib.f32p)))
         return row_ptr, type_end, nbr[:tot], pw[:tot], tp
 
+    def side_index(self):
+        """(bytes, lines, overflowing lines) of the header + window side index that hop 2 of the
+        2-hop fanout draws through on plain weighted graphs (csrc/wb_hw.h); bytes 0 = the graph
+        has none (not that kind of graph, over the index budget, too many overflows).  Builds
+        the indexes if needed; the bytes are part of `device_bytes`."""
+        b, n, o = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(lib().euler_gpu_graph_side_index(self._h, C.byref(b), C.byref(n), C.byref(o)))
+        return b.value, n.value, o.value
+
     def index_overflow_rows(self, cap=4096):
         """Node ids (identity id maps only) of rows in which a bucket of the weight-bucket index
         overflows its block, as found while the index was built (at most 4 096): draws that land

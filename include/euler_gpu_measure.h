@@ -153,6 +153,10 @@ extern "C" {
  *        long rows are done), 0 = two launches.  key 73: PROCESS-WIDE: 1 (default) = the node2vec
  *        walk of more than 16 384 walkers (one launch, a wave per walker) hands the walkers out by
  *        ticket, 0 = every 16 384th walker to a wave (100 000 x 10 on the metric graph: 17.2 / 19.1 ms).
+ * key 75: hop 2 of the plain-graph 2-hop fanout (the kernel of csrc/fanout_plain.h and the lean
+ *        build of fanout_local.h) draws through the header + window side index (csrc/wb_hw.h: two
+ *        16-byte requests per draw) when the graph has one (1 [default]); 0 = through the
+ *        weight-bucket blocks, as hop 1 does (four requests).
  * key 74: hash bits of the graph-label index (1 .. 64, default 64): fewer bits make different
  *        labels share a hash, which the build must still tell apart (tests force collisions).
  * All settings produce identical results; the knobs exist for A/B measurements
@@ -177,6 +181,13 @@ const char* euler_gpu_last_fanout_kernel(void);
  * index if it is not built yet.  Tests draw roots from these rows on purpose. */
 int euler_gpu_graph_index_overflow_rows(const euler_gpu_graph* g, uint64_t* ids_host, int64_t cap,
                                         int64_t* n_host);
+
+/* The header + window side index of the weight-bucket index (csrc/wb_hw.h; plain weighted graphs
+ * only): its bytes (0 = not built: not a plain graph, over the index budget, or more than 2 of its
+ * buckets in a thousand overflow their line), its lines and how many of them overflow.  Builds
+ * the indexes if they are not built yet.  The bytes are part of euler_gpu_graph_bytes. */
+int euler_gpu_graph_side_index(const euler_gpu_graph* g, int64_t* bytes_host, int64_t* lines_host,
+                               int64_t* overflows_host);
 
 /* ---- measurement helper -------------------------------------------------------
  * Runs the sample_neighbor kernel `iters` times on `stream` between two HIP
