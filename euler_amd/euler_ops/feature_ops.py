@@ -60,3 +60,13 @@ def get_binary_feature(nodes, feature_names, thread_num=1):
     g = base.get_default_graph()
     pairs = g.get_binary_feature(nodes, _slots(g, feature_names, "binary", False))
     return _as_bytes(pairs, pairs[0][0].numel() - 1 if pairs else 0)
+
+
+def sparse_feature_embedding(nodes, feature_names, tables, combiner="sum", default_values=None,
+                             out_dtype=None, sparse_grad=False):
+    """nodes -> per (sparse feature, table [V, dim]) the [n, dim] combined embedding rows
+    (ShallowEncoder, utils/encoders.py:146-170), fused and differentiable in the table:
+    Graph.sparse_feature_embedding."""
+    g = base.get_default_graph()
+    return g.sparse_feature_embedding(nodes, _slots(g, feature_names, "sparse", False), tables, combiner,
+                                      default_values, out_dtype, sparse_grad)

@@ -217,6 +217,74 @@ def _label_triple(idx, ids):
     return torch.stack([row, col], 1), vals, [b, width]
 
 
+_SE_COMBINER = {"sum": 0, "mean": 1, "sqrtn": 2}
+
+
+def _sparse_embedding_raw(graph, nodes, fid, default_value, table, combiner, od):
+    """euler_gpu_sparse_feature_embedding: (out [n, dim] of dtype od, counts [n] int32 - the
+    entries each node's combiner counted).  Enqueue only."""
+    n, (n_rows, dim) = nodes.numel(), table.shape
+    out = torch.empty((n, dim), dtype=od, device=graph.device)
+    counts = torch.empty(n, dtype=torch.int32, device=graph.device)
+    with graph._on_device():
+        check(lib().euler_gpu_sparse_feature_embedding(
+            graph._h, _stream(), _ptr(nodes), n, int(fid), int(default_value is not None),
+            int(default_value or 0), _ptr(table), Graph._FEAT_DT[table.dtype], int(n_rows), int(dim),
+            _SE_COMBINER[combiner], _ptr(out), Graph._FEAT_DT[od], _ptr(counts)))
+    return out, counts
+
+
+def _sparse_embedding_pairs(graph, nodes, fid, default_value, n_rows):
+    """(row of the batch, table row) of every entry, in batch order then stored order, from
+    get_sparse_feature (one host wait).  An id that names no row is -1: the mask is taken on the
+    int64 values, unsigned - before any cast to int32, which would wrap 2^32 + 5 into row 5."""
+    # without a default the one entry of an empty node must name no row: -1 does
+    (ind, val, _), = graph.get_sparse_feature(nodes, [fid], [-1 if default_value is None else default_value])
+    ids = torch.where((val < 0) | (val >= n_rows), torch.full_like(val, -1), val)
+    return ind[:, 0].contiguous(), ids
+
+
+class _SparseFeatureEmbedding(torch.autograd.Function):
+    """The fused lookup; the gradient of the table is the composition's:
+    scatter_add(gather(s, row_of_entry), id_of_entry, V) with s = grad / (what the combiner
+    divided by), through the fused gather_scatter (no [nnz, dim] intermediate), rounded once to
+    the table's dtype.  Entries that name no row get exactly 0; nodes get no gradient."""
+
+    @staticmethod
+    def forward(ctx, table, graph, nodes, fid, default_value, combiner, od, sparse_grad):
+        out, counts = _sparse_embedding_raw(graph, nodes, fid, default_value, table, combiner, od)
+        ctx.save_for_backward(nodes, counts)
+        ctx.graph, ctx.fid, ctx.default_value, ctx.combiner = graph, fid, default_value, combiner
+        ctx.shape, ctx.dt, ctx.sparse_grad = tuple(table.shape), table.dtype, sparse_grad
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        from . import ops
+        nodes, counts = ctx.saved_tensors
+        n_rows, dim = ctx.shape
+        s = grad.float()
+        if ctx.combiner != "sum":
+            denom = counts.to(torch.float32)
+            if ctx.combiner == "sqrtn":
+                denom = denom.sqrt()
+            s = s / denom.reshape(-1, 1)
+        s = s.masked_fill((counts == 0).reshape(-1, 1), 0).contiguous()
+        rows, ids = _sparse_embedding_pairs(ctx.graph, nodes, ctx.fid, ctx.default_value, n_rows)
+        none = (None,) * 7
+        if not ctx.sparse_grad:
+            return (ops.gather_scatter("add", s, rows, ids, n_rows).to(ctx.dt),) + none
+        keep = ids >= 0
+        rows, ids = rows[keep], ids[keep]
+        if ids.numel() == 0:
+            return (torch.sparse_coo_tensor(torch.zeros((1, 0), dtype=torch.int64, device=grad.device),
+                                            torch.zeros((0, dim), dtype=ctx.dt, device=grad.device),
+                                            (n_rows, dim)),) + none
+        distinct, inverse = ops.id_unique(ids)
+        values = ops.gather_scatter("add", s, rows, inverse, distinct.numel()).to(ctx.dt)
+        return (torch.sparse_coo_tensor(distinct.reshape(1, -1), values, (n_rows, dim)),) + none
+
+
 class Graph:
     """Immutable graph in HBM (CSR + row metadata + alias tables)."""
 
@@ -973,6 +1041,44 @@ class Graph:
                         _ptr(row_off), C.byref(nnz), C.byref(max_len), _ptr(ind),
                         _ptr(val)))
                 outs.append((ind, val, [n, int(max_len.value)] if n else [0, 0]))
+        return outs
+
+    def sparse_feature_embedding(self, nodes, feature_ids, tables, combiner="sum", default_values=None,
+                                 out_dtype=None, sparse_grad=False):
+        """ShallowEncoder's lookup of sparse features (tf_euler/python/utils/encoders.py:146-170:
+        get_sparse_feature, then tf.nn.embedding_lookup_sparse(table, sp, None, combiner)) in one
+        kernel per feature and without a host wait: nodes [n] int64 -> one [n, dim] tensor per
+        (feature id, table [V, dim]; float32, bfloat16 or float16).
+        A node's entries are the values of its uint64 slot; a node without any has the one entry
+        default_values[j] - or none at all when default_values (or that element) is None.  An
+        entry >= V, compared unsigned, names no row: it is left out of the sum and of the count,
+        and its gradient is exactly 0.  The counted rows are added in fp32 in stored order;
+        combiner "sum", "mean" (sum / count) or "sqrtn" (sum / sqrt(count)); count 0 gives a zero
+        row.  out_dtype: None = the table's dtype, or torch.float32.
+        The table receives a gradient (nodes do not): dense [V, dim], or with sparse_grad=True a
+        torch.sparse_coo_tensor over the distinct rows that were read - what
+        torch.optim.SparseAdam and SGD take - with the same bits once coalesced."""
+        from . import ops
+        if combiner not in _SE_COMBINER:
+            raise ValueError("sparse_feature_embedding: combiner is sum, mean or sqrtn")
+        feature_ids, tables = list(feature_ids), list(tables)
+        if len(feature_ids) != len(tables):
+            raise ValueError("sparse_feature_embedding: one table per feature id")
+        if default_values is None:
+            default_values = [None] * len(feature_ids)
+        nodes = _as_i64_cuda(nodes, self.device).reshape(-1)
+        outs = []
+        for fid, table, dv in zip(feature_ids, tables, default_values):
+            if table.dim() != 2 or table.shape[0] < 1 or table.shape[1] < 1:
+                raise ValueError("sparse_feature_embedding: a table is [V, dim]")
+            ops._need_cuda(table)
+            ops._dt("sparse_feature_embedding", table)
+            od = ops._out_dt("sparse_feature_embedding", table, out_dtype)
+            if not table.is_contiguous():
+                table = table.contiguous()
+            outs.append(_SparseFeatureEmbedding.apply(
+                table, self, nodes, int(fid), None if dv is None else int(dv), combiner, od,
+                bool(sparse_grad)))
         return outs
 
     def get_sparse_feature_core(self, nodes, fid):

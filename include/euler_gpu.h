@@ -624,6 +624,32 @@ int euler_gpu_get_sparse_feature_core(const euler_gpu_graph* g, void* stream,
                                       int32_t* idx_dev, int64_t* total_host,
                                       uint64_t* values_dev);
 
+/* The lookup ShallowEncoder makes of a sparse feature (tf_euler/python/utils/encoders.py:146-170:
+ * get_sparse_feature, then tf.nn.embedding_lookup_sparse(table, sp, None, combiner)) in one
+ * kernel: out_dev [n, dim] = the combined rows of table_dev [n_rows, dim] named by the values of
+ * uint64 slot `fid` of each node.  No SparseTensor is written; the call only enqueues (no
+ * allocation, no host wait: safe under stream capture).
+ * Entry list of a node: its stored values; a node without any (unknown node, empty slot, fid
+ * outside the table) has the one entry default_value when has_default != 0, else none.
+ * An entry >= n_rows (compared UNSIGNED, so values at or above 2^63 too) names no row: it is left
+ * out of the sum and of the count (the default value obeys the rule as well).
+ * The counted rows are widened exactly to fp32 and added in stored order, one fp32 add per entry
+ * starting from the first row; combiner 0 sum, 1 mean = sum / (float)cnt, 2 sqrtn =
+ * sum / sqrtf((float)cnt) (IEEE fp32; what embedding_lookup_sparse with sp_weights = None divides
+ * by); cnt == 0 gives a zero row.  counts_dev [n] (or NULL) receives cnt.
+ * table_dtype: EULER_GPU_F32 / _BF16 / _F16; out_dtype: EULER_GPU_F32 or table_dtype (rounded once
+ * at the store).  16-byte-aligned table and output with dim a multiple of 4 (fp32) / 8 (16-bit)
+ * take 16-byte lanes, everything else one element per lane.
+ * EULER_GPU_ENOGRAPH: null graph.  EULER_GPU_EINVAL: n < 0, dim < 1, n_rows < 1 or >= 2^31, an
+ * unknown dtype or combiner, out_dtype neither fp32 nor table_dtype, a null buffer with n > 0.
+ * n == 0 returns EULER_GPU_OK and touches nothing. */
+int euler_gpu_sparse_feature_embedding(const euler_gpu_graph* g, void* stream,
+                                       const uint64_t* nodes_dev, int64_t n, int32_t fid,
+                                       int32_t has_default, int64_t default_value,
+                                       const void* table_dev, int32_t table_dtype, int64_t n_rows,
+                                       int32_t dim, int32_t combiner /* 0 sum, 1 mean, 2 sqrtn */,
+                                       void* out_dev, int32_t out_dtype, int32_t* counts_dev);
+
 /* ---- block construction (SageDataFlow) on the device ---------------------------
  * tf_euler/python/dataflow/sage_dataflow.py:35-50 + neighbor_dataflow.py:84-110
  * (UniqueDataFlow.produce_subgraph) for `layers` hops, enqueued on `stream` with NO
