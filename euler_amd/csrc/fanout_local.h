@@ -413,6 +413,34 @@ __device__ __forceinline__ int64_t LeanFindRow(const GraphView& g, uint64_t id) 
   return (r * g.id_stride == d && r < (uint64_t)g.n_rows) ? (int64_t)r : -1;
 }
 
+// The cold draws of a pair (Q3: r rounded up to the end of its range; a draw the index does not
+// settle): the reference's own bisection over the flat running sums (RandomSelect,
+// common/compact_weighted_collection.h:30-52) - right on every row, slow, rare; once in the code
+// for both draws.  Draw s replays over the row that starts at flat edge row[s] (the sums restart
+// at every row), positions [b[s], e[s]] of it: the whole row, or one type group.  m = nullptr:
+// the drawn edge's number is not kept.  TWO = false: draw 0 only.
+template <bool TWO = true>
+__device__ __forceinline__ void ColdReplayPair(const float* prefix_w, const uint64_t* nbr, const bool cold0,
+                                               const bool cold1, const double u0, const double u1,
+                                               const uint32_t row0, const uint64_t b0, const uint64_t e0,
+                                               const uint32_t row1, const uint64_t b1, const uint64_t e1,
+                                               uint64_t id[2], float w[2], uint32_t* m) {
+  if (__ballot(cold0 || cold1) != 0ull) {
+#pragma nounroll
+    for (int s = 0; s < (TWO ? 2 : 1); ++s) {
+      if (s == 0 ? cold0 : cold1) {
+        const uint32_t row = s == 0 ? row0 : row1;
+        const float* nw = prefix_w + row;
+        const uint32_t mid = (uint32_t)RandomSelect(nw, s == 0 ? b0 : b1, s == 0 ? e0 : e1, s == 0 ? u0 : u1);
+        const uint64_t ci = nbr[row + mid];
+        const float cw = __fsub_rn(nw[mid], mid == 0u ? 0.f : nw[mid - 1]);
+        if (s == 0) { id[0] = ci; w[0] = cw; if (m != nullptr) m[0] = row + mid; }
+        else { id[1] = ci; w[1] = cw; if (m != nullptr) m[1] = row + mid; }
+      }
+    }
+  }
+}
+
 // largest float <= r (r >= 0)
 __device__ __forceinline__ float FloorToFloat(double r) {
   float f = (float)r;
@@ -585,22 +613,8 @@ __device__ __forceinline__ void LeanSamplePair(const GraphView& g, const uint32_
       w[s] = __fsub_rn(nw_m, prev);
     }
   }
-  if (__ballot(cold0 || cold1) != 0ull) {
-    // the reference's own bisection over the flat running sums (RandomSelect,
-    // compact_weighted_collection.h:30-52) - right on every row, slow, rare; once in
-    // the code for both draws
-#pragma nounroll
-    for (int s = 0; s < (TWO ? 2 : 1); ++s) {
-      if (s == 0 ? cold0 : cold1) {
-        const float* nw = g.prefix_w + lo;
-        const uint32_t mid = (uint32_t)RandomSelect(nw, 0, (uint64_t)(deg - 1), s == 0 ? u0 : u1);
-        const uint64_t ci = g.nbr[lo + mid];
-        const float cw = __fsub_rn(nw[mid], mid == 0u ? 0.f : nw[mid - 1]);
-        if (s == 0) { id[0] = ci; w[0] = cw; m[0] = lo + mid; }
-        else { id[1] = ci; w[1] = cw; m[1] = lo + mid; }
-      }
-    }
-  }
+  ColdReplayPair<TWO>(g.prefix_w, g.nbr, cold0, cold1, u0, u1, lo, 0, (uint64_t)(deg - 1), lo, 0,
+                      (uint64_t)(deg - 1), id, w, m);
 }
 
 // The same pair of draws on a graph whose weights are all 1.0f (H1, configs[1]): the running
@@ -617,70 +631,75 @@ __device__ __forceinline__ void LeanSamplePairUniform(const GraphView& g, const 
   id[0] = 0; id[1] = 0; w[0] = 1.0f; w[1] = 1.0f;
   if (live && !cold0) id[0] = g.nbr[m[0]];
   if (live && !cold1) id[1] = g.nbr[m[1]];
-  if (__ballot(cold0 || cold1) != 0ull) {
-#pragma nounroll
-    for (int s = 0; s < 2; ++s) {
-      if (s == 0 ? cold0 : cold1) {           // Q3: r rounded up to the row's end
-        const float* nw = g.prefix_w + lo;
-        const uint32_t mid = (uint32_t)RandomSelect(nw, 0, (uint64_t)(deg - 1), s == 0 ? u0 : u1);
-        const uint64_t ci = g.nbr[lo + mid];
-        const float cw = __fsub_rn(nw[mid], mid == 0u ? 0.f : nw[mid - 1]);
-        if (s == 0) { id[0] = ci; w[0] = cw; m[0] = lo + mid; }
-        else { id[1] = ci; w[1] = cw; m[1] = lo + mid; }
-      }
-    }
+  // Q3: r rounded up to the row's end
+  ColdReplayPair(g.prefix_w, g.nbr, cold0, cold1, u0, u1, lo, 0, (uint64_t)(deg - 1), lo, 0,
+                 (uint64_t)(deg - 1), id, w, m);
+}
+
+// What a draw needs before it reads the weight-bucket index (wb_index.h), from r as the reference
+// rounds it: whether r rounded up to the end of its range (Q3: the draw replays the bisection),
+// the largest float <= r and the bucket of the row that holds it.
+struct WbBucketDraw {
+  bool q3;
+  float f;
+  uint32_t j;
+};
+
+// the two draws of a pair on ONE row (row_deg edges, running sums up to row_total); draw s lies
+// in a range - the row, or a type group of it - that ends at end[s]
+__device__ __forceinline__ void WbBucketPair(const double r0, const double r1, const float end0,
+                                             const float end1, const uint32_t row_deg,
+                                             const float row_total, WbBucketDraw d[2]) {
+  d[0].q3 = !((double)end0 > r0); d[1].q3 = !((double)end1 > r1);
+  d[0].f = WbFloorToFloat(r0); d[1].f = WbFloorToFloat(r1);
+  const uint32_t nbk = WbBuckets(row_deg);
+  d[0].j = 0u; d[1].j = 0u;
+  if (nbk > 1u) {
+    const float scale = WbScale(nbk, row_total);
+    d[0].j = WbBucketOf(d[0].f, nbk, scale);
+    d[1].j = WbBucketOf(d[1].f, nbk, scale);
   }
+}
+
+// ... of a plain graph's row: r = u * (total - 0) + 0, the subtraction and the addition exact
+__device__ __forceinline__ void WbBucketPair(const WbRec rec, const double u0, const double u1, WbBucketDraw d[2]) {
+  WbBucketPair(__dmul_rn(u0, (double)rec.total), __dmul_rn(u1, (double)rec.total), rec.total, rec.total,
+               rec.deg, rec.total, d);
 }
 
 // Both draws of one Philox block on one row through the weight-bucket index (wb_index.h):
 // per draw ONE 128-byte line - the bucket's block - instead of a walk over pivot levels and
 // a leaf.  Same contract as LeanSamplePair: m[] = the flat edge drawn; draws that round up to
 // the row's total (Q3) and draws whose block does not bracket them replay the reference's
-// bisection.  The two blocks' loads are issued before either is examined.
+// bisection.  The two blocks' loads are issued before either is examined.  live0 / live1: the
+// draw exists (hop 1 of an odd count has no second one in its last pair).
 template <bool TWO = true>
-__device__ __forceinline__ void WbSamplePair(const GraphView& g, const WbRec rec, const bool live,
+__device__ __forceinline__ void WbSamplePair(const EdgeBlock* wb, const float* prefix_w, const uint64_t* nbr,
+                                             const WbRec rec, const bool live0, const bool live1,
                                              const double u0, const double u1, uint64_t id[2],
                                              float w[2], uint32_t m[2]) {
-  const double r0 = __dmul_rn(u0, (double)rec.total), r1 = __dmul_rn(u1, (double)rec.total);
-  bool cold0 = live && !((double)rec.total > r0);
-  bool cold1 = TWO && live && !((double)rec.total > r1);
-  const float f0 = WbFloorToFloat(r0), f1 = WbFloorToFloat(r1);
-  const uint32_t nbk = WbBuckets(rec.deg);
-  uint32_t j0 = 0u, j1 = 0u;
-  if (nbk > 1u) {
-    const float scale = WbScale(nbk, rec.total);
-    j0 = WbBucketOf(f0, nbk, scale);
-    j1 = WbBucketOf(f1, nbk, scale);
-  }
+  WbBucketDraw d[2];
+  WbBucketPair(rec, u0, u1, d);
+  bool cold0 = live0 && d[0].q3;
+  bool cold1 = TWO && live1 && d[1].q3;
   // (a dead lane's record is all zeros: block 0, a valid line nobody uses)
-  const EdgeBlock* b0 = g.wb + rec.wb_lo + j0;
-  const EdgeBlock* b1 = g.wb + rec.wb_lo + (TWO ? j1 : j0);
+  const EdgeBlock* b0 = wb + rec.wb_lo + d[0].j;
+  const EdgeBlock* b1 = wb + rec.wb_lo + (TWO ? d[1].j : d[0].j);
   const WbKeys k0 = WbLoadKeys(b0);
   WbKeys k1 = k0;
   if (TWO) k1 = WbLoadKeys(b1);
   id[0] = 0; id[1] = 0; w[0] = 0.f; w[1] = 0.f; m[0] = rec.lo; m[1] = rec.lo;
-  const int32_t i0 = WbPickKeys(k0, f0, &w[0], &m[0]);
-  const int32_t i1 = TWO ? WbPickKeys(k1, f1, &w[1], &m[1]) : 0;
-  const bool hot0 = live && !cold0 && i0 >= 0;
-  const bool hot1 = TWO && live && !cold1 && i1 >= 0;
+  const int32_t i0 = WbPickKeys(k0, d[0].f, &w[0], &m[0]);
+  const int32_t i1 = TWO ? WbPickKeys(k1, d[1].f, &w[1], &m[1]) : 0;
+  const bool hot0 = live0 && !cold0 && i0 >= 0;
+  const bool hot1 = TWO && live1 && !cold1 && i1 >= 0;
   if (hot0) id[0] = b0->nbr[i0];
   if (hot1) id[1] = b1->nbr[i1];
-  cold0 = live && !hot0;
-  cold1 = TWO && live && !hot1;
+  cold0 = live0 && !hot0;
+  cold1 = TWO && live1 && !hot1;
   if (!TWO) { id[1] = 0; w[1] = 0.f; m[1] = rec.lo; }
-  if (__ballot(cold0 || cold1) != 0ull) {
-#pragma nounroll
-    for (int s = 0; s < (TWO ? 2 : 1); ++s) {
-      if (s == 0 ? cold0 : cold1) {
-        const float* nw = g.prefix_w + rec.lo;
-        const uint32_t mid = (uint32_t)RandomSelect(nw, 0, (uint64_t)(rec.deg - 1u), s == 0 ? u0 : u1);
-        const uint64_t ci = g.nbr[rec.lo + mid];
-        const float cw = __fsub_rn(nw[mid], mid == 0u ? 0.f : nw[mid - 1]);
-        if (s == 0) { id[0] = ci; w[0] = cw; m[0] = rec.lo + mid; }
-        else { id[1] = ci; w[1] = cw; m[1] = rec.lo + mid; }
-      }
-    }
-  }
+  ColdReplayPair<TWO>(prefix_w, nbr, cold0, cold1, u0, u1, rec.lo, 0, (uint64_t)(rec.deg - 1u), rec.lo, 0,
+                      (uint64_t)(rec.deg - 1u), id, w, m);
 }
 
 // Hop 2 of the plain-graph fanout through the header + window lines (wb_hw.h): hop 2 needs
@@ -696,6 +715,7 @@ __device__ __forceinline__ void WbSamplePair(const GraphView& g, const WbRec rec
 __device__ __forceinline__ void HwSamplePair(const HwLine* hw, const float* prefix_w, const uint64_t* nbr,
                                              const WbRec rec, const bool live, const double u0,
                                              const double u1, uint64_t id[2], float w[2]) {
+  // (WbBucketPair's statements, spelled out: sharing them rescheduled the HW kernels)
   const double r0 = __dmul_rn(u0, (double)rec.total), r1 = __dmul_rn(u1, (double)rec.total);
   const bool t0 = live && (double)rec.total > r0, t1 = live && (double)rec.total > r1;
   const float f0 = WbFloorToFloat(r0), f1 = WbFloorToFloat(r1);
@@ -718,20 +738,8 @@ __device__ __forceinline__ void HwSamplePair(const HwLine* hw, const float* pref
   const bool hot0 = t0 && d0 == 0, hot1 = t1 && d1 == 0;
   if (!hot0) { id[0] = 0; w[0] = 0.f; }
   if (!hot1) { id[1] = 0; w[1] = 0.f; }
-  const bool cold0 = live && !hot0, cold1 = live && !hot1;
-  if (__ballot(cold0 || cold1) != 0ull) {
-#pragma nounroll
-    for (int s = 0; s < 2; ++s) {
-      if (s == 0 ? cold0 : cold1) {
-        const float* nw = prefix_w + rec.lo;
-        const uint32_t mid = (uint32_t)RandomSelect(nw, 0, (uint64_t)(rec.deg - 1u), s == 0 ? u0 : u1);
-        const uint64_t ci = nbr[rec.lo + mid];
-        const float cw = __fsub_rn(nw[mid], mid == 0u ? 0.f : nw[mid - 1]);
-        if (s == 0) { id[0] = ci; w[0] = cw; }
-        else { id[1] = ci; w[1] = cw; }
-      }
-    }
-  }
+  ColdReplayPair(prefix_w, nbr, live && !hot0, live && !hot1, u0, u1, rec.lo, 0, (uint64_t)(rec.deg - 1u),
+                 rec.lo, 0, (uint64_t)(rec.deg - 1u), id, w, nullptr);
 }
 
 // The same pair of draws on ANY graph the weight-bucket index serves - several edge-type
@@ -744,6 +752,18 @@ struct WbSeg {
   uint32_t row_lo;              // the row's first flat edge: the cold path replays RandomSelect over
                                 // prefix_w + row_lo (the sums restart at every row)
 };
+
+// the cold draws of a pair whose draws lie in type groups: the bisection over the group's running
+// sums (they restart at the row's first edge: positions are row-relative, b = the group's first)
+template <bool TWO = true>
+__device__ __forceinline__ void ColdReplaySegs(const GraphView& g, const WbSeg& sg0, const WbSeg& sg1,
+                                               const bool cold0, const bool cold1, const double u0,
+                                               const double u1, uint64_t id[2], float w[2], uint32_t m[2]) {
+  const uint32_t b0 = sg0.lo - sg0.row_lo, b1 = sg1.lo - sg1.row_lo;
+  ColdReplayPair<TWO>(g.prefix_w, g.nbr, cold0, cold1, u0, u1, sg0.row_lo, (uint64_t)b0,
+                      (uint64_t)(b0 + sg0.deg - 1u), sg1.row_lo, (uint64_t)b1, (uint64_t)(b1 + sg1.deg - 1u),
+                      id, w, m);
+}
 
 // Graphs with a hash id map and at most two edge-type groups (what a converted dataset looks
 // like: arbitrary ids, 'train' / 'train_removed'): the hash slot CARRIES the row's record
@@ -810,26 +830,19 @@ __device__ __forceinline__ void WbSamplePairG2(const GraphView& g, const WbSeg s
   // r = u * (limit_end - limit_begin) + limit_begin as the reference rounds it (ScaleDraw)
   const double span0 = (double)__fsub_rn(sg0.lim_e, sg0.lim_b);
   const double span1 = (double)__fsub_rn(sg1.lim_e, sg1.lim_b);
-  const double r0 = __dadd_rn(__dmul_rn(u0, span0), (double)sg0.lim_b);
-  const double r1 = __dadd_rn(__dmul_rn(u1, span1), (double)sg1.lim_b);
-  bool cold0 = live0 && !((double)sg0.lim_e > r0);
-  bool cold1 = TWO && live1 && !((double)sg1.lim_e > r1);
-  const float f0 = WbFloorToFloat(r0), f1 = WbFloorToFloat(r1);
-  const uint32_t nbk = WbBuckets(sg0.row_deg);          // (the buckets are the ROW's)
-  uint32_t j0 = 0u, j1 = 0u;
-  if (nbk > 1u) {
-    const float scale = WbScale(nbk, sg0.row_total);
-    j0 = WbBucketOf(f0, nbk, scale);
-    j1 = WbBucketOf(f1, nbk, scale);
-  }
-  const EdgeBlock* b0 = g.wb + sg0.wb_lo + j0;
-  const EdgeBlock* b1 = g.wb + sg0.wb_lo + (TWO ? j1 : j0);
+  WbBucketDraw d[2];
+  WbBucketPair(__dadd_rn(__dmul_rn(u0, span0), (double)sg0.lim_b), __dadd_rn(__dmul_rn(u1, span1), (double)sg1.lim_b),
+               sg0.lim_e, sg1.lim_e, sg0.row_deg, sg0.row_total, d);          // (the buckets are the ROW's)
+  bool cold0 = live0 && d[0].q3;
+  bool cold1 = TWO && live1 && d[1].q3;
+  const EdgeBlock* b0 = g.wb + sg0.wb_lo + d[0].j;
+  const EdgeBlock* b1 = g.wb + sg0.wb_lo + (TWO ? d[1].j : d[0].j);
   const WbKeys k0 = WbLoadKeys(b0);
   WbKeys k1 = k0;
   if (TWO) k1 = WbLoadKeys(b1);
   id[0] = 0; id[1] = 0; w[0] = 0.f; w[1] = 0.f; m[0] = sg0.lo; m[1] = sg1.lo;
-  const int32_t i0 = WbPickKeys(k0, f0, &w[0], &m[0]);
-  const int32_t i1 = TWO ? WbPickKeys(k1, f1, &w[1], &m[1]) : 0;
+  const int32_t i0 = WbPickKeys(k0, d[0].f, &w[0], &m[0]);
+  const int32_t i1 = TWO ? WbPickKeys(k1, d[1].f, &w[1], &m[1]) : 0;
   const bool hot0 = live0 && !cold0 && i0 >= 0;
   const bool hot1 = TWO && live1 && !cold1 && i1 >= 0;
   if (hot0) id[0] = b0->nbr[i0];
@@ -837,23 +850,7 @@ __device__ __forceinline__ void WbSamplePairG2(const GraphView& g, const WbSeg s
   cold0 = live0 && !hot0;
   cold1 = TWO && live1 && !hot1;
   if (!TWO) { id[1] = 0; w[1] = 0.f; m[1] = sg1.lo; }
-  if (__ballot(cold0 || cold1) != 0ull) {
-#pragma nounroll
-    for (int s = 0; s < (TWO ? 2 : 1); ++s) {
-      if (s == 0 ? cold0 : cold1) {
-        // the reference's bisection over the group's running sums (they restart at the row's
-        // first edge: positions are row-relative, b = the group's first)
-        const WbSeg& sg = s == 0 ? sg0 : sg1;
-        const float* nw = g.prefix_w + sg.row_lo;
-        const uint32_t b = sg.lo - sg.row_lo;
-        const uint32_t mid = (uint32_t)RandomSelect(nw, (uint64_t)b, (uint64_t)(b + sg.deg - 1u), s == 0 ? u0 : u1);
-        const uint64_t ci = g.nbr[sg.row_lo + mid];
-        const float cw = __fsub_rn(nw[mid], mid == 0u ? 0.f : nw[mid - 1]);
-        if (s == 0) { id[0] = ci; w[0] = cw; m[0] = sg.row_lo + mid; }
-        else { id[1] = ci; w[1] = cw; m[1] = sg.row_lo + mid; }
-      }
-    }
-  }
+  ColdReplaySegs<TWO>(g, sg0, sg1, cold0, cold1, u0, u1, id, w, m);
 }
 
 template <bool TWO = true>
@@ -1072,23 +1069,7 @@ __device__ __forceinline__ void UniformSamplePairG2(const GraphView& g, const Wb
     m[1] = sg1.lo + ((uint32_t)r1 - (uint32_t)sg1.lim_b);
     id[1] = g.nbr[m[1]]; w[1] = 1.0f;
   }
-  if (__ballot(cold0 || cold1) != 0ull) {
-#pragma nounroll
-    for (int s = 0; s < 2; ++s) {
-      if (s == 0 ? cold0 : cold1) {
-        // the reference's bisection over the group's running sums (they restart at the row's
-        // first edge: positions are row-relative, b = the group's first)
-        const WbSeg& sg = s == 0 ? sg0 : sg1;
-        const float* nw = g.prefix_w + sg.row_lo;
-        const uint32_t b = sg.lo - sg.row_lo;
-        const uint32_t mid = (uint32_t)RandomSelect(nw, (uint64_t)b, (uint64_t)(b + sg.deg - 1u), s == 0 ? u0 : u1);
-        const uint64_t ci = g.nbr[sg.row_lo + mid];
-        const float cw = __fsub_rn(nw[mid], mid == 0u ? 0.f : nw[mid - 1]);
-        if (s == 0) { id[0] = ci; w[0] = cw; m[0] = sg.row_lo + mid; }
-        else { id[1] = ci; w[1] = cw; m[1] = sg.row_lo + mid; }
-      }
-    }
-  }
+  ColdReplaySegs(g, sg0, sg1, cold0, cold1, u0, u1, id, w, m);
 }
 
 template <bool UNI = false>
@@ -1256,7 +1237,7 @@ __global__ __launch_bounds__(256, WPS) void SampleFanoutLeanKernel(
                                             UnitFromWords(pb.w[0], pb.w[1]), UnitFromWords(pb.w[2], pb.w[3]), id, w, m);
       else if (WB == 2) WbSamplePairG(g, ws, a.t1, live, UnitFromWords(pb.w[0], pb.w[1]),
                                  UnitFromWords(pb.w[2], pb.w[3]), id, w, m);
-      else if (WB) WbSamplePair(g, wr, live, UnitFromWords(pb.w[0], pb.w[1]),
+      else if (WB) WbSamplePair(g.wb, g.prefix_w, g.nbr, wr, live, live, UnitFromWords(pb.w[0], pb.w[1]),
                                 UnitFromWords(pb.w[2], pb.w[3]), id, w, m);
       else if (UNIFORM) LeanSamplePairUniform(g, lo, deg, total, live, UnitFromWords(pb.w[0], pb.w[1]),
                                          UnitFromWords(pb.w[2], pb.w[3]), id, w, m);
@@ -1408,7 +1389,7 @@ __global__ __launch_bounds__(256, WPS) void SampleFanoutLeanKernel(
                                    UnitFromWords(pb.w[2], pb.w[3]), id, w, m);
         else if (WB == 1 && HW) HwSamplePair(g.hw, g.prefix_w, g.nbr, wr, live, UnitFromWords(pb.w[0], pb.w[1]),
                                              UnitFromWords(pb.w[2], pb.w[3]), id, w);
-        else if (WB) WbSamplePair(g, wr, live, UnitFromWords(pb.w[0], pb.w[1]),
+        else if (WB) WbSamplePair(g.wb, g.prefix_w, g.nbr, wr, live, live, UnitFromWords(pb.w[0], pb.w[1]),
                                   UnitFromWords(pb.w[2], pb.w[3]), id, w, m);
         else if (UNIFORM) LeanSamplePairUniform(g, lo, deg, total, live, UnitFromWords(pb.w[0], pb.w[1]),
                                            UnitFromWords(pb.w[2], pb.w[3]), id, w, m);

@@ -22,19 +22,12 @@
 //     second id array): 5.3 KB of LDS per wave at 32 slots per pass (9-10 KB before);
 //   * weights / types leave as 16-byte stores over PAIRS of rows (2 c2 floats = c2 / 2 chunks,
 //     the chunk -> (row, column) pattern a per-lane constant).
-// COOP = true (tuning key 54; NOT the shipped build): a draw's block is fetched by THREE lanes, 16 bytes
-// each, as one coalesced request per line, staged in LDS and read back by the lane that owns the
-// draw.  Why it was built (tools/ubench_block.hip, profiles/r6_ubench_block.txt): a lane that asks
-// for its own line with three 16-byte loads and then a dependent 8-byte one - what every build
-// does - makes FOUR requests per line, and the chip completes 19.5 G such lines/s at ANY residency
-// (8 to 32 waves per CU): the rate the kernel's read side runs at however its geometry is tuned.
-// One request per line: 48 G lines/s; lanes sharing a line + a dependent id request: 34-36 G.
-// (What a request costs is its address translation: inside ~2 GiB three loads of a line cost what
-// one costs - profiles/r6_ubench_block_footprint.txt)  In the kernel the staging
-// gives the saving back: 0.237-0.244 ms against 0.222-0.229 (profiles/r6_sweep3_plain_coop.txt).
-// LITE2 = true (key 57): hop 2 asks for two key chunks and the third only at a block's ends -
-// 0.247 against 0.233 ms (profiles/r6_sweep4_plain_lite.txt).  Both stay as parity-tested variants.
-// Bit-identical outputs (tests/test_gpu_parity.py runs every fanout test through both builds).
+// Hop 1 draws through the weight-bucket blocks (WbSamplePair: the slot pass needs the drawn
+// edge's number); hop 2 through the header + window lines where the graph has them (HW, tuning
+// key 75: HwSamplePair), else through the blocks too.  Two more builds of this kernel - a block's
+// keys fetched by three lanes as one request per line and staged in LDS, and a hop 2 that asked
+// for two of a block's three key chunks - were built, measured slower and removed.
+// Bit-identical outputs with the lean kernel and the oracle (tests/test_gpu_parity.py).
 #ifndef EULER_AMD_CSRC_FANOUT_PLAIN_H_
 #define EULER_AMD_CSRC_FANOUT_PLAIN_H_
 
@@ -61,23 +54,14 @@ struct FanoutPlainArgs {
   int32_t c1, c2, gr, cap, wave_lds;
 };
 
-constexpr uint32_t kStageLines = 128;      // two blocks per lane
-constexpr uint32_t kStageBytes = kStageLines * 48 + kStageLines * 4;   // keys of 128 blocks + their numbers
-constexpr uint32_t kSkipLine = 0xFFFFFFFFu;
-
 struct FanoutPlainLds {
-  uint32_t o_stage, o_blk, o_sid, o_c1, o_mask, o_sw, o_w1, o_slot, o_rep, o_st, o_rvalid, bytes;
+  uint32_t o_sid, o_c1, o_mask, o_sw, o_w1, o_slot, o_rep, o_st, o_rvalid, bytes;
 };
-// coop: the key staging area [128][48 B] + block numbers [128] (cooperative fetch).  The hop-2
-// results (sid / sw / st) may lie over the staged keys when a pass of hop 2 is ONE sampling step
-// (cap <= the slots a step takes): the keys are in registers before a result is written.
 __host__ __device__ inline FanoutPlainLds FanoutPlainLayout(int32_t gr, int32_t c1, int32_t c2,
-                                                            int32_t cap, bool coop = false) {
+                                                            int32_t cap) {
   FanoutPlainLds L;
   const uint32_t p = (uint32_t)gr * (uint32_t)c1;
   const uint32_t s = (uint32_t)cap * (uint32_t)c2;
-  const uint32_t hp2 = (uint32_t)c2 >> 1;
-  const uint32_t rpi = hp2 <= 1u ? 64u : 64u / hp2;
   uint32_t o = 0;
   // what a tile keeps from hop 1 to its end
   L.o_c1 = o; o += (p + (p & 1)) * 8;       // u64 [gr][c1]   hop-1 ids (0 for a row without samples)
@@ -87,19 +71,10 @@ __host__ __device__ inline FanoutPlainLds FanoutPlainLayout(int32_t gr, int32_t 
   L.o_rep = o; o += (p + 3) & ~3u;          // u8  [slots]    a sample that drew the slot's child
   L.o_rvalid = o; o += ((uint32_t)gr + 3) & ~3u;
   o = (o + 15) & ~15u;
-  // the finished hop-2 rows of one pass ...
-  const uint32_t o_res = o;
+  // the finished hop-2 rows of one pass
   L.o_sid = o; o += s * 8;                  // u64 [cap][c2]  ids
   L.o_sw = o; o += ((s + 3) & ~3u) * 4;     // f32 [cap][c2]  weights (16-byte aligned)
   L.o_st = o; o += ((uint32_t)cap + 3) & ~3u;    // i8 [cap]  type of the slot's row: 0, or -1 (no samples)
-  o = (o + 15) & ~15u;
-  // ... and the staged keys: over them when a pass is one sampling step, else behind them
-  L.o_stage = 0; L.o_blk = 0;
-  if (coop) {
-    const uint32_t at = (uint32_t)cap <= rpi ? o_res : o;
-    L.o_stage = at; L.o_blk = at + kStageLines * 48;
-    if (at + kStageBytes > o) o = at + kStageBytes;
-  }
   L.bytes = (o + 15) & ~15u;
   return L;
 }
@@ -112,229 +87,6 @@ struct TinyDiv {
     return m == 0u ? n : (__umul24(n, m) >> 20);
   }
 };
-
-// the two draws of one Philox block on one row through the weight-bucket index: WbSamplePair
-// (fanout_local.h) over four pointers instead of a GraphView
-__device__ __forceinline__ void PlainSamplePair(const FanoutPlainArgs& a, const WbRec rec,
-                                                const bool live0, const bool live1, const double u0,
-                                                const double u1, uint64_t id[2], float w[2],
-                                                uint32_t m[2]) {
-  const double r0 = __dmul_rn(u0, (double)rec.total), r1 = __dmul_rn(u1, (double)rec.total);
-  bool cold0 = live0 && !((double)rec.total > r0);
-  bool cold1 = live1 && !((double)rec.total > r1);
-  const float f0 = WbFloorToFloat(r0), f1 = WbFloorToFloat(r1);
-  const uint32_t nbk = WbBuckets(rec.deg);
-  uint32_t j0 = 0u, j1 = 0u;
-  if (nbk > 1u) {
-    const float scale = WbScale(nbk, rec.total);
-    j0 = WbBucketOf(f0, nbk, scale);
-    j1 = WbBucketOf(f1, nbk, scale);
-  }
-  // (a dead lane's record is all zeros: block 0, a valid line nobody uses)
-  const EdgeBlock* b0 = a.wb + rec.wb_lo + j0;
-  const EdgeBlock* b1 = a.wb + rec.wb_lo + j1;
-  const WbKeys k0 = WbLoadKeys(b0);
-  const WbKeys k1 = WbLoadKeys(b1);
-  id[0] = 0; id[1] = 0; w[0] = 0.f; w[1] = 0.f; m[0] = rec.lo; m[1] = rec.lo;
-  const int32_t i0 = WbPickKeys(k0, f0, &w[0], &m[0]);
-  const int32_t i1 = WbPickKeys(k1, f1, &w[1], &m[1]);
-  const bool hot0 = live0 && !cold0 && i0 >= 0;
-  const bool hot1 = live1 && !cold1 && i1 >= 0;
-  if (hot0) id[0] = b0->nbr[i0];
-  if (hot1) id[1] = b1->nbr[i1];
-  cold0 = live0 && !hot0;
-  cold1 = live1 && !hot1;
-  if (__ballot(cold0 || cold1) != 0ull) {
-    // the reference's own bisection over the flat running sums (RandomSelect,
-    // common/compact_weighted_collection.h:30-52): right on every row, slow, rare
-#pragma nounroll
-    for (int s = 0; s < 2; ++s) {
-      if (s == 0 ? cold0 : cold1) {
-        const float* nw = a.prefix_w + rec.lo;
-        const uint32_t mid = (uint32_t)RandomSelect(nw, 0, (uint64_t)(rec.deg - 1u), s == 0 ? u0 : u1);
-        const uint64_t ci = a.nbr[rec.lo + mid];
-        const float cw = __fsub_rn(nw[mid], mid == 0u ? 0.f : nw[mid - 1]);
-        if (s == 0) { id[0] = ci; w[0] = cw; m[0] = rec.lo + mid; }
-        else { id[1] = ci; w[1] = cw; m[1] = rec.lo + mid; }
-      }
-    }
-  }
-}
-
-// The same two draws with the blocks' keys fetched COOPERATIVELY: every lane names its two
-// blocks in LDS, three lanes fetch each block's key half (16 bytes each: one request per line
-// instead of three per lane), the keys go through LDS to the lane that owns the draw; only the
-// id of the drawn edge is a private (dependent) load.  All 64 lanes call; lanes [0, ntask) own
-// draws (ntask wave-uniform).  A pair whose draws fall into one block names it once.
-__device__ __forceinline__ void WaveSamplePairs(const FanoutPlainArgs& a, const uint32_t lane,
-                                                const uint32_t ntask, float4* s_stage, uint32_t* s_blk,
-                                                const WbRec rec, const bool live0, const bool live1,
-                                                const double u0, const double u1, uint64_t id[2],
-                                                float w[2], uint32_t m[2]) {
-  const double r0 = __dmul_rn(u0, (double)rec.total), r1 = __dmul_rn(u1, (double)rec.total);
-  bool cold0 = live0 && !((double)rec.total > r0);
-  bool cold1 = live1 && !((double)rec.total > r1);
-  const float f0 = WbFloorToFloat(r0), f1 = WbFloorToFloat(r1);
-  const uint32_t nbk = WbBuckets(rec.deg);
-  uint32_t j0 = 0u, j1 = 0u;
-  if (nbk > 1u) {
-    const float scale = WbScale(nbk, rec.total);
-    j0 = WbBucketOf(f0, nbk, scale);
-    j1 = WbBucketOf(f1, nbk, scale);
-  }
-  const bool same = j0 == j1;
-  const uint32_t bi0 = rec.wb_lo + j0, bi1 = rec.wb_lo + j1;
-  if (lane < ntask) {
-    s_blk[2u * lane] = live0 ? bi0 : kSkipLine;
-    s_blk[2u * lane + 1u] = (live1 && !same) ? bi1 : kSkipLine;
-  }
-  WaveSync();
-  // ---- fetch: lane = (line fl of a group of 21, chunk fc); every load of the wave is issued
-  // before the first is waited for
-  const uint32_t nlines = 2u * ntask;
-  const uint32_t fl = (lane * 21846u) >> 16, fc = lane - 3u * fl;      // lane / 3, lane % 3
-  // LDS-DMA: the 16 bytes of lane L land at (step's base) + 16 L - and (line, chunk) = (21 it +
-  // L / 3, L % 3) makes that the staged layout [line][3] itself; no register holds them
-  {
-    const uint32_t lds0 = (uint32_t)(size_t)(__attribute__((address_space(3))) uint8_t*)s_stage;
-#pragma unroll
-    for (int it = 0; it < 7; ++it) {
-      if ((uint32_t)it * 21u < nlines) {                                  // (wave-uniform)
-        const uint32_t line = (uint32_t)it * 21u + fl;
-        const uint32_t bi = (fl < 21u && line < nlines) ? s_blk[line] : kSkipLine;
-        if (bi != kSkipLine) {
-          const uint8_t* src = reinterpret_cast<const uint8_t*>(a.wb) + (size_t)bi * 128u + fc * 16u;
-          const uint32_t dst = lds0 + (uint32_t)it * (63u * 16u);
-          unsigned keep;
-          asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                       : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-        }
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  WaveSync();
-  WbKeys k0, k1;
-  k0.a0 = s_stage[6u * lane]; k0.a1 = s_stage[6u * lane + 1u]; k0.a2 = s_stage[6u * lane + 2u];
-  k1 = k0;
-  if (!same) { k1.a0 = s_stage[6u * lane + 3u]; k1.a1 = s_stage[6u * lane + 4u]; k1.a2 = s_stage[6u * lane + 5u]; }
-  id[0] = 0; id[1] = 0; w[0] = 0.f; w[1] = 0.f; m[0] = rec.lo; m[1] = rec.lo;
-  const int32_t i0 = WbPickKeys(k0, f0, &w[0], &m[0]);
-  const int32_t i1 = WbPickKeys(k1, f1, &w[1], &m[1]);
-  const bool hot0 = live0 && !cold0 && i0 >= 0;
-  const bool hot1 = live1 && !cold1 && i1 >= 0;
-  if (hot0) id[0] = a.wb[bi0].nbr[i0];
-  if (hot1) id[1] = a.wb[bi1].nbr[i1];
-  cold0 = live0 && !hot0;
-  cold1 = live1 && !hot1;
-  if (__ballot(cold0 || cold1) != 0ull) {
-#pragma nounroll
-    for (int s = 0; s < 2; ++s) {
-      if (s == 0 ? cold0 : cold1) {
-        const float* nw = a.prefix_w + rec.lo;
-        const uint32_t mid = (uint32_t)RandomSelect(nw, 0, (uint64_t)(rec.deg - 1u), s == 0 ? u0 : u1);
-        const uint64_t ci = a.nbr[rec.lo + mid];
-        const float cw = __fsub_rn(nw[mid], mid == 0u ? 0.f : nw[mid - 1]);
-        if (s == 0) { id[0] = ci; w[0] = cw; m[0] = rec.lo + mid; }
-        else { id[1] = ci; w[1] = cw; m[1] = rec.lo + mid; }
-      }
-    }
-  }
-}
-
-// Hop 2 does not need the drawn edge's number, and most draws do not need the third key chunk:
-// the answer i = #{keys <= f} is known from keys 0 .. 7 unless all eight are <= f, and for
-// 1 <= i <= 7 both nw[i] and nw[i - 1] are among them and key 0 <= f proves the block brackets
-// the draw from below.  So a draw asks for TWO key chunks, then - together with its id -
-// for the third only when i == 0 (prev_last: the weight and the bracket check; the id is
-// nbr[0] either way) or i == 8 (keys 8, 9 and the two candidate ids in the same trip):
-// ~3.3 requests per line instead of 4 on a kernel whose read side is bound by requests
-// (tools/ubench_block.hip).  LITE2 of the sampler below.
-__device__ __forceinline__ float Sel8(const float4 a0, const float4 a1, const uint32_t i) {
-  const bool b0 = (i & 1u) != 0, b1 = (i & 2u) != 0, b2 = (i & 4u) != 0;
-  const float s01 = b0 ? a0.y : a0.x, s23 = b0 ? a0.w : a0.z, s45 = b0 ? a1.y : a1.x, s67 = b0 ? a1.w : a1.z;
-  const float q03 = b1 ? s23 : s01, q47 = b1 ? s67 : s45;
-  return b2 ? q47 : q03;
-}
-
-__device__ __forceinline__ void PlainSamplePairLite(const FanoutPlainArgs& a, const WbRec rec,
-                                                    const bool live0, const bool live1, const double u0,
-                                                    const double u1, uint64_t id[2], float w[2]) {
-  const double r0 = __dmul_rn(u0, (double)rec.total), r1 = __dmul_rn(u1, (double)rec.total);
-  bool cold0 = live0 && !((double)rec.total > r0);
-  bool cold1 = live1 && !((double)rec.total > r1);
-  const float f0 = WbFloorToFloat(r0), f1 = WbFloorToFloat(r1);
-  const uint32_t nbk = WbBuckets(rec.deg);
-  uint32_t j0 = 0u, j1 = 0u;
-  if (nbk > 1u) {
-    const float scale = WbScale(nbk, rec.total);
-    j0 = WbBucketOf(f0, nbk, scale);
-    j1 = WbBucketOf(f1, nbk, scale);
-  }
-  const EdgeBlock* b0 = a.wb + rec.wb_lo + j0;
-  const EdgeBlock* b1 = a.wb + rec.wb_lo + j1;
-  const float4 p0 = *reinterpret_cast<const float4*>(b0->pw), p1 = *reinterpret_cast<const float4*>(b0->pw + 4);
-  const float4 q0 = *reinterpret_cast<const float4*>(b1->pw), q1 = *reinterpret_cast<const float4*>(b1->pw + 4);
-  uint32_t i0 = 0, i1 = 0;
-  i0 += !(p0.x > f0) ? 1u : 0u; i0 += !(p0.y > f0) ? 1u : 0u; i0 += !(p0.z > f0) ? 1u : 0u; i0 += !(p0.w > f0) ? 1u : 0u;
-  i0 += !(p1.x > f0) ? 1u : 0u; i0 += !(p1.y > f0) ? 1u : 0u; i0 += !(p1.z > f0) ? 1u : 0u; i0 += !(p1.w > f0) ? 1u : 0u;
-  i1 += !(q0.x > f1) ? 1u : 0u; i1 += !(q0.y > f1) ? 1u : 0u; i1 += !(q0.z > f1) ? 1u : 0u; i1 += !(q0.w > f1) ? 1u : 0u;
-  i1 += !(q1.x > f1) ? 1u : 0u; i1 += !(q1.y > f1) ? 1u : 0u; i1 += !(q1.z > f1) ? 1u : 0u; i1 += !(q1.w > f1) ? 1u : 0u;
-  const bool t0 = live0 && !cold0, t1 = live1 && !cold1;
-  const bool edge0 = t0 && (i0 == 0u || i0 == 8u), edge1 = t1 && (i1 == 0u || i1 == 8u);
-  // the second trip: the id (nbr[min(i, 8)]: for i == 8 the pair nbr[8], nbr[9]) and, at the
-  // two ends, the third chunk
-  fl_u64x2 n0, n1;
-  n0.x = 0; n0.y = 0; n1 = n0;
-  float4 p2 = make_float4(0.f, 0.f, 0.f, 0.f), q2 = p2;
-  if (t0) {
-    if (i0 == 8u) n0 = *reinterpret_cast<const fl_u64x2*>(b0->nbr + 8);
-    else n0.x = b0->nbr[i0];
-  }
-  if (t1) {
-    if (i1 == 8u) n1 = *reinterpret_cast<const fl_u64x2*>(b1->nbr + 8);
-    else n1.x = b1->nbr[i1];
-  }
-  if (edge0) p2 = *reinterpret_cast<const float4*>(b0->pw + 8);
-  if (edge1) q2 = *reinterpret_cast<const float4*>(b1->pw + 8);
-  id[0] = 0; id[1] = 0; w[0] = 0.f; w[1] = 0.f;
-  bool hot0 = t0, hot1 = t1;
-  if (t0) {
-    if (!edge0) { id[0] = n0.x; w[0] = __fsub_rn(Sel8(p0, p1, i0), Sel8(p0, p1, i0 - 1u)); }
-    else if (i0 == 0u) { hot0 = !(p2.z > f0); id[0] = n0.x; w[0] = __fsub_rn(p0.x, p2.z); }
-    else {              // all of keys 0 .. 7 <= f: the answer is edge 8 or 9 of the block, or beyond it
-      const bool k8 = p2.x > f0, k9 = p2.y > f0;
-      hot0 = k8 || k9;
-      id[0] = k8 ? n0.x : n0.y;
-      w[0] = k8 ? __fsub_rn(p2.x, p1.w) : __fsub_rn(p2.y, p2.x);
-    }
-  }
-  if (t1) {
-    if (!edge1) { id[1] = n1.x; w[1] = __fsub_rn(Sel8(q0, q1, i1), Sel8(q0, q1, i1 - 1u)); }
-    else if (i1 == 0u) { hot1 = !(q2.z > f1); id[1] = n1.x; w[1] = __fsub_rn(q0.x, q2.z); }
-    else {
-      const bool k8 = q2.x > f1, k9 = q2.y > f1;
-      hot1 = k8 || k9;
-      id[1] = k8 ? n1.x : n1.y;
-      w[1] = k8 ? __fsub_rn(q2.x, q1.w) : __fsub_rn(q2.y, q2.x);
-    }
-  }
-  cold0 = live0 && !hot0;
-  cold1 = live1 && !hot1;
-  if (__ballot(cold0 || cold1) != 0ull) {
-#pragma nounroll
-    for (int s = 0; s < 2; ++s) {
-      if (s == 0 ? cold0 : cold1) {
-        const float* nw = a.prefix_w + rec.lo;
-        const uint32_t mid = (uint32_t)RandomSelect(nw, 0, (uint64_t)(rec.deg - 1u), s == 0 ? u0 : u1);
-        const uint64_t ci = a.nbr[rec.lo + mid];
-        const float cw = __fsub_rn(nw[mid], mid == 0u ? 0.f : nw[mid - 1]);
-        if (s == 0) { id[0] = ci; w[0] = cw; }
-        else { id[1] = ci; w[1] = cw; }
-      }
-    }
-  }
-}
 
 __device__ __forceinline__ uint32_t OpaqueLane(uint32_t lane) {
   asm volatile("" : "+v"(lane));
@@ -356,19 +108,17 @@ __device__ __forceinline__ WbRec PlainLoadRec(const FanoutPlainArgs& a, const ui
   return wr;
 }
 
-// HW = true (tuning key 75, the default where the graph has the side index; not with COOP /
-// LITE2): hop 2 draws through the header + window lines - two requests per draw (HwSamplePair).
-template <int WPS, bool COOP, bool LITE2 = false, bool HW = false>
+// HW = true (tuning key 75, the default where the graph has the side index): hop 2 draws through
+// the header + window lines - two requests per draw (HwSamplePair).
+template <int WPS, bool HW>
 __global__ __launch_bounds__(256, WPS) void SampleFanoutPlainKernel(const FanoutPlainArgs a) {
   extern __shared__ __align__(16) uint8_t fp_smem[];
   const uint32_t lane = threadIdx.x & 63u;
   const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int waves_per_block = blockDim.x >> 6;
   const uint32_t c1 = (uint32_t)a.c1, c2 = (uint32_t)a.c2, gr = (uint32_t)a.gr, cap = (uint32_t)a.cap;
-  const FanoutPlainLds L = FanoutPlainLayout(a.gr, a.c1, a.c2, a.cap, COOP);
+  const FanoutPlainLds L = FanoutPlainLayout(a.gr, a.c1, a.c2, a.cap);
   uint8_t* base = fp_smem + (size_t)wave_in_block * a.wave_lds;
-  float4* s_stage = reinterpret_cast<float4*>(base + L.o_stage);
-  uint32_t* s_blk = reinterpret_cast<uint32_t*>(base + L.o_blk);
   uint64_t* s_sid = reinterpret_cast<uint64_t*>(base + L.o_sid);
   uint64_t* s_c1 = reinterpret_cast<uint64_t*>(base + L.o_c1);
   unsigned long long* s_mask = reinterpret_cast<unsigned long long*>(base + L.o_mask);
@@ -414,10 +164,8 @@ __global__ __launch_bounds__(256, WPS) void SampleFanoutPlainKernel(const Fanout
     uint64_t id[2]; float w[2]; uint32_t m[2];
     {
       const Philox4 pb = RngBlock(a.seed, call, kDomainNeighbor, node, jp1);
-      if (COOP) WaveSamplePairs(a, lane, __umul24(nr, hp1), s_stage, s_blk, wr, live, live && two1,
-                                UnitFromWords(pb.w[0], pb.w[1]), UnitFromWords(pb.w[2], pb.w[3]), id, w, m);
-      else PlainSamplePair(a, wr, live, live && two1, UnitFromWords(pb.w[0], pb.w[1]),
-                           UnitFromWords(pb.w[2], pb.w[3]), id, w, m);
+      WbSamplePair(a.wb, a.prefix_w, a.nbr, wr, live, live && two1, UnitFromWords(pb.w[0], pb.w[1]),
+                   UnitFromWords(pb.w[2], pb.w[3]), id, w, m);
     }
     const bool by_edge = __ballot(in1 && wr.deg > 64u) == 0ull;   // every root of the tile has <= 64 edges
     const uint32_t off0 = live ? (m[0] - wr.lo) & 63u : 0u;
@@ -516,18 +264,12 @@ __global__ __launch_bounds__(256, WPS) void SampleFanoutPlainKernel(const Fanout
         const bool lv = in && cr.deg > 0u;
         uint64_t i2[2]; float w2[2]; uint32_t m2[2];
         const Philox4 pb = RngBlock(a.seed, call + 1u, kDomainNeighbor, child, x2);
-        if (COOP) {
-          const uint32_t left = ns - sb < RPI ? ns - sb : RPI;        // slots of this step
-          WaveSamplePairs(a, lane, __umul24(left, hp2), s_stage, s_blk, cr, lv, lv, UnitFromWords(pb.w[0], pb.w[1]),
-                          UnitFromWords(pb.w[2], pb.w[3]), i2, w2, m2);
-        } else if (HW) {
+        if (HW) {
           HwSamplePair(a.hw, a.prefix_w, a.nbr, cr, lv, UnitFromWords(pb.w[0], pb.w[1]),
                        UnitFromWords(pb.w[2], pb.w[3]), i2, w2);
-        } else if (LITE2) {
-          PlainSamplePairLite(a, cr, lv, lv, UnitFromWords(pb.w[0], pb.w[1]), UnitFromWords(pb.w[2], pb.w[3]), i2, w2);
         } else {
-          PlainSamplePair(a, cr, lv, lv, UnitFromWords(pb.w[0], pb.w[1]), UnitFromWords(pb.w[2], pb.w[3]),
-                          i2, w2, m2);
+          WbSamplePair(a.wb, a.prefix_w, a.nbr, cr, lv, lv, UnitFromWords(pb.w[0], pb.w[1]),
+                       UnitFromWords(pb.w[2], pb.w[3]), i2, w2, m2);
         }
         if (in) {
           fl_u64x2 iv;

@@ -579,10 +579,6 @@ thread_local int g_fl_plain = 2;      // key 34: plain graphs: 2 = the lean kern
 thread_local int g_fl_wps = 5;        // key 35: register budget, waves per SIMD (8, 6 or 5; 5: nothing spilled)
 thread_local int g_fp_on = 1;         // key 53: plain graphs with the weight-bucket index take the kernel of
                                       // fanout_plain.h (1); 0 = the lean build of fanout_local.h (round 5)
-thread_local int g_fp_coop = 0;       // key 54: ... a block's keys fetched by three lanes as ONE request per line and
-                                      // staged in LDS (1); 0 = three 16-byte loads per lane and line (round 5's pattern)
-thread_local int g_fp_lite2 = 0;      // key 57: ... hop 2 asks for two key chunks per draw and for the third only at
-                                      // the ends of its block (1); 0 = all three
 thread_local int g_fp_hw = 1;         // key 75: hop 2 of the plain-graph 2-hop fanout (both kernels) draws through the header +
                                       // window side index (wb_hw.h: two requests per draw) when the graph has it (1);
                                       // 0 = through the weight-bucket blocks (four)
@@ -1564,16 +1560,15 @@ static int RunFanout(const euler_gpu_graph* g, hipStream_t stream, uint64_t seed
         if (g_fp_on != 0 && (t_concurrent != 1 || g_fp_on == 2 || big) && plain && !typed_hops && use_wb0 && f.wide) {
           int32_t pgr = g_fl_roots > 0 ? gr : 4;
           while (multi != nullptr && pgr > 1 && multi->n_per % pgr != 0) pgr >>= 1;
-          int32_t pcap = g_fl_cap > 0 ? g_fl_cap : (g_fp_coop != 0 ? 64 / (c2 / 2 > 0 ? c2 / 2 : 1) : 32);
+          int32_t pcap = g_fl_cap > 0 ? g_fl_cap : 32;
           if (pcap > pgr * c1) pcap = pgr * c1;
           const int pblock = (g_fl_block == 64 || g_fl_block == 128 || g_fl_block == 256) ? g_fl_block : 128;
-          const bool coop = g_fp_coop != 0;
-          const FanoutPlainLds pl = FanoutPlainLayout(pgr, c1, c2, pcap, coop);
+          const FanoutPlainLds pl = FanoutPlainLayout(pgr, c1, c2, pcap);
           const int64_t tp = (int64_t)pgr * c1 * c2;
           if (pgr * ((c1 + 1) / 2) <= 64 && pgr * c1 <= 255 && pgr * c1 % 4 == 0 && tp % 4 == 0 && c2 <= 64 &&
               c1 <= 128 && (int64_t)pcap * c2 < 4096 && (size_t)pl.bytes * (pblock / 64) <= 64 * 1024) {
             FanoutPlainArgs pa{};
-            const bool hw2 = g_fp_hw != 0 && f.g.hw != nullptr && !coop && g_fp_lite2 == 0;
+            const bool hw2 = g_fp_hw != 0 && f.g.hw != nullptr;
             pa.wrec = f.g.wrec; pa.wb = f.g.wb; pa.hw = f.g.hw; pa.prefix_w = f.g.prefix_w; pa.nbr = f.g.nbr;
             pa.roots = roots_dev;
             pa.id1 = f.id1; pa.w1 = f.w1; pa.ty1 = f.ty1; pa.id2 = f.id2; pa.w2 = f.w2; pa.ty2 = f.ty2;
@@ -1588,8 +1583,7 @@ static int RunFanout(const euler_gpu_graph* g, hipStream_t stream, uint64_t seed
             int64_t pwaves = g_fl_grid_cap > 0 ? g_fl_grid_cap : 0;
             if (pwaves > 0 && pblocks > (pwaves + pwpb - 1) / pwpb) pblocks = (pwaves + pwpb - 1) / pwpb;
             void (*pk)(const FanoutPlainArgs) = nullptr;
-#define EG_FP(W) (coop ? SampleFanoutPlainKernel<W, true, false> : g_fp_lite2 != 0 ? SampleFanoutPlainKernel<W, false, true> \
-                       : hw2 ? SampleFanoutPlainKernel<W, false, false, true> : SampleFanoutPlainKernel<W, false, false>)
+#define EG_FP(W) (hw2 ? SampleFanoutPlainKernel<W, true> : SampleFanoutPlainKernel<W, false>)
             pk = g_fp_wps >= 8 ? EG_FP(8) : g_fp_wps == 7 ? EG_FP(7) : g_fp_wps == 6 ? EG_FP(6)
                  : g_fp_wps == 5 ? EG_FP(5) : EG_FP(4);
 #undef EG_FP
@@ -1879,8 +1873,6 @@ int euler_gpu_set_tuning(int32_t key, int32_t value) {
   if (key == 51 && (value == 0 || value == 1)) { g_blk_policy = value; return EULER_GPU_OK; }
   if (key == 52 && (value == 0 || value == 1)) { g_sharded_self_exchange.store(value); return EULER_GPU_OK; }
   if (key == 53 && value >= 0 && value <= 2) { g_fp_on = value; return EULER_GPU_OK; }
-  if (key == 54 && (value == 0 || value == 1)) { g_fp_coop = value; return EULER_GPU_OK; }
-  if (key == 57 && (value == 0 || value == 1)) { g_fp_lite2 = value; return EULER_GPU_OK; }
   if (key == 60 && (value == 0 || value == 1)) { g_flow_fused.store(value); return EULER_GPU_OK; }
   if (key == 62 && value >= 0 && value <= 2) { g_flow_rowpos.store(value); return EULER_GPU_OK; }
   if (key == 69 && value >= 0) { g_n2v_list_big.store(value); return EULER_GPU_OK; }

@@ -622,7 +622,7 @@ __device__ __forceinline__ uint64_t CwDraw(const CwArgs& a, const uint64_t cur, 
     const bool live = wr.deg > 0u;
     const Philox4 blk = RngBlock(a.seed, a.call_id + (uint32_t)s, kDomainNeighbor, cur, 0);
     uint64_t id2[2]; float w2[2]; uint32_t m2[2];
-    WbSamplePair<false>(g, wr, live, UnitFromWords(blk.w[0], blk.w[1]), 0.0, id2, w2, m2);
+    WbSamplePair<false>(g.wb, g.prefix_w, g.nbr, wr, live, false, UnitFromWords(blk.w[0], blk.w[1]), 0.0, id2, w2, m2);
     return live ? id2[0] : 0;
   }
   if (MODE == 2) {

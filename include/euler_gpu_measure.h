@@ -122,11 +122,9 @@ extern "C" {
  * key 53: plain graphs served by the weight-bucket index take the 2-hop fanout kernel of
  *        csrc/fanout_plain.h when the caller keeps ONE stream (1 [default]; 2 = also when it
  *        alternates streams); 0 = round 5's lean build (fanout_local.h).
- * key 54: ... with a block's keys fetched by three lanes through LDS-DMA and staged in LDS (1);
- *        0 [default] = by the lane that owns the draw.  key 55: its register budget in waves per
- *        SIMD (4 .. 8, default 5).  key 57: its hop 2 asks for two of a block's three key chunks
- *        and for the third only when the pick lands on the block's first edge or past its
- *        eighth (1); 0 [default] = all three at once.
+ * key 55: ... its register budget in waves per SIMD (4 .. 8, default 5).
+ * keys 54, 57: retired (a cooperative key fetch through LDS and a two-chunk hop 2 of that kernel:
+ *        both measured slower, DESIGN 4.2, and removed); setting them is EULER_GPU_EINVAL.
  * key 56: test hook, PROCESS-WIDE: the next `value` builds of the EdgeBlocks fail the way an
  *        allocation failure would (the graph is then served without them: same results).
  * key 60: PROCESS-WIDE: a Sage flow whose hops list one edge type runs as three launches per hop -

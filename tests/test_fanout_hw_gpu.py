@@ -207,3 +207,95 @@ def test_declined_side_index_same_outputs(EA, torch_cuda, world):
     finally:
         L.euler_gpu_set_index_budget(-1, 0.5)
         L.euler_gpu_set_index_budget(2 ** 62, 0.5)
+
+
+# ---- cold draws in both hops of both kernels ------------------------------------------------
+# Draws the index does not settle replay the reference's bisection (fanout_local.h:
+# ColdReplayPair).  On the synthetic graph that happens by accident of the data; this graph makes
+# it certain.  A "bad" row has 44 edges - 40 of weight 1, then 4 of weight 100 - so 11 buckets of
+# width 40: all forty unit edges fall into bucket 0, which overflows a block and a header line,
+# and every draw that lands there (one in eleven) is cold on both paths.  The unit edges point at
+# other bad rows, the heavy ones at ordinary rows (1 - 12 edges of weight in [0.5, 8)), and 200
+# ordinary rows have an edge into a bad row, so hop 2 meets bad rows from ordinary roots as well.
+# The 40 overflowing lines must stay within 2 in a thousand for the launcher to keep the graph on
+# the index: 18 000 rows give about 25 000 lines, and no ordinary row may overflow its own.
+CN, N_BAD, N_FEED = 18000, 40, 200
+C_EMPTY = 9001                # a node without edges
+
+
+@pytest.fixture(scope="module")
+def cold_world(EA, O, torch_cuda):
+    rng = np.random.default_rng(4401)
+    ids = (1 + np.arange(CN)).astype(np.uint64)
+    bad_rows = 100 + 400 * np.arange(N_BAD)
+    is_bad = np.zeros(CN, bool)
+    is_bad[bad_rows] = True
+    deg = rng.choice([1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 12], CN)     # (a row of exactly 10 edges overflows its 9-entry line)
+    deg[bad_rows] = 44
+    deg[C_EMPTY - 1] = 0
+    seg = np.zeros(CN + 1, np.int64)
+    seg[1:] = np.cumsum(deg)
+    E = int(seg[-1])
+    ordinary = ids[~is_bad]
+    nbr = rng.choice(ordinary, E).astype(np.uint64)
+    w = (rng.random(E) * 7.5 + 0.5).astype(np.float32)
+    bad_ids = ids[bad_rows]
+    for i, r in enumerate(bad_rows):
+        lo = int(seg[r])
+        nbr[lo:lo + 40] = bad_ids[(i + 1 + np.arange(40) % (N_BAD - 1)) % N_BAD]     # never itself
+        w[lo:lo + 40] = 1.0
+        w[lo + 40:lo + 44] = 100.0            # (their targets stay ordinary rows)
+    cand = np.flatnonzero(~is_bad & (deg > 0))
+    feed_rows = rng.choice(cand, N_FEED, replace=False)
+    nbr[seg[feed_rows]] = bad_ids[np.arange(N_FEED) % N_BAD]
+    csr = O.csr_from_raw(ids, seg, nbr, w, 1, np.zeros(CN, np.int32), np.ones(CN, np.float32))
+    L = _lib(EA)
+    L.euler_gpu_set_tuning(33, 0)            # the one-kernel step serves 1 024 roots
+    G = EA.Graph.from_csr(csr.row_id, csr.row_ptr, csr.type_end, csr.nbr, csr.prefix_w,
+                          csr.type_prefix, 1, csr.node_type, csr.node_weight)
+    G.set_seed(SEED)
+    roots = np.concatenate([bad_ids.astype(np.int64), ids[feed_rows].astype(np.int64),
+                            rng.integers(1, CN + 1, 1024 - N_BAD - N_FEED - 2), [N + 5, C_EMPTY]]).astype(np.int64)
+    yield {"G": G, "OG": O.OracleGraph(csr), "roots": roots, "bad_ids": bad_ids.astype(np.int64)}
+    L.euler_gpu_set_tuning(33, 32768)
+    L.euler_gpu_set_tuning(75, 1)
+
+
+def test_cold_graph_stays_on_the_index(cold_world):
+    nbytes, lines, ovf = cold_world["G"].side_index()
+    print("side index: %d lines, %d overflow" % (lines, ovf))
+    assert 0 < ovf <= 0.002 * lines           # (else the launcher keeps the graph off the index)
+
+
+@pytest.mark.parametrize("fanout", ([25, 10], [3, 2]), ids=lambda f: "x".join(map(str, f)))
+def test_cold_draws_in_both_hops_of_both_kernels(EA, torch_cuda, cold_world, fanout):
+    torch = torch_cuda
+    G, roots_np, bad = cold_world["G"], cold_world["roots"], cold_world["bad_ids"]
+    assert len(roots_np) == 1024
+    call_id = 300 + fanout[0]
+    on, ow, ot = cold_world["OG"].sample_fanout(SEED, call_id, roots_np, [[0], [0]], fanout, N + 1)
+    on = [np.asarray(x).reshape(-1).astype(np.int64) for x in on]
+    # the oracle's own draws: from a bad row, a unit-edge target (= a bad row) was drawn only
+    # through bucket 0 - cold by construction; expected share 1 / 11
+    src = roots_np
+    for hop in range(2):
+        from_bad = np.repeat(np.isin(src, bad), fanout[hop])
+        cold = int((from_bad & np.isin(on[hop], bad)).sum())
+        print("hop %d: %d cold draws of %d from bad rows" % (hop + 1, cold, int(from_bad.sum())))
+        assert from_bad.sum() > 0 and cold >= 0.01 * from_bad.sum(), (hop, cold, int(from_bad.sum()))
+        src = on[hop]
+    roots = torch.as_tensor(roots_np).cuda()
+    first = None
+    for key, alternate, want in ((1, False, "SampleFanoutPlainKernel"), (0, False, "SampleFanoutPlainKernel"),
+                                 (1, True, "SampleFanoutLeanKernel"), (0, True, "SampleFanoutLeanKernel")):
+        out, name = _run(EA, torch, G, roots, fanout, call_id, key, alternate)
+        assert name == want, (key, alternate, name)
+        if first is None:
+            first = out
+            for hop in range(2):
+                assert np.array_equal(t2n(out[0][hop + 1]).reshape(-1), on[hop]), (key, alternate, hop)
+                assert np.array_equal(t2n(out[1][hop]).reshape(-1).view(np.uint32),
+                                      np.asarray(ow[hop], np.float32).reshape(-1).view(np.uint32)), (key, alternate, hop)
+                assert np.array_equal(t2n(out[2][hop]).reshape(-1), np.asarray(ot[hop]).reshape(-1)), (key, alternate, hop)
+        else:
+            assert _same(first, out), (key, alternate)

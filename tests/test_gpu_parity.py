@@ -1956,7 +1956,7 @@ def test_full_neighbor_fill_kernels_agree(EA, O, torch_cuda, big_pair):
         _lib.lib().euler_gpu_set_tuning(24, 1)
 
 
-_FL_DEFAULTS = {27: 1, 28: 0, 29: 0, 30: 0, 31: 1, 32: -1, 33: 32768, 34: 2, 35: 5, 45: 1, 53: 1, 54: 0, 55: 5, 57: 0}
+_FL_DEFAULTS = {27: 1, 28: 0, 29: 0, 30: 0, 31: 1, 32: -1, 33: 32768, 34: 2, 35: 5, 45: 1, 53: 1, 55: 5}
 
 
 @pytest.mark.parametrize("geom", [(4, 0, 256, 1, 8, 2, 0, 1), (1, 1, 64, 0, 5, 0, 0, 1), (2, 3, 128, 1, 8, 0, 0, 1),
@@ -2093,17 +2093,15 @@ def test_fanout_local_dedup_kernel(EA, O, torch_cuda, big_pair, geom):
             L.euler_gpu_set_tuning(k_, v_)
 
 
-@pytest.mark.parametrize("geom", [(0, 0, 0, 5, 0, -1, 1), (4, 32, 128, 5, 1, -1, 0), (4, 3, 64, 8, 1, -1, 0), (4, 100, 256, 4, 0, 0, 1),
-                                  (2, 7, 128, 7, 1, 5, 0), (4, 12, 128, 6, 1, -1, 0), (4, 2, 64, 5, 0, 3, 0), (1, 1, 64, 6, 0, 1, 1),
-                                  (4, 32, 128, 4, 0, -1, 0), (4, 13, 256, 4, 1, 7, 0), (4, 5, 64, 6, 0, 2, 1)],
-                         ids=["shipped", "coop_cap32", "coop_cap3_wps8", "cap100_wps4", "coop_gr2_grid5", "coop_cap12_wps6",
-                              "three_chunks_cap2_grid3", "gr1_grid1", "three_chunks", "coop_cap13_grid7", "cap5_wps6_grid2"])
+@pytest.mark.parametrize("geom", [(0, 0, 0, 5, -1, 0), (4, 32, 128, 5, -1, 0), (4, 3, 64, 8, -1, 0), (4, 100, 256, 4, 0, 0),
+                                  (2, 7, 128, 7, 5, 0), (4, 12, 128, 6, -1, 0), (4, 2, 64, 5, 3, 1), (1, 1, 64, 6, 1, 0),
+                                  (4, 32, 128, 4, -1, 1), (4, 13, 256, 4, 7, 0), (4, 5, 64, 6, 2, 0)],
+                         ids=["default_geometry", "cap32", "cap3_wps8", "cap100_wps4", "gr2_grid5", "cap12_wps6",
+                              "three_chunks_cap2_grid3", "gr1_grid1", "three_chunks", "cap13_grid7", "cap5_wps6_grid2"])
 def test_fanout_plain_kernel(EA, O, torch_cuda, geom):
     """fanout_plain.h (round 6): the one-kernel 2-hop fanout rebuilt for plain graphs served by
-    the weight-bucket index.  Every build (register budget; a block's keys fetched by three
-    lanes through LDS-DMA - key 54 = 1, staged over the results when a pass is one step and
-    beside them otherwise - or by the lane that owns the draw, hop 2 with two or all three of a
-    block's key chunks per draw - key 57) and geometry (roots per wave, slots per pass incl. several
+    the weight-bucket index.  Every build (register budget; hop 2 through the header + window
+    lines - key 75 = 1 - or through the weight-bucket blocks) and geometry (roots per wave, slots per pass incl. several
     passes, block size, grid-stride loop) must write the oracle's ids / weights / types and
     what round 5's kernel (key 53 = 0) writes: unknown roots, id 0, duplicate roots, ragged
     last tiles, strided ids, dangling neighbour ids, hub rows (> 64 edges: duplicates by id;
@@ -2112,8 +2110,8 @@ def test_fanout_plain_kernel(EA, O, torch_cuda, geom):
     torch = torch_cuda
     from euler_amd import _lib
     L = _lib.lib()
-    gr, cap, block, wps, coop, grid, lite = geom
-    keys = {27: 2, 28: gr, 29: cap, 30: block, 32: grid, 33: 0, 55: wps, 54: coop, 57: lite, 53: 2}
+    gr, cap, block, wps, grid, hw = geom
+    keys = {27: 2, 28: gr, 29: cap, 30: block, 32: grid, 33: 0, 55: wps, 75: hw, 53: 2}
 
     def check(G, OG, q, counts, default, seed, call, took=True):
         qt = torch.as_tensor(q).cuda()
@@ -2193,6 +2191,31 @@ def test_fanout_plain_kernel(EA, O, torch_cuda, geom):
     finally:
         for k_, v_ in _FL_DEFAULTS.items():
             L.euler_gpu_set_tuning(k_, v_)
+        L.euler_gpu_set_tuning(75, 1)
+
+
+def test_retired_fanout_keys_are_refused(EA, O, torch_cuda):
+    """Tuning keys 54 and 57 selected two builds of the plain-graph fanout kernel that were removed:
+    setting them is an error (no stub that accepts and ignores), and the call changes nothing -
+    a [3, 2] fanout gives the same tensors before and after."""
+    torch = torch_cuda
+    from euler_amd import _lib
+    L = _lib.lib()
+    p = EA.synth_params(977, 20000, 260000, n_types=1, weighted=True)
+    G = EA.Graph.synthetic(p)
+    q = torch.as_tensor(np.array([1, 2, 17, 4000, 19999, 20000, 17], np.int64)).cuda()
+    G.set_seed(3)
+    try:
+        _lib.check(L.euler_gpu_set_tuning(33, 0))
+        bn, bw, bt = G.sample_fanout(q, [[0], [0]], [3, 2], 20001, call_id=6)
+        for k_ in (54, 57):
+            for v_ in (0, 1):
+                assert L.euler_gpu_set_tuning(k_, v_) != 0, (k_, v_)
+        an, aw, at = G.sample_fanout(q, [[0], [0]], [3, 2], 20001, call_id=6)
+        for h in range(2):
+            assert torch.equal(bn[h + 1], an[h + 1]) and torch.equal(bw[h], aw[h]) and torch.equal(bt[h], at[h])
+    finally:
+        L.euler_gpu_set_tuning(33, 32768)
 
 
 def test_sample_fanout_multi_equals_separate_calls(EA, O, torch_cuda, big_pair):
