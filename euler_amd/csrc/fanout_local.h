@@ -1142,10 +1142,13 @@ template <bool WIDE, int WPS, bool UNIFORM = false, int WB = 0, bool HW = false>
 __global__ __launch_bounds__(256, WPS) void SampleFanoutLeanKernel(
     const FanoutLocalArgs a) {
   extern __shared__ __align__(16) uint8_t fl_smem[];
+  constexpr bool kTyped = WB >= 3 && WB <= 5;     // a type draw per sample
+  constexpr bool kSeg = WB == 2 || WB == 6;       // one listed type: that type's segment of the row
+  constexpr bool kReg4 = WB == 4 || WB == 5;      // the typed row record in registers
   const int lane = threadIdx.x & 63;
   const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int waves_per_block = blockDim.x >> 6;
-  const FanoutLeanLds L = FanoutLeanLayout(a.gr, a.c1, a.c2, a.cap, WB >= 3 && WB <= 5);
+  const FanoutLeanLds L = FanoutLeanLayout(a.gr, a.c1, a.c2, a.cap, kTyped);
   uint8_t* base = fl_smem + (size_t)wave_in_block * a.wave_lds;
   uint64_t* s_sid = reinterpret_cast<uint64_t*>(base + L.o_sid);
   uint64_t* s_c1 = reinterpret_cast<uint64_t*>(base + L.o_c1);
@@ -1192,21 +1195,21 @@ __global__ __launch_bounds__(256, WPS) void SampleFanoutLeanKernel(
       uint64_t node = 0;
       WbRec wr{0u, 0u, 0u, 0.f};
       WbSeg ws;
-      if (WB == 2 || WB == 6) { ws.wb_lo = 0; ws.row_deg = 0; ws.lo = 0; ws.deg = 0; ws.row_total = 0.f; ws.lim_b = 0.f; ws.lim_e = 0.f; ws.row_lo = 0; }
+      if (kSeg) { ws.wb_lo = 0; ws.row_deg = 0; ws.lo = 0; ws.deg = 0; ws.row_total = 0.f; ws.lim_b = 0.f; ws.lim_e = 0.f; ws.row_lo = 0; }
       WbRowT wt;
       WbRowT4 w4;
       if (WB == 3) { wt.hd = nullptr; wt.te = nullptr; wt.lim = nullptr; wt.tsum = nullptr; wt.row = -1; wt.row_lo = 0; wt.row_deg = 0; wt.valid = false; }
-      if (WB == 4 || WB == 5) { w4.wb_lo = 0; w4.row_lo = 0; w4.row = -1; w4.row_deg = 0; w4.row_total = 0.f; w4.valid = false;
+      if (kReg4) { w4.wb_lo = 0; w4.row_lo = 0; w4.row = -1; w4.row_deg = 0; w4.row_total = 0.f; w4.valid = false;
                      for (int i = 0; i < 4; ++i) { w4.te[i] = 0; w4.lim[i] = 0.f; w4.ts[i] = 0.f; } }
       if (in) {
         node = a.roots[r0 + q];
-        if (WB == 4 || WB == 5) {
+        if (kReg4) {
           LoadWbRowT4(g, node, a.type_mode, a.et1, a.k, &w4);
           lo = w4.row_lo; deg = w4.valid ? (int32_t)w4.row_deg : 0;
         } else if (WB == 3) {
           LoadWbRowT(g, node, a.type_mode, a.et1, a.k, &wt);
           lo = wt.row_lo; deg = wt.valid ? (int32_t)wt.row_deg : 0;
-        } else if (WB == 2 || WB == 6) {
+        } else if (kSeg) {
           LoadWbSeg(g, node, a.t1, &ws);
           lo = ws.lo; deg = (int32_t)ws.deg;
         } else {
@@ -1227,12 +1230,12 @@ __global__ __launch_bounds__(256, WPS) void SampleFanoutLeanKernel(
       int32_t tt[2] = {a.t1, a.t1};
       bool sentinel = false;
       Philox4 pb;
-      if (WB == 4 || WB == 5) WbSampleTypedPair4<WB == 5>(g, w4, a.type_mode, a.et1, a.k, a.seed, tile_call, node, jp, live,
+      if (kReg4) WbSampleTypedPair4<WB == 5>(g, w4, a.type_mode, a.et1, a.k, a.seed, tile_call, node, jp, live,
                                       2u * jp + 1u < c1, id, w, m, tt, &sentinel);
       else if (WB == 3) WbSampleTypedPair(g, wt, a.type_mode, a.et1, a.k, a.seed, tile_call, node, jp, live,
                                           2u * jp + 1u < c1, id, w, m, tt, &sentinel);
       else pb = RngBlock(a.seed, tile_call, kDomainNeighbor, node, jp);
-      if (WB >= 3 && WB <= 5) {}
+      if (kTyped) {}
       else if (WB == 6) UniformSamplePairG2(g, ws, ws, a.t1, a.t1, live, live && 2u * jp + 1u < c1,
                                             UnitFromWords(pb.w[0], pb.w[1]), UnitFromWords(pb.w[2], pb.w[3]), id, w, m);
       else if (WB == 2) WbSamplePairG(g, ws, a.t1, live, UnitFromWords(pb.w[0], pb.w[1]),
@@ -1249,12 +1252,12 @@ __global__ __launch_bounds__(256, WPS) void SampleFanoutLeanKernel(
         const uint32_t e0 = q * c1 + j0;
         s_c1[e0] = live ? id[0] : 0;        // a row without samples hands node id 0 on
         s_w1[e0] = live ? w[0] : 0.f;
-        if (WB >= 3 && WB <= 5) s_t1[e0] = (int8_t)(live ? tt[0] : -1);
+        if (kTyped) s_t1[e0] = (int8_t)(live ? tt[0] : -1);
         unsigned long long bits = live ? 1ull << ((m[0] - lo) & 63u) : 1ull;
         if (j0 + 1u < c1) {
           s_c1[e0 + 1] = live ? id[1] : 0;
           s_w1[e0 + 1] = live ? w[1] : 0.f;
-          if (WB >= 3 && WB <= 5) s_t1[e0 + 1] = (int8_t)(live ? tt[1] : -1);
+          if (kTyped) s_t1[e0 + 1] = (int8_t)(live ? tt[1] : -1);
           if (live) bits |= 1ull << ((m[1] - lo) & 63u);
           // the slot pass below needs the edge of every sample: park it in s_slot
           s_slot[e0 + 1] = (uint16_t)(live ? (m[1] - lo) & 63u : 0u);
@@ -1342,21 +1345,21 @@ __global__ __launch_bounds__(256, WPS) void SampleFanoutLeanKernel(
         uint64_t node = 0;
         WbRec wr{0u, 0u, 0u, 0.f};
         WbSeg ws;
-        if (WB == 2 || WB == 6) { ws.wb_lo = 0; ws.row_deg = 0; ws.lo = 0; ws.deg = 0; ws.row_total = 0.f; ws.lim_b = 0.f; ws.lim_e = 0.f; ws.row_lo = 0; }
+        if (kSeg) { ws.wb_lo = 0; ws.row_deg = 0; ws.lo = 0; ws.deg = 0; ws.row_total = 0.f; ws.lim_b = 0.f; ws.lim_e = 0.f; ws.row_lo = 0; }
         WbRowT wt;
         WbRowT4 w4;
         if (WB == 3) { wt.hd = nullptr; wt.te = nullptr; wt.lim = nullptr; wt.tsum = nullptr; wt.row = -1; wt.row_lo = 0; wt.row_deg = 0; wt.valid = false; }
-        if (WB == 4 || WB == 5) { w4.wb_lo = 0; w4.row_lo = 0; w4.row = -1; w4.row_deg = 0; w4.row_total = 0.f; w4.valid = false;
+        if (kReg4) { w4.wb_lo = 0; w4.row_lo = 0; w4.row = -1; w4.row_deg = 0; w4.row_total = 0.f; w4.valid = false;
                        for (int i = 0; i < 4; ++i) { w4.te[i] = 0; w4.lim[i] = 0.f; w4.ts[i] = 0.f; } }
         if (in) {
           node = s_slotid[s0 + sl];
-          if (WB == 4 || WB == 5) {
+          if (kReg4) {
             LoadWbRowT4(g, node, a.type_mode, a.et2, a.k, &w4);
             lo = w4.row_lo; deg = w4.valid ? (int32_t)w4.row_deg : 0;
           } else if (WB == 3) {
             LoadWbRowT(g, node, a.type_mode, a.et2, a.k, &wt);
             lo = wt.row_lo; deg = wt.valid ? (int32_t)wt.row_deg : 0;
-          } else if (WB == 2 || WB == 6) {
+          } else if (kSeg) {
             LoadWbSeg(g, node, a.t2, &ws);
             lo = ws.lo; deg = (int32_t)ws.deg;
           } else {
@@ -1377,12 +1380,12 @@ __global__ __launch_bounds__(256, WPS) void SampleFanoutLeanKernel(
         int32_t tt[2] = {a.t2, a.t2};
         bool sentinel = false;
         Philox4 pb;
-        if (WB == 4 || WB == 5) WbSampleTypedPair4<WB == 5>(g, w4, a.type_mode, a.et2, a.k, a.seed, tile_call + 1u, node, xp, live,
+        if (kReg4) WbSampleTypedPair4<WB == 5>(g, w4, a.type_mode, a.et2, a.k, a.seed, tile_call + 1u, node, xp, live,
                                         true, id, w, m, tt, &sentinel);
         else if (WB == 3) WbSampleTypedPair(g, wt, a.type_mode, a.et2, a.k, a.seed, tile_call + 1u, node, xp, live,
                                             true, id, w, m, tt, &sentinel);
         else pb = RngBlock(a.seed, tile_call + 1u, kDomainNeighbor, node, xp);
-        if (WB >= 3 && WB <= 5) {}
+        if (kTyped) {}
         else if (WB == 6) UniformSamplePairG2(g, ws, ws, a.t2, a.t2, live, live, UnitFromWords(pb.w[0], pb.w[1]),
                                               UnitFromWords(pb.w[2], pb.w[3]), id, w, m);
         else if (WB == 2) WbSamplePairG(g, ws, a.t2, live, UnitFromWords(pb.w[0], pb.w[1]),
@@ -1403,7 +1406,7 @@ __global__ __launch_bounds__(256, WPS) void SampleFanoutLeanKernel(
           *reinterpret_cast<float2*>(s_sw + sl * c2 + 2u * xp) =
               make_float2(live ? w[0] : 0.f, live ? w[1] : 0.f);
           if (xp == 0) s_st[sl] = live ? a.t2 : -1;
-          if (WB >= 3 && WB <= 5) {
+          if (kTyped) {
             s_t2[sl * c2 + 2u * xp] = (int8_t)(live ? tt[0] : -1);
             s_t2[sl * c2 + 2u * xp + 1u] = (int8_t)(live ? tt[1] : -1);
           }
@@ -1421,7 +1424,7 @@ __global__ __launch_bounds__(256, WPS) void SampleFanoutLeanKernel(
             *reinterpret_cast<float2*>(a.w2 + row0 + e) = *reinterpret_cast<const float2*>(s_sw + e);
             const int32_t tv = s_st[a.div_c2(e)];
             *reinterpret_cast<int2*>(a.ty2 + row0 + e) =
-                (WB >= 3 && WB <= 5) ? make_int2((int32_t)s_t2[e], (int32_t)s_t2[e + 1]) : make_int2(tv, tv);
+                kTyped ? make_int2((int32_t)s_t2[e], (int32_t)s_t2[e + 1]) : make_int2(tv, tv);
           }
         }
       } else
@@ -1442,7 +1445,7 @@ __global__ __launch_bounds__(256, WPS) void SampleFanoutLeanKernel(
                   *reinterpret_cast<const float2*>(s_sw + sl * c2 + x);
               const int32_t tv = s_st[sl];
               *reinterpret_cast<int2*>(a.ty2 + out2 + p) =
-                  (WB >= 3 && WB <= 5) ? make_int2((int32_t)s_t2[sl * c2 + x], (int32_t)s_t2[sl * c2 + x + 1]) : make_int2(tv, tv);
+                  kTyped ? make_int2((int32_t)s_t2[sl * c2 + x], (int32_t)s_t2[sl * c2 + x + 1]) : make_int2(tv, tv);
             }
           }
         }
@@ -1464,7 +1467,7 @@ __global__ __launch_bounds__(256, WPS) void SampleFanoutLeanKernel(
             int32_t ta = -1, tb = -1, ta2 = -1, tb2 = -1;
             if (ina) { wa = *reinterpret_cast<const float2*>(s_sw + sla * c2 + xa); ta = s_st[sla]; ta2 = ta; }
             if (inb) { wb = *reinterpret_cast<const float2*>(s_sw + slb * c2 + xb); tb = s_st[slb]; tb2 = tb; }
-            if (WB >= 3 && WB <= 5) {
+            if (kTyped) {
               if (ina) { ta = (int32_t)s_t2[sla * c2 + xa]; ta2 = (int32_t)s_t2[sla * c2 + xa + 1]; }
               if (inb) { tb = (int32_t)s_t2[slb * c2 + xb]; tb2 = (int32_t)s_t2[slb * c2 + xb + 1]; }
             }
@@ -1502,7 +1505,7 @@ __global__ __launch_bounds__(256, WPS) void SampleFanoutLeanKernel(
         const bool ok = s_rvalid[q] != 0;
         a.id1[out1 + tk] = ok ? s_c1[tk] : (uint64_t)a.default_node;
         a.w1[out1 + tk] = s_w1[tk];
-        a.ty1[out1 + tk] = (WB >= 3 && WB <= 5) ? (int32_t)s_t1[tk] : ok ? a.t1 : -1;
+        a.ty1[out1 + tk] = kTyped ? (int32_t)s_t1[tk] : ok ? a.t1 : -1;
       }
     }
     WaveSync();

@@ -1607,42 +1607,27 @@ static int RunFanout(const euler_gpu_graph* g, hipStream_t stream, uint64_t seed
           t_fl_took_lean = 1;
           void (*lk)(const FanoutLocalArgs) = nullptr;
           const bool use_wb = v.uniform_w == 0 && f.g.wrec != nullptr && f.g.wb != nullptr && v.wb_lean_ok != 0;
-          if (lean_gu) {
-            lk = f.wide ? SampleFanoutLeanKernel<true, 5, false, 6> : SampleFanoutLeanKernel<false, 5, false, 6>;
-          } else if (lean_tu) {                                  // ... and the draw an index computation
-            lk = f.wide ? SampleFanoutLeanKernel<true, 5, false, 5> : SampleFanoutLeanKernel<false, 5, false, 5>;
-          } else if (lean_t && v.T <= 4 && g_fl_typed_regs != 0) {      // the row record in registers
-            lk = f.wide ? SampleFanoutLeanKernel<true, 5, false, 4> : SampleFanoutLeanKernel<false, 5, false, 4>;
-          } else if (lean_t) {
-            lk = f.wide ? SampleFanoutLeanKernel<true, 5, false, 3> : SampleFanoutLeanKernel<false, 5, false, 3>;
-          } else if (lean_g) {
-            lk = f.wide ? (g_fl_wps == 6 ? SampleFanoutLeanKernel<true, 6, false, 2> : SampleFanoutLeanKernel<true, 5, false, 2>)
-                        : (g_fl_wps == 6 ? SampleFanoutLeanKernel<false, 6, false, 2> : SampleFanoutLeanKernel<false, 5, false, 2>);
-          } else if (v.uniform_w != 0) {
-            lk = g_fl_wps == 8 ? (f.wide ? SampleFanoutLeanKernel<true, 8, true> : SampleFanoutLeanKernel<false, 8, true>)
-                               : (f.wide ? SampleFanoutLeanKernel<true, 5, true> : SampleFanoutLeanKernel<false, 5, true>);
-          } else if (use_wb && plain && g_fp_hw != 0 && f.g.hw != nullptr) {      // hop 2 through the side index
-            lk = f.wide ? (g_fl_wps == 8 ? SampleFanoutLeanKernel<true, 8, false, 1, true>
-                                         : g_fl_wps == 5 ? SampleFanoutLeanKernel<true, 5, false, 1, true>
-                                                         : SampleFanoutLeanKernel<true, 6, false, 1, true>)
-                        : (g_fl_wps == 8 ? SampleFanoutLeanKernel<false, 8, false, 1, true>
-                                         : g_fl_wps == 5 ? SampleFanoutLeanKernel<false, 5, false, 1, true>
-                                                         : SampleFanoutLeanKernel<false, 6, false, 1, true>);
-          } else if (use_wb) {
-            lk = f.wide ? (g_fl_wps == 8 ? SampleFanoutLeanKernel<true, 8, false, 1>
-                                         : g_fl_wps == 5 ? SampleFanoutLeanKernel<true, 5, false, 1>
-                                                         : SampleFanoutLeanKernel<true, 6, false, 1>)
-                        : (g_fl_wps == 8 ? SampleFanoutLeanKernel<false, 8, false, 1>
-                                         : g_fl_wps == 5 ? SampleFanoutLeanKernel<false, 5, false, 1>
-                                                         : SampleFanoutLeanKernel<false, 6, false, 1>);
-          } else {
-            lk = f.wide ? (g_fl_wps == 8 ? SampleFanoutLeanKernel<true, 8>
-                                         : g_fl_wps == 5 ? SampleFanoutLeanKernel<true, 5>
-                                                         : SampleFanoutLeanKernel<true, 6>)
-                        : (g_fl_wps == 8 ? SampleFanoutLeanKernel<false, 8>
-                                         : g_fl_wps == 5 ? SampleFanoutLeanKernel<false, 5>
-                                                         : SampleFanoutLeanKernel<false, 6>);
-          }
+          // the build of one draw mode (UNIFORM, WB, HW) for W waves per SIMD, and W as key 35 asks: the
+          // builds that exist are 8 / 5 / else 6, 8 / else 5, 6 / else 5, and 5 alone
+#define EG_LW(W, ...) (f.wide ? SampleFanoutLeanKernel<true, W, __VA_ARGS__> : SampleFanoutLeanKernel<false, W, __VA_ARGS__>)
+#define EG_LEAN_5(...) EG_LW(5, __VA_ARGS__)
+#define EG_LEAN_65(...) (g_fl_wps == 6 ? EG_LW(6, __VA_ARGS__) : EG_LW(5, __VA_ARGS__))
+#define EG_LEAN_85(...) (g_fl_wps == 8 ? EG_LW(8, __VA_ARGS__) : EG_LW(5, __VA_ARGS__))
+#define EG_LEAN_856(...) (g_fl_wps == 8 ? EG_LW(8, __VA_ARGS__) : g_fl_wps == 5 ? EG_LW(5, __VA_ARGS__) : EG_LW(6, __VA_ARGS__))
+          if (lean_gu) lk = EG_LEAN_5(false, 6, false);
+          else if (lean_tu) lk = EG_LEAN_5(false, 5, false);                 // the draw an index computation
+          else if (lean_t && v.T <= 4 && g_fl_typed_regs != 0) lk = EG_LEAN_5(false, 4, false);   // the row record in registers
+          else if (lean_t) lk = EG_LEAN_5(false, 3, false);
+          else if (lean_g) lk = EG_LEAN_65(false, 2, false);
+          else if (v.uniform_w != 0) lk = EG_LEAN_85(true, 0, false);
+          else if (use_wb && plain && g_fp_hw != 0 && f.g.hw != nullptr) lk = EG_LEAN_856(false, 1, true);   // hop 2: the side index
+          else if (use_wb) lk = EG_LEAN_856(false, 1, false);
+          else lk = EG_LEAN_856(false, 0, false);
+#undef EG_LEAN_856
+#undef EG_LEAN_85
+#undef EG_LEAN_65
+#undef EG_LEAN_5
+#undef EG_LW
           t_fl_last_kernel = "SampleFanoutLeanKernel";
           hipLaunchKernelGGL(lk, dim3((unsigned)blocks), dim3(block), llds, stream, f);
           EG_HIP(hipGetLastError());
