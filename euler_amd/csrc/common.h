@@ -128,7 +128,7 @@ struct GraphView {
   // builds of the one-kernel fanout (fanout_local.h: FatFind) find a root's record with ONE
   // cold line instead of slot -> record.  nullptr: not built (T > 2, identity map, no room).
   const uint8_t* fat;
-  // header + window lines of the SAME buckets (wb_hw.h; plain graphs whose index the lean kernels
+  // header + window lines of the SAME buckets (wb_hw.h or wb_hw2.h; plain graphs whose index the lean kernels
   // may use, no neighbour id 0): hop 2 of the 2-hop fanout draws through them.  nullptr: not built.
   const struct HwLine* hw;
   int32_t wb_lean_ok;           // at most 2 buckets in a thousand overflow their block (counted at
@@ -301,6 +301,7 @@ struct euler_gpu_graph {
   mutable std::atomic<void*> last_stream{nullptr};
   mutable std::atomic<int> wb_tried{0};     // EnsureWbIndex ran (whatever it decided)
   int64_t hw_bytes = 0, hw_lines = 0, hw_overflows = 0;   // the side index of wb_hw.h (bytes 0: declined)
+  int32_t hw_format = 0;       // ... the lines it holds: 1 = wb_hw.h, 2 = wb_hw2.h (tuning key 76 when it was built)
   std::vector<uint32_t> wb_overflow_rows;   // rows with a bucket that overflows its block (the first 4 096 found)
   mutable std::atomic<int> blk_ready{0};    // EnsureBlockedIndex built the EdgeBlocks (view.blk / skip1 / bpiv)
   // Block construction (dataflow_kernels.hip): first-occurrence unique of a hop's node list

@@ -42,6 +42,7 @@
 #include "k1_search.h"
 #include "wb_index.h"
 #include "wb_hw.h"
+#include "wb_hw2.h"
 
 namespace euler_gpu {
 
@@ -742,6 +743,52 @@ __device__ __forceinline__ void HwSamplePair(const HwLine* hw, const float* pref
                  rec.lo, 0, (uint64_t)(rec.deg - 1u), id, w, nullptr);
 }
 
+// The same pair of draws through the 12-bit lines of wb_hw2.h: TWO requests per draw.  The header's
+// codes run over the bucket's span, so the guess is one entry too high for ~5e-4 of the draws
+// instead of ~1e-2 and the 12 bytes before the window are not asked for; a draw whose window says
+// "before" (i > 0) loads window i - 1 in a second dependent trip that only one wave-step in ten
+// takes at all (one ballot).  As above: both headers before either window, both windows before
+// either is examined, the checks are selects, and the second trip's load shares its `if` with no
+// copy of another load's result (a lane that does not ask checks a window of zeros, which
+// HwCheck reads as "after" and leaves id / weight alone).
+__device__ __forceinline__ void Hw2SamplePair(const HwLine* hw, const float* prefix_w, const uint64_t* nbr,
+                                              const WbRec rec, const bool live, const double u0,
+                                              const double u1, uint64_t id[2], float w[2]) {
+  const double r0 = __dmul_rn(u0, (double)rec.total), r1 = __dmul_rn(u1, (double)rec.total);
+  const bool t0 = live && (double)rec.total > r0, t1 = live && (double)rec.total > r1;
+  const float f0 = WbFloorToFloat(r0), f1 = WbFloorToFloat(r1);
+  const uint32_t nbk = WbBuckets(rec.deg);
+  const float scale = WbScale(nbk, rec.total);
+  uint32_t j0 = 0u, j1 = 0u;
+  if (nbk > 1u) {
+    j0 = WbBucketOf(f0, nbk, scale);
+    j1 = WbBucketOf(f1, nbk, scale);
+  }
+  // (a dead lane's record is all zeros: line 0, a valid line nobody uses)
+  const HwLine* l0 = hw + rec.wb_lo + j0;
+  const HwLine* l1 = hw + rec.wb_lo + j1;
+  const Hw2Head h0 = Hw2LoadHead(l0), h1 = Hw2LoadHead(l1);
+  const uint32_t i0 = Hw2Guess(h0, Hw2Code(Hw2Pos(f0, scale, j0)));
+  const uint32_t i1 = Hw2Guess(h1, Hw2Code(Hw2Pos(f1, scale, j1)));
+  const HwWin x0 = HwLoadWin(l0, i0), x1 = HwLoadWin(l1, i1);
+  id[0] = 0; id[1] = 0; w[0] = 0.f; w[1] = 0.f;
+  const int32_t d0 = HwCheck(x0, f0, &id[0], &w[0]), d1 = HwCheck(x1, f1, &id[1], &w[1]);
+  bool hot0 = t0 && d0 == 0, hot1 = t1 && d1 == 0;
+  const bool ask0 = t0 && d0 < 0 && i0 != 0u, ask1 = t1 && d1 < 0 && i1 != 0u;
+  if (__ballot(ask0 || ask1) != 0ull) {
+    HwWin y0{0u, 0u, 0u, 0u}, y1{0u, 0u, 0u, 0u};
+    if (ask0) y0 = HwLoadWin(l0, i0 - 1u);
+    if (ask1) y1 = HwLoadWin(l1, i1 - 1u);
+    const int32_t e0 = HwCheck(y0, f0, &id[0], &w[0]), e1 = HwCheck(y1, f1, &id[1], &w[1]);
+    hot0 = hot0 || (ask0 && e0 == 0);
+    hot1 = hot1 || (ask1 && e1 == 0);
+  }
+  if (!hot0) { id[0] = 0; w[0] = 0.f; }
+  if (!hot1) { id[1] = 0; w[1] = 0.f; }
+  ColdReplayPair(prefix_w, nbr, live && !hot0, live && !hot1, u0, u1, rec.lo, 0, (uint64_t)(rec.deg - 1u),
+                 rec.lo, 0, (uint64_t)(rec.deg - 1u), id, w, nullptr);
+}
+
 // The same pair of draws on ANY graph the weight-bucket index serves - several edge-type
 // groups per node, hashed ids - for one listed type: the segment's limits and the row's first
 // block come out of the row's weight-bucket record (common.h: GraphView::wbg) alone.
@@ -1137,8 +1184,10 @@ __host__ __device__ inline FanoutLeanLds FanoutLeanLayout(int32_t gr, int32_t c1
 // sample, WbSampleTypedPair; at most 127 types); 4 = 3 with the row record in registers (at most 4
 // type groups); 5 = 4 on a graph of uniform weights (the neighbour draw is an index computation);
 // 6 = 2 on a graph of uniform weights.
-// HW (with WB = 1): hop 2 draws through the header + window side index (HwSamplePair, g.hw).
-template <bool WIDE, int WPS, bool UNIFORM = false, int WB = 0, bool HW = false>
+// HW (with WB = 1): hop 2 draws through the header + window side index g.hw - 1 = the lines of
+// wb_hw.h (HwSamplePair), 2 = those of wb_hw2.h (Hw2SamplePair); the launcher picks the build by
+// the format the graph's side index has.
+template <bool WIDE, int WPS, bool UNIFORM = false, int WB = 0, int HW = 0>
 __global__ __launch_bounds__(256, WPS) void SampleFanoutLeanKernel(
     const FanoutLocalArgs a) {
   extern __shared__ __align__(16) uint8_t fl_smem[];
@@ -1390,8 +1439,10 @@ __global__ __launch_bounds__(256, WPS) void SampleFanoutLeanKernel(
                                               UnitFromWords(pb.w[2], pb.w[3]), id, w, m);
         else if (WB == 2) WbSamplePairG(g, ws, a.t2, live, UnitFromWords(pb.w[0], pb.w[1]),
                                    UnitFromWords(pb.w[2], pb.w[3]), id, w, m);
-        else if (WB == 1 && HW) HwSamplePair(g.hw, g.prefix_w, g.nbr, wr, live, UnitFromWords(pb.w[0], pb.w[1]),
-                                             UnitFromWords(pb.w[2], pb.w[3]), id, w);
+        else if (WB == 1 && HW == 2) Hw2SamplePair(g.hw, g.prefix_w, g.nbr, wr, live, UnitFromWords(pb.w[0], pb.w[1]),
+                                                   UnitFromWords(pb.w[2], pb.w[3]), id, w);
+        else if (WB == 1 && HW == 1) HwSamplePair(g.hw, g.prefix_w, g.nbr, wr, live, UnitFromWords(pb.w[0], pb.w[1]),
+                                                  UnitFromWords(pb.w[2], pb.w[3]), id, w);
         else if (WB) WbSamplePair(g.wb, g.prefix_w, g.nbr, wr, live, live, UnitFromWords(pb.w[0], pb.w[1]),
                                   UnitFromWords(pb.w[2], pb.w[3]), id, w, m);
         else if (UNIFORM) LeanSamplePairUniform(g, lo, deg, total, live, UnitFromWords(pb.w[0], pb.w[1]),

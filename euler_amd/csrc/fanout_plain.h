@@ -24,7 +24,7 @@
 //     the chunk -> (row, column) pattern a per-lane constant).
 // Hop 1 draws through the weight-bucket blocks (WbSamplePair: the slot pass needs the drawn
 // edge's number); hop 2 through the header + window lines where the graph has them (HW, tuning
-// key 75: HwSamplePair), else through the blocks too.  Two more builds of this kernel - a block's
+// key 75: Hw2SamplePair or HwSamplePair, by the lines' format), else through the blocks too.  Two more builds of this kernel - a block's
 // keys fetched by three lanes as one request per line and staged in LDS, and a hop 2 that asked
 // for two of a block's three key chunks - were built, measured slower and removed.
 // Bit-identical outputs with the lean kernel and the oracle (tests/test_gpu_parity.py).
@@ -40,7 +40,7 @@ namespace euler_gpu {
 struct FanoutPlainArgs {
   const WbRec* wrec;
   const EdgeBlock* wb;
-  const HwLine* hw;             // HW builds: hop 2's header + window lines (wb_hw.h), same buckets
+  const HwLine* hw;             // HW builds: hop 2's header + window lines (wb_hw.h / wb_hw2.h), same buckets
   const float* prefix_w;        // cold draws only (Q3, a bucket that overflows its block)
   const uint64_t* nbr;
   const uint64_t* roots;
@@ -108,9 +108,10 @@ __device__ __forceinline__ WbRec PlainLoadRec(const FanoutPlainArgs& a, const ui
   return wr;
 }
 
-// HW = true (tuning key 75, the default where the graph has the side index): hop 2 draws through
-// the header + window lines - two requests per draw (HwSamplePair).
-template <int WPS, bool HW>
+// HW != 0 (tuning key 75, the default where the graph has the side index): hop 2 draws through
+// the header + window lines - 1: those of wb_hw.h, three requests per draw (HwSamplePair); 2: those
+// of wb_hw2.h, two (Hw2SamplePair).  The launcher picks by the format the side index was built in.
+template <int WPS, int HW>
 __global__ __launch_bounds__(256, WPS) void SampleFanoutPlainKernel(const FanoutPlainArgs a) {
   extern __shared__ __align__(16) uint8_t fp_smem[];
   const uint32_t lane = threadIdx.x & 63u;
@@ -264,7 +265,10 @@ __global__ __launch_bounds__(256, WPS) void SampleFanoutPlainKernel(const Fanout
         const bool lv = in && cr.deg > 0u;
         uint64_t i2[2]; float w2[2]; uint32_t m2[2];
         const Philox4 pb = RngBlock(a.seed, call + 1u, kDomainNeighbor, child, x2);
-        if (HW) {
+        if (HW == 2) {
+          Hw2SamplePair(a.hw, a.prefix_w, a.nbr, cr, lv, UnitFromWords(pb.w[0], pb.w[1]),
+                        UnitFromWords(pb.w[2], pb.w[3]), i2, w2);
+        } else if (HW == 1) {
           HwSamplePair(a.hw, a.prefix_w, a.nbr, cr, lv, UnitFromWords(pb.w[0], pb.w[1]),
                        UnitFromWords(pb.w[2], pb.w[3]), i2, w2);
         } else {

@@ -19,6 +19,7 @@
 #include "device_mem.h"
 #include "wb_index.h"
 #include "wb_hw.h"
+#include "wb_hw2.h"
 
 namespace euler_gpu {
 
@@ -882,7 +883,8 @@ __global__ __launch_bounds__(256) void WbFillKernel(GraphView g, const uint32_t*
   if (mine != 0) atomicAdd(overflows, mine);
 }
 
-// the header + window lines of the same buckets (wb_hw.h), one lane per line
+// the header + window lines of the same buckets (FORMAT 1: wb_hw.h, 2: wb_hw2.h), one lane per line
+template <int FORMAT>
 __global__ __launch_bounds__(256) void HwFillKernel(GraphView g, const uint32_t* wb_lo, int64_t n_wb,
                                                     HwLine* hw, unsigned long long* overflows) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -896,8 +898,10 @@ __global__ __launch_bounds__(256) void HwFillKernel(GraphView g, const uint32_t*
     const RowMeta m = LoadRowMeta(g, lo);
     const uint32_t deg = (uint32_t)m.type_end[g.T - 1];
     HwLine e;
-    if (HwBuildLine(g.prefix_w, g.nbr, (uint32_t)m.row_ptr, deg, g.prefix_w[m.row_ptr + deg - 1],
-                    (uint32_t)(b - (int64_t)wb_lo[lo]), &e))
+    const uint32_t j = (uint32_t)(b - (int64_t)wb_lo[lo]);
+    const float total = g.prefix_w[m.row_ptr + deg - 1];
+    if (FORMAT == 2 ? Hw2BuildLine(g.prefix_w, g.nbr, (uint32_t)m.row_ptr, deg, total, j, &e)
+                    : HwBuildLine(g.prefix_w, g.nbr, (uint32_t)m.row_ptr, deg, total, j, &e))
       ++mine;
     hw[b] = e;
   }
@@ -986,7 +990,13 @@ bool WbFits(size_t need) {
   return need + ((size_t)1 << 30) <= free_b;
 }
 
-// The side index of wb_hw.h, for the graphs whose hop 2 the plain fanout kernels serve.  An
+// tuning key 76 (process-wide: the index is built once, by whichever thread samples first): the
+// lines a side index is built with - 2 = wb_hw2.h (two requests per draw; the default: 0.183-0.185
+// against 0.191-0.194 ms per step), 1 = wb_hw.h (three).  A graph keeps the format it
+// was built in; the launcher picks the kernel by it.
+std::atomic<int> g_hw_format{2};
+
+// The side index of wb_hw.h / wb_hw2.h, for the graphs whose hop 2 the plain fanout kernels serve.  An
 // optimisation on top of an optimisation: whatever goes wrong DECLINES it (said once per
 // process), gives its memory back and leaves the weight-bucket index as it is.
 void BuildHwSide(GraphBuilder* b, const uint32_t* wb_lo, int64_t n_wb) {
@@ -1008,8 +1018,9 @@ void BuildHwSide(GraphBuilder* b, const uint32_t* wb_lo, int64_t n_wb) {
     decline("no memory");
     return;
   }
-  hipLaunchKernelGGL(HwFillKernel, dim3(GridFor(n_wb, 256)), dim3(256), 0, 0, v, wb_lo, n_wb, hw,
-                     cnt.as<unsigned long long>());
+  const int format = g_hw_format.load() == 2 ? 2 : 1;
+  hipLaunchKernelGGL(format == 2 ? HwFillKernel<2> : HwFillKernel<1>, dim3(GridFor(n_wb, 256)), dim3(256), 0, 0, v,
+                     wb_lo, n_wb, hw, cnt.as<unsigned long long>());
   unsigned long long n_ovf = 0;
   if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
       hipMemcpy(&n_ovf, cnt.as(), 8, hipMemcpyDeviceToHost) != hipSuccess) {
@@ -1029,6 +1040,7 @@ void BuildHwSide(GraphBuilder* b, const uint32_t* wb_lo, int64_t n_wb) {
   b->g->hw_bytes = (int64_t)std::max<size_t>(bytes, 16);
   b->g->hw_lines = n_wb;
   b->g->hw_overflows = (int64_t)n_ovf;
+  b->g->hw_format = format;
 }
 
 int BuildWbIndex(GraphBuilder* b) {
@@ -1134,7 +1146,7 @@ int EnsureWbIndex(const euler_gpu_graph* cg) {
     GraphView& v = g->view;
     v.wb = nullptr; v.wbg = nullptr; v.wrec = nullptr; v.n_wb = 0; v.wb_lean_ok = 0;
     v.trec = nullptr; v.trec_stride = 0; v.fat = nullptr;
-    v.hw = nullptr; g->hw_bytes = 0; g->hw_lines = 0; g->hw_overflows = 0;
+    v.hw = nullptr; g->hw_bytes = 0; g->hw_lines = 0; g->hw_overflows = 0; g->hw_format = 0;
   }
   g->wb_tried.store(1, std::memory_order_release);
   return EULER_GPU_OK;
@@ -1424,6 +1436,14 @@ int euler_gpu_graph_side_index(const euler_gpu_graph* g, int64_t* bytes_host, in
   const int rc = EnsureWbIndex(g);
   if (rc != EULER_GPU_OK) return rc;
   *bytes_host = g->hw_bytes; *lines_host = g->hw_lines; *overflows_host = g->hw_overflows;
+  return EULER_GPU_OK;
+}
+
+int euler_gpu_graph_side_index_format(const euler_gpu_graph* g, int32_t* format_host) {
+  if (!g || !format_host) return Fail(EULER_GPU_EINVAL, "graph_side_index_format: null argument");
+  const int rc = EnsureWbIndex(g);
+  if (rc != EULER_GPU_OK) return rc;
+  *format_host = g->hw_format;
   return EULER_GPU_OK;
 }
 

@@ -21,6 +21,7 @@ namespace euler_gpu { extern thread_local int g_walk_collapse, g_walk_grid, g_wa
 namespace euler_gpu { extern std::atomic<int> g_sharded_self_exchange, g_sharded_walk_enqueued, g_sharded_walk_tail, g_sharded_walk_split; }   // sharded.cc (process-wide)
 namespace euler_gpu { extern std::atomic<int> g_flow_fused; extern std::atomic<int> g_flow_rowpos; }              // dataflow_kernels.hip (key 60)
 namespace euler_gpu { extern std::atomic<int> g_blk_fail_next; }           // graph_build.hip (test hook)
+namespace euler_gpu { extern std::atomic<int> g_hw_format; }               // graph_build.hip (key 76)
 namespace euler_gpu { extern thread_local int g_label_hash_bits; }     // graph_label_kernels.hip (key 74)
 namespace euler_gpu { extern thread_local int g_root_host_batch, g_adj_scan, g_adj_long_row, g_sum_scalar; }   // layer_kernels.hip
 
@@ -580,8 +581,9 @@ thread_local int g_fl_wps = 5;        // key 35: register budget, waves per SIMD
 thread_local int g_fp_on = 1;         // key 53: plain graphs with the weight-bucket index take the kernel of
                                       // fanout_plain.h (1); 0 = the lean build of fanout_local.h (round 5)
 thread_local int g_fp_hw = 1;         // key 75: hop 2 of the plain-graph 2-hop fanout (both kernels) draws through the header +
-                                      // window side index (wb_hw.h: two requests per draw) when the graph has it (1);
-                                      // 0 = through the weight-bucket blocks (four)
+                                      // window side index (wb_hw.h: three requests per draw; wb_hw2.h: two - key 76 when
+                                      // the index is built) when the graph has it (1); 0 = through the weight-bucket
+                                      // blocks (four)
 thread_local int g_fp_wps = 5;        // key 55: ... its register budget, waves per SIMD (4 .. 8)
 thread_local int g_fl_wb = 1;         // key 45: the lean kernel draws through the weight-bucket index (wb_index.h:
                                       // one line per draw); 0 = the pivot-level search of rounds 2-3
@@ -1568,7 +1570,7 @@ static int RunFanout(const euler_gpu_graph* g, hipStream_t stream, uint64_t seed
           if (pgr * ((c1 + 1) / 2) <= 64 && pgr * c1 <= 255 && pgr * c1 % 4 == 0 && tp % 4 == 0 && c2 <= 64 &&
               c1 <= 128 && (int64_t)pcap * c2 < 4096 && (size_t)pl.bytes * (pblock / 64) <= 64 * 1024) {
             FanoutPlainArgs pa{};
-            const bool hw2 = g_fp_hw != 0 && f.g.hw != nullptr;
+            const int hw2 = g_fp_hw != 0 && f.g.hw != nullptr ? g->hw_format : 0;     // the side index's lines: 1 / 2
             pa.wrec = f.g.wrec; pa.wb = f.g.wb; pa.hw = f.g.hw; pa.prefix_w = f.g.prefix_w; pa.nbr = f.g.nbr;
             pa.roots = roots_dev;
             pa.id1 = f.id1; pa.w1 = f.w1; pa.ty1 = f.ty1; pa.id2 = f.id2; pa.w2 = f.w2; pa.ty2 = f.ty2;
@@ -1583,7 +1585,7 @@ static int RunFanout(const euler_gpu_graph* g, hipStream_t stream, uint64_t seed
             int64_t pwaves = g_fl_grid_cap > 0 ? g_fl_grid_cap : 0;
             if (pwaves > 0 && pblocks > (pwaves + pwpb - 1) / pwpb) pblocks = (pwaves + pwpb - 1) / pwpb;
             void (*pk)(const FanoutPlainArgs) = nullptr;
-#define EG_FP(W) (hw2 ? SampleFanoutPlainKernel<W, true> : SampleFanoutPlainKernel<W, false>)
+#define EG_FP(W) (hw2 == 2 ? SampleFanoutPlainKernel<W, 2> : hw2 == 1 ? SampleFanoutPlainKernel<W, 1> : SampleFanoutPlainKernel<W, 0>)
             pk = g_fp_wps >= 8 ? EG_FP(8) : g_fp_wps == 7 ? EG_FP(7) : g_fp_wps == 6 ? EG_FP(6)
                  : g_fp_wps == 5 ? EG_FP(5) : EG_FP(4);
 #undef EG_FP
@@ -1614,15 +1616,17 @@ static int RunFanout(const euler_gpu_graph* g, hipStream_t stream, uint64_t seed
 #define EG_LEAN_65(...) (g_fl_wps == 6 ? EG_LW(6, __VA_ARGS__) : EG_LW(5, __VA_ARGS__))
 #define EG_LEAN_85(...) (g_fl_wps == 8 ? EG_LW(8, __VA_ARGS__) : EG_LW(5, __VA_ARGS__))
 #define EG_LEAN_856(...) (g_fl_wps == 8 ? EG_LW(8, __VA_ARGS__) : g_fl_wps == 5 ? EG_LW(5, __VA_ARGS__) : EG_LW(6, __VA_ARGS__))
-          if (lean_gu) lk = EG_LEAN_5(false, 6, false);
-          else if (lean_tu) lk = EG_LEAN_5(false, 5, false);                 // the draw an index computation
-          else if (lean_t && v.T <= 4 && g_fl_typed_regs != 0) lk = EG_LEAN_5(false, 4, false);   // the row record in registers
-          else if (lean_t) lk = EG_LEAN_5(false, 3, false);
-          else if (lean_g) lk = EG_LEAN_65(false, 2, false);
-          else if (v.uniform_w != 0) lk = EG_LEAN_85(true, 0, false);
-          else if (use_wb && plain && g_fp_hw != 0 && f.g.hw != nullptr) lk = EG_LEAN_856(false, 1, true);   // hop 2: the side index
-          else if (use_wb) lk = EG_LEAN_856(false, 1, false);
-          else lk = EG_LEAN_856(false, 0, false);
+          const bool side = use_wb && plain && g_fp_hw != 0 && f.g.hw != nullptr;      // hop 2: the side index
+          if (lean_gu) lk = EG_LEAN_5(false, 6, 0);
+          else if (lean_tu) lk = EG_LEAN_5(false, 5, 0);                 // the draw an index computation
+          else if (lean_t && v.T <= 4 && g_fl_typed_regs != 0) lk = EG_LEAN_5(false, 4, 0);   // the row record in registers
+          else if (lean_t) lk = EG_LEAN_5(false, 3, 0);
+          else if (lean_g) lk = EG_LEAN_65(false, 2, 0);
+          else if (v.uniform_w != 0) lk = EG_LEAN_85(true, 0, 0);
+          else if (side && g->hw_format == 2) lk = EG_LEAN_856(false, 1, 2);          // ... of wb_hw2.h
+          else if (side) lk = EG_LEAN_856(false, 1, 1);
+          else if (use_wb) lk = EG_LEAN_856(false, 1, 0);
+          else lk = EG_LEAN_856(false, 0, 0);
 #undef EG_LEAN_856
 #undef EG_LEAN_85
 #undef EG_LEAN_65
@@ -1870,6 +1874,7 @@ int euler_gpu_set_tuning(int32_t key, int32_t value) {
   if (key == 63 && (value == 0 || value == 1)) { g_sharded_walk_enqueued.store(value); return EULER_GPU_OK; }
   if (key == 55 && value >= 4 && value <= 8) { g_fp_wps = value; return EULER_GPU_OK; }
   if (key == 75 && (value == 0 || value == 1)) { g_fp_hw = value; return EULER_GPU_OK; }
+  if (key == 76 && (value == 1 || value == 2)) { g_hw_format.store(value); return EULER_GPU_OK; }
   if (key == 56 && value >= 0) { g_blk_fail_next.store(value); return EULER_GPU_OK; }
   return Fail(EULER_GPU_EINVAL, "set_tuning: unknown key");
 }

@@ -453,12 +453,19 @@ class Graph:
 
     def side_index(self):
         """(bytes, lines, overflowing lines) of the header + window side index that hop 2 of the
-        2-hop fanout draws through on plain weighted graphs (csrc/wb_hw.h); bytes 0 = the graph
+        2-hop fanout draws through on plain weighted graphs (csrc/wb_hw.h, csrc/wb_hw2.h); bytes 0 = the graph
         has none (not that kind of graph, over the index budget, too many overflows).  Builds
         the indexes if needed; the bytes are part of `device_bytes`."""
         b, n, o = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         check(lib().euler_gpu_graph_side_index(self._h, C.byref(b), C.byref(n), C.byref(o)))
         return b.value, n.value, o.value
+
+    def side_index_format(self):
+        """0 = no side index, 1 = the lines of csrc/wb_hw.h, 2 = those of csrc/wb_hw2.h (tuning key
+        76 when the index was built).  Builds the indexes if needed."""
+        f = C.c_int32(0)
+        check(lib().euler_gpu_graph_side_index_format(self._h, C.byref(f)))
+        return f.value
 
     def index_overflow_rows(self, cap=4096):
         """Node ids (identity id maps only) of rows in which a bucket of the weight-bucket index

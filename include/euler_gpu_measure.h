@@ -187,6 +187,11 @@ int euler_gpu_graph_index_overflow_rows(const euler_gpu_graph* g, uint64_t* ids_
 int euler_gpu_graph_side_index(const euler_gpu_graph* g, int64_t* bytes_host, int64_t* lines_host,
                                int64_t* overflows_host);
 
+/* ... and the format of its lines: 0 = the graph has none, 1 = csrc/wb_hw.h (8-bit offsets, three
+ * requests per draw), 2 = csrc/wb_hw2.h (12-bit offsets, two) - what tuning key 76 said when the
+ * index was built. */
+int euler_gpu_graph_side_index_format(const euler_gpu_graph* g, int32_t* format_host);
+
 /* ---- measurement helper -------------------------------------------------------
  * Runs the sample_neighbor kernel `iters` times on `stream` between two HIP
  * events recorded on that same stream and returns the mean kernel time in
