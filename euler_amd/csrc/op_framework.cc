@@ -54,8 +54,10 @@ uint64_t ProcessSeed() {
 // staging buffers from the arena, enqueues copies and kernels on the stream and
 // synchronises once (twice when a size has to come back first).  No hipMalloc /
 // hipFree in steady state, nothing on the null stream, every HIP call checked:
-// a failure marks the scope and the op logs and returns WITHOUT allocating its
-// outputs.
+// a failure marks the scope and the op logs and returns.  On every return from
+// every Compute either all of the op's outputs are in the context and complete,
+// or none of the names this invocation created is - and then nothing of the op
+// is in flight on the stream any more (OpOutputs below).
 struct Arena {
   hipStream_t stream = nullptr;
   struct Chunk { void* p; size_t cap; size_t used; };
@@ -85,8 +87,9 @@ class OpScope {
   ~OpScope() {
     if (arena_ == nullptr) return;
     // an op that leaves early (a failed call, a bad argument) may have copies and kernels
-    // queued that read or write its locals, its just-freed outputs or this arena: wait
-    // for them before any of that memory is reused
+    // queued that read or write its host vectors or this arena: wait for them before any
+    // of that memory is reused.  This is the one drain of a failing exit, so the host
+    // vectors an op copies into or from are declared BEFORE its scope and outlive it.
     if (arena_->stream != nullptr && dirty_) (void)hipStreamSynchronize(arena_->stream);
     if (arena_->chunks.size() > 1) {
       // the op outgrew the arena: one chunk of the total size for the next call
@@ -159,6 +162,54 @@ class OpScope {
   bool ok_ = true;
   bool dirty_ = false;        // work was enqueued on the stream since the last Sync()
   std::string err_;
+};
+
+// The outputs "<node>:<i>" of one op invocation.  They survive the return from Compute only
+// through Commit() / Finish().  A guard that dies uncommitted first drains the scope's stream -
+// an earlier asynchronous copy may still be writing into a tensor, and a pinned block that goes
+// back to the pool is handed to the next Tensor of any thread - and then removes exactly the
+// names it created: tensors with Deallocate, aliases with RemoveAlias.  A name that is already
+// taken fails the guard and is never touched: it is not this invocation's.
+// Declare the guard AFTER the OpScope it is given, so that it unwinds first: the drain is valid
+// only while the scope is alive.  Host-only ops pass no scope.
+class OpOutputs {
+ public:
+  OpOutputs(const NodeDef& nd, OpKernelContext* ctx, OpScope* sc = nullptr) : nd_(nd), ctx_(ctx), sc_(sc) {}
+  OpOutputs(const OpOutputs&) = delete;
+  OpOutputs& operator=(const OpOutputs&) = delete;
+  ~OpOutputs() {
+    if (committed_) return;
+    if (sc_ != nullptr) sc_->Drain();
+    for (int i = 0; i < 32; ++i) {
+      if (tensors_ >> i & 1) ctx_->Deallocate(OutputName(nd_, i));
+      if (aliases_ >> i & 1) ctx_->RemoveAlias(OutputName(nd_, i));
+    }
+  }
+  // null (and logged) when the name is taken or an earlier output of this guard failed
+  Tensor* Add(int i, const TensorShape& shape, DataType type) {
+    Tensor* t = nullptr;
+    if (ok_) Made(ctx_->Allocate(OutputName(nd_, i), shape, type, &t) == 0, i, &tensors_);
+    return t;
+  }
+  bool Alias(int i, Tensor* t) {
+    if (ok_) Made(ctx_->AddAlias(OutputName(nd_, i), t) == 0, i, &aliases_);
+    return ok_;
+  }
+  bool ok() const { return ok_; }
+  void Commit() { committed_ = ok_; }
+  // the op's one closing synchronise; the outputs stay when it succeeds
+  bool Finish() { return committed_ = ok_ && sc_->Sync(); }
+
+ private:
+  void Made(bool made, int i, uint32_t* set) {
+    if (made) *set |= 1u << i;
+    else { ok_ = false; LogError("Allocate output tensor failed!"); }
+  }
+  const NodeDef& nd_;
+  OpKernelContext* ctx_;
+  OpScope* sc_;
+  uint32_t tensors_ = 0, aliases_ = 0;      // bit i: this guard created "<node>:<i>"
+  bool ok_ = true, committed_ = false;
 };
 
 bool GetIntArg(const NodeDef& nd, int i, OpKernelContext* ctx,
@@ -463,7 +514,12 @@ class GpuSampleNeighborOp : public OpKernel {
       int32_t ob, de; int64_t li;
       post = post || ParsePostProcess(pp, &ob, &de, &li);
     }
+    std::vector<int32_t> idx, pidx, ht;      // host staging of the post-process path
+    std::vector<uint8_t> mask;
+    std::vector<uint64_t> hid;
+    std::vector<float> hw;
     OpScope sc(g);
+    OpOutputs outs(nd, ctx, &sc);
     uint64_t* d_ids = sc.Alloc<uint64_t>(n);
     uint64_t* d_oid = sc.Alloc<uint64_t>(total);
     float* d_ow = sc.Alloc<float>(total);
@@ -475,8 +531,6 @@ class GpuSampleNeighborOp : public OpKernel {
             edge_types.data(), (int32_t)edge_types.size(), count, EULER_GPU_LAYOUT_CORE, 0,
             d_oid, d_ow, d_ot, d_mask)))
       OP_FAIL(sc, "API_SAMPLE_NB");
-    std::vector<int32_t> idx;
-    std::vector<uint8_t> mask;
     int64_t out_total = total;
     if (post && n > 0) {
       idx.resize((size_t)n * 2);
@@ -505,10 +559,8 @@ class GpuSampleNeighborOp : public OpKernel {
         const size_t src = (size_t)i * count, dst = (size_t)idx[2 * i], len = (size_t)(j - i) * count;
         if (hipMemcpyAsync(p_id + dst, d_oid + src, len * 8, hipMemcpyDeviceToDevice, (hipStream_t)sc.stream()) != hipSuccess ||
             hipMemcpyAsync(p_w + dst, d_ow + src, len * 4, hipMemcpyDeviceToDevice, (hipStream_t)sc.stream()) != hipSuccess ||
-            hipMemcpyAsync(p_t + dst, d_ot + src, len * 4, hipMemcpyDeviceToDevice, (hipStream_t)sc.stream()) != hipSuccess) {
-          LogError("API_SAMPLE_NB: device copy failed");
-          return;
-        }
+            hipMemcpyAsync(p_t + dst, d_ot + src, len * 4, hipMemcpyDeviceToDevice, (hipStream_t)sc.stream()) != hipSuccess)
+          OP_FAIL(sc, "API_SAMPLE_NB: device copy failed");
         i = j;
       }
       if (!sc.Upload(d_idx, idx.data(), (size_t)n * 8)) OP_FAIL(sc, "API_SAMPLE_NB");
@@ -520,10 +572,10 @@ class GpuSampleNeighborOp : public OpKernel {
                                                      order_by, desc, limit, &cur)))
           OP_FAIL(sc, "API_SAMPLE_NB post process");
       }
-      std::vector<int32_t> pidx((size_t)n * 2);
-      std::vector<uint64_t> hid((size_t)cur);
-      std::vector<float> hw((size_t)cur);
-      std::vector<int32_t> ht((size_t)cur);
+      pidx.resize((size_t)n * 2);
+      hid.resize((size_t)cur);
+      hw.resize((size_t)cur);
+      ht.resize((size_t)cur);
       if (!sc.Download(pidx.data(), d_idx, (size_t)n * 8) || !sc.Download(hid.data(), p_id, (size_t)cur * 8) ||
           !sc.Download(hw.data(), p_w, (size_t)cur * 4) || !sc.Download(ht.data(), p_t, (size_t)cur * 4) ||
           !sc.Sync())
@@ -535,14 +587,13 @@ class GpuSampleNeighborOp : public OpKernel {
         if (pidx[2 * i + 1] == pidx[2 * i]) mask[i] = 1;
       out_total = 0;
       for (int64_t i = 0; i < n; ++i) out_total += mask[i] ? count : pidx[2 * i + 1] - pidx[2 * i];
-      Tensor *t_idx = nullptr, *oid = nullptr, *ow = nullptr, *ot = nullptr;
-      if (ctx->Allocate(OutputName(nd, 0), {(size_t)n, 2}, kInt32, &t_idx) != 0 ||
-          ctx->Allocate(OutputName(nd, 1), {(size_t)out_total}, kUInt64, &oid) != 0 ||
-          ctx->Allocate(OutputName(nd, 2), {(size_t)out_total}, kFloat, &ow) != 0 ||
-          ctx->Allocate(OutputName(nd, 3), {(size_t)out_total}, kInt32, &ot) != 0) {
-        LogError("Allocate output tensor failed!");
-        return;
-      }
+    }
+    Tensor* t_idx = outs.Add(0, {(size_t)n, 2}, kInt32);
+    Tensor* oid = outs.Add(1, {(size_t)out_total}, kUInt64);
+    Tensor* ow = outs.Add(2, {(size_t)out_total}, kFloat);
+    Tensor* ot = outs.Add(3, {(size_t)out_total}, kInt32);
+    if (!outs.ok()) return;
+    if (post && n > 0) {       // the rows are on the host already
       int64_t o = 0;
       for (int64_t i = 0; i < n; ++i) {
         t_idx->Raw<int32_t>()[2 * i] = (int32_t)o;
@@ -557,14 +608,7 @@ class GpuSampleNeighborOp : public OpKernel {
         }
         t_idx->Raw<int32_t>()[2 * i + 1] = (int32_t)o;
       }
-      return;
-    }
-    Tensor *t_idx = nullptr, *oid = nullptr, *ow = nullptr, *ot = nullptr;
-    if (ctx->Allocate(OutputName(nd, 0), {(size_t)n, 2}, kInt32, &t_idx) != 0 ||
-        ctx->Allocate(OutputName(nd, 1), {(size_t)total}, kUInt64, &oid) != 0 ||
-        ctx->Allocate(OutputName(nd, 2), {(size_t)total}, kFloat, &ow) != 0 ||
-        ctx->Allocate(OutputName(nd, 3), {(size_t)total}, kInt32, &ot) != 0) {
-      LogError("Allocate output tensor failed!");
+      outs.Commit();
       return;
     }
     // the copies first, the row offsets while they are in flight
@@ -575,11 +619,7 @@ class GpuSampleNeighborOp : public OpKernel {
       t_idx->Raw<int32_t>()[2 * i] = (int32_t)(i * count);
       t_idx->Raw<int32_t>()[2 * i + 1] = (int32_t)((i + 1) * count);
     }
-    if (!queued || !sc.Sync()) {
-      sc.Drain();            // a copy may still be writing into the tensors
-      for (int i = 0; i < 4; ++i) ctx->Deallocate(OutputName(nd, i));
-      OP_FAIL(sc, "API_SAMPLE_NB");
-    }
+    if (!queued || !outs.Finish()) OP_FAIL(sc, "API_SAMPLE_NB");
   }
 };
 REGISTER_OP_KERNEL("API_SAMPLE_NB", GpuSampleNeighborOp);
@@ -599,6 +639,7 @@ class GpuSampleNodeOp : public OpKernel {
     if (!g) { LogError("API_SAMPLE_NODE: no graph initialised"); return; }
     const int32_t count = cnt[0];
     OpScope sc(g);
+    OpOutputs outs(nd, ctx, &sc);
     uint64_t* d_out = sc.Alloc<uint64_t>((size_t)(count > 0 ? count : 0));
     if (!sc.ok()) OP_FAIL(sc, "API_SAMPLE_NODE");
     if (!sc.Call(euler_gpu_sample_node(g, sc.stream(), ctx->seed(), ctx->NextCallId(), types.data(),
@@ -606,15 +647,10 @@ class GpuSampleNodeOp : public OpKernel {
       LogError("Expect sample count: " + std::to_string(count) + ", real got:0 (" + sc.error() + ")");
       return;
     }
-    Tensor* out = nullptr;
-    if (ctx->Allocate(OutputName(nd, 0), {(size_t)count}, kInt64, &out) != 0) {
-      LogError("Allocate output tensor failed!");
-      return;
-    }
-    if (!sc.Download(out->Raw<int64_t>(), d_out, (size_t)count * 8) || !sc.Sync()) {
-      ctx->Deallocate(OutputName(nd, 0));
+    Tensor* out = outs.Add(0, {(size_t)count}, kInt64);
+    if (out == nullptr) return;
+    if (!sc.Download(out->Raw<int64_t>(), d_out, (size_t)count * 8) || !outs.Finish())
       OP_FAIL(sc, "API_SAMPLE_NODE");
-    }
   }
 };
 REGISTER_OP_KERNEL("API_SAMPLE_NODE", GpuSampleNodeOp);
@@ -634,25 +670,18 @@ class GpuSampleEdgeOp : public OpKernel {
     if (!g) { LogError("API_SAMPLE_EDGE: no graph initialised"); return; }
     const int32_t count = cnt[0];
     OpScope sc(g);
+    OpOutputs outs(nd, ctx, &sc);
     int64_t* d_out = sc.Alloc<int64_t>((size_t)(count > 0 ? count : 0) * 3);
     if (!sc.ok()) OP_FAIL(sc, "API_SAMPLE_EDGE");
     if (!sc.Call(euler_gpu_sample_edge(g, sc.stream(), ctx->seed(), ctx->NextCallId(), types.data(),
                                        (int32_t)types.size(), count, d_out))) {
-      sc.Drain();
       LogError("Expect sample count: " + std::to_string(count) + ", real got:0 (" + sc.error() + ")");
       return;
     }
-    Tensor* out = nullptr;
-    if (ctx->Allocate(OutputName(nd, 0), {(size_t)count, 3}, kInt64, &out) != 0) {
-      sc.Drain();
-      LogError("Allocate output tensor failed!");
-      return;
-    }
-    if (!sc.Download(out->Raw<int64_t>(), d_out, (size_t)count * 24) || !sc.Sync()) {
-      sc.Drain();            // a copy may still be writing into the tensor
-      ctx->Deallocate(OutputName(nd, 0));
+    Tensor* out = outs.Add(0, {(size_t)count, 3}, kInt64);
+    if (out == nullptr) return;
+    if (!sc.Download(out->Raw<int64_t>(), d_out, (size_t)count * 24) || !outs.Finish())
       OP_FAIL(sc, "API_SAMPLE_EDGE");
-    }
   }
 };
 REGISTER_OP_KERNEL("API_SAMPLE_EDGE", GpuSampleEdgeOp);
@@ -689,14 +718,9 @@ class GpuSampleGraphLabelOp : public OpKernel {
       int64_t* d_out = sc.Alloc<int64_t>((size_t)(count > 0 ? count : 1));
       if (!sc.ok()) OP_FAIL(sc, "API_SAMPLE_GRAPH_LABEL");
       if (!sc.Call(euler_gpu_sample_graph_label(g, sc.stream(), ctx->seed(), ctx->NextCallId(), count,
-                                                d_out))) {
-        sc.Drain();
+                                                d_out)))
         OP_FAIL(sc, "API_SAMPLE_GRAPH_LABEL");
-      }
-      if (!sc.Download(ids.data(), d_out, (size_t)count * 8) || !sc.Sync()) {
-        sc.Drain();
-        OP_FAIL(sc, "API_SAMPLE_GRAPH_LABEL");
-      }
+      if (!sc.Download(ids.data(), d_out, (size_t)count * 8) || !sc.Sync()) OP_FAIL(sc, "API_SAMPLE_GRAPH_LABEL");
     }
     std::string joined;
     for (int32_t i = 0; i < count; ++i) {
@@ -704,19 +728,18 @@ class GpuSampleGraphLabelOp : public OpKernel {
       const int64_t r = ids[i];
       joined.append(reinterpret_cast<const char*>(bytes.data()) + off[r], (size_t)(off[r + 1] - off[r]));
     }
-    Tensor* out = nullptr;
-    if (ctx->Allocate(OutputName(nd, 0), {joined.size()}, kInt8, &out) != 0) {
-      LogError("Allocate output tensor failed!");
-      return;
-    }
+    OpOutputs outs(nd, ctx);
+    Tensor* out = outs.Add(0, {joined.size()}, kInt8);
+    if (out == nullptr) return;
     std::copy(joined.begin(), joined.end(), out->Raw<char>());
+    outs.Commit();
   }
 };
 REGISTER_OP_KERNEL("API_SAMPLE_GRAPH_LABEL", GpuSampleGraphLabelOp);
 
 // API_GET_GRAPH_BY_LABEL (core/kernels/get_graph_by_label_op.cc:32-75): input a kString tensor of
 // labels; outputs "<name>:0" int32 [B, 2] (start, end) and "<name>:1" uint64 node ids.  An unknown
-// label is an empty range.  Any failure drains the stream and leaves no output.
+// label is an empty range.
 class GpuGetGraphByLabelOp : public OpKernel {
  public:
   explicit GpuGetGraphByLabelOp(const std::string& name) : OpKernel(name) {}
@@ -748,35 +771,24 @@ class GpuGetGraphByLabelOp : public OpKernel {
       int32_t* d_idx = sc.Alloc<int32_t>((size_t)B * 2);
       int64_t total = 0;
       if (!sc.Upload(d_ids, ids.data(), (size_t)B * 8) ||
-          !sc.Call(euler_gpu_get_graph_by_label(g, sc.stream(), d_ids, B, d_idx, &total, nullptr))) {
-        sc.Drain();
+          !sc.Call(euler_gpu_get_graph_by_label(g, sc.stream(), d_ids, B, d_idx, &total, nullptr)))
         OP_FAIL(sc, "API_GET_GRAPH_BY_LABEL");
-      }
       uint64_t* d_v = sc.Alloc<uint64_t>((size_t)(total > 0 ? total : 1));
       if (!sc.ok() || (total > 0 && !sc.Call(euler_gpu_get_graph_by_label(g, sc.stream(), d_ids, B, d_idx,
-                                                                         &total, d_v)))) {
-        sc.Drain();
+                                                                         &total, d_v))))
         OP_FAIL(sc, "API_GET_GRAPH_BY_LABEL");
-      }
       vals.resize((size_t)total);
       if (!sc.Download(idx.data(), d_idx, (size_t)B * 8) ||
-          (total > 0 && !sc.Download(vals.data(), d_v, (size_t)total * 8)) || !sc.Sync()) {
-        sc.Drain();
+          (total > 0 && !sc.Download(vals.data(), d_v, (size_t)total * 8)) || !sc.Sync())
         OP_FAIL(sc, "API_GET_GRAPH_BY_LABEL");
-      }
     }
-    Tensor *o_idx = nullptr, *o_data = nullptr;
-    if (ctx->Allocate(OutputName(nd, 0), {(size_t)B, 2}, kInt32, &o_idx) != 0) {
-      LogError("Allocate output tensor failed!");
-      return;
-    }
-    if (ctx->Allocate(OutputName(nd, 1), {vals.size()}, kUInt64, &o_data) != 0) {
-      ctx->Deallocate(OutputName(nd, 0));
-      LogError("Allocate output tensor failed!");
-      return;
-    }
+    OpOutputs outs(nd, ctx);
+    Tensor* o_idx = outs.Add(0, {(size_t)B, 2}, kInt32);
+    Tensor* o_data = outs.Add(1, {vals.size()}, kUInt64);
+    if (!outs.ok()) return;
     std::copy(idx.begin(), idx.end(), o_idx->Raw<int32_t>());
     std::copy(vals.begin(), vals.end(), o_data->Raw<uint64_t>());
+    outs.Commit();
   }
 };
 REGISTER_OP_KERNEL("API_GET_GRAPH_BY_LABEL", GpuGetGraphByLabelOp);
@@ -790,23 +802,19 @@ class GpuIdUniqueOp : public OpKernel {
     if (nd.inputs.empty() || ctx->tensor(nd.inputs[0], &ids_t) != 0) { LogError("ID_UNIQUE: missing input"); return; }
     const int64_t n = ids_t->NumElements();
     OpScope sc(ctx->graph());
+    OpOutputs outs(nd, ctx, &sc);
     uint64_t* d_ids = sc.Alloc<uint64_t>(n);
     uint64_t* d_uq = sc.Alloc<uint64_t>(n);
     int32_t* d_gi = sc.Alloc<int32_t>(n);
     if (!sc.Upload(d_ids, ids_t->Raw<uint64_t>(), (size_t)n * 8)) OP_FAIL(sc, "ID_UNIQUE");
     int64_t nu = 0;
     if (!sc.Call(euler_gpu_id_unique(sc.stream(), d_ids, n, d_uq, d_gi, &nu))) OP_FAIL(sc, "ID_UNIQUE");
-    Tensor *uq = nullptr, *gi = nullptr;
-    if (ctx->Allocate(OutputName(nd, 0), {(size_t)nu}, kUInt64, &uq) != 0 ||
-        ctx->Allocate(OutputName(nd, 1), {(size_t)n}, kInt32, &gi) != 0) {
-      LogError("ID_UNIQUE: allocate failed");
-      return;
-    }
+    Tensor* uq = outs.Add(0, {(size_t)nu}, kUInt64);
+    Tensor* gi = outs.Add(1, {(size_t)n}, kInt32);
+    if (!outs.ok()) return;
     if (!sc.Download(uq->Raw<uint64_t>(), d_uq, (size_t)nu * 8) ||
-        !sc.Download(gi->Raw<int32_t>(), d_gi, (size_t)n * 4) || !sc.Sync()) {
-      ctx->Deallocate(OutputName(nd, 0)); ctx->Deallocate(OutputName(nd, 1));
+        !sc.Download(gi->Raw<int32_t>(), d_gi, (size_t)n * 4) || !outs.Finish())
       OP_FAIL(sc, "ID_UNIQUE");
-    }
   }
 };
 REGISTER_OP_KERNEL("ID_UNIQUE", GpuIdUniqueOp);
@@ -821,6 +829,7 @@ class GpuIdxGatherOp : public OpKernel {
         ctx->tensor(nd.inputs[1], &gi_t) != 0) { LogError("IDX_GATHER: missing input"); return; }
     const int64_t n = gi_t->NumElements();
     OpScope sc(ctx->graph());
+    OpOutputs outs(nd, ctx, &sc);
     int32_t* d_idx = (int32_t*)sc.AllocBytes(idx_t->TotalBytes());
     int32_t* d_gi = sc.Alloc<int32_t>(n);
     int32_t* d_out = sc.Alloc<int32_t>(n * 2);
@@ -828,12 +837,9 @@ class GpuIdxGatherOp : public OpKernel {
         !sc.Upload(d_gi, gi_t->Raw<int32_t>(), (size_t)n * 4)) OP_FAIL(sc, "IDX_GATHER");
     int64_t total = 0;
     if (!sc.Call(euler_gpu_idx_gather(sc.stream(), d_idx, d_gi, n, d_out, &total))) OP_FAIL(sc, "IDX_GATHER");
-    Tensor* out = nullptr;
-    if (ctx->Allocate(OutputName(nd, 0), {(size_t)n, 2}, kInt32, &out) != 0) return;
-    if (!sc.Download(out->Raw<int32_t>(), d_out, (size_t)n * 8) || !sc.Sync()) {
-      ctx->Deallocate(OutputName(nd, 0));
-      OP_FAIL(sc, "IDX_GATHER");
-    }
+    Tensor* out = outs.Add(0, {(size_t)n, 2}, kInt32);
+    if (out == nullptr) return;
+    if (!sc.Download(out->Raw<int32_t>(), d_out, (size_t)n * 8) || !outs.Finish()) OP_FAIL(sc, "IDX_GATHER");
   }
 };
 REGISTER_OP_KERNEL("IDX_GATHER", GpuIdxGatherOp);
@@ -855,6 +861,7 @@ class GpuDataGatherOp : public OpKernel {
     const int64_t n = gi_t->NumElements();
     const int32_t es = (int32_t)SizeOfType(type);
     OpScope sc(ctx->graph());
+    OpOutputs outs(nd, ctx, &sc);
     void* d_data = sc.AllocBytes(data_t->TotalBytes());
     int32_t* d_idx = (int32_t*)sc.AllocBytes(idx_t->TotalBytes());
     int32_t* d_gi = sc.Alloc<int32_t>(n);
@@ -868,12 +875,9 @@ class GpuDataGatherOp : public OpKernel {
     if (!sc.ok()) OP_FAIL(sc, "DATA_GATHER");
     if (!sc.Call(euler_gpu_data_gather(sc.stream(), d_data, es, d_idx, d_gi, d_oidx, n, d_out)))
       OP_FAIL(sc, "DATA_GATHER");
-    Tensor* out = nullptr;
-    if (ctx->Allocate(OutputName(nd, 0), {(size_t)total}, type, &out) != 0) return;
-    if (!sc.Download(out->Raw<char>(), d_out, (size_t)total * es) || !sc.Sync()) {
-      ctx->Deallocate(OutputName(nd, 0));
-      OP_FAIL(sc, "DATA_GATHER");
-    }
+    Tensor* out = outs.Add(0, {(size_t)total}, type);
+    if (out == nullptr) return;
+    if (!sc.Download(out->Raw<char>(), d_out, (size_t)total * es) || !outs.Finish()) OP_FAIL(sc, "DATA_GATHER");
   }
 };
 REGISTER_OP_KERNEL("DATA_GATHER", GpuDataGatherOp);
@@ -892,6 +896,7 @@ class GpuGetNeighborOp : public OpKernel {
     if (!g) { LogError("API_GET_NB_NODE: no graph initialised"); return; }
     const int64_t n = ids_t->NumElements();
     OpScope sc(g);
+    OpOutputs outs(nd, ctx, &sc);
     uint64_t* d_ids = sc.Alloc<uint64_t>(n);
     int32_t* d_idx = sc.Alloc<int32_t>(n * 2);
     if (!sc.Upload(d_ids, ids_t->Raw<uint64_t>(), (size_t)n * 8)) OP_FAIL(sc, "API_GET_NB_NODE");
@@ -914,21 +919,16 @@ class GpuGetNeighborOp : public OpKernel {
                                                    order_by, desc, limit, &total)))
         OP_FAIL(sc, "API_GET_NB_NODE post process");
     }
-    Tensor *idx = nullptr, *oid = nullptr, *ow = nullptr, *ot = nullptr;
-    if (ctx->Allocate(OutputName(nd, 0), {(size_t)n, 2}, kInt32, &idx) != 0 ||
-        ctx->Allocate(OutputName(nd, 1), {(size_t)total}, kUInt64, &oid) != 0 ||
-        ctx->Allocate(OutputName(nd, 2), {(size_t)total}, kFloat, &ow) != 0 ||
-        ctx->Allocate(OutputName(nd, 3), {(size_t)total}, kInt32, &ot) != 0) {
-      LogError("Allocate output tensor failed!");
-      return;
-    }
+    Tensor* idx = outs.Add(0, {(size_t)n, 2}, kInt32);
+    Tensor* oid = outs.Add(1, {(size_t)total}, kUInt64);
+    Tensor* ow = outs.Add(2, {(size_t)total}, kFloat);
+    Tensor* ot = outs.Add(3, {(size_t)total}, kInt32);
+    if (!outs.ok()) return;
     if (!sc.Download(idx->Raw<int32_t>(), d_idx, (size_t)n * 8) ||
         !sc.Download(oid->Raw<uint64_t>(), d_oid, (size_t)total * 8) ||
         !sc.Download(ow->Raw<float>(), d_ow, (size_t)total * 4) ||
-        !sc.Download(ot->Raw<int32_t>(), d_ot, (size_t)total * 4) || !sc.Sync()) {
-      for (int i = 0; i < 4; ++i) ctx->Deallocate(OutputName(nd, i));
+        !sc.Download(ot->Raw<int32_t>(), d_ot, (size_t)total * 4) || !outs.Finish())
       OP_FAIL(sc, "API_GET_NB_NODE");
-    }
   }
 };
 REGISTER_OP_KERNEL("API_GET_NB_NODE", GpuGetNeighborOp);
@@ -953,22 +953,17 @@ class GpuGetEdgeSumWeightOp : public OpKernel {
     if (!g) { LogError("API_GET_EDGE_SUM_WEIGHT: no graph initialised"); return; }
     const int64_t n = root_t->NumElements();
     OpScope sc(g);
+    OpOutputs outs(nd, ctx, &sc);
     uint64_t* d_ids = sc.Alloc<uint64_t>(n);
     float* d_w = sc.Alloc<float>(n);
     if (!sc.Upload(d_ids, root_t->Raw<uint64_t>(), (size_t)n * 8)) OP_FAIL(sc, "API_GET_EDGE_SUM_WEIGHT");
     if (!sc.Call(euler_gpu_get_edge_sum_weight(g, sc.stream(), d_ids, n, et.data(), (int32_t)et.size(), d_w)))
       OP_FAIL(sc, "API_GET_EDGE_SUM_WEIGHT");
-    Tensor *o_root = nullptr, *o_w = nullptr;
-    if (ctx->Allocate(OutputName(nd, 0), {(size_t)n, 1}, kUInt64, &o_root) != 0 ||
-        ctx->Allocate(OutputName(nd, 1), {(size_t)n, 1}, kFloat, &o_w) != 0) {
-      LogError("Allocate output tensor failed!");
-      return;
-    }
+    Tensor* o_root = outs.Add(0, {(size_t)n, 1}, kUInt64);
+    Tensor* o_w = outs.Add(1, {(size_t)n, 1}, kFloat);
+    if (!outs.ok()) return;
     memcpy(o_root->Raw<uint64_t>(), root_t->Raw<uint64_t>(), (size_t)n * 8);
-    if (!sc.Download(o_w->Raw<float>(), d_w, (size_t)n * 4) || !sc.Sync()) {
-      ctx->Deallocate(OutputName(nd, 0)); ctx->Deallocate(OutputName(nd, 1));
-      OP_FAIL(sc, "API_GET_EDGE_SUM_WEIGHT");
-    }
+    if (!sc.Download(o_w->Raw<float>(), d_w, (size_t)n * 4) || !outs.Finish()) OP_FAIL(sc, "API_GET_EDGE_SUM_WEIGHT");
   }
 };
 REGISTER_OP_KERNEL("API_GET_EDGE_SUM_WEIGHT", GpuGetEdgeSumWeightOp);
@@ -993,6 +988,7 @@ class GpuSampleRootOp : public OpKernel {
     if (batch == 0) { LogError("batch size is zero!"); abort(); }   // EULER_LOG(FATAL)
     const int64_t cells = batch * n, draws = batch * m;
     OpScope sc(ctx->graph());
+    OpOutputs outs(nd, ctx, &sc);
     uint64_t* d_r = sc.Alloc<uint64_t>(cells);
     float* d_w = sc.Alloc<float>(cells);
     uint64_t* d_o = sc.Alloc<uint64_t>(draws);
@@ -1001,15 +997,9 @@ class GpuSampleRootOp : public OpKernel {
     if (!sc.Call(euler_gpu_sample_root(sc.stream(), ctx->seed(), ctx->NextCallId(), d_r, d_w, batch, n, m,
                                        default_node, d_o)))
       OP_FAIL(sc, "API_SAMPLE_ROOT");
-    Tensor* out = nullptr;
-    if (ctx->Allocate(OutputName(nd, 0), {(size_t)draws}, kUInt64, &out) != 0) {
-      LogError("Allocate output tensor failed!");
-      return;
-    }
-    if (!sc.Download(out->Raw<uint64_t>(), d_o, (size_t)draws * 8) || !sc.Sync()) {
-      ctx->Deallocate(OutputName(nd, 0));
-      OP_FAIL(sc, "API_SAMPLE_ROOT");
-    }
+    Tensor* out = outs.Add(0, {(size_t)draws}, kUInt64);
+    if (out == nullptr) return;
+    if (!sc.Download(out->Raw<uint64_t>(), d_o, (size_t)draws * 8) || !outs.Finish()) OP_FAIL(sc, "API_SAMPLE_ROOT");
   }
 };
 REGISTER_OP_KERNEL("API_SAMPLE_ROOT", GpuSampleRootOp);
@@ -1030,6 +1020,7 @@ class GpuSampleLayerOp : public OpKernel {
     if (!g) { LogError("API_SAMPLE_L: no graph initialised"); return; }
     const int64_t n = root_t->NumElements();
     OpScope sc(g);
+    OpOutputs outs(nd, ctx, &sc);
     uint64_t* d_r = sc.Alloc<uint64_t>(n);
     uint64_t* d_id = sc.Alloc<uint64_t>(n);
     float* d_w = sc.Alloc<float>(n);
@@ -1038,19 +1029,14 @@ class GpuSampleLayerOp : public OpKernel {
     if (!sc.Call(euler_gpu_sample_layer(g, sc.stream(), ctx->seed(), ctx->NextCallId(), d_r, n, et.data(),
                                         (int32_t)et.size(), default_node, d_id, d_w, d_t)))
       OP_FAIL(sc, "API_SAMPLE_L");
-    Tensor *o_nb = nullptr, *o_w = nullptr, *o_t = nullptr;
-    if (ctx->Allocate(OutputName(nd, 0), {(size_t)n, 1}, kUInt64, &o_nb) != 0 ||
-        ctx->Allocate(OutputName(nd, 1), {(size_t)n, 1}, kFloat, &o_w) != 0 ||
-        ctx->Allocate(OutputName(nd, 2), {(size_t)n, 1}, kInt32, &o_t) != 0) {
-      LogError("Allocate output tensor failed!");
-      return;
-    }
+    Tensor* o_nb = outs.Add(0, {(size_t)n, 1}, kUInt64);
+    Tensor* o_w = outs.Add(1, {(size_t)n, 1}, kFloat);
+    Tensor* o_t = outs.Add(2, {(size_t)n, 1}, kInt32);
+    if (!outs.ok()) return;
     if (!sc.Download(o_nb->Raw<uint64_t>(), d_id, (size_t)n * 8) ||
         !sc.Download(o_w->Raw<float>(), d_w, (size_t)n * 4) ||
-        !sc.Download(o_t->Raw<int32_t>(), d_t, (size_t)n * 4) || !sc.Sync()) {
-      for (int i = 0; i < 3; ++i) ctx->Deallocate(OutputName(nd, i));
+        !sc.Download(o_t->Raw<int32_t>(), d_t, (size_t)n * 4) || !outs.Finish())
       OP_FAIL(sc, "API_SAMPLE_L");
-    }
   }
 };
 REGISTER_OP_KERNEL("API_SAMPLE_L", GpuSampleLayerOp);
@@ -1078,6 +1064,7 @@ class GpuLocalSampleLayerOp : public OpKernel {
     const int64_t batch = idx_t->NumElements() / (n * 2);
     const int64_t total = id_t->NumElements(), draws = batch * m;
     OpScope sc(ctx->graph());
+    OpOutputs outs(nd, ctx, &sc);
     int32_t* d_idx = sc.Alloc<int32_t>(idx_t->NumElements());
     uint64_t* d_id = sc.Alloc<uint64_t>(total);
     float* d_w = sc.Alloc<float>(total);
@@ -1093,19 +1080,14 @@ class GpuLocalSampleLayerOp : public OpKernel {
                                               d_t, total, batch, n, m, weight_func.c_str(),
                                               default_node, o_id, o_w, o_t)))
       OP_FAIL(sc, "API_LOCAL_SAMPLE_L");
-    Tensor *r_id = nullptr, *r_w = nullptr, *r_t = nullptr;
-    if (ctx->Allocate(OutputName(nd, 0), {(size_t)draws, 1}, kUInt64, &r_id) != 0 ||
-        ctx->Allocate(OutputName(nd, 1), {(size_t)draws, 1}, kFloat, &r_w) != 0 ||
-        ctx->Allocate(OutputName(nd, 2), {(size_t)draws, 1}, kInt32, &r_t) != 0) {
-      LogError("Allocate output tensor failed!");
-      return;
-    }
+    Tensor* r_id = outs.Add(0, {(size_t)draws, 1}, kUInt64);
+    Tensor* r_w = outs.Add(1, {(size_t)draws, 1}, kFloat);
+    Tensor* r_t = outs.Add(2, {(size_t)draws, 1}, kInt32);
+    if (!outs.ok()) return;
     if (!sc.Download(r_id->Raw<uint64_t>(), o_id, (size_t)draws * 8) ||
         !sc.Download(r_w->Raw<float>(), o_w, (size_t)draws * 4) ||
-        !sc.Download(r_t->Raw<int32_t>(), o_t, (size_t)draws * 4) || !sc.Sync()) {
-      for (int i = 0; i < 3; ++i) ctx->Deallocate(OutputName(nd, i));
+        !sc.Download(r_t->Raw<int32_t>(), o_t, (size_t)draws * 4) || !outs.Finish())
       OP_FAIL(sc, "API_LOCAL_SAMPLE_L");
-    }
   }
 };
 REGISTER_OP_KERNEL("API_LOCAL_SAMPLE_L", GpuLocalSampleLayerOp);
@@ -1124,18 +1106,17 @@ class SparseGenAdjOp : public OpKernel {
     const int32_t n = n_v[0];
     const int32_t batch = roots_t->NumElements() / n;
     if (batch == 0) { LogError("batch size is zero!"); abort(); }
-    Tensor* rb = nullptr;
-    if (ctx->Allocate(OutputName(nd, 0), {(size_t)roots_t->NumElements(), 2}, kUInt64, &rb) != 0) {
-      LogError("Allocate output tensor failed!");
-      return;
-    }
+    OpOutputs outs(nd, ctx);
+    Tensor* rb = outs.Add(0, {(size_t)roots_t->NumElements(), 2}, kUInt64);
+    if (rb == nullptr) return;
     for (int32_t i = 0; i < batch; ++i)
       for (int32_t j = 0; j < n; ++j) {
         const int32_t cnt = i * n + j;
         rb->Raw<uint64_t>()[cnt * 2] = roots_t->Raw<uint64_t>()[cnt];
         rb->Raw<uint64_t>()[cnt * 2 + 1] = (uint64_t)i;
       }
-    ctx->AddAlias(OutputName(nd, 1), l_nb_t);
+    outs.Alias(1, l_nb_t);
+    outs.Commit();
   }
 };
 REGISTER_OP_KERNEL("API_SPARSE_GEN_ADJ", SparseGenAdjOp);
@@ -1197,14 +1178,13 @@ class GpuSparseGetAdjOp : public OpKernel {
           (total && !sc.Download(vals.data(), d_v, (size_t)total * 8)) || !sc.Sync())
         OP_FAIL(sc, "API_SPARSE_GET_ADJ");
     }
-    Tensor *o_idx = nullptr, *o_data = nullptr;
-    if (ctx->Allocate(OutputName(nd, 0), {(size_t)R, 2}, kInt32, &o_idx) != 0 ||
-        ctx->Allocate(OutputName(nd, 1), {(size_t)total}, kUInt64, &o_data) != 0) {
-      LogError("Allocate output tensor failed!");
-      return;
-    }
+    OpOutputs outs(nd, ctx);
+    Tensor* o_idx = outs.Add(0, {(size_t)R, 2}, kInt32);
+    Tensor* o_data = outs.Add(1, {(size_t)total}, kUInt64);
+    if (!outs.ok()) return;
     if (R) memcpy(o_idx->Raw<int32_t>(), idx.data(), (size_t)R * 8);
     if (total) memcpy(o_data->Raw<uint64_t>(), vals.data(), (size_t)total * 8);
+    outs.Commit();
   }
 };
 REGISTER_OP_KERNEL("API_SPARSE_GET_ADJ", GpuSparseGetAdjOp);
@@ -1214,20 +1194,60 @@ class GatherResultOp : public OpKernel {
  public:
   explicit GatherResultOp(const std::string& name) : OpKernel(name) {}
   void Compute(const NodeDef& nd, OpKernelContext* ctx) override {
+    OpOutputs outs(nd, ctx);
     for (int i = 0; i < 3; ++i) {
       Tensor* t = nullptr;
       if ((int)nd.inputs.size() <= i || ctx->tensor(nd.inputs[i], &t) != 0) {
         LogError("API_GATHER_RESULT: missing input");
         return;
       }
-      ctx->AddAlias(OutputName(nd, i), t);
+      if (!outs.Alias(i, t)) return;
     }
+    outs.Commit();
   }
 };
 REGISTER_OP_KERNEL("API_GATHER_RESULT", GatherResultOp);
 
 }  // namespace gpu_abi
 }  // namespace euler
+
+namespace {
+
+// the ';'-separated post-process strings of the C harnesses -> DAGNodeProto.post_process
+std::vector<std::string> SplitPostProcess(const char* post_process) {
+  std::vector<std::string> out;
+  std::string cur;
+  for (const char* p = post_process ? post_process : ""; ; ++p) {
+    if (*p == ';' || *p == 0) {
+      if (!cur.empty()) out.push_back(cur);
+      cur.clear();
+      if (*p == 0) break;
+    } else {
+      cur.push_back(*p);
+    }
+  }
+  return out;
+}
+
+// Copies the four neighbour outputs of `nd` (idx, ids, weights, types) out of the context: the
+// number of neighbours, -2 when the op logged an error and produced no output, -3 when they
+// exceed `capacity`.
+int64_t CopyNeighborOutputs(euler::OpKernelContext* ctx, const euler::NodeDef& nd, int64_t capacity,
+                            int32_t* idx_out, uint64_t* id_out, float* w_out, int32_t* t_out) {
+  using namespace euler;
+  Tensor *idx = nullptr, *oid = nullptr, *ow = nullptr, *ot = nullptr;
+  if (ctx->tensor(OutputName(nd, 0), &idx) != 0 || ctx->tensor(OutputName(nd, 1), &oid) != 0 ||
+      ctx->tensor(OutputName(nd, 2), &ow) != 0 || ctx->tensor(OutputName(nd, 3), &ot) != 0)
+    return -2;
+  if (oid->NumElements() > capacity) return -3;
+  memcpy(idx_out, idx->Raw<int32_t>(), idx->TotalBytes());
+  memcpy(id_out, oid->Raw<uint64_t>(), oid->TotalBytes());
+  memcpy(w_out, ow->Raw<float>(), ow->TotalBytes());
+  memcpy(t_out, ot->Raw<int32_t>(), ot->TotalBytes());
+  return oid->NumElements();
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -1265,31 +1285,12 @@ int64_t euler_op_run_sample_nb_post(euler_gpu_graph* g, uint64_t seed, uint32_t 
   *t_cnt->Raw<int32_t>() = count;
   *t_def->Raw<int32_t>() = -1;
   NodeDef nd{"API_SAMPLE_NB,0", "API_SAMPLE_NB",
-             {"nodes", "edge_types", "nb_count", "default_node"}, {}};
-  {
-    std::string cur;
-    for (const char* p = post_process ? post_process : ""; ; ++p) {
-      if (*p == ';' || *p == 0) {
-        if (!cur.empty()) nd.post_process.push_back(cur);
-        cur.clear();
-        if (*p == 0) break;
-      } else {
-        cur.push_back(*p);
-      }
-    }
-  }
+             {"nodes", "edge_types", "nb_count", "default_node"}, SplitPostProcess(post_process)};
   OpKernel* kernel = nullptr;
   if (CreateOpKernel("API_SAMPLE_NB", &kernel) != 0) return -1;
   kernel->Compute(nd, &ctx);
-  Tensor *idx = nullptr, *oid = nullptr, *ow = nullptr, *ot = nullptr;
-  if (ctx.tensor(OutputName(nd, 0), &idx) != 0 || ctx.tensor(OutputName(nd, 1), &oid) != 0 ||
-      ctx.tensor(OutputName(nd, 2), &ow) != 0 || ctx.tensor(OutputName(nd, 3), &ot) != 0)
-    return -2;   // op logged an error and produced no output
-  memcpy(idx_out, idx->Raw<int32_t>(), idx->TotalBytes());
-  memcpy(id_out, oid->Raw<uint64_t>(), oid->TotalBytes());
-  memcpy(w_out, ow->Raw<float>(), ow->TotalBytes());
-  memcpy(t_out, ot->Raw<int32_t>(), ot->TotalBytes());
-  return oid->NumElements();
+  // (the caller's buffers have room for n * count entries, and no row grows)
+  return CopyNeighborOutputs(&ctx, nd, n * (int64_t)count, idx_out, id_out, w_out, t_out);
 }
 
 // Runs the registered API_GET_NB_NODE kernel (with its post-process strings,
@@ -1308,30 +1309,11 @@ int64_t euler_op_run_get_nb(euler_gpu_graph* g, const uint64_t* node_ids, int64_
   ctx.Allocate("edge_types", {(size_t)k}, kInt32, &t_et);
   memcpy(t_ids->Raw<uint64_t>(), node_ids, (size_t)n * 8);
   if (k) memcpy(t_et->Raw<int32_t>(), edge_types, (size_t)k * 4);
-  NodeDef nd{"API_GET_NB_NODE,0", "API_GET_NB_NODE", {"nodes", "edge_types"}, {}};
-  std::string cur;
-  for (const char* p = post_process ? post_process : ""; ; ++p) {
-    if (*p == ';' || *p == 0) {
-      if (!cur.empty()) nd.post_process.push_back(cur);
-      cur.clear();
-      if (*p == 0) break;
-    } else {
-      cur.push_back(*p);
-    }
-  }
+  NodeDef nd{"API_GET_NB_NODE,0", "API_GET_NB_NODE", {"nodes", "edge_types"}, SplitPostProcess(post_process)};
   OpKernel* kernel = nullptr;
   if (CreateOpKernel("API_GET_NB_NODE", &kernel) != 0) return -1;
   kernel->Compute(nd, &ctx);
-  Tensor *idx = nullptr, *oid = nullptr, *ow = nullptr, *ot = nullptr;
-  if (ctx.tensor(OutputName(nd, 0), &idx) != 0 || ctx.tensor(OutputName(nd, 1), &oid) != 0 ||
-      ctx.tensor(OutputName(nd, 2), &ow) != 0 || ctx.tensor(OutputName(nd, 3), &ot) != 0)
-    return -2;
-  if (oid->NumElements() > capacity) return -3;
-  memcpy(idx_out, idx->Raw<int32_t>(), idx->TotalBytes());
-  memcpy(id_out, oid->Raw<uint64_t>(), oid->TotalBytes());
-  memcpy(w_out, ow->Raw<float>(), ow->TotalBytes());
-  memcpy(t_out, ot->Raw<int32_t>(), ot->TotalBytes());
-  return oid->NumElements();
+  return CopyNeighborOutputs(&ctx, nd, capacity, idx_out, id_out, w_out, t_out);
 }
 
 // Runs the DAG the reference's translator builds for
