@@ -783,6 +783,171 @@ def edge_softmax(logits, indices=None, size=None, seg_ptr=None, count=None, out_
     return _EdgeSoftmax.apply(logits, si, sp, 0 if count is None else count, int(size), od)
 
 
+# ---- per-relation aggregation (RGCN) ----------------------------------------------------------
+_REL_MODE = {"add": 0, "max": 1, "mean": 2, "mean_rel": 3}
+
+
+def _relation_reduce_raw(mode, params, gi, as_ids, et, num_relations, si, sp, count, size, od, want_counts):
+    """euler_gpu_relation_reduce on prepared tensors -> (out [size, R, D], counts [size, R] or None)"""
+    e, d = et.numel(), params.shape[1]
+    out = torch.empty((size, num_relations, d), dtype=od, device=params.device)
+    counts = None
+    if want_counts:     # (d == 0: the entry touches nothing)
+        counts = (torch.zeros if d == 0 else torch.empty)((size, num_relations), dtype=torch.int32,
+                                                          device=params.device)
+    with _on(params.device):
+        check(lib().euler_gpu_relation_reduce(
+            _stream(), mode, _ptr(params), _DT[params.dtype], int(params.shape[0]), _ptr(gi), int(as_ids),
+            _ptr(et), num_relations, _ptr(si), _ptr(sp), int(count), e, d, size, _ptr(out), _DT[od],
+            _ptr(counts)))
+    return out, counts
+
+
+class _RelationReduce(torch.autograd.Function):
+    """out[r, t] = reduce(op) of params[gi[p]] over the valid updates of destination r with
+    relation t (euler_gpu_relation_reduce).  The gradient is that of the composition
+    gather_scatter(op, params, gi, dst * R + t, size * R), built from the same ops."""
+
+    @staticmethod
+    def forward(ctx, params, gi, as_ids, et, num_relations, si, sp, count, size, op, od, want_counts):
+        need_grad = ctx.needs_input_grad[0]
+        mean = op in ("mean", "mean_rel")
+        out, counts = _relation_reduce_raw(_REL_MODE[op], params, gi, as_ids, et, num_relations, si, sp, count,
+                                           size, od, want_counts or (mean and need_grad))
+        if need_grad:
+            if gi is None:
+                gi = torch.arange(et.numel(), dtype=torch.int32, device=params.device)
+            elif as_ids:
+                # the clamp-to-last-row rule of the forward kernel for the saved indices
+                # (_GatherSegmentReduce.forward)
+                gi = torch.clamp(gi & 0xFFFFFFFF, max=int(params.shape[0]) - 1).to(torch.int32)
+            none = torch.empty(0)
+            ctx.save_for_backward(params, gi, et, si if si is not None else none, sp if sp is not None else none,
+                                  counts if mean else none, out if op == "max" else none)
+        ctx.form = "indices" if si is not None else "seg_ptr" if sp is not None else "count"
+        ctx.count, ctx.size, ctx.R, ctx.op = count, size, num_relations, op
+        if not want_counts:
+            return out
+        ctx.mark_non_differentiable(counts)
+        return out, counts
+
+    @staticmethod
+    def backward(ctx, grad, *unused):
+        params, gi, et, si, sp, counts, out = ctx.saved_tensors
+        size, R, op = ctx.size, ctx.R, ctx.op
+        e, d = et.numel(), params.shape[1]
+        dev = grad.device
+        # 1. the scatter key of the composition: bucket dst * R + t, -1 for an update of no bucket
+        if ctx.form == "indices":
+            dst = si.to(torch.int64)
+        elif ctx.form == "seg_ptr":      # the segment that holds position p; `size` past the last one
+            dst = torch.searchsorted(sp, torch.arange(e, dtype=torch.int64, device=dev), right=True) - 1
+        else:
+            dst = torch.arange(size, dtype=torch.int64, device=dev).repeat_interleave(ctx.count)
+        t = et.to(torch.int64)
+        valid = (dst >= 0) & (dst < size) & (t >= 0) & (t < R)
+        key = torch.where(valid, dst * R + t, torch.full_like(dst, -1)).to(torch.int32)
+        # 2. the gradient per edge
+        if op == "max":
+            per_edge = _max_per_edge(_gather_raw(params, gi, _F32), out.view(size * R, d), key, size * R,
+                                     grad.reshape(size * R, d).contiguous())
+        elif op == "add":
+            per_edge = _gather_by_key(grad.reshape(size * R, d).contiguous(), key, _F32)
+        else:
+            if op == "mean":
+                denom = (counts.sum(1) + 1e-7).view(size, 1, 1)
+            else:
+                denom = (counts + 1e-7).view(size, R, 1)
+            per_edge = _gather_by_key((grad / denom).reshape(size * R, d), key)
+        # 3. into the rows the edges read, rounded once
+        grad_params = _scatter_raw(_ADD, per_edge, gi, params.shape[0]).to(params.dtype)
+        return (grad_params,) + (None,) * 11
+
+
+def relation_reduce(op, params, gather_indices, edge_type, num_relations, size,
+                    indices=None, seg_ptr=None, count=None, out_dtype=None, return_counts=False):
+    """The typed aggregation of an RGCN layer: out[r, t] reduces (op = "add", "max", "mean" - over
+    the destination - or "mean_rel" - over the bucket) the rows params[gather_indices[p]] of the
+    updates p of destination r whose relation edge_type[p] is t, in input order and in one pass
+    (euler_gpu_relation_reduce).  Returns [size, num_relations, D] (and the int32 counts
+    [size, num_relations] with return_counts=True).
+    The destinations come in exactly one form - `indices` (int32 [E] scatter keys in any order),
+    `seg_ptr` (int64 [size + 1] offsets) or `count` (updates per destination) - the forms of
+    gather_scatter and gather_segment_reduce; seg_ptr and count only enqueue (no host wait).
+    gather_indices: int32 [E], the int64 ids a sampler returned (read in place: index = low word,
+    clamped to the last row, as gather_segment_reduce) or None (update p is row p).
+    An update is valid when its destination is in [0, size) and 0 <= edge_type < num_relations; an
+    invalid one - the -1 type the samplers write beside a default_node fill - is left out of every
+    sum, maximum and count and its gradient is exactly 0.  "mean" divides a bucket's sum by (the
+    destination's valid updates + 1e-7) - RelationConv's scatter_mean, relation_conv.py:59 -,
+    "mean_rel" by (the bucket's own count + 1e-7); an empty bucket is 0 (-1e9 for max).
+    The bits are those of gather_scatter(op, params, gather_indices, dst * R + edge_type, size * R)
+    (add, max, "mean_rel" as its mean; "mean" as its add over the destination's denominator), and
+    the gradient with respect to params is that composition's.  out_dtype as scatter_add."""
+    if op not in _REL_MODE:
+        raise ValueError("relation_reduce: op is add, max, mean or mean_rel")
+    _dt("relation_reduce", params)
+    od = _out_dt("relation_reduce", params, out_dtype)
+    if params.dim() != 2:
+        raise ValueError("relation_reduce: params is a [rows, D] table")
+    if (indices is not None) + (seg_ptr is not None) + (count is not None) != 1:
+        raise ValueError("relation_reduce: pass exactly one of indices, seg_ptr and count")
+    num_relations, size = int(num_relations), int(size)
+    if num_relations < 1 or size < 0:
+        raise ValueError("relation_reduce: num_relations >= 1 and size >= 0")
+    params = params.contiguous()
+    et = edge_type.reshape(-1).to(torch.int32).contiguous()
+    _need_cuda(params, et)
+    e = et.numel()
+    gi, as_ids = None, False
+    if gather_indices is not None:
+        as_ids = gather_indices.dtype == torch.int64
+        gi = gather_indices.reshape(-1)
+        gi = gi.contiguous() if as_ids else gi.to(torch.int32).contiguous()
+        _need_cuda(gi)
+        if gi.numel() != e:
+            raise ValueError("relation_reduce: one gather index and one edge type per update")
+    elif params.shape[0] < e:
+        raise ValueError("relation_reduce: without gather_indices update p is row p of params")
+    si = sp = None
+    if indices is not None:
+        si = indices.reshape(-1).to(torch.int32).contiguous()
+        _need_cuda(si)
+        if si.numel() != e:
+            raise ValueError("relation_reduce: one scatter index and one edge type per update")
+        if e == 0:      # (an empty tensor has no address to name the form with)
+            si, sp = None, torch.zeros(size + 1, dtype=torch.int64, device=params.device)
+    elif seg_ptr is not None:
+        sp = seg_ptr.to(torch.int64).contiguous()
+        _need_cuda(sp)
+        if sp.numel() != size + 1:
+            raise ValueError("relation_reduce: seg_ptr has size + 1 entries")
+    else:
+        if int(count) < 1 or size * int(count) != e:
+            raise ValueError("relation_reduce: count >= 1 and size * count updates")
+    return _RelationReduce.apply(params, gi, as_ids, et, num_relations, si, sp, 0 if count is None else int(count),
+                                 size, op, od, bool(return_counts))
+
+
+def relation_conv(x, weight, gather_indices, edge_type, size, indices=None, seg_ptr=None, count=None,
+                  aggr="mean"):
+    """RelationConv.__call__ (relation_conv.py:53-70) without apply_node's fc(x), which stays the
+    caller's own Linear: out[r] = aggr over the updates p of destination r of
+    weight[edge_type[p]] @ x[gather_indices[p]].  weight is [R, dim, F] (the reference's `matrix`),
+    x is [rows, F]; returns [size, dim].  By linearity the per-edge matrices are never gathered:
+    relation_reduce(aggr, ...) gives [size, R, F], and one GEMM with the [R * F, dim] matrix
+    finishes (plain autograd for weight; relation_reduce's gradient for x).  aggr is "add", "mean"
+    (over the destination, the reference's) or "mean_rel"; the arguments are relation_reduce's."""
+    if aggr not in ("add", "mean", "mean_rel"):
+        raise ValueError("relation_conv: aggr is add, mean or mean_rel (a max does not commute with the matrices)")
+    if weight.dim() != 3 or x.dim() != 2 or weight.shape[2] != x.shape[1]:
+        raise ValueError("relation_conv: weight is [R, dim, F] and x is [rows, F]")
+    r, dim, f = weight.shape
+    h = relation_reduce(aggr, x, gather_indices, edge_type, r, size, indices=indices, seg_ptr=seg_ptr,
+                        count=count)
+    return h.reshape(int(size), r * f) @ weight.permute(0, 2, 1).reshape(r * f, dim)
+
+
 def scatter_softmax(updates, indices, size, out_dtype=None):
     """mp_ops.py:76-79.  16-bit updates: the fp32 softmax of updates.float(), rounded once at the end
     unless out_dtype is torch.float32 (and its gradient once on the way back)."""

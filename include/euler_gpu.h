@@ -965,6 +965,40 @@ int euler_gpu_edge_softmax_grad(void* stream, const void* y_dev, int32_t y_dtype
                                 const int32_t* indices_dev, const int64_t* seg_ptr_dev,
                                 int64_t count, int64_t e, int32_t heads, int32_t size,
                                 void* out_dev, int32_t out_dtype);
+/* relation_reduce: the aggregation of RGCN's RelationConv (relation_conv.py:53-70) by linearity -
+ * mean_e W[t_e] x_e = (sum_t W_t * sum_{e: t_e = t} x_e) / deg - as the reduce of gathered rows
+ * per (destination, relation): out_dev is [size, num_relations, d], which one dense GEMM with the
+ * relation matrices then finishes; the [e, dim, fea_dim] block of per-edge matrices is never built.
+ * Update p has a destination (below), a row of params and the relation edge_type_dev[p] (int32,
+ * by the update's position in the INPUT).  It is valid when it has a destination in [0, size) and
+ * 0 <= type < num_relations; an invalid update (the -1 the samplers write beside a default_node
+ * fill) belongs to no bucket: it is left out of every sum, maximum and count and its row is not
+ * read.  out[r][t][c] folds the widened params rows of the valid updates of bucket (r, t) in input
+ * order, all in fp32: mode 0 add, 1 max (from -1e9), 2 the sum / fl(n_valid(r) + 1e-7f) with
+ * n_valid(r) the valid updates of the destination (RelationConv's aggr = 'mean'), 3 the sum /
+ * fl(cnt(r, t) + 1e-7f) (the 1 / c_{i,r} of the RGCN paper).  The bits are those of
+ * euler_gpu_gather_scatter with the keys dst * R + type (-1 for an invalid update): add, max and
+ * mode 3 as its add, max and mean; mode 2 its add divided by the destination's denominator.
+ * Every bucket is written exactly once: an empty one is 0 (add, the means) or -1e9 (max).
+ * counts_dev (may be NULL) receives cnt(r, t) as [size, num_relations] int32.
+ * gather_dev: NULL (update p is row p; params_rows >= e), int32 indices (gather_is_ids == 0) or
+ * the int64 ids a sampler returned (index = low word), either clamped to params_rows - 1 exactly
+ * as euler_gpu_gather_segment_reduce_ids does.  The destinations come in exactly one of the
+ * three forms of euler_gpu_edge_softmax: indices_dev (int32 keys, any order; grouped by one
+ * stable sort a call when they are not non-decreasing, which waits on the host), seg_ptr_dev or
+ * count > 0 with e == size * count; the last two only enqueue - no allocation, no host wait.
+ * Storage: params fp32 / bf16 / fp16, out_dtype fp32 or in_dtype (one rounding at the store).
+ * EULER_GPU_EINVAL: mode outside 0..3, num_relations < 1, size * num_relations >= 2^31,
+ * e >= 2^31, a mean with e or count >= 2^24, not exactly one segment form, count with
+ * e != size * count, a null buffer, an unknown dtype, out_dtype neither fp32 nor in_dtype, a
+ * table shorter than the rows read.  size == 0 or d == 0 returns EULER_GPU_OK and touches
+ * nothing; e == 0 with size > 0 writes the empty-bucket values (and zero counts). */
+int euler_gpu_relation_reduce(void* stream, int32_t mode, const void* params_dev, int32_t in_dtype,
+                              int64_t params_rows, const void* gather_dev, int32_t gather_is_ids,
+                              const int32_t* edge_type_dev, int32_t num_relations,
+                              const int32_t* indices_dev, const int64_t* seg_ptr_dev, int64_t count,
+                              int64_t e, int64_t d, int32_t size,
+                              void* out_dev, int32_t out_dtype, int32_t* counts_dev);
 
 /* ---- shard ops (multi-GPU) --------------------------------------------------
  * ID_SPLIT (core/kernels/id_split_op.cc:46-99): stable bucket of ids by
