@@ -948,6 +948,142 @@ def relation_conv(x, weight, gather_indices, edge_type, size, indices=None, seg_
     return h.reshape(int(size), r * f) @ weight.permute(0, 2, 1).reshape(r * f, dim)
 
 
+_KG_KIND = {"trans_l1": 0, "trans_l2": 1, "distmult": 2}
+_KG_CORRUPT = {"front": 0, "tail": 1, "both": 2}
+
+
+def _triple_head(ent, rel, src, rel_id, dst, neg, kind, corrupt, normalize):
+    """the arguments the two triple_score entries share, from prepared tensors"""
+    b, k = src.numel(), (neg.shape[1] if neg is not None else 0)
+    return (_stream(), _KG_KIND[kind], int(bool(normalize)), _KG_CORRUPT[corrupt],
+            _ptr(ent), _DT[ent.dtype], ent.shape[0], _ptr(rel), _DT[rel.dtype], rel.shape[0],
+            _ptr(src), _ptr(rel_id), _ptr(dst), _ptr(neg), b, k, ent.shape[1])
+
+
+def _triple_score_raw(ent, rel, src, rel_id, dst, neg, kind, corrupt, normalize):
+    """euler_gpu_triple_score on prepared tensors -> (pos [B], neg_out [B, K'])"""
+    b, k, d = src.numel(), (neg.shape[1] if neg is not None else 0), ent.shape[1]
+    kp = 2 * k if corrupt == "both" else k
+    if b == 0 or d == 0:
+        return torch.zeros(b, dtype=_F32, device=ent.device), torch.zeros((b, kp), dtype=_F32, device=ent.device)
+    pos = torch.empty(b, dtype=_F32, device=ent.device)
+    out = torch.empty((b, kp), dtype=_F32, device=ent.device)
+    with _on(ent.device):
+        check(lib().euler_gpu_triple_score(*_triple_head(ent, rel, src, rel_id, dst, neg, kind, corrupt, normalize),
+                                           _ptr(pos), _ptr(out) if k else None))
+    return pos, out
+
+
+def _triple_score_grad_raw(ent, rel, src, rel_id, dst, neg, kind, corrupt, normalize, g_pos, g_neg):
+    """euler_gpu_triple_score_grad -> the fp32 gradients of the raw rows per occurrence:
+    G_src, G_rel, G_dst [B, d] and G_neg [B, K, d]"""
+    b, k, d = src.numel(), (neg.shape[1] if neg is not None else 0), ent.shape[1]
+    make = torch.zeros if b == 0 or d == 0 else torch.empty
+    gs, gr, gd = (make((b, d), dtype=_F32, device=ent.device) for _ in range(3))
+    gn = make((b, k, d), dtype=_F32, device=ent.device)
+    if b == 0 or d == 0:
+        return gs, gr, gd, gn
+    g_pos = g_pos.to(_F32).contiguous()
+    g_neg = g_neg.to(_F32).contiguous() if k else None
+    with _on(ent.device):
+        check(lib().euler_gpu_triple_score_grad(
+            *_triple_head(ent, rel, src, rel_id, dst, neg, kind, corrupt, normalize), _ptr(g_pos), _ptr(g_neg),
+            _ptr(gs), _ptr(gr), _ptr(gd), _ptr(gn) if k else None))
+    return gs, gr, gd, gn
+
+
+def _table_grad(rows, ids, n_rows, dt, sparse_grad):
+    """The gradient of a [n_rows, d] table from the fp32 gradient rows of its occurrences, added in
+    occurrence order (scatter_add) and rounded once to the table's dtype.  An id that names no
+    row becomes key -1.  sparse_grad: a sparse_coo_tensor over the distinct rows, built as
+    _SparseFeatureEmbedding.backward of graph.py builds it."""
+    valid = (ids >= 0) & (ids < n_rows)
+    keys = torch.where(valid, ids, torch.full_like(ids, -1))
+    if not sparse_grad:
+        return scatter_add(rows, keys, n_rows).to(dt)
+    rows, keys = rows[valid], keys[valid]
+    dim = rows.shape[1]
+    if keys.numel() == 0:
+        return torch.sparse_coo_tensor(torch.zeros((1, 0), dtype=torch.int64, device=rows.device),
+                                       torch.zeros((0, dim), dtype=dt, device=rows.device), (n_rows, dim))
+    distinct, inverse = id_unique(keys)
+    values = scatter_add(rows, inverse, distinct.numel()).to(dt)
+    return torch.sparse_coo_tensor(distinct.reshape(1, -1), values, (n_rows, dim))
+
+
+class _TripleScore(torch.autograd.Function):
+    """The fused scores; the gradients of the two tables are the composition's: the kernel returns
+    the gradient of every looked-up row, and scatter_add adds them at the keys
+    [src | dst | neg] (ent) and rel_id (rel).  The index tensors get no gradient."""
+
+    @staticmethod
+    def forward(ctx, ent, rel, src, rel_id, dst, neg, kind, corrupt, normalize, sparse_grad):
+        ctx.save_for_backward(ent, rel, src, rel_id, dst, neg)
+        ctx.conf = (kind, corrupt, normalize, sparse_grad)
+        return _triple_score_raw(ent, rel, src, rel_id, dst, neg, kind, corrupt, normalize)
+
+    @staticmethod
+    def backward(ctx, g_pos, g_neg):
+        ent, rel, src, rel_id, dst, neg = ctx.saved_tensors
+        kind, corrupt, normalize, sparse_grad = ctx.conf
+        gs, gr, gd, gn = _triple_score_grad_raw(ent, rel, src, rel_id, dst, neg, kind, corrupt, normalize,
+                                                g_pos, g_neg)
+        g_ent = g_rel = None
+        if ctx.needs_input_grad[0]:
+            rows, ids = [gs, gd], [src, dst]
+            if neg is not None:
+                rows.append(gn.reshape(-1, gn.shape[2]))
+                ids.append(neg.reshape(-1))
+            g_ent = _table_grad(torch.cat(rows), torch.cat(ids), ent.shape[0], ent.dtype, sparse_grad)
+        if ctx.needs_input_grad[1]:
+            g_rel = _table_grad(gr, rel_id, rel.shape[0], rel.dtype, sparse_grad)
+        return (g_ent, g_rel) + (None,) * 8
+
+
+def triple_score(ent, rel, src, rel_id, dst, neg=None, kind="trans_l1", corrupt="both", normalize=True,
+                 sparse_grad=False):
+    """The energies of knowledge-graph embedding in one pass (calculate_energy of the reference's
+    examples/TransX/transX.py:105-133 and examples/distmult/distmult.py:99-126): the rows of src,
+    dst and the [B, K] negatives in the entity table `ent` and of rel_id in the relation table
+    `rel` (both [rows, d]; fp32, bf16 or fp16, each its own dtype) are looked up, l2-normalised
+    (normalize; tf.nn.l2_normalize with its 1e-12 clamp) and scored, without any [B, K, d] block:
+        kind "trans_l1"  -sum |a + r - c|      "trans_l2"  -sqrt(sum (a + r - c)^2)
+             "distmult"   sum a * r * c
+    Returns pos [B] = s(h, r, t) and neg [B, K'] - corrupt "front": s(n_k, r, t); "tail":
+    s(h, r, n_k); "both": the K front scores, then the K tail scores of the same negatives
+    (transX.py:130) - both fp32; pos alone when neg is None.  Ids are int64; an id outside
+    [0, rows) names no row: it reads as a row of zeros and gets no gradient.  All arithmetic is
+    fp32 in a fixed order (euler_amd/csrc/kg_score.h); the same call returns the same bits.
+    Gradients: the kernel's per-row gradients are added at the keys [src | dst | neg] / rel_id by
+    scatter_add and rounded once to the table's dtype; sparse_grad=True returns them as
+    torch.sparse_coo_tensor over the distinct rows (for torch.optim.SparseAdam).  trans_l1 uses
+    sign(0) = 0; trans_l2 gives a zero gradient where the norm is 0.  No host wait on the forward
+    path."""
+    if kind not in _KG_KIND:
+        raise ValueError("triple_score: kind is trans_l1, trans_l2 or distmult")
+    if corrupt not in _KG_CORRUPT:
+        raise ValueError("triple_score: corrupt is front, tail or both")
+    _dt("triple_score", ent)
+    _dt("triple_score", rel)
+    if ent.dim() != 2 or rel.dim() != 2 or ent.shape[1] != rel.shape[1] or ent.shape[0] < 1 or rel.shape[0] < 1:
+        raise ValueError("triple_score: ent is [rows, d] and rel is [relations, d], one row at least")
+    src, rel_id, dst = (t.to(torch.int64).reshape(-1).contiguous() for t in (src, rel_id, dst))
+    b = src.numel()
+    if rel_id.numel() != b or dst.numel() != b:
+        raise ValueError("triple_score: one src, rel_id and dst per triple")
+    if neg is not None:
+        neg = neg.to(torch.int64)
+        neg = (neg if neg.dim() == 2 else neg.reshape(b, -1)).contiguous()
+        if neg.shape[0] != b:
+            raise ValueError("triple_score: neg is [B, K]")
+    _need_cuda(ent, rel, src, rel_id, dst, *(() if neg is None else (neg,)))
+    if b * max(1 if neg is None else neg.shape[1], 1) * 2 >= 2 ** 31 or ent.shape[0] >= 2 ** 31:
+        raise ValueError("triple_score: B * max(K, 1) * 2 and the table's rows must stay below 2^31")
+    pos, out = _TripleScore.apply(ent.contiguous(), rel.contiguous(), src, rel_id, dst, neg, kind, corrupt,
+                                  bool(normalize), bool(sparse_grad))
+    return pos if neg is None else (pos, out)
+
+
 def scatter_softmax(updates, indices, size, out_dtype=None):
     """mp_ops.py:76-79.  16-bit updates: the fp32 softmax of updates.float(), rounded once at the end
     unless out_dtype is torch.float32 (and its gradient once on the way back)."""

@@ -999,6 +999,43 @@ int euler_gpu_relation_reduce(void* stream, int32_t mode, const void* params_dev
                               const int32_t* indices_dev, const int64_t* seg_ptr_dev, int64_t count,
                               int64_t e, int64_t d, int32_t size,
                               void* out_dev, int32_t out_dtype, int32_t* counts_dev);
+/* triple_score: the energies of knowledge-graph embedding (calculate_energy of
+ * examples/TransX/transX.py:72-79,105-133 and examples/distmult/distmult.py:74-79,99-126) - the
+ * lookup of the rows of src, rel_id, dst and the [b, k] negatives, their l2 normalisation
+ * (normalize != 0: x / sqrt(max(sum x^2, 1e-12f)), tf.nn.l2_normalize) and the scores - in one
+ * pass: 3 + k table rows read and 1 + K' floats written per triple, no [b, k, d] intermediate.
+ * With h, r, t, n_j the (normalised) rows and e = a + r - c, the score s(a, r, c) is
+ * kind 0 trans_l1 -sum |e|, 1 trans_l2 -sqrt(sum e * e), 2 distmult sum (a * r) * c.
+ * pos_out_dev [b] = s(h, r, t).  neg_out_dev [b, K']: corrupt 0 front, K' = k, s(n_j, r, t);
+ * 1 tail, K' = k, s(h, r, n_j); 2 both, K' = 2 k, the front scores then the tail scores of the
+ * same negatives.  Ids are signed int64; an id outside [0, rows) of its table names no row: it is
+ * never dereferenced, reads as a row of zeros and gets a zero gradient row.  The tables are fp32,
+ * bf16 or fp16, each its own type, widened exactly; all arithmetic is fp32, every sum over columns
+ * in the fixed order stated in euler_amd/csrc/kg_score.h (it depends on d, the types and the
+ * 16-byte alignment of the two tables, never on b, k or the launch).
+ * triple_score_grad: from g_pos_dev [b] and g_neg_dev [b, K'] the fp32 gradients of the RAW rows
+ * per occurrence - g_src_dev, g_rel_dev, g_dst_dev [b, d], g_neg_rows_dev [b, k, d] - through
+ * the scores and the normalisation (sign(0) = 0 for trans_l1; a zero gradient where the l2 norm
+ * is 0); a table's gradient is their scatter_add by id.
+ * Both only enqueue: no allocation, no host wait.  EULER_GPU_EINVAL: kind or corrupt outside
+ * 0..2, an unknown dtype, k < 0, a table with fewer than 1 row, b * max(k, 1) * 2 >= 2^31,
+ * d >= 2^31, a null required buffer, k > 0 with neg_dev or its outputs null, a buffer not aligned
+ * to its type.  b == 0 or d == 0 returns EULER_GPU_OK and touches nothing; k == 0 leaves the
+ * negative outputs untouched (neg_dev and they may be NULL). */
+int euler_gpu_triple_score(void* stream, int32_t kind, int32_t normalize, int32_t corrupt,
+                           const void* ent_dev, int32_t ent_dtype, int64_t ent_rows,
+                           const void* rel_dev, int32_t rel_dtype, int64_t rel_rows,
+                           const int64_t* src_dev, const int64_t* rel_id_dev,
+                           const int64_t* dst_dev, const int64_t* neg_dev, int64_t b, int64_t k,
+                           int64_t d, float* pos_out_dev, float* neg_out_dev);
+int euler_gpu_triple_score_grad(void* stream, int32_t kind, int32_t normalize, int32_t corrupt,
+                                const void* ent_dev, int32_t ent_dtype, int64_t ent_rows,
+                                const void* rel_dev, int32_t rel_dtype, int64_t rel_rows,
+                                const int64_t* src_dev, const int64_t* rel_id_dev,
+                                const int64_t* dst_dev, const int64_t* neg_dev, int64_t b,
+                                int64_t k, int64_t d, const float* g_pos_dev,
+                                const float* g_neg_dev, float* g_src_dev, float* g_rel_dev,
+                                float* g_dst_dev, float* g_neg_rows_dev);
 
 /* ---- shard ops (multi-GPU) --------------------------------------------------
  * ID_SPLIT (core/kernels/id_split_op.cc:46-99): stable bucket of ids by
