@@ -1,0 +1,364 @@
+// In-place embedding stores on gfx950 - update / add / take of embed_store.h, which states the
+// contract - with their C-ABI entry points.
+//
+// A call is: one kernel that writes (key, position) per occurrence, one stable radix sort of those
+// pairs over the bits `rows` needs (rocPRIM via hipCUB - the one library primitive used here),
+// and one kernel in which every segment of equal keys has ONE owner.  A wave looks at 64 adjacent
+// sorted entries at a time (one coalesced load of the keys, one ballot of the entries that start
+// a task); the tasks of a window go round robin to the wave's 64 / L groups of L lanes, L = the
+// power of two >= d / V, so narrow rows fill the wave.  The owner reads the table row once, walks
+// its segment in position order - keys, positions and source rows are loaded eight entries ahead
+// of the add chain, which is sequential by definition - and writes the row once.  No lane of any
+// other task reads or writes that table row.  Nothing here waits on the host: the three entries
+// only enqueue, scratch comes from StreamBuf and goes back in stream order on every exit, and
+// every check precedes the first write to the table.  take without clear needs no grouping: it is
+// a plain lookup per occurrence.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include "device_fns.h"
+#include "device_mem.h"
+#include "embed_store.h"
+
+namespace euler_gpu {
+namespace {
+
+constexpr int kBytes[3] = {4, 2, 2};
+
+// V adjacent elements as their bits: 16-byte (8-byte) accesses where the type and V allow
+template <int DT, int V>
+__device__ __forceinline__ void EsLoad(const void* base, int64_t at, uint32_t r[V]) {
+  if constexpr (DT == kF32) {
+    const uint32_t* p = static_cast<const uint32_t*>(base) + at;
+    if constexpr (V == 1) {
+      r[0] = *p;
+    } else {
+#pragma unroll
+      for (int q = 0; q < V / 4; ++q) {
+        const uint4 v = reinterpret_cast<const uint4*>(p)[q];
+        r[4 * q] = v.x; r[4 * q + 1] = v.y; r[4 * q + 2] = v.z; r[4 * q + 3] = v.w;
+      }
+    }
+  } else {
+    const uint16_t* p = static_cast<const uint16_t*>(base) + at;
+    if constexpr (V == 1) {
+      r[0] = *p;
+    } else if constexpr (V == 4) {
+      const uint2 v = *reinterpret_cast<const uint2*>(p);
+      r[0] = v.x & 0xffffu; r[1] = v.x >> 16; r[2] = v.y & 0xffffu; r[3] = v.y >> 16;
+    } else {
+      const uint4 v = *reinterpret_cast<const uint4*>(p);
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { r[2 * q] = w[q] & 0xffffu; r[2 * q + 1] = w[q] >> 16; }
+    }
+  }
+}
+
+template <int DT, int V>
+__device__ __forceinline__ void EsStore(void* base, int64_t at, const uint32_t r[V]) {
+  if constexpr (DT == kF32) {
+    uint32_t* p = static_cast<uint32_t*>(base) + at;
+    if constexpr (V == 1) {
+      *p = r[0];
+    } else {
+#pragma unroll
+      for (int q = 0; q < V / 4; ++q)
+        reinterpret_cast<uint4*>(p)[q] = make_uint4(r[4 * q], r[4 * q + 1], r[4 * q + 2], r[4 * q + 3]);
+    }
+  } else {
+    uint16_t* p = static_cast<uint16_t*>(base) + at;
+    if constexpr (V == 1) {
+      *p = (uint16_t)r[0];
+    } else if constexpr (V == 4) {
+      *reinterpret_cast<uint2*>(p) = make_uint2(r[0] | (r[1] << 16), r[2] | (r[3] << 16));
+    } else {
+      *reinterpret_cast<uint4*>(p) =
+          make_uint4(r[0] | (r[1] << 16), r[2] | (r[3] << 16), r[4] | (r[5] << 16), r[6] | (r[7] << 16));
+    }
+  }
+}
+
+struct EsArgs {
+  void* table; int64_t rows, d;
+  const int64_t* ids; int64_t e;
+  const void* values; int64_t m; const int32_t* row_index; int64_t count;     // update / add
+  void* out; int32_t clear;                                                    // take
+  const uint64_t* keys; const uint32_t* perm;                                  // the sorted pairs
+  int32_t log_l;
+};
+
+__global__ __launch_bounds__(256) void EsKeysKernel(const int64_t* __restrict__ ids, int64_t e, int64_t rows,
+                                                    const int32_t* __restrict__ row_index, int64_t m,
+                                                    uint64_t* __restrict__ keys, uint32_t* __restrict__ pos) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < e; p += stride) {
+    keys[p] = EsKey(ids[p], rows, EsSourceLive(p, row_index, m));
+    pos[p] = (uint32_t)p;
+  }
+}
+
+// K sorted entries from q on: which of them belong to the segment of `key` (ok), and their
+// positions.  An entry past the segment stands in as entry i (the head), which is always valid.
+template <int K>
+__device__ __forceinline__ void EsAhead(const EsArgs& a, uint64_t key, int64_t i, int64_t q, bool ok[K],
+                                        int64_t pos[K]) {
+#pragma unroll
+  for (int x = 0; x < K; ++x) ok[x] = q + x < a.e && a.keys[q + x < a.e ? q + x : i] == key;
+#pragma unroll
+  for (int x = 0; x < K; ++x) pos[x] = a.perm[ok[x] ? q + x : i];
+}
+
+// The task that sorted entry i starts (update: ends), run by the L lanes of a group; l = the
+// lane's number in its group.  DV: the dtype of values (update, add) or of out (take).
+template <int OP, int DT, int DV, int V>
+__device__ __forceinline__ void EsTask(const EsArgs& a, int64_t i, int32_t l, int32_t lanes, int32_t chunks) {
+  if constexpr (OP == kEsTake) {
+    const int64_t id = a.ids[i];
+    const bool in = EsInRange(id, a.rows);
+    for (int32_t j = l; j < chunks; j += lanes) {
+      uint32_t r[V];
+      if (in) EsLoad<DT, V>(a.table, id * a.d + (int64_t)j * V, r);
+#pragma unroll
+      for (int k = 0; k < V; ++k) r[k] = in ? EsConvert<DT, DV>(r[k]) : 0u;
+      EsStore<DV, V>(a.out, i * a.d + (int64_t)j * V, r);
+    }
+  } else if constexpr (OP == kEsUpdate) {
+    const int64_t id = (int64_t)a.keys[i];
+    const int64_t src = EsSourceRow(a.perm[i], a.row_index, a.count);
+    for (int32_t j = l; j < chunks; j += lanes) {
+      uint32_t r[V];
+      EsLoad<DV, V>(a.values, src * a.d + (int64_t)j * V, r);
+#pragma unroll
+      for (int k = 0; k < V; ++k) r[k] = EsConvert<DV, DT>(r[k]);
+      EsStore<DT, V>(a.table, id * a.d + (int64_t)j * V, r);
+    }
+  } else if constexpr (OP == kEsAdd) {
+    const uint64_t key = a.keys[i];
+    for (int32_t j = l; j < chunks; j += lanes) {
+      const int64_t at = (int64_t)key * a.d + (int64_t)j * V;
+      uint32_t r[V];
+      float acc[V];
+      EsLoad<DT, V>(a.table, at, r);
+#pragma unroll
+      for (int k = 0; k < V; ++k) acc[k] = EsWiden<DT>(r[k]);
+      // the adds stay in position order; only the loads of eight entries are issued together
+      for (int64_t q = i;; q += 8) {
+        bool ok[8];
+        int64_t pos[8];
+        uint32_t v[8][V];
+        EsAhead<8>(a, key, i, q, ok, pos);
+#pragma unroll
+        for (int x = 0; x < 8; ++x)
+          EsLoad<DV, V>(a.values, EsSourceRow(pos[x], a.row_index, a.count) * a.d + (int64_t)j * V, v[x]);
+#pragma unroll
+        for (int x = 0; x < 8; ++x) {
+#pragma unroll
+          for (int k = 0; k < V; ++k) acc[k] = ok[x] ? EsAddStep<DV>(acc[k], v[x][k]) : acc[k];
+        }
+        if (!ok[7]) break;
+      }
+#pragma unroll
+      for (int k = 0; k < V; ++k) r[k] = EsNarrow<DT>(acc[k]);
+      EsStore<DT, V>(a.table, at, r);
+    }
+  } else {                                        // kEsTakeClear
+    const uint64_t key = a.keys[i];
+    const bool in = key < (uint64_t)a.rows;
+    for (int32_t j = l; j < chunks; j += lanes) {
+      const int64_t at = (int64_t)key * a.d + (int64_t)j * V;
+      uint32_t r[V], z[V];
+#pragma unroll
+      for (int k = 0; k < V; ++k) z[k] = 0u;
+      if (!in) {                                  // a removed id reads as a row of +0
+        EsStore<DV, V>(a.out, (int64_t)a.perm[i] * a.d + (int64_t)j * V, z);
+        continue;
+      }
+      EsLoad<DT, V>(a.table, at, r);
+#pragma unroll
+      for (int k = 0; k < V; ++k) r[k] = EsConvert<DT, DV>(r[k]);
+      // the old row to every occurrence of the segment
+      for (int64_t q = i;; q += 8) {
+        bool ok[8];
+        int64_t pos[8];
+        EsAhead<8>(a, key, i, q, ok, pos);
+#pragma unroll
+        for (int x = 0; x < 8; ++x)
+          if (ok[x]) EsStore<DV, V>(a.out, pos[x] * a.d + (int64_t)j * V, r);
+        if (!ok[7]) break;
+      }
+      if (a.clear) EsStore<DT, V>(a.table, at, z);
+    }
+  }
+}
+
+template <int OP, int DT, int DV, int V>
+__global__ __launch_bounds__(256) void EsStoreKernel(const EsArgs a) {
+  const int32_t lanes = 1 << a.log_l, groups = 64 >> a.log_l;
+  const int32_t lane = threadIdx.x & 63;
+  const int32_t g = lane >> a.log_l, l = lane & (lanes - 1);
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const int32_t chunks = (int32_t)(a.d / V);
+  for (int64_t base = wave * 64; base < a.e; base += waves * 64) {       // (the same trips for a whole wave)
+    const int64_t i = base + lane;
+    bool task = i < a.e;
+    if constexpr (OP != kEsTake) {
+      if (task) {
+        const bool live = a.keys[i] < (uint64_t)a.rows;
+        if constexpr (OP == kEsUpdate) task = live && EsIsTail(a.keys, i, a.e);
+        else if constexpr (OP == kEsAdd) task = live && EsIsHead(a.keys, i);
+        else task = !live || EsIsHead(a.keys, i);         // a removed id: every occurrence on its own
+      }
+    }
+    uint64_t todo = __ballot(task);
+    // group g takes the tasks g, g + groups, ... of the window
+    for (int32_t x = 0; x < g && todo; ++x) todo &= todo - 1;
+    while (todo) {
+      EsTask<OP, DT, DV, V>(a, base + __builtin_ctzll(todo), l, lanes, chunks);
+      for (int32_t x = 0; x < groups && todo; ++x) todo &= todo - 1;
+    }
+  }
+}
+
+template <int OP, int DT, int DV>
+int LaunchStore(hipStream_t st, EsArgs a, const void* other) {
+  const int32_t v = EsChunkWidth(a.d, (uintptr_t)a.table, kBytes[DT], (uintptr_t)other, kBytes[DV]);
+  a.log_l = EsLogLanes(a.d / v);
+  const int64_t waves = (a.e + 63) / 64;
+  int64_t blocks = (waves + 3) / 4;
+  if (blocks > 256 * 32) blocks = 256 * 32;
+  const dim3 grid((unsigned)blocks), block(256);
+  if (v == 8) hipLaunchKernelGGL((EsStoreKernel<OP, DT, DV, 8>), grid, block, 0, st, a);
+  else if (v == 4) hipLaunchKernelGGL((EsStoreKernel<OP, DT, DV, 4>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((EsStoreKernel<OP, DT, DV, 1>), grid, block, 0, st, a);
+  EG_HIP(hipGetLastError());
+  return EULER_GPU_OK;
+}
+
+template <int OP, int DT>
+int DispatchOther(hipStream_t st, const EsArgs& a, const void* other, int32_t other_dtype) {
+  if (other_dtype == EULER_GPU_F32) return LaunchStore<OP, DT, kF32>(st, a, other);
+  return LaunchStore<OP, DT, DT>(st, a, other);
+}
+
+template <int OP>
+int DispatchTable(hipStream_t st, const EsArgs& a, int32_t table_dtype, const void* other, int32_t other_dtype) {
+  if (table_dtype == EULER_GPU_F32) return LaunchStore<OP, kF32, kF32>(st, a, other);
+  if (table_dtype == EULER_GPU_BF16) return DispatchOther<OP, kBF16>(st, a, other, other_dtype);
+  return DispatchOther<OP, kF16>(st, a, other, other_dtype);
+}
+
+bool EsKnownDtype(int32_t t) { return t == EULER_GPU_F32 || t == EULER_GPU_BF16 || t == EULER_GPU_F16; }
+
+// The checks the three entries share: the table, the ids and the other data buffer (values / out).
+// -> EULER_GPU_OK with *run = false when there is nothing to do.
+int CheckStoreArgs(const std::string& what, const EsArgs& a, int32_t table_dtype, const void* other,
+                   int32_t other_dtype, bool* run) {
+  *run = false;
+  if (!EsKnownDtype(table_dtype) || !EsKnownDtype(other_dtype))
+    return Fail(EULER_GPU_EINVAL, what + ": unknown dtype (0 fp32, 1 bf16, 2 fp16)");
+  if (other_dtype != EULER_GPU_F32 && other_dtype != table_dtype)
+    return Fail(EULER_GPU_EINVAL, what + ": values / out are fp32 or of the table's dtype");
+  if (a.rows < 1) return Fail(EULER_GPU_EINVAL, what + ": a table with fewer than 1 row");
+  if (a.e < 0 || a.d < 0) return Fail(EULER_GPU_EINVAL, what + ": e or d < 0");
+  if (a.e >= (1LL << 31) || a.d >= (1LL << 31)) return Fail(EULER_GPU_EINVAL, what + ": e or d >= 2^31");
+  if (a.e == 0 || a.d == 0) return EULER_GPU_OK;
+  if (!a.table || !a.ids || !other) return Fail(EULER_GPU_EINVAL, what + ": null buffer");
+  if ((uintptr_t)a.table % kBytes[table_dtype] != 0 || (uintptr_t)other % kBytes[other_dtype] != 0 ||
+      (uintptr_t)a.ids % 8 != 0)
+    return Fail(EULER_GPU_EINVAL, what + ": a buffer is not aligned to its type");
+  *run = true;
+  return EULER_GPU_OK;
+}
+
+// (key, position) of every occurrence, stably sorted by key, into `pairs` (released by its owner)
+int GroupOccurrences(hipStream_t st, EsArgs* a, StreamBuf* pairs) {
+  const size_t n = (size_t)a->e;
+  EG_HIP(pairs->alloc(n * (8 + 8 + 4 + 4) + 64));
+  uint64_t* keys_in = pairs->as<uint64_t>();
+  uint64_t* keys_out = keys_in + n;
+  uint32_t* pos_in = reinterpret_cast<uint32_t*>(keys_out + n);
+  uint32_t* pos_out = pos_in + n;
+  int64_t blocks = ((int64_t)n + 255) / 256;
+  if (blocks > 256 * 32) blocks = 256 * 32;
+  hipLaunchKernelGGL(EsKeysKernel, dim3((unsigned)blocks), dim3(256), 0, st, a->ids, a->e, a->rows, a->row_index,
+                     a->m, keys_in, pos_in);
+  EG_HIP(hipGetLastError());
+  const int bits = EsKeyBits(a->rows);
+  size_t tmp_bytes = 0;
+  EG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys_in, keys_out, pos_in, pos_out, (int)n, 0, bits,
+                                            st));
+  StreamBuf tmp(st);          // (the library's scratch goes back before the store kernel runs)
+  EG_HIP(tmp.alloc(tmp_bytes + 16));
+  EG_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.as(), tmp_bytes, keys_in, keys_out, pos_in, pos_out, (int)n, 0, bits,
+                                            st));
+  a->keys = keys_out;
+  a->perm = pos_out;
+  return EULER_GPU_OK;
+}
+
+template <int OP>
+int StoreWrite(const char* name, void* stream, void* table_dev, int32_t table_dtype, int64_t rows, int64_t d,
+               const int64_t* ids_dev, int64_t e, const void* values_dev, int32_t values_dtype, int64_t m,
+               const int32_t* row_index_dev, int64_t count) {
+  const std::string what(name);
+  EsArgs a{};
+  a.table = table_dev; a.rows = rows; a.d = d; a.ids = ids_dev; a.e = e;
+  a.values = values_dev; a.m = m; a.row_index = row_index_dev; a.count = count;
+  if (row_index_dev && count != 0) return Fail(EULER_GPU_EINVAL, what + ": row_index and count both given");
+  if (count < 0) return Fail(EULER_GPU_EINVAL, what + ": count < 0");
+  if (m < 0) return Fail(EULER_GPU_EINVAL, what + ": m < 0");
+  if (e >= 0 && count > 0 && (e % count != 0 || m != e / count))
+    return Fail(EULER_GPU_EINVAL, what + ": count needs e % count == 0 and m == e / count");
+  if (!row_index_dev && count == 0 && m != e) return Fail(EULER_GPU_EINVAL, what + ": values are [e, d]: m != e");
+  if (row_index_dev && (uintptr_t)row_index_dev % 4 != 0)
+    return Fail(EULER_GPU_EINVAL, what + ": a buffer is not aligned to its type");
+  bool run;
+  const int rc = CheckStoreArgs(what, a, table_dtype, values_dev, values_dtype, &run);
+  if (rc != EULER_GPU_OK || !run) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  StreamBuf pairs(st);
+  const int rg = GroupOccurrences(st, &a, &pairs);
+  if (rg != EULER_GPU_OK) return rg;
+  return DispatchTable<OP>(st, a, table_dtype, values_dev, values_dtype);
+}
+
+}  // namespace
+}  // namespace euler_gpu
+
+using namespace euler_gpu;
+
+extern "C" {
+
+int euler_gpu_store_update(void* stream, void* table_dev, int32_t table_dtype, int64_t rows, int64_t d,
+                           const int64_t* ids_dev, int64_t e, const void* values_dev, int32_t values_dtype,
+                           int64_t m, const int32_t* row_index_dev, int64_t count) {
+  return StoreWrite<kEsUpdate>("store_update", stream, table_dev, table_dtype, rows, d, ids_dev, e, values_dev,
+                               values_dtype, m, row_index_dev, count);
+}
+
+int euler_gpu_store_add(void* stream, void* table_dev, int32_t table_dtype, int64_t rows, int64_t d,
+                        const int64_t* ids_dev, int64_t e, const void* values_dev, int32_t values_dtype,
+                        int64_t m, const int32_t* row_index_dev, int64_t count) {
+  return StoreWrite<kEsAdd>("store_add", stream, table_dev, table_dtype, rows, d, ids_dev, e, values_dev,
+                            values_dtype, m, row_index_dev, count);
+}
+
+int euler_gpu_store_take(void* stream, void* table_dev, int32_t table_dtype, int64_t rows, int64_t d,
+                         const int64_t* ids_dev, int64_t e, int32_t clear, void* out_dev, int32_t out_dtype) {
+  EsArgs a{};
+  a.table = table_dev; a.rows = rows; a.d = d; a.ids = ids_dev; a.e = e;
+  a.out = out_dev; a.clear = clear;
+  bool run;
+  const int rc = CheckStoreArgs("store_take", a, table_dtype, out_dev, out_dtype, &run);
+  if (rc != EULER_GPU_OK || !run) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (!clear) return DispatchTable<kEsTake>(st, a, table_dtype, out_dev, out_dtype);
+  StreamBuf pairs(st);
+  const int rg = GroupOccurrences(st, &a, &pairs);
+  if (rg != EULER_GPU_OK) return rg;
+  return DispatchTable<kEsTakeClear>(st, a, table_dtype, out_dev, out_dtype);
+}
+
+}  // extern "C"

@@ -1084,6 +1084,110 @@ def triple_score(ent, rel, src, rel_id, dst, neg=None, kind="trans_l1", corrupt=
     return pos if neg is None else (pos, out)
 
 
+# ---- in-place embedding stores (tf_euler/python/utils/embedding.py:24-68) ---------------------
+# The stores of ScalableSageEncoder / ScalableGCNEncoder (utils/encoders.py:629-748, 294-409): a
+# non-trainable [max_id + 1, d] table per layer that lives in HBM across steps and is changed IN
+# PLACE - no [rows, d] temporary, no [E, d] block of per-occurrence rows.  The contract is stated
+# in euler_amd/csrc/embed_store.h.  The reference sizes its stores [max_id + 2, d] and spends the
+# last row as a dump for the default_node = max_id + 1 fills of the samplers; here an id outside
+# [0, rows) names no row, so a store of [max_id + 1, d] drops those fills by the range rule.
+
+def _store_table(name, table, ids):
+    """checks of the table and the ids -> (ids as flat int64, E, d)"""
+    if not torch.is_tensor(table) or table.dtype not in _DT:
+        raise ValueError("%s: table must be float32, bfloat16 or float16" % name)
+    if table.dim() != 2 or table.shape[0] < 1 or not table.is_contiguous():
+        raise ValueError("%s: table is a contiguous [rows, d] tensor, one row at least (it is modified in place)"
+                         % name)
+    if table.requires_grad:
+        raise RuntimeError("%s: table requires grad, but a store is changed in place and is not differentiable"
+                           % name)
+    if ids.dtype.is_floating_point or ids.dtype == torch.bool:
+        raise ValueError("%s: ids are integers, not %s" % (name, ids.dtype))
+    flat = ids.to(torch.int64).reshape(-1).contiguous()
+    _need_cuda(table, flat)
+    if flat.numel() >= 2 ** 31 or table.shape[1] >= 2 ** 31:
+        raise ValueError("%s: the number of ids and d must stay below 2^31" % name)
+    return flat, flat.numel(), table.shape[1]
+
+
+def _store_write(name, table, ids, values, row_index, count):
+    flat, e, d = _store_table(name, table, ids)
+    if not torch.is_tensor(values) or values.dim() != 2 or values.shape[1] != d:
+        raise ValueError("%s: values is [M, d] with the table's d" % name)
+    if values.dtype != _F32 and values.dtype != table.dtype:
+        raise ValueError("%s: values are float32 or of the table's dtype (%s), not %s"
+                         % (name, table.dtype, values.dtype))
+    if row_index is not None and count is not None:
+        raise ValueError("%s: pass row_index or count, not both" % name)
+    m = values.shape[0]
+    if row_index is not None:
+        if row_index.dtype.is_floating_point or row_index.numel() != e:
+            raise ValueError("%s: row_index holds one integer per id" % name)
+        row_index = row_index.to(torch.int32).reshape(-1).contiguous()
+    elif count is not None:
+        count = int(count)
+        if count <= 0 or e % count != 0 or m != e // count:
+            raise ValueError("%s: count > 0 divides the number of ids and values is [ids / count, d]" % name)
+    elif m != e:
+        raise ValueError("%s: values holds one row per id (or pass row_index / count)" % name)
+    values = values.contiguous()
+    _need_cuda(values, *(() if row_index is None else (row_index,)))
+    fn = getattr(lib(), "euler_gpu_store_" + name.split("_")[1])
+    with torch.no_grad(), _on(table.device):
+        check(fn(_stream(), _ptr(table), _DT[table.dtype], table.shape[0], d, _ptr(flat), e, _ptr(values),
+                 _DT[values.dtype], m, _ptr(row_index), count or 0))
+        torch.autograd.graph.increment_version(table)
+    return table
+
+
+def embedding_update(table, ids, values, row_index=None, count=None):
+    """embedding_update of the reference's utils/embedding.py (tf.scatter_update), IN PLACE on
+    `table` ([rows, d], contiguous; fp32, bf16 or fp16): table[id] = the source row of the LAST
+    occurrence of id in `ids` (any shape, flattened; the sequential loop of the CPU op).  The source
+    row of occurrence p is values[p], values[row_index[p]] (one int per id; an entry outside
+    [0, M) removes the occurrence) or values[p // count] (values is [E / count, d]: one row
+    broadcast over the `count` sampled neighbours of a node - the [E, d] block is never built).
+    values is fp32 or of the table's dtype: the same dtype copies bits, fp32 into a 16-bit table
+    rounds once to nearest even.  An id outside [0, rows) names no row and is left out - a store
+    sized [max_id + 1, d] so drops the default_node = max_id + 1 fills for which the reference
+    keeps a dump row ([max_id + 2, d]).  Not differentiable; returns `table` (the same tensor, its
+    version counter advanced).  The same call gives the same bits; no host wait."""
+    return _store_write("embedding_update", table, ids, values, row_index, count)
+
+
+def embedding_add(table, ids, values, row_index=None, count=None):
+    """embedding_add of the reference's utils/embedding.py (tf.scatter_add), IN PLACE on `table`:
+    for every distinct in-range id, acc = table[id] widened to fp32, then one correctly rounded
+    fp32 add per occurrence of the id IN INPUT ORDER, then one rounding to the table's dtype - the
+    bits of the reference's sequential loop, without float atomics, the same on every call.
+    Arguments as embedding_update; count=fanout adds the gradient row of a node's mean / sum to
+    each of its `fanout` sampled neighbours without materialising the [B * fanout, d] block.
+    Not differentiable; returns `table`.  No host wait."""
+    return _store_write("embedding_add", table, ids, values, row_index, count)
+
+
+def embedding_take(table, ids, clear=False, out_dtype=None):
+    """embedding_lookup of the reference's utils/embedding.py on a store: out[p] = table[ids[p]]
+    as it was BEFORE the call, for every occurrence (duplicates included), shaped
+    ids.shape + (d,), in the table's dtype or fp32 (out_dtype).  An id outside [0, rows) reads
+    as a row of +0.  clear=True also sets every row an in-range id names to +0 in the same call -
+    the embedding_update(gradient_store, node, zeros) under a control dependency of
+    utils/encoders.py:738-743.  Not differentiable.  No host wait."""
+    flat, e, d = _store_table("embedding_take", table, ids)
+    od = _out_dt("embedding_take", table, out_dtype)
+    shape = tuple(ids.shape) + (d,)
+    if e == 0 or d == 0:
+        return torch.zeros(shape, dtype=od, device=table.device)
+    out = torch.empty((e, d), dtype=od, device=table.device)
+    with torch.no_grad(), _on(table.device):
+        check(lib().euler_gpu_store_take(_stream(), _ptr(table), _DT[table.dtype], table.shape[0], d, _ptr(flat), e,
+                                         int(bool(clear)), _ptr(out), _DT[od]))
+        if clear:
+            torch.autograd.graph.increment_version(table)
+    return out.reshape(shape)
+
+
 def scatter_softmax(updates, indices, size, out_dtype=None):
     """mp_ops.py:76-79.  16-bit updates: the fp32 softmax of updates.float(), rounded once at the end
     unless out_dtype is torch.float32 (and its gradient once on the way back)."""

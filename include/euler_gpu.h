@@ -1036,6 +1036,40 @@ int euler_gpu_triple_score_grad(void* stream, int32_t kind, int32_t normalize, i
                                 int64_t k, int64_t d, const float* g_pos_dev,
                                 const float* g_neg_dev, float* g_src_dev, float* g_rel_dev,
                                 float* g_dst_dev, float* g_neg_rows_dev);
+/* store_update / store_add / store_take: the in-place embedding stores of ScalableSage /
+ * ScalableGCN (tf_euler/python/utils/embedding.py:24-68, encoders.py:713-748) - tf.scatter_update,
+ * tf.scatter_add and embedding_lookup with the optional clearing update of encoders.py:738-743 -
+ * on a table [rows, d] (fp32 / bf16 / fp16, contiguous) that is MODIFIED IN PLACE; no [rows, d]
+ * temporary and no [e, d] block of per-occurrence rows exists.  The contract is stated in
+ * euler_amd/csrc/embed_store.h.  ids_dev: signed int64 [e], the row index is the id; an id outside
+ * [0, rows) names no row: it is never dereferenced, is left out of update / add and reads as a
+ * row of +0 in take.  The source row of occurrence p is values[p] (row_index_dev == NULL and
+ * count == 0; m must equal e), values[row_index_dev[p]] (int32 [e]; an entry outside [0, m) removes
+ * the occurrence) or values[p / count] (count > 0, e % count == 0, m == e / count).  values_dev is
+ * [m, d], fp32 or the table's dtype (narrowing: one round to nearest even).
+ * update: table[id] = the source row of the LAST occurrence of id (same dtype: the bits).
+ * add: acc = widen(table[id]); acc = fl32(acc + widen(source row)) for the occurrences of id in
+ * increasing p; table[id] = round(acc) - no float atomics, the same bits on every call and for
+ * every launch geometry.
+ * take: out_dev [e, d] (the table's dtype or fp32) receives table[ids[p]] as it was before the
+ * call for every occurrence; clear != 0 leaves every row an in-range id names at +0.
+ * All three only enqueue: no host wait, no device-to-host copy; scratch is stream-ordered and
+ * every check precedes the first write, so an error leaves the table untouched.
+ * EULER_GPU_EINVAL: an unknown dtype, a values / out dtype that is neither fp32 nor the table's,
+ * rows < 1, e or d >= 2^31 (or < 0), row_index and count both given, count < 0, count > 0 with
+ * e % count != 0 or m != e / count, the plain form with m != e, a null required buffer, a buffer
+ * not aligned to its element type.  e == 0 or d == 0 returns EULER_GPU_OK and touches nothing. */
+int euler_gpu_store_update(void* stream, void* table_dev, int32_t table_dtype, int64_t rows,
+                           int64_t d, const int64_t* ids_dev, int64_t e, const void* values_dev,
+                           int32_t values_dtype, int64_t m, const int32_t* row_index_dev,
+                           int64_t count);
+int euler_gpu_store_add(void* stream, void* table_dev, int32_t table_dtype, int64_t rows,
+                        int64_t d, const int64_t* ids_dev, int64_t e, const void* values_dev,
+                        int32_t values_dtype, int64_t m, const int32_t* row_index_dev,
+                        int64_t count);
+int euler_gpu_store_take(void* stream, void* table_dev, int32_t table_dtype, int64_t rows,
+                         int64_t d, const int64_t* ids_dev, int64_t e, int32_t clear,
+                         void* out_dev, int32_t out_dtype);
 
 /* ---- shard ops (multi-GPU) --------------------------------------------------
  * ID_SPLIT (core/kernels/id_split_op.cc:46-99): stable bucket of ids by
