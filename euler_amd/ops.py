@@ -432,6 +432,137 @@ def gather_segment_reduce(op, params, gather_indices, size, seg_ptr=None, count=
                                       int(size), op, bool(validate), out_dtype)
 
 
+# ---- per-column top-k of a sampled block (LGCN: utils/encoders.py:872-922) --------------------
+def _segment_topk_raw(params, gi, sp, count, e, size, k, fill, od, want_sel):
+    """euler_gpu_gather_segment_topk on prepared tensors -> (out [size, k, d], sel [size, k, d] | None)"""
+    d = params.shape[1]
+    make = torch.zeros if size == 0 or d == 0 else torch.empty
+    out = make((size, k, d), dtype=od, device=params.device)
+    sel = make((size, k, d), dtype=torch.int32, device=params.device) if want_sel else None
+    if size == 0 or d == 0:
+        return out, sel
+    with _on(params.device):
+        check(lib().euler_gpu_gather_segment_topk(
+            _stream(), _ptr(params), _DT[params.dtype], int(params.shape[0]), _ptr(gi),
+            int(gi is not None and gi.dtype == torch.int64), _ptr(sp), int(count), e, d, size, k, float(fill),
+            _ptr(out), _DT[od], _ptr(sel)))
+    return out, sel
+
+
+def _segment_topk_grad_raw(grad, sel, e):
+    """euler_gpu_segment_topk_grad -> the fp32 per-edge block [e, d]: grad at the selected positions,
+    +0 elsewhere"""
+    size, k, d = sel.shape
+    if e == 0 or d == 0:
+        return torch.zeros((e, d), dtype=_F32, device=sel.device)
+    if grad.dtype not in _DT:
+        grad = grad.to(_F32)
+    grad = grad.contiguous()
+    per_edge = torch.empty((e, d), dtype=_F32, device=sel.device)
+    with _on(sel.device):
+        check(lib().euler_gpu_segment_topk_grad(_stream(), _ptr(grad), _DT[grad.dtype], _ptr(sel), e, d, size, k,
+                                                _ptr(per_edge)))
+    return per_edge
+
+
+class _GatherSegmentTopk(torch.autograd.Function):
+    """The fused top-k; the gradient is the composition's: grad lands on the selected positions
+    (the helper kernel, one writer per element) and the existing scatter-add carries the per-edge
+    block to the rows of params - in input order, indices that name no row left out."""
+
+    @staticmethod
+    def forward(ctx, params, gi, sp, count, e, size, k, fill, od, return_indices, need):
+        out, sel = _segment_topk_raw(params, gi, sp, count, e, size, k, fill, od, need or return_indices)
+        if need:
+            ctx.save_for_backward(sel, gi if gi is not None else torch.empty(0))
+            ctx.conf = (gi is not None, e, int(params.shape[0]), params.dtype)
+        if not return_indices:
+            return out, None
+        ctx.mark_non_differentiable(sel)
+        return out, sel
+
+    @staticmethod
+    def backward(ctx, grad, _unused=None):
+        sel, gi = ctx.saved_tensors
+        has_gi, e, rows, dt = ctx.conf
+        if e == 0 or sel.shape[2] == 0:
+            return (torch.zeros((rows, sel.shape[2]), dtype=dt, device=sel.device),) + (None,) * 10
+        per_edge = _segment_topk_grad_raw(grad, sel, e)
+        if not has_gi:      # position p is row p; scatter_add leaves out the positions past the table
+            gi = torch.arange(e, device=sel.device, dtype=torch.int32)
+        elif gi.dtype == torch.int64:
+            gi = torch.where((gi >= 0) & (gi < rows), gi, torch.full_like(gi, -1))
+        return (_scatter_raw(_ADD, per_edge, gi, rows).to(dt),) + (None,) * 10
+
+
+def gather_segment_topk(params, gather_indices, size, k, seg_ptr=None, count=None, fill=0.0, out_dtype=None,
+                        return_indices=False, validate=False):
+    """The step of the reference's LGCEncoder (LGCN, utils/encoders.py:911-914: get_dense_feature,
+    reshape [B, nb, d], transpose, tf.nn.top_k, transpose) in one pass: for destination r and
+    EVERY COLUMN c on its own, the k largest values among params[gather_indices[p]][c] over the
+    positions p of r's segment - [seg_ptr[r], seg_ptr[r + 1]) or its `count` consecutive positions,
+    as gather_segment_reduce - in descending order.  Returns out [size, k, d] in the dtype of
+    params (fp32, bf16 or fp16) or fp32 (out_dtype); with return_indices=True also sel
+    [size, k, d] int32, the position p each entry came from.
+    gather_indices: int32 indices, the int64 ids a sampler returned (read in place, compared in 64
+    bits), or None (position p reads row p).  RANGE RULE: an index outside [0, rows) names no row;
+    it is never dereferenced, reads as a row of +0 and does take part as a candidate - the zero
+    feature row of a default_node fill enters the reference's top_k too - and gets no gradient.
+    ORDER: larger first, NaN greatest (as torch.topk); among equals (+0 == -0, NaN == NaN) the
+    earlier position first, so the result is the stable descending sort.  An entry j >= the
+    segment's length is `fill` (rounded once to the output dtype) with sel = -1.  1 <= k <= 16.
+    A pure selection: out carries the bits of the table's elements (a NaN stays a NaN), the same on
+    every call, and equals torch.topk(gather(params, gi).view(B, nb, d), k, dim=1) wherever the
+    values of a column are distinct - without the [E, d] block or the transposes.
+    The gradient of params is the composition's: grad at the selected positions, scatter-added in
+    input order and rounded once to the dtype of params.  sel is kept, and asked of the kernel,
+    only when params needs a gradient or return_indices is set.  No host wait (validate=True
+    checks the gather indices first, which is one)."""
+    _dt("gather_segment_topk", params)
+    od = _out_dt("gather_segment_topk", params, out_dtype)
+    if params.dim() != 2 or params.shape[0] < 1:
+        raise ValueError("gather_segment_topk: params is [rows, d], one row at least")
+    if (seg_ptr is None) == (count is None):
+        raise ValueError("gather_segment_topk: pass seg_ptr or count")
+    size, k = int(size), int(k)
+    if not 1 <= k <= 16:
+        raise ValueError("gather_segment_topk: k is 1..16")
+    if size < 0 or size >= 2 ** 31:
+        raise ValueError("gather_segment_topk: size is 0 .. 2^31 - 1")
+    params = params.contiguous()
+    _need_cuda(params)
+    gi = gather_indices
+    if gi is not None:
+        if gi.dtype.is_floating_point or gi.dtype == torch.bool:
+            raise ValueError("gather_segment_topk: gather indices are integers, not %s" % gi.dtype)
+        gi = gi.reshape(-1)
+        gi = gi.contiguous() if gi.dtype == torch.int64 else gi.to(torch.int32).contiguous()
+        _need_cuda(params, gi)
+        if validate:
+            _check_rows("gather_segment_topk", gi, params.shape[0])
+    sp = None
+    if seg_ptr is not None:
+        sp = seg_ptr.to(torch.int64).contiguous()
+        _need_cuda(params, sp)
+        if sp.numel() != size + 1:
+            raise ValueError("gather_segment_topk: seg_ptr has size + 1 entries")
+        e = gi.numel() if gi is not None else int(params.shape[0])
+        count = 0
+    else:
+        count = int(count)
+        if count < 1:
+            raise ValueError("gather_segment_topk: count >= 1")
+        e = size * count
+        if gi is not None and gi.numel() != e:
+            raise ValueError("gather_segment_topk: size * count gather indices")
+    if e >= 2 ** 31:
+        raise ValueError("gather_segment_topk: fewer than 2^31 positions")
+    # (the positions are asked of the kernel only where a backward pass can follow)
+    need = params.requires_grad and torch.is_grad_enabled()
+    out, sel = _GatherSegmentTopk.apply(params, gi, sp, count, e, size, k, float(fill), od, bool(return_indices), need)
+    return (out, sel) if return_indices else out
+
+
 # ---- edge-weighted aggregation ---------------------------------------------------------------
 def _edge_weight(name, w, e, params):
     """checks an edge_weight argument; -> (the weights as a contiguous [E, H] tensor, H)"""

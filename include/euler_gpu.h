@@ -1070,6 +1070,42 @@ int euler_gpu_store_add(void* stream, void* table_dev, int32_t table_dtype, int6
 int euler_gpu_store_take(void* stream, void* table_dev, int32_t table_dtype, int64_t rows,
                          int64_t d, const int64_t* ids_dev, int64_t e, int32_t clear,
                          void* out_dev, int32_t out_dtype);
+/* gather_segment_topk: the step of the reference's LGCEncoder (LGCN,
+ * tf_euler/python/utils/encoders.py:911-914: get_dense_feature, reshape [B, nb, d], transpose,
+ * tf.nn.top_k, transpose) in one pass - for every destination r and every column c the k largest
+ * values among the rows its segment gathers, in descending order, without the [e, d] block.  The
+ * rules are stated in euler_amd/csrc/mp_topk.h:
+ * Segment of r: seg_ptr_dev[r] .. seg_ptr_dev[r + 1] (int64 [size + 1]), or r * count ..
+ * (r + 1) * count (seg_ptr_dev NULL, count > 0, e == size * count); exactly one of the two.
+ * Candidate of position p and column c: params[g[p]][c] widened exactly to fp32, g = gather_dev:
+ * int32 [e] (gather_is_ids == 0), signed int64 ids [e] (gather_is_ids != 0, compared in 64 bits)
+ * or NULL (g[p] = p).  An index outside [0, params_rows) names no row: it is never dereferenced,
+ * reads as a row of +0 and DOES take part as a candidate (a default_node fill's feature row is
+ * zeros in the reference); its gradient is dropped.
+ * Order: a precedes b iff a > b, or a is NaN and b is not (NaN greatest, as torch.topk); otherwise
+ * the earlier position precedes (stable); +0 == -0, NaN == NaN.
+ * out_dev [size, k, d] (fp32 or in_dtype): out[r][j][c] = the j-th candidate in that order for
+ * j < min(k, len) - the bits of the table element for every non-NaN, a NaN for a NaN -, `fill`
+ * rounded once to out_dtype for j >= len.  sel_dev [size, k, d] int32 (NULL: not wanted): that
+ * candidate's position p, -1 for j >= len.
+ * segment_topk_grad: per_edge_dev [e, d] fp32 is +0 everywhere except
+ * per_edge[sel[r][j][c]][c] = grad[r][j][c] (grad_dev [size, k, d], fp32 / bf16 / fp16, widened)
+ * for sel >= 0 - one writer per element at most, no atomics; positions outside every segment stay
+ * +0.  The table gradient is the scatter_add of per_edge by g, indices outside the table left out.
+ * Both only enqueue on `stream`: no allocation, no host wait, no LDS, no atomics.
+ * EULER_GPU_EINVAL: k outside 1..16, an unknown dtype, out_dtype neither fp32 nor in_dtype, both
+ * or neither of seg_ptr_dev / count, the count form with e != size * count, e or d >= 2^31 (or a
+ * negative extent), a null required buffer, params_rows < 1, a buffer not aligned to its element
+ * type; every check precedes the first write.  size == 0 or d == 0 (grad: e == 0 or d == 0)
+ * returns EULER_GPU_OK and touches nothing. */
+int euler_gpu_gather_segment_topk(void* stream, const void* params_dev, int32_t in_dtype,
+                                  int64_t params_rows, const void* gather_dev,
+                                  int32_t gather_is_ids, const int64_t* seg_ptr_dev, int64_t count,
+                                  int64_t e, int64_t d, int32_t size, int32_t k, float fill,
+                                  void* out_dev, int32_t out_dtype, int32_t* sel_dev);
+int euler_gpu_segment_topk_grad(void* stream, const void* grad_dev, int32_t grad_dtype,
+                                const int32_t* sel_dev, int64_t e, int64_t d, int32_t size,
+                                int32_t k, float* per_edge_dev);
 
 /* ---- shard ops (multi-GPU) --------------------------------------------------
  * ID_SPLIT (core/kernels/id_split_op.cc:46-99): stable bucket of ids by
