@@ -701,11 +701,12 @@ __global__ void SegLenKernel(const int32_t* idx, const int32_t* gather_idx,
 }
 
 __global__ void EmitIdxKernel(const int64_t* len, const int64_t* off, int64_t n,
-                              int32_t* out_idx) {
+                              int32_t* out_idx, int64_t* total) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) {
     out_idx[2 * i] = (int32_t)off[i];
     out_idx[2 * i + 1] = (int32_t)(off[i] + len[i]);
+    if (i == n - 1) *total = off[i] + len[i];      // in 64 bits: the host refuses >= 2^31
   }
 }
 
@@ -1231,11 +1232,13 @@ int euler_gpu_idx_gather(void* stream, const int32_t* idx_dev,
   int rc = ExclusiveScanI64(st, len, off, n);
   if (rc != EULER_GPU_OK) return rc;
   hipLaunchKernelGGL(EmitIdxKernel, grid, dim3(block), 0, st, len, off, n,
-                     out_idx_dev);
-  int32_t last[2];
-  EG_HIP(hipMemcpyAsync(last, out_idx_dev + 2 * (n - 1), 8, hipMemcpyDeviceToHost, st));
+                     out_idx_dev, off + n);
+  int64_t total = 0;
+  EG_HIP(hipMemcpyAsync(&total, off + n, 8, hipMemcpyDeviceToHost, st));
   EG_HIP(hipStreamSynchronize(st));
-  if (total_host) *total_host = last[1];
+  // (out_idx holds wrapped offsets then: DATA_GATHER must not be run through it)
+  if (total >= (1LL << 31)) return Fail(EULER_GPU_EINVAL, "idx_gather: total >= 2^31");
+  if (total_host) *total_host = total;
   return EULER_GPU_OK;
 }
 

@@ -57,13 +57,15 @@ __global__ void FullNbCountKernel(const FullNbArgs a, int64_t* counts) {
   if (i < a.n) counts[i] = FullNbCount(a, FindRow(a.g, a.ids[i]));
 }
 
-// idx[i] = (offset[i], offset[i+1]) as int32 pairs (FillNeighbor layout).
+// idx[i] = (offset[i], offset[i+1]) as int32 pairs (FillNeighbor layout); the call's total
+// goes out in 64 bits, for the host to refuse what the int32 pairs cannot hold.
 __global__ void OffsetsToIdxKernel(const int64_t* counts, const int64_t* offsets,
-                                   int64_t n, int32_t* idx) {
+                                   int64_t n, int32_t* idx, int64_t* total) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) {
     idx[2 * i] = (int32_t)offsets[i];
     idx[2 * i + 1] = (int32_t)(offsets[i] + counts[i]);
+    if (i == n - 1) *total = offsets[i] + counts[i];
   }
 }
 
@@ -1630,11 +1632,13 @@ int euler_gpu_get_full_neighbor(const euler_gpu_graph* g, void* stream,
     int rc = ExclusiveScanI64(st, counts, offsets, n);
     if (rc != EULER_GPU_OK) return rc;
     hipLaunchKernelGGL(OffsetsToIdxKernel, dim3((n + block - 1) / block),
-                       dim3(block), 0, st, counts, offsets, n, idx_dev);
-    int32_t last[2];
-    EG_HIP(hipMemcpyAsync(last, idx_dev + 2 * (n - 1), 8, hipMemcpyDeviceToHost, st));
+                       dim3(block), 0, st, counts, offsets, n, idx_dev, offsets + n);
+    int64_t total = 0;
+    EG_HIP(hipMemcpyAsync(&total, offsets + n, 8, hipMemcpyDeviceToHost, st));
     EG_HIP(hipStreamSynchronize(st));
-    if (total_host) *total_host = last[1];
+    // (idx holds wrapped offsets then: nothing may be filled through it)
+    if (total >= (1LL << 31)) return Fail(EULER_GPU_EINVAL, "get_full_neighbor: total >= 2^31");
+    if (total_host) *total_host = total;
     return EULER_GPU_OK;
   }
   if (g_full_nb_balanced != 0) {

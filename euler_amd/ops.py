@@ -1471,6 +1471,12 @@ def inflate_idx(idx):
     ValueError (the reference's InvalidArgument), a non-vector too."""
     if idx.dim() != 1:
         raise ValueError("InflateIdx expects a 1-D vector.")
+    if idx.dtype != torch.int32 and idx.numel():
+        # before the narrowing: a value such as 2^32 + 1 would wrap into range and be answered.
+        # The number of distinct values is at most numel(), so this refuses nothing valid.
+        lo, hi = torch.aminmax(idx)
+        if int(lo) < 0 or int(hi) >= idx.numel():
+            raise ValueError("InflateIdx: expect input idx in [0,unique_cnt).")
     idx = idx.to(torch.int32).contiguous()
     _need_cuda(idx)
     out = torch.empty_like(idx)

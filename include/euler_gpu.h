@@ -394,7 +394,9 @@ int euler_gpu_sample_n_with_types(const euler_gpu_graph* g, void* stream, uint64
  * (core/graph/node.cc:175-197) in the FillNeighbor layout.  Two calls: first
  * with out_id_dev == NULL fills idx_dev [n,2] (int32 offsets) and *total_host
  * (synchronises the stream); the second call writes the values (out_t_dev may be
- * NULL: the edge types are not written - the sharded node2vec walk does not read them). */
+ * NULL: the edge types are not written - the sharded node2vec walk does not read them).
+ * A call that lists 2^31 entries or more does not fit the int32 offsets: the first call
+ * returns EULER_GPU_EINVAL, leaves *total_host alone, and idx_dev is not to be used. */
 int euler_gpu_get_full_neighbor(const euler_gpu_graph* g, void* stream,
                                 const uint64_t* ids_dev, int64_t n,
                                 const int32_t* edge_types_host, int32_t k,
@@ -767,7 +769,9 @@ int euler_gpu_gen_pair(void* stream, const int64_t* paths_dev, int64_t batch,
 /* ---- ID_UNIQUE / IDX_GATHER / DATA_GATHER ----------------------------------
  * core/kernels/id_unique_op.cc:35-64 (first-occurrence order),
  * idx_gather_op.cc:33-55, data_gather_op.cc:33-80.
- * euler_gpu_id_unique synchronises the stream to return *n_unique_host. */
+ * euler_gpu_id_unique synchronises the stream to return *n_unique_host, euler_gpu_idx_gather
+ * to return *total_host; gathered segments of 2^31 entries or more in all do not fit the int32
+ * offsets: EULER_GPU_EINVAL, *total_host left alone, out_idx_dev not to be used. */
 int euler_gpu_id_unique(void* stream, const uint64_t* ids_dev, int64_t n,
                         uint64_t* unique_dev, int32_t* gather_idx_dev,
                         int64_t* n_unique_host);
