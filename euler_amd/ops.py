@@ -1503,6 +1503,21 @@ def id_split(ids, partitions, shards):
     return list(off), sid, mi
 
 
+def _root_mask_arg(name, root_mask, n, root_group):
+    """root_mask as contiguous uint8, with a byte for every group of n positions: the kernels
+    index it by position // group and do not know its length"""
+    if root_mask is None:
+        return None
+    root_mask = root_mask.to(torch.uint8).contiguous()
+    _need_cuda(root_mask)
+    group = max(int(root_group), 1)
+    need = (n + group - 1) // group
+    if root_mask.numel() < need:
+        raise ValueError("%s: root_mask has %d elements, %d positions in groups of %d need %d"
+                         % (name, root_mask.numel(), n, group, need))
+    return root_mask
+
+
 def dedup_split(ids, partitions, shards, root_mask=None, root_group=1, dense_table=None):
     """Distinct ids bucketed by owner + the bucketed index of every position
     (ID_UNIQUE + ID_SPLIT in one call, one host sync).  Returns (shard_off
@@ -1514,8 +1529,7 @@ def dedup_split(ids, partitions, shards, root_mask=None, root_group=1, dense_tab
     ids = ids.to(torch.int64).contiguous().reshape(-1)
     _need_cuda(ids)
     n = ids.numel()
-    if root_mask is not None:
-        root_mask = root_mask.to(torch.uint8).contiguous()
+    root_mask = _root_mask_arg("dedup_split", root_mask, n, root_group)
     limit = 0
     if dense_table is not None:
         _need_cuda(dense_table)
@@ -1547,8 +1561,7 @@ class FrontHandle(object):
         ids = ids.to(torch.int64).contiguous().reshape(-1)
         _need_cuda(ids)
         n = ids.numel()
-        if root_mask is not None:
-            root_mask = root_mask.to(torch.uint8).contiguous()
+        root_mask = _root_mask_arg("FrontHandle.begin", root_mask, n, root_group)
         limit = dense_table.numel() - 1 if dense_table is not None else 0
         sid = torch.empty(n, dtype=torch.int64, device=ids.device)
         pos = torch.empty(n, dtype=torch.int32, device=ids.device)
