@@ -1215,6 +1215,147 @@ def triple_score(ent, rel, src, rel_id, dst, neg=None, kind="trans_l1", corrupt=
     return pos if neg is None else (pos, out)
 
 
+_KG_PROJ = {"hyperplane": 1, "transfer": 2}
+
+
+def _triple_proj_head(proj, ent, ent_aux, rel, rel_aux, src, rel_id, dst, neg, kind, corrupt):
+    """the arguments the two triple_score_proj entries share, from prepared tensors"""
+    b, k = src.numel(), (neg.shape[1] if neg is not None else 0)
+    return (_stream(), _KG_PROJ[proj], _KG_KIND[kind], _KG_CORRUPT[corrupt],
+            _ptr(ent), _ptr(ent_aux), _DT[ent.dtype], ent.shape[0], _ptr(rel), _ptr(rel_aux), _DT[rel.dtype],
+            rel.shape[0], _ptr(src), _ptr(rel_id), _ptr(dst), _ptr(neg), b, k, ent.shape[1])
+
+
+def _triple_score_proj_raw(proj, ent, ent_aux, rel, rel_aux, src, rel_id, dst, neg, kind, corrupt):
+    """euler_gpu_triple_score_proj on prepared tensors -> (pos [B], neg_out [B, K'])"""
+    b, k, d = src.numel(), (neg.shape[1] if neg is not None else 0), ent.shape[1]
+    kp = 2 * k if corrupt == "both" else k
+    if b == 0 or d == 0:
+        return torch.zeros(b, dtype=_F32, device=ent.device), torch.zeros((b, kp), dtype=_F32, device=ent.device)
+    pos = torch.empty(b, dtype=_F32, device=ent.device)
+    out = torch.empty((b, kp), dtype=_F32, device=ent.device)
+    with _on(ent.device):
+        check(lib().euler_gpu_triple_score_proj(
+            *_triple_proj_head(proj, ent, ent_aux, rel, rel_aux, src, rel_id, dst, neg, kind, corrupt),
+            _ptr(pos), _ptr(out) if k else None))
+    return pos, out
+
+
+def _triple_score_proj_grad_raw(proj, ent, ent_aux, rel, rel_aux, src, rel_id, dst, neg, kind, corrupt, g_pos, g_neg):
+    """euler_gpu_triple_score_proj_grad -> the fp32 gradients of the raw rows per occurrence:
+    (G_src, G_rel, G_dst [B, d], G_neg [B, K, d], G_rel_aux [B, d], then for "transfer" G_src_aux,
+    G_dst_aux [B, d] and G_neg_aux [B, K, d], else three None)"""
+    b, k, d = src.numel(), (neg.shape[1] if neg is not None else 0), ent.shape[1]
+    make = torch.zeros if b == 0 or d == 0 else torch.empty
+    flat = lambda: make((b, d), dtype=_F32, device=ent.device)                          # noqa: E731
+    block = lambda: make((b, k, d), dtype=_F32, device=ent.device)                      # noqa: E731
+    gs, gr, gd, gn, gra = flat(), flat(), flat(), block(), flat()
+    gsa, gda, gna = (flat(), flat(), block()) if proj == "transfer" else (None, None, None)
+    if b == 0 or d == 0:
+        return gs, gr, gd, gn, gra, gsa, gda, gna
+    g_pos = g_pos.to(_F32).contiguous()
+    g_neg = g_neg.to(_F32).contiguous() if k else None
+    with _on(ent.device):
+        check(lib().euler_gpu_triple_score_proj_grad(
+            *_triple_proj_head(proj, ent, ent_aux, rel, rel_aux, src, rel_id, dst, neg, kind, corrupt),
+            _ptr(g_pos), _ptr(g_neg), _ptr(gs), _ptr(gr), _ptr(gd), _ptr(gn) if k else None, _ptr(gra),
+            _ptr(gsa), _ptr(gda), _ptr(gna) if k and gna is not None else None))
+    return gs, gr, gd, gn, gra, gsa, gda, gna
+
+
+class _TripleScoreProj(torch.autograd.Function):
+    """The fused scores with a projection; the tables' gradients are the composition's, as
+    _TripleScore's: the per-occurrence rows go through _table_grad at [src | dst | neg] (ent,
+    ent_transfer) and at rel_id (rel, hyper / rel_transfer).  ent_aux is None for "hyperplane"."""
+
+    @staticmethod
+    def forward(ctx, ent, ent_aux, rel, rel_aux, src, rel_id, dst, neg, proj, kind, corrupt, sparse_grad):
+        ctx.save_for_backward(ent, ent_aux, rel, rel_aux, src, rel_id, dst, neg)
+        ctx.conf = (proj, kind, corrupt, sparse_grad)
+        return _triple_score_proj_raw(proj, ent, ent_aux, rel, rel_aux, src, rel_id, dst, neg, kind, corrupt)
+
+    @staticmethod
+    def backward(ctx, g_pos, g_neg):
+        ent, ent_aux, rel, rel_aux, src, rel_id, dst, neg = ctx.saved_tensors
+        proj, kind, corrupt, sparse_grad = ctx.conf
+        gs, gr, gd, gn, gra, gsa, gda, gna = _triple_score_proj_grad_raw(
+            proj, ent, ent_aux, rel, rel_aux, src, rel_id, dst, neg, kind, corrupt, g_pos, g_neg)
+        ids = torch.cat([src, dst] + ([neg.reshape(-1)] if neg is not None else []))
+
+        def ent_grad(a, c, n, table):
+            rows = [a, c] + ([n.reshape(-1, n.shape[2])] if neg is not None else [])
+            return _table_grad(torch.cat(rows), ids, table.shape[0], table.dtype, sparse_grad)
+
+        g_ent = ent_grad(gs, gd, gn, ent) if ctx.needs_input_grad[0] else None
+        g_ent_aux = ent_grad(gsa, gda, gna, ent_aux) if ent_aux is not None and ctx.needs_input_grad[1] else None
+        g_rel = _table_grad(gr, rel_id, rel.shape[0], rel.dtype, sparse_grad) if ctx.needs_input_grad[2] else None
+        g_rel_aux = _table_grad(gra, rel_id, rel_aux.shape[0], rel_aux.dtype, sparse_grad) \
+            if ctx.needs_input_grad[3] else None
+        return (g_ent, g_ent_aux, g_rel, g_rel_aux) + (None,) * 8
+
+
+def triple_score_proj(ent, rel, src, rel_id, dst, neg=None, proj="hyperplane", hyper=None, ent_transfer=None,
+                      rel_transfer=None, kind="trans_l1", corrupt="both", sparse_grad=False):
+    """triple_score with the projection of TransH or TransD fused in (generate_embedding of the
+    reference's examples/TransX/transH.py:43-66 and transD.py:46-73): the lookups of the extra
+    tables, the projection of every entity row, the normalisations and the scores in one pass,
+    without any [B, K, d] block.  N is tf.nn.l2_normalize with its 1e-12 clamp.
+        proj "hyperplane" (TransH)  hyper [relations, d]: w = N(hyper[rel_id]); an entity row x is
+             not normalised and becomes x - (x . w) w
+        proj "transfer" (TransD)    ent_transfer [rows, d], rel_transfer [relations, d]: with
+             rho = rel_transfer[rel_id] and a = ent_transfer[id] an entity row x = ent[id] becomes
+             N(x + (x . a) rho)
+    r = N(rel[rel_id]) in both.  kind is "trans_l1" or "trans_l2" ("distmult" takes no projection);
+    corrupt, the returned pos [B] and neg [B, K'] (pos alone when neg is None) and the rule for
+    ids that name no row are triple_score's.  ent_transfer has ent's dtype and rows, hyper /
+    rel_transfer have rel's; each pair is fp32, bf16 or fp16.  All arithmetic is fp32 in a fixed
+    order (euler_amd/csrc/kg_proj.h); the same call returns the same bits.  Gradients reach every
+    table passed, as triple_score's: the kernel's per-row gradients are added at the keys
+    [src | dst | neg] (ent, ent_transfer) / rel_id (rel, hyper, rel_transfer) by scatter_add and
+    rounded once to the table's dtype; sparse_grad=True returns sparse_coo tensors over the
+    distinct rows.  No host wait on the forward path."""
+    name = "triple_score_proj"
+    if proj not in _KG_PROJ:
+        raise ValueError("%s: proj is hyperplane or transfer" % name)
+    if kind not in ("trans_l1", "trans_l2"):
+        raise ValueError("%s: kind is trans_l1 or trans_l2 (distmult takes no projection)" % name)
+    if corrupt not in _KG_CORRUPT:
+        raise ValueError("%s: corrupt is front, tail or both" % name)
+    if proj == "hyperplane":
+        if hyper is None or ent_transfer is not None or rel_transfer is not None:
+            raise ValueError("%s: proj hyperplane takes hyper and neither ent_transfer nor rel_transfer" % name)
+        ent_aux, rel_aux = None, hyper
+    else:
+        if hyper is not None or ent_transfer is None or rel_transfer is None:
+            raise ValueError("%s: proj transfer takes ent_transfer and rel_transfer and no hyper" % name)
+        ent_aux, rel_aux = ent_transfer, rel_transfer
+    for t in (ent, rel, rel_aux) + (() if ent_aux is None else (ent_aux,)):
+        _dt(name, t)
+    if ent.dim() != 2 or rel.dim() != 2 or ent.shape[1] != rel.shape[1] or ent.shape[0] < 1 or rel.shape[0] < 1:
+        raise ValueError("%s: ent is [rows, d] and rel is [relations, d], one row at least" % name)
+    if rel_aux.shape != rel.shape or (ent_aux is not None and ent_aux.shape != ent.shape):
+        raise ValueError("%s: ent_transfer has ent's shape, hyper / rel_transfer have rel's" % name)
+    if rel_aux.dtype != rel.dtype or (ent_aux is not None and ent_aux.dtype != ent.dtype):
+        raise TypeError("%s: ent_transfer has ent's dtype, hyper / rel_transfer have rel's" % name)
+    src, rel_id, dst = (t.to(torch.int64).reshape(-1).contiguous() for t in (src, rel_id, dst))
+    b = src.numel()
+    if rel_id.numel() != b or dst.numel() != b:
+        raise ValueError("%s: one src, rel_id and dst per triple" % name)
+    if neg is not None:
+        neg = neg.to(torch.int64)
+        neg = (neg if neg.dim() == 2 else neg.reshape(b, -1)).contiguous()
+        if neg.shape[0] != b:
+            raise ValueError("%s: neg is [B, K]" % name)
+    _need_cuda(ent, rel, rel_aux, src, rel_id, dst, *(() if neg is None else (neg,)),
+               *(() if ent_aux is None else (ent_aux,)))
+    if b * max(1 if neg is None else neg.shape[1], 1) * 2 >= 2 ** 31 or ent.shape[0] >= 2 ** 31:
+        raise ValueError("%s: B * max(K, 1) * 2 and the table's rows must stay below 2^31" % name)
+    pos, out = _TripleScoreProj.apply(ent.contiguous(), None if ent_aux is None else ent_aux.contiguous(),
+                                      rel.contiguous(), rel_aux.contiguous(), src, rel_id, dst, neg, proj, kind,
+                                      corrupt, bool(sparse_grad))
+    return pos if neg is None else (pos, out)
+
+
 # ---- in-place embedding stores (tf_euler/python/utils/embedding.py:24-68) ---------------------
 # The stores of ScalableSageEncoder / ScalableGCNEncoder (utils/encoders.py:629-748, 294-409): a
 # non-trainable [max_id + 1, d] table per layer that lives in HBM across steps and is changed IN

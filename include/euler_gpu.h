@@ -1040,6 +1040,52 @@ int euler_gpu_triple_score_grad(void* stream, int32_t kind, int32_t normalize, i
                                 int64_t k, int64_t d, const float* g_pos_dev,
                                 const float* g_neg_dev, float* g_src_dev, float* g_rel_dev,
                                 float* g_dst_dev, float* g_neg_rows_dev);
+/* triple_score_proj: triple_score with the projection of TransH or TransD fused in
+ * (projection / generate_embedding of examples/TransX/transH.py:43-66 and transD.py:46-73): the
+ * lookups of the extra tables, the projection of every entity row, the normalisations and the
+ * scores in one pass, no [b, k, d] intermediate.  N(x) is tf.nn.l2_normalize as in triple_score.
+ * proj 1 "hyperplane" (TransH): ent_aux_dev is NULL and rel_aux_dev is hyper [rel_rows, d];
+ *   w = N(hyper[rel_id]), r = N(rel[rel_id]); an entity row x is NOT normalised and becomes
+ *   x - (sum x * w) w; the scores take the projected h, t, n_j.
+ * proj 2 "transfer" (TransD): ent_aux_dev is ent_transfer [ent_rows, d] and rel_aux_dev is
+ *   rel_transfer [rel_rows, d]; with rho = rel_transfer[rel_id] (raw), x = ent[i] and
+ *   a = ent_transfer[i] an entity row becomes N(x + (sum x * a) rho); r = N(rel[rel_id]).
+ * kind is 0 trans_l1 or 1 trans_l2 of triple_score; corrupt, pos_out_dev [b] and neg_out_dev
+ * [b, K'] are triple_score's; the projection of n_j serves its front and its tail score.  The
+ * tables indexed by an entity id share ent_dtype and ent_rows, those indexed by a relation id
+ * rel_dtype and rel_rows (fp32, bf16 or fp16, widened exactly).  Ids are signed int64; an id
+ * outside [0, rows) names no row in any table it indexes: it is never dereferenced, reads as
+ * zeros and gets zero gradient rows.  All arithmetic is fp32 in the fixed order stated in
+ * euler_amd/csrc/kg_proj.h (it depends on d, the types and the alignment of all tables passed,
+ * never on b, k or the launch).
+ * triple_score_proj_grad: from g_pos_dev [b] and g_neg_dev [b, K'] the fp32 gradients of the RAW
+ * rows per occurrence - g_src_dev, g_rel_dev, g_dst_dev [b, d] and g_neg_rows_dev [b, k, d] as in
+ * triple_score_grad, g_rel_aux_dev [b, d] for hyper / rel_transfer and, for proj 2 only (NULL for
+ * proj 1), g_src_aux_dev, g_dst_aux_dev [b, d] and g_neg_aux_rows_dev [b, k, d] for ent_transfer;
+ * a table's gradient is their scatter_add by id.
+ * Both only enqueue: no allocation, no host wait.  EULER_GPU_EINVAL: the rules of triple_score,
+ * proj outside 1..2, kind outside 0..1 (distmult takes no projection), a missing aux table or
+ * aux gradient buffer, an aux table or aux gradient buffer that should be NULL.  b == 0 or
+ * d == 0 returns EULER_GPU_OK and touches nothing; k == 0 leaves the negative outputs untouched
+ * (neg_dev and they may be NULL). */
+int euler_gpu_triple_score_proj(void* stream, int32_t proj, int32_t kind, int32_t corrupt,
+                                const void* ent_dev, const void* ent_aux_dev, int32_t ent_dtype,
+                                int64_t ent_rows, const void* rel_dev, const void* rel_aux_dev,
+                                int32_t rel_dtype, int64_t rel_rows, const int64_t* src_dev,
+                                const int64_t* rel_id_dev, const int64_t* dst_dev,
+                                const int64_t* neg_dev, int64_t b, int64_t k, int64_t d,
+                                float* pos_out_dev, float* neg_out_dev);
+int euler_gpu_triple_score_proj_grad(void* stream, int32_t proj, int32_t kind, int32_t corrupt,
+                                     const void* ent_dev, const void* ent_aux_dev,
+                                     int32_t ent_dtype, int64_t ent_rows, const void* rel_dev,
+                                     const void* rel_aux_dev, int32_t rel_dtype, int64_t rel_rows,
+                                     const int64_t* src_dev, const int64_t* rel_id_dev,
+                                     const int64_t* dst_dev, const int64_t* neg_dev, int64_t b,
+                                     int64_t k, int64_t d, const float* g_pos_dev,
+                                     const float* g_neg_dev, float* g_src_dev, float* g_rel_dev,
+                                     float* g_dst_dev, float* g_neg_rows_dev, float* g_rel_aux_dev,
+                                     float* g_src_aux_dev, float* g_dst_aux_dev,
+                                     float* g_neg_aux_rows_dev);
 /* store_update / store_add / store_take: the in-place embedding stores of ScalableSage /
  * ScalableGCN (tf_euler/python/utils/embedding.py:24-68, encoders.py:713-748) - tf.scatter_update,
  * tf.scatter_add and embedding_lookup with the optional clearing update of encoders.py:738-743 -
