@@ -178,72 +178,20 @@ __global__ __launch_bounds__(256) void SegmentReduceVec8Kernel(
 }
 
 template <int MODE, int DT, bool OUT16>
-int LaunchReduce(hipStream_t st, const void* upd, const SegSpec& seg, const uint32_t* perm,
-                 const int32_t* gsrc, int64_t d, void* out, int32_t gstride, uint32_t row_max) {
-  const dim3 block(64, 4);
-  const int64_t d8 = d / 8;
-  const int32_t size = seg.size;
-  if (d % 8 == 0 && d8 <= 64 && 64 % d8 == 0 && ((uintptr_t)upd % 16 == 0) &&
-      ((uintptr_t)out % 16 == 0)) {
-    const int64_t rows_per_block = 4 * (64 / d8);
-    int64_t blocks = ((int64_t)size + rows_per_block - 1) / rows_per_block;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL((SegmentReduceVec8Kernel<MODE, DT, OUT16>), dim3((unsigned)blocks), block, 0, st,
-                       static_cast<const uint4*>(upd), seg, perm, gsrc, (int32_t)d8, out, gstride, row_max);
+int LaunchReduce(hipStream_t st, const void* upd, const SegSpec& seg, const MpwIndex& ix, int64_t d,
+                 void* out) {
+  const LaneShape s = RowLaneShape(seg.size, d, 8, 0, upd, out);
+  if (s.vec) {
+    hipLaunchKernelGGL((SegmentReduceVec8Kernel<MODE, DT, OUT16>), dim3(s.blocks), dim3(64, 4), 0, st,
+                       static_cast<const uint4*>(upd), seg, ix.perm, ix.gsrc, (int32_t)s.dv, out, ix.gstride,
+                       ix.row_max);
   } else {
-    int64_t blocks = ((int64_t)size + 3) / 4;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL((SegmentReduceHalfKernel<MODE, DT, OUT16>), dim3((unsigned)blocks), block, 0, st,
-                       static_cast<const uint16_t*>(upd), seg, perm, gsrc, d, out, gstride, row_max);
+    hipLaunchKernelGGL((SegmentReduceHalfKernel<MODE, DT, OUT16>), dim3(s.blocks), dim3(64, 4), 0, st,
+                       static_cast<const uint16_t*>(upd), seg, ix.perm, ix.gsrc, d, out, ix.gstride,
+                       ix.row_max);
   }
   EG_HIP(hipGetLastError());
   return EULER_GPU_OK;
-}
-
-// in_dtype is bf16 or fp16, out_dtype fp32 or in_dtype (checked by the entries)
-int DispatchReduce(hipStream_t st, int32_t mode, int32_t in_dtype, int32_t out_dtype, const void* upd,
-                   const SegSpec& seg, const uint32_t* perm, const int32_t* gsrc, int64_t d, void* out,
-                   int32_t gstride, uint32_t row_max) {
-#define EG_REDUCE(M, DT)                                                                              \
-  return out_dtype == EULER_GPU_F32                                                                   \
-             ? LaunchReduce<M, DT, false>(st, upd, seg, perm, gsrc, d, out, gstride, row_max)         \
-             : LaunchReduce<M, DT, true>(st, upd, seg, perm, gsrc, d, out, gstride, row_max)
-  if (in_dtype == EULER_GPU_BF16) {
-    if (mode == 0) { EG_REDUCE(0, kBF16); }
-    if (mode == 1) { EG_REDUCE(1, kBF16); }
-    EG_REDUCE(2, kBF16);
-  }
-  if (mode == 0) { EG_REDUCE(0, kF16); }
-  if (mode == 1) { EG_REDUCE(1, kF16); }
-  EG_REDUCE(2, kF16);
-#undef EG_REDUCE
-}
-
-int CheckDtypes(const char* what, int32_t in_dtype, int32_t out_dtype) {
-  if (in_dtype != EULER_GPU_F32 && in_dtype != EULER_GPU_BF16 && in_dtype != EULER_GPU_F16)
-    return Fail(EULER_GPU_EINVAL, std::string(what) + ": unknown dtype " + std::to_string(in_dtype) +
-                                      " (0 fp32, 1 bf16, 2 fp16)");
-  if (out_dtype != EULER_GPU_F32 && out_dtype != in_dtype)
-    return Fail(EULER_GPU_EINVAL, std::string(what) + ": out_dtype " + std::to_string(out_dtype) +
-                                      " is neither fp32 nor the input's dtype");
-  return EULER_GPU_OK;
-}
-
-int ScatterHalf(hipStream_t st, int32_t mode, const void* upd, int32_t in_dtype, const int32_t* idx,
-                int64_t e, int64_t d, int32_t size, void* out, int32_t out_dtype, const int32_t* gsrc) {
-  if (e < 0 || d < 0 || size < 0) return Fail(EULER_GPU_EINVAL, "scatter: bad shape");
-  if (size == 0 || d == 0) return EULER_GPU_OK;
-  if (!out || (e > 0 && (!upd || !idx))) return Fail(EULER_GPU_EINVAL, "scatter: null buffer");
-  if (e >= (1LL << 31)) return Fail(EULER_GPU_EINVAL, "scatter: e >= 2^31");
-  if ((uintptr_t)upd % 2 != 0 || (uintptr_t)out % 2 != 0)
-    return Fail(EULER_GPU_EINVAL, "scatter: 16-bit data must be 2-byte aligned");
-  const int32_t* keys = idx;
-  const uint32_t* perm = nullptr;
-  StreamBuf scratch(st);
-  const int rc = GroupScatterKeys(st, idx, e, &scratch, &keys, &perm);
-  if (rc != EULER_GPU_OK) return rc;
-  return DispatchReduce(st, mode, in_dtype, out_dtype, upd, SegSpec{keys, nullptr, 0, e, size}, perm,
-                        gsrc, d, out, 1, 0xFFFFFFFFu);
 }
 
 // ---- edge-weighted reduces (the weighted kernels of mp_kernels.hip over 16-bit rows) -----------
@@ -325,52 +273,16 @@ __global__ __launch_bounds__(256) void WeightedSegmentReduceVec8Kernel(
 template <int MODE, int DT, bool OUT16>
 int LaunchWeightedReduce(hipStream_t st, const void* upd, const SegSpec& seg, const MpwIndex& ix,
                          int64_t d, void* out, const void* w, bool w16, int32_t heads) {
-  const dim3 block(64, 4);
-  const int64_t d8 = d / 8;
   const int32_t dh = (int32_t)(d / heads);
-  const int32_t size = seg.size;
-  if (d % 8 == 0 && d8 <= 64 && 64 % d8 == 0 && dh % 8 == 0 && ((uintptr_t)upd % 16 == 0) &&
-      ((uintptr_t)out % 16 == 0)) {
-    const int64_t rows_per_block = 4 * (64 / d8);
-    int64_t blocks = ((int64_t)size + rows_per_block - 1) / rows_per_block;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL((WeightedSegmentReduceVec8Kernel<MODE, DT, OUT16>), dim3((unsigned)blocks), block,
-                       0, st, static_cast<const uint4*>(upd), seg, ix, (int32_t)d8, out, w, w16, heads, dh);
+  const LaneShape s = RowLaneShape(seg.size, d, 8, dh, upd, out);
+  if (s.vec) {
+    hipLaunchKernelGGL((WeightedSegmentReduceVec8Kernel<MODE, DT, OUT16>), dim3(s.blocks), dim3(64, 4),
+                       0, st, static_cast<const uint4*>(upd), seg, ix, (int32_t)s.dv, out, w, w16, heads, dh);
   } else {
-    int64_t blocks = ((int64_t)size + 3) / 4;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL((WeightedSegmentReduceHalfKernel<MODE, DT, OUT16>), dim3((unsigned)blocks), block,
+    hipLaunchKernelGGL((WeightedSegmentReduceHalfKernel<MODE, DT, OUT16>), dim3(s.blocks), dim3(64, 4),
                        0, st, static_cast<const uint16_t*>(upd), seg, ix, d, out, w, w16, heads, dh);
   }
   EG_HIP(hipGetLastError());
-  return EULER_GPU_OK;
-}
-
-int DispatchWeightedReduce(hipStream_t st, int32_t mode, int32_t in_dtype, int32_t out_dtype,
-                           const void* upd, const SegSpec& seg, const MpwIndex& ix, int64_t d,
-                           void* out, const void* w, bool w16, int32_t heads) {
-#define EG_WREDUCE(M, DT)                                                                        \
-  return out_dtype == EULER_GPU_F32                                                              \
-             ? LaunchWeightedReduce<M, DT, false>(st, upd, seg, ix, d, out, w, w16, heads)       \
-             : LaunchWeightedReduce<M, DT, true>(st, upd, seg, ix, d, out, w, w16, heads)
-  if (in_dtype == EULER_GPU_BF16) {
-    if (mode == 0) { EG_WREDUCE(0, kBF16); }
-    if (mode == 1) { EG_WREDUCE(1, kBF16); }
-    EG_WREDUCE(2, kBF16);
-  }
-  if (mode == 0) { EG_WREDUCE(0, kF16); }
-  if (mode == 1) { EG_WREDUCE(1, kF16); }
-  EG_WREDUCE(2, kF16);
-#undef EG_WREDUCE
-}
-
-// w_dtype is fp32 or the dtype of the rows
-int CheckWeightDtype(const char* what, int32_t in_dtype, int32_t w_dtype, const void* w) {
-  if (w_dtype != EULER_GPU_F32 && w_dtype != in_dtype)
-    return Fail(EULER_GPU_EINVAL, std::string(what) + ": w_dtype " + std::to_string(w_dtype) +
-                                      " is neither fp32 nor the input's dtype");
-  if ((uintptr_t)w % (w_dtype == EULER_GPU_F32 ? 4 : 2) != 0)
-    return Fail(EULER_GPU_EINVAL, std::string(what) + ": the weights are not aligned to their type");
   return EULER_GPU_OK;
 }
 
@@ -475,6 +387,37 @@ __global__ __launch_bounds__(256) void NarrowTableKernel(const float* __restrict
 }
 
 }  // namespace
+
+// c.in_dtype is bf16 or fp16, c.out_dtype fp32 or c.in_dtype (CheckMpReduce)
+#define EG_BY_MODE_DTYPE(LAUNCH)                \
+  if (c.in_dtype == EULER_GPU_BF16) {           \
+    if (c.mode == 0) { LAUNCH(0, kBF16); }      \
+    if (c.mode == 1) { LAUNCH(1, kBF16); }      \
+    LAUNCH(2, kBF16);                           \
+  }                                             \
+  if (c.mode == 0) { LAUNCH(0, kF16); }         \
+  if (c.mode == 1) { LAUNCH(1, kF16); }         \
+  LAUNCH(2, kF16)
+
+int ReduceHalf(hipStream_t st, const MpReduceCall& c, const SegSpec& seg, const MpwIndex& ix) {
+#define EG_REDUCE(M, DT)                                                                     \
+  return c.out_dtype == EULER_GPU_F32 ? LaunchReduce<M, DT, false>(st, c.params, seg, ix, c.d, c.out) \
+                                      : LaunchReduce<M, DT, true>(st, c.params, seg, ix, c.d, c.out)
+  EG_BY_MODE_DTYPE(EG_REDUCE);
+#undef EG_REDUCE
+}
+
+int WeightedReduceHalf(hipStream_t st, const MpReduceCall& c, const SegSpec& seg, const MpwIndex& ix) {
+  const bool w16 = c.w_dtype != EULER_GPU_F32;
+#define EG_WREDUCE(M, DT)                                                                               \
+  return c.out_dtype == EULER_GPU_F32                                                                   \
+             ? LaunchWeightedReduce<M, DT, false>(st, c.params, seg, ix, c.d, c.out, c.w, w16, c.heads) \
+             : LaunchWeightedReduce<M, DT, true>(st, c.params, seg, ix, c.d, c.out, c.w, w16, c.heads)
+  EG_BY_MODE_DTYPE(EG_WREDUCE);
+#undef EG_WREDUCE
+}
+#undef EG_BY_MODE_DTYPE
+
 }  // namespace euler_gpu
 
 using namespace euler_gpu;
@@ -484,8 +427,11 @@ extern "C" {
 int euler_gpu_gather_t(void* stream, const void* params_dev, int32_t in_dtype,
                        const int32_t* indices_dev, int64_t e, int64_t d, int64_t n_params,
                        void* out_dev, int32_t out_dtype) {
-  const int rc = CheckDtypes("gather", in_dtype, out_dtype);
-  if (rc != EULER_GPU_OK) return rc;
+  if (in_dtype != EULER_GPU_F32 && in_dtype != EULER_GPU_BF16 && in_dtype != EULER_GPU_F16)
+    return Fail(EULER_GPU_EINVAL, "gather: unknown dtype " + std::to_string(in_dtype) + " (0 fp32, 1 bf16, 2 fp16)");
+  if (out_dtype != EULER_GPU_F32 && out_dtype != in_dtype)
+    return Fail(EULER_GPU_EINVAL, "gather: out_dtype " + std::to_string(out_dtype) +
+                                      " is neither fp32 nor the input's dtype");
   if (in_dtype == EULER_GPU_F32)
     return euler_gpu_gather(stream, static_cast<const float*>(params_dev), indices_dev, e, d, n_params,
                             static_cast<float*>(out_dev));
@@ -531,60 +477,27 @@ int euler_gpu_gather_t(void* stream, const void* params_dev, int32_t in_dtype,
 int euler_gpu_scatter_t(void* stream, int32_t mode, const void* updates_dev, int32_t in_dtype,
                         const int32_t* indices_dev, int64_t e, int64_t d, int32_t size,
                         void* out_dev, int32_t out_dtype) {
-  if (mode < 0 || mode > 2) return Fail(EULER_GPU_EINVAL, "scatter: mode is 0 add, 1 max, 2 mean");
-  const int rc = CheckDtypes("scatter", in_dtype, out_dtype);
-  if (rc != EULER_GPU_OK) return rc;
-  if (in_dtype == EULER_GPU_F32) {
-    const float* u = static_cast<const float*>(updates_dev);
-    float* o = static_cast<float*>(out_dev);
-    if (mode == 0) return euler_gpu_scatter_add(stream, u, indices_dev, e, d, size, o);
-    if (mode == 1) return euler_gpu_scatter_max(stream, u, indices_dev, e, d, size, o);
-    return euler_gpu_scatter_mean(stream, u, indices_dev, e, d, size, o);
-  }
-  if (mode == 2 && e >= (1LL << 24))
-    return Fail(EULER_GPU_EINVAL, "scatter_mean: e >= 2^24, compose scatter_add instead");
-  return ScatterHalf((hipStream_t)stream, mode, updates_dev, in_dtype, indices_dev, e, d, size, out_dev,
-                     out_dtype, nullptr);
+  return RunMpReduce((hipStream_t)stream, MpReduceCall{"scatter", mode, updates_dev, d, size, out_dev}
+                                              .Typed(in_dtype, out_dtype).Keys(indices_dev, e));
 }
 
 int euler_gpu_gather_scatter_t(void* stream, int32_t mode, const void* params_dev, int32_t in_dtype,
                                const int32_t* gather_indices_dev, const int32_t* scatter_indices_dev,
                                int64_t e, int64_t d, int32_t size, void* out_dev, int32_t out_dtype) {
-  const int rc = CheckDtypes("gather_scatter", in_dtype, out_dtype);
-  if (rc != EULER_GPU_OK) return rc;
-  if (in_dtype == EULER_GPU_F32)
-    return euler_gpu_gather_scatter(stream, mode, static_cast<const float*>(params_dev), gather_indices_dev,
-                                    scatter_indices_dev, e, d, size, static_cast<float*>(out_dev));
-  if (mode < 0 || mode > 2) return Fail(EULER_GPU_EINVAL, "gather_scatter: mode is 0 add, 1 max, 2 mean");
-  if (e > 0 && !gather_indices_dev) return Fail(EULER_GPU_EINVAL, "gather_scatter: null buffer");
-  if (mode == 2 && e >= (1LL << 24)) return Fail(EULER_GPU_EINVAL, "gather_scatter: mean needs e < 2^24");
-  return ScatterHalf((hipStream_t)stream, mode, params_dev, in_dtype, scatter_indices_dev, e, d, size,
-                     out_dev, out_dtype, gather_indices_dev);
+  return RunMpReduce((hipStream_t)stream,
+                     MpReduceCall{"gather_scatter", mode, params_dev, d, size, out_dev}
+                         .Typed(in_dtype, out_dtype).Gather(kGatherNeeded, gather_indices_dev)
+                         .Keys(scatter_indices_dev, e));
 }
 
 int euler_gpu_gather_segment_reduce_t(void* stream, int32_t mode, const void* params_dev, int32_t in_dtype,
                                       const int32_t* gather_indices_dev, const int64_t* seg_ptr_dev,
                                       int64_t count, int64_t d, int32_t size, void* out_dev,
                                       int32_t out_dtype) {
-  const int rc = CheckDtypes("gather_segment_reduce", in_dtype, out_dtype);
-  if (rc != EULER_GPU_OK) return rc;
-  if (in_dtype == EULER_GPU_F32)
-    return euler_gpu_gather_segment_reduce(stream, mode, static_cast<const float*>(params_dev),
-                                           gather_indices_dev, seg_ptr_dev, count, d, size,
-                                           static_cast<float*>(out_dev));
-  if (mode < 0 || mode > 2)
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce: mode is 0 add, 1 max, 2 mean");
-  if (d < 0 || size < 0 || (!seg_ptr_dev && count < 0))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce: bad shape");
-  if (size == 0 || d == 0) return EULER_GPU_OK;
-  if (!out_dev || !params_dev) return Fail(EULER_GPU_EINVAL, "gather_segment_reduce: null buffer");
-  if (!seg_ptr_dev && mode == 2 && count >= (1LL << 24))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce: mean needs segments shorter than 2^24");
-  if ((uintptr_t)params_dev % 2 != 0 || (uintptr_t)out_dev % 2 != 0)
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce: 16-bit data must be 2-byte aligned");
-  return DispatchReduce((hipStream_t)stream, mode, in_dtype, out_dtype, params_dev,
-                        SegSpec{nullptr, seg_ptr_dev, count, 0, size}, nullptr, gather_indices_dev, d,
-                        out_dev, 1, 0xFFFFFFFFu);
+  return RunMpReduce((hipStream_t)stream,
+                     MpReduceCall{"gather_segment_reduce", mode, params_dev, d, size, out_dev}
+                         .Typed(in_dtype, out_dtype).Gather(kGatherOrNull, gather_indices_dev)
+                         .Segments(seg_ptr_dev, count));
 }
 
 int euler_gpu_gather_segment_reduce_ids_t(void* stream, int32_t mode, const void* params_dev,
@@ -592,61 +505,20 @@ int euler_gpu_gather_segment_reduce_ids_t(void* stream, int32_t mode, const void
                                           const int64_t* gather_ids_dev, const int64_t* seg_ptr_dev,
                                           int64_t count, int64_t d, int32_t size, void* out_dev,
                                           int32_t out_dtype) {
-  const int rc = CheckDtypes("gather_segment_reduce_ids", in_dtype, out_dtype);
-  if (rc != EULER_GPU_OK) return rc;
-  if (in_dtype == EULER_GPU_F32)
-    return euler_gpu_gather_segment_reduce_ids(stream, mode, static_cast<const float*>(params_dev),
-                                               params_rows, gather_ids_dev, seg_ptr_dev, count, d, size,
-                                               static_cast<float*>(out_dev));
-  if (mode < 0 || mode > 2)
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids: mode is 0 add, 1 max, 2 mean");
-  if (d < 0 || size < 0 || (!seg_ptr_dev && count < 0))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids: bad shape");
-  if (size == 0 || d == 0) return EULER_GPU_OK;
-  if (!out_dev || !params_dev || !gather_ids_dev)
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids: null buffer");
-  if (!seg_ptr_dev && mode == 2 && count >= (1LL << 24))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids: mean needs segments shorter than 2^24");
-  if (params_rows < 0 || params_rows >= ((int64_t)1 << 31))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids: the table must have fewer than 2^31 rows");
-  if ((uintptr_t)params_dev % 2 != 0 || (uintptr_t)out_dev % 2 != 0)
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids: 16-bit data must be 2-byte aligned");
-  const uint32_t row_max = params_rows > 0 ? (uint32_t)(params_rows - 1) : 0xFFFFFFFFu;
-  const int32_t* lo = reinterpret_cast<const int32_t*>(gather_ids_dev);     // little endian: word 0 of every id
-  return DispatchReduce((hipStream_t)stream, mode, in_dtype, out_dtype, params_dev,
-                        SegSpec{nullptr, seg_ptr_dev, count, 0, size}, nullptr, lo, d, out_dev, 2, row_max);
+  return RunMpReduce((hipStream_t)stream,
+                     MpReduceCall{"gather_segment_reduce_ids", mode, params_dev, d, size, out_dev}
+                         .Typed(in_dtype, out_dtype).Gather(kGatherIds, gather_ids_dev, params_rows)
+                         .Segments(seg_ptr_dev, count));
 }
 
 int euler_gpu_gather_scatter_w_t(void* stream, int32_t mode, const void* params_dev, int32_t in_dtype,
                                  const int32_t* gather_indices_dev, const int32_t* scatter_indices_dev,
                                  int64_t e, int64_t d, int32_t size, void* out_dev, int32_t out_dtype,
                                  const void* w_dev, int32_t w_dtype, int32_t heads) {
-  int rc = CheckDtypes("gather_scatter_w", in_dtype, out_dtype);
-  if (rc == EULER_GPU_OK) rc = CheckWeightDtype("gather_scatter_w", in_dtype, w_dtype, w_dev);
-  if (rc != EULER_GPU_OK) return rc;
-  if (in_dtype == EULER_GPU_F32)
-    return euler_gpu_gather_scatter_w(stream, mode, static_cast<const float*>(params_dev),
-                                      gather_indices_dev, scatter_indices_dev, e, d, size,
-                                      static_cast<float*>(out_dev), static_cast<const float*>(w_dev), heads);
-  rc = CheckWeightedShape("gather_scatter_w", mode, d, heads);
-  if (rc != EULER_GPU_OK) return rc;
-  if (e < 0 || size < 0) return Fail(EULER_GPU_EINVAL, "gather_scatter_w: bad shape");
-  if (size == 0 || d == 0) return EULER_GPU_OK;
-  if (!out_dev || (e > 0 && (!params_dev || !scatter_indices_dev || !w_dev)))
-    return Fail(EULER_GPU_EINVAL, "gather_scatter_w: null buffer");
-  if (e >= (1LL << 31)) return Fail(EULER_GPU_EINVAL, "gather_scatter_w: e >= 2^31");
-  if (mode == 2 && e >= (1LL << 24)) return Fail(EULER_GPU_EINVAL, "gather_scatter_w: mean needs e < 2^24");
-  if ((uintptr_t)params_dev % 2 != 0 || (uintptr_t)out_dev % 2 != 0)
-    return Fail(EULER_GPU_EINVAL, "gather_scatter_w: 16-bit data must be 2-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const int32_t* keys = scatter_indices_dev;
-  const uint32_t* perm = nullptr;
-  StreamBuf scratch(st);
-  rc = GroupScatterKeys(st, scatter_indices_dev, e, &scratch, &keys, &perm);
-  if (rc != EULER_GPU_OK) return rc;
-  return DispatchWeightedReduce(st, mode, in_dtype, out_dtype, params_dev, SegSpec{keys, nullptr, 0, e, size},
-                                MpwIndex{perm, gather_indices_dev, 1, 0xFFFFFFFFu}, d, out_dev, w_dev,
-                                w_dtype != EULER_GPU_F32, heads);
+  return RunMpReduce((hipStream_t)stream,
+                     MpReduceCall{"gather_scatter_w", mode, params_dev, d, size, out_dev}
+                         .Typed(in_dtype, out_dtype).Gather(kGatherOrNull, gather_indices_dev)
+                         .Keys(scatter_indices_dev, e).Weights(w_dev, heads, w_dtype));
 }
 
 int euler_gpu_gather_segment_reduce_w_t(void* stream, int32_t mode, const void* params_dev, int32_t in_dtype,
@@ -654,31 +526,10 @@ int euler_gpu_gather_segment_reduce_w_t(void* stream, int32_t mode, const void* 
                                         int64_t count, int64_t d, int32_t size, void* out_dev,
                                         int32_t out_dtype, const void* w_dev, int32_t w_dtype,
                                         int32_t heads) {
-  int rc = CheckDtypes("gather_segment_reduce_w", in_dtype, out_dtype);
-  if (rc == EULER_GPU_OK) rc = CheckWeightDtype("gather_segment_reduce_w", in_dtype, w_dtype, w_dev);
-  if (rc != EULER_GPU_OK) return rc;
-  if (in_dtype == EULER_GPU_F32)
-    return euler_gpu_gather_segment_reduce_w(stream, mode, static_cast<const float*>(params_dev),
-                                             gather_indices_dev, seg_ptr_dev, count, d, size,
-                                             static_cast<float*>(out_dev), static_cast<const float*>(w_dev),
-                                             heads);
-  rc = CheckWeightedShape("gather_segment_reduce_w", mode, d, heads);
-  if (rc != EULER_GPU_OK) return rc;
-  if (size < 0 || (!seg_ptr_dev && count < 0))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_w: bad shape");
-  if (size == 0 || d == 0) return EULER_GPU_OK;
-  if (!out_dev || !params_dev || !w_dev)
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_w: null buffer");
-  if (!seg_ptr_dev && (int64_t)size * count >= (1LL << 31))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_w: e >= 2^31");
-  if (!seg_ptr_dev && mode == 2 && count >= (1LL << 24))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_w: mean needs segments shorter than 2^24");
-  if ((uintptr_t)params_dev % 2 != 0 || (uintptr_t)out_dev % 2 != 0)
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_w: 16-bit data must be 2-byte aligned");
-  return DispatchWeightedReduce((hipStream_t)stream, mode, in_dtype, out_dtype, params_dev,
-                                SegSpec{nullptr, seg_ptr_dev, count, 0, size},
-                                MpwIndex{nullptr, gather_indices_dev, 1, 0xFFFFFFFFu}, d, out_dev, w_dev,
-                                w_dtype != EULER_GPU_F32, heads);
+  return RunMpReduce((hipStream_t)stream,
+                     MpReduceCall{"gather_segment_reduce_w", mode, params_dev, d, size, out_dev}
+                         .Typed(in_dtype, out_dtype).Gather(kGatherOrNull, gather_indices_dev)
+                         .Segments(seg_ptr_dev, count).Weights(w_dev, heads, w_dtype));
 }
 
 int euler_gpu_gather_segment_reduce_ids_w_t(void* stream, int32_t mode, const void* params_dev,
@@ -687,34 +538,10 @@ int euler_gpu_gather_segment_reduce_ids_w_t(void* stream, int32_t mode, const vo
                                             int64_t count, int64_t d, int32_t size, void* out_dev,
                                             int32_t out_dtype, const void* w_dev, int32_t w_dtype,
                                             int32_t heads) {
-  int rc = CheckDtypes("gather_segment_reduce_ids_w", in_dtype, out_dtype);
-  if (rc == EULER_GPU_OK) rc = CheckWeightDtype("gather_segment_reduce_ids_w", in_dtype, w_dtype, w_dev);
-  if (rc != EULER_GPU_OK) return rc;
-  if (in_dtype == EULER_GPU_F32)
-    return euler_gpu_gather_segment_reduce_ids_w(stream, mode, static_cast<const float*>(params_dev),
-                                                 params_rows, gather_ids_dev, seg_ptr_dev, count, d, size,
-                                                 static_cast<float*>(out_dev),
-                                                 static_cast<const float*>(w_dev), heads);
-  rc = CheckWeightedShape("gather_segment_reduce_ids_w", mode, d, heads);
-  if (rc != EULER_GPU_OK) return rc;
-  if (size < 0 || (!seg_ptr_dev && count < 0))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: bad shape");
-  if (size == 0 || d == 0) return EULER_GPU_OK;
-  if (!out_dev || !params_dev || !gather_ids_dev || !w_dev)
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: null buffer");
-  if (!seg_ptr_dev && (int64_t)size * count >= (1LL << 31))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: e >= 2^31");
-  if (!seg_ptr_dev && mode == 2 && count >= (1LL << 24))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: mean needs segments shorter than 2^24");
-  if (params_rows < 0 || params_rows >= ((int64_t)1 << 31))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: the table must have fewer than 2^31 rows");
-  if ((uintptr_t)params_dev % 2 != 0 || (uintptr_t)out_dev % 2 != 0)
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: 16-bit data must be 2-byte aligned");
-  const uint32_t row_max = params_rows > 0 ? (uint32_t)(params_rows - 1) : 0xFFFFFFFFu;
-  const int32_t* lo = reinterpret_cast<const int32_t*>(gather_ids_dev);     // little endian: word 0 of every id
-  return DispatchWeightedReduce((hipStream_t)stream, mode, in_dtype, out_dtype, params_dev,
-                                SegSpec{nullptr, seg_ptr_dev, count, 0, size}, MpwIndex{nullptr, lo, 2, row_max},
-                                d, out_dev, w_dev, w_dtype != EULER_GPU_F32, heads);
+  return RunMpReduce((hipStream_t)stream,
+                     MpReduceCall{"gather_segment_reduce_ids_w", mode, params_dev, d, size, out_dev}
+                         .Typed(in_dtype, out_dtype).Gather(kGatherIds, gather_ids_dev, params_rows)
+                         .Segments(seg_ptr_dev, count).Weights(w_dev, heads, w_dtype));
 }
 
 int32_t euler_gpu_graph_dense_feature_dtype(const euler_gpu_graph* g) {

@@ -261,61 +261,17 @@ int GroupScatterKeys(hipStream_t st, const int32_t* idx, int64_t e, StreamBuf* s
   return EULER_GPU_OK;
 }
 
+// the fp32 reduce of the destinations of `seg`: update p is row ix.Row(ix.Pos(p)) of `upd`
 template <int MODE>
-static int ScatterImpl(hipStream_t st, const float* upd, const int32_t* idx,
-                       int64_t e, int64_t d, int32_t size, float* out,
-                       const int32_t* gsrc = nullptr) {
-  if (e < 0 || d < 0 || size < 0) return Fail(EULER_GPU_EINVAL, "scatter: bad shape");
-  if (size == 0 || d == 0) return EULER_GPU_OK;
-  if (!out || (e > 0 && (!upd || !idx)))
-    return Fail(EULER_GPU_EINVAL, "scatter: null buffer");
-  if (e >= (1LL << 31)) return Fail(EULER_GPU_EINVAL, "scatter: e >= 2^31");
-  const int32_t* keys = idx;
-  const uint32_t* perm = nullptr;
-  // stream-ordered scratch of the unsorted path, released on every exit
-  StreamBuf scratch(st);
-  {
-    const int rc = GroupScatterKeys(st, idx, e, &scratch, &keys, &perm);
-    if (rc != EULER_GPU_OK) return rc;
-  }
-  const dim3 block(64, 4);
-  const int64_t d4 = d / 4;
-  if (d % 4 == 0 && d4 <= 64 && 64 % d4 == 0 && ((uintptr_t)upd % 16 == 0) &&
-      ((uintptr_t)out % 16 == 0)) {
-    const int64_t rows_per_block = 4 * (64 / d4);
-    int64_t blocks = ((int64_t)size + rows_per_block - 1) / rows_per_block;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL(SegmentReduceVec4Kernel<MODE>, dim3((unsigned)blocks), block, 0, st, upd,
-                       SegSpec{keys, nullptr, 0, e, size}, perm, gsrc, (int32_t)d4, out, 1, 0xFFFFFFFFu);
+static int LaunchReduce(hipStream_t st, const float* upd, const SegSpec& seg, const MpwIndex& ix,
+                        int64_t d, float* out) {
+  const LaneShape s = RowLaneShape(seg.size, d, 4, 0, upd, out);
+  if (s.vec) {
+    hipLaunchKernelGGL(SegmentReduceVec4Kernel<MODE>, dim3(s.blocks), dim3(64, 4), 0, st, upd, seg, ix.perm,
+                       ix.gsrc, (int32_t)s.dv, out, ix.gstride, ix.row_max);
   } else {
-    int64_t blocks = ((int64_t)size + 3) / 4;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL(SegmentReduceKernel<MODE>, dim3((unsigned)blocks), block, 0,
-                       st, upd, SegSpec{keys, nullptr, 0, e, size}, perm, gsrc, d, out, 1, 0xFFFFFFFFu);
-  }
-  EG_HIP(hipGetLastError());
-  return EULER_GPU_OK;
-}
-
-template <int MODE>
-static int SegmentReduceImpl(hipStream_t st, const float* params, const int32_t* gsrc,
-                             const int64_t* seg_ptr, int64_t count, int64_t d, int32_t size,
-                             float* out, int32_t gstride = 1, uint32_t row_max = 0xFFFFFFFFu) {
-  const dim3 block(64, 4);
-  const int64_t d4 = d / 4;
-  const SegSpec seg{nullptr, seg_ptr, count, 0, size};
-  if (d % 4 == 0 && d4 <= 64 && 64 % d4 == 0 && ((uintptr_t)params % 16 == 0) &&
-      ((uintptr_t)out % 16 == 0)) {
-    const int64_t rows_per_block = 4 * (64 / d4);
-    int64_t blocks = ((int64_t)size + rows_per_block - 1) / rows_per_block;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL(SegmentReduceVec4Kernel<MODE>, dim3((unsigned)blocks), block, 0, st, params,
-                       seg, nullptr, gsrc, (int32_t)d4, out, gstride, row_max);
-  } else {
-    int64_t blocks = ((int64_t)size + 3) / 4;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL(SegmentReduceKernel<MODE>, dim3((unsigned)blocks), block, 0, st, params, seg,
-                       nullptr, gsrc, d, out, gstride, row_max);
+    hipLaunchKernelGGL(SegmentReduceKernel<MODE>, dim3(s.blocks), dim3(64, 4), 0, st, upd, seg, ix.perm,
+                       ix.gsrc, d, out, ix.gstride, ix.row_max);
   }
   EG_HIP(hipGetLastError());
   return EULER_GPU_OK;
@@ -402,42 +358,96 @@ template <int MODE>
 static int LaunchWeightedReduce(hipStream_t st, const float* params, const SegSpec& seg,
                                 const MpwIndex& ix, int64_t d, float* out, const float* w,
                                 int32_t heads) {
-  const dim3 block(64, 4);
-  const int64_t d4 = d / 4;
   const int32_t dh = (int32_t)(d / heads);
-  const int32_t size = seg.size;
-  if (d % 4 == 0 && d4 <= 64 && 64 % d4 == 0 && dh % 4 == 0 && ((uintptr_t)params % 16 == 0) &&
-      ((uintptr_t)out % 16 == 0)) {
-    const int64_t rows_per_block = 4 * (64 / d4);
-    int64_t blocks = ((int64_t)size + rows_per_block - 1) / rows_per_block;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL(WeightedSegmentReduceVec4Kernel<MODE>, dim3((unsigned)blocks), block, 0, st,
-                       params, seg, ix, (int32_t)d4, out, w, heads, dh);
+  const LaneShape s = RowLaneShape(seg.size, d, 4, dh, params, out);
+  if (s.vec) {
+    hipLaunchKernelGGL(WeightedSegmentReduceVec4Kernel<MODE>, dim3(s.blocks), dim3(64, 4), 0, st,
+                       params, seg, ix, (int32_t)s.dv, out, w, heads, dh);
   } else {
-    int64_t blocks = ((int64_t)size + 3) / 4;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL(WeightedSegmentReduceKernel<MODE>, dim3((unsigned)blocks), block, 0, st,
+    hipLaunchKernelGGL(WeightedSegmentReduceKernel<MODE>, dim3(s.blocks), dim3(64, 4), 0, st,
                        params, seg, ix, d, out, w, heads, dh);
   }
   EG_HIP(hipGetLastError());
   return EULER_GPU_OK;
 }
 
-static int DispatchWeightedReduce(hipStream_t st, int32_t mode, const float* params,
-                                  const SegSpec& seg, const MpwIndex& ix, int64_t d, float* out,
-                                  const float* w, int32_t heads) {
-  if (mode == 0) return LaunchWeightedReduce<0>(st, params, seg, ix, d, out, w, heads);
-  if (mode == 1) return LaunchWeightedReduce<1>(st, params, seg, ix, d, out, w, heads);
-  return LaunchWeightedReduce<2>(st, params, seg, ix, d, out, w, heads);
+int CheckMpReduce(const MpReduceCall& c, bool* nothing_to_do) {
+  *nothing_to_do = false;
+  const auto fail = [&c](const std::string& why) {
+    return Fail(EULER_GPU_EINVAL, std::string(c.name) + ": " + why);
+  };
+  const char* const not_in = " is neither fp32 nor the input's dtype";
+  if (c.typed) {
+    if (c.in_dtype != EULER_GPU_F32 && c.in_dtype != EULER_GPU_BF16 && c.in_dtype != EULER_GPU_F16)
+      return fail("unknown dtype " + std::to_string(c.in_dtype) + " (0 fp32, 1 bf16, 2 fp16)");
+    if (c.out_dtype != EULER_GPU_F32 && c.out_dtype != c.in_dtype)
+      return fail("out_dtype " + std::to_string(c.out_dtype) + not_in);
+    if (c.weighted && c.w_dtype != EULER_GPU_F32 && c.w_dtype != c.in_dtype)
+      return fail("w_dtype " + std::to_string(c.w_dtype) + not_in);
+    if (c.weighted && (uintptr_t)c.w % (c.w_dtype == EULER_GPU_F32 ? 4 : 2) != 0)
+      return fail("the weights are not aligned to their type");
+  }
+  if (c.mode < 0 || c.mode > 2) return fail("mode is 0 add, 1 max, 2 mean");
+  if (c.weighted && c.heads < 1) return fail("heads < 1");
+  if (c.weighted && (c.d < 0 || c.d % c.heads != 0)) return fail("heads must divide d");
+  if (c.d < 0 || c.size < 0 || (c.keyed ? c.e < 0 : !c.seg_ptr && c.count < 0)) return fail("bad shape");
+  if (c.size == 0 || c.d == 0) {
+    *nothing_to_do = true;
+    return EULER_GPU_OK;
+  }
+  // (a keyed call without updates reads nothing, and still fills `out`)
+  if (!c.out || ((!c.keyed || c.e > 0) && (!c.params || (c.keyed && !c.keys) || (c.weighted && !c.w) ||
+                                           (c.gather_kind >= kGatherNeeded && !c.gather))))
+    return fail("null buffer");
+  // the sort of the keys and the weights' positions are 32-bit; the unweighted kernels walk seg_ptr /
+  // count segments with 64-bit positions
+  const int64_t e = c.keyed ? c.e : c.seg_ptr ? 0 : (int64_t)c.size * c.count;
+  if ((c.keyed || c.weighted) && e >= (1LL << 31)) return fail("e >= 2^31");
+  // a destination could collect 2^24 or more updates: its f32 count would no longer be its length
+  if (c.mode == 2 && c.keyed && c.e >= (1LL << 24))
+    return c.gather_kind == kNoGatherArg     // (callers compose scatter_add as the reference does)
+               ? Fail(EULER_GPU_EINVAL, "scatter_mean: e >= 2^24, compose scatter_add instead")
+               : fail("mean needs e < 2^24");
+  if (c.mode == 2 && !c.keyed && !c.seg_ptr && c.count >= (1LL << 24))
+    return fail("mean needs segments shorter than 2^24");
+  // the index is the low 32-bit word of the id: the table must be addressable by it
+  if (c.gather_kind == kGatherIds && (c.params_rows < 0 || c.params_rows >= ((int64_t)1 << 31)))
+    return fail("the table must have fewer than 2^31 rows");
+  if (c.in_dtype != EULER_GPU_F32 && ((uintptr_t)c.params % 2 != 0 || (uintptr_t)c.out % 2 != 0))
+    return fail("16-bit data must be 2-byte aligned");
+  return EULER_GPU_OK;
 }
 
-int CheckWeightedShape(const char* what, int32_t mode, int64_t d, int32_t heads) {
-  if (mode < 0 || mode > 2)
-    return Fail(EULER_GPU_EINVAL, std::string(what) + ": mode is 0 add, 1 max, 2 mean");
-  if (heads < 1) return Fail(EULER_GPU_EINVAL, std::string(what) + ": heads < 1");
-  if (d < 0 || d % heads != 0)
-    return Fail(EULER_GPU_EINVAL, std::string(what) + ": heads must divide d");
-  return EULER_GPU_OK;
+int RunMpReduce(hipStream_t st, const MpReduceCall& c) {
+  bool nothing_to_do;
+  int rc = CheckMpReduce(c, &nothing_to_do);
+  if (rc != EULER_GPU_OK || nothing_to_do) return rc;
+  SegSpec seg{nullptr, c.seg_ptr, c.count, 0, c.size};
+  const uint32_t* perm = nullptr;
+  StreamBuf scratch(st);      // stream-ordered scratch of the unsorted path, released on every exit
+  if (c.keyed) {
+    seg = SegSpec{c.keys, nullptr, 0, c.e, c.size};
+    rc = GroupScatterKeys(st, c.keys, c.e, &scratch, &seg.keys, &perm);
+    if (rc != EULER_GPU_OK) return rc;
+  }
+  // int64 ids: the index is word 0 of every id (little endian), and an id past the table (a
+  // neighbour that is not a node of this graph, a dangling edge) reads the LAST row instead of
+  // memory outside the table
+  const bool ids = c.gather_kind == kGatherIds;
+  const MpwIndex ix{perm, static_cast<const int32_t*>(c.gather), ids ? 2 : 1,
+                    ids && c.params_rows > 0 ? (uint32_t)(c.params_rows - 1) : 0xFFFFFFFFu};
+  if (c.in_dtype != EULER_GPU_F32)
+    return c.weighted ? WeightedReduceHalf(st, c, seg, ix) : ReduceHalf(st, c, seg, ix);
+  const float* params = static_cast<const float*>(c.params);
+  float* out = static_cast<float*>(c.out);
+  const float* w = static_cast<const float*>(c.w);
+#define EG_REDUCE(M)                                                                      \
+  return c.weighted ? LaunchWeightedReduce<M>(st, params, seg, ix, c.d, out, w, c.heads)  \
+                    : LaunchReduce<M>(st, params, seg, ix, c.d, out)
+  if (c.mode == 0) { EG_REDUCE(0); }
+  if (c.mode == 1) { EG_REDUCE(1); }
+  EG_REDUCE(2);
+#undef EG_REDUCE
 }
 
 // ------------------------------------------------------------------------
@@ -830,114 +840,59 @@ int euler_gpu_gather(void* stream, const float* params_dev,
 int euler_gpu_scatter_add(void* stream, const float* updates_dev,
                           const int32_t* indices_dev, int64_t e, int64_t d,
                           int32_t size, float* out_dev) {
-  return ScatterImpl<0>((hipStream_t)stream, updates_dev, indices_dev, e, d,
-                        size, out_dev);
+  return RunMpReduce((hipStream_t)stream,
+                     MpReduceCall{"scatter", 0, updates_dev, d, size, out_dev}.Keys(indices_dev, e));
 }
 
 int euler_gpu_scatter_mean(void* stream, const float* updates_dev,
                            const int32_t* indices_dev, int64_t e, int64_t d,
                            int32_t size, float* out_dev) {
-  if (e >= (1LL << 24)) {
-    // a destination could collect 2^24 or more updates: its f32 count would no longer
-    // be its length - callers compose scatter_add as the reference does
-    return Fail(EULER_GPU_EINVAL, "scatter_mean: e >= 2^24, compose scatter_add instead");
-  }
-  return ScatterImpl<2>((hipStream_t)stream, updates_dev, indices_dev, e, d, size, out_dev);
+  return RunMpReduce((hipStream_t)stream,
+                     MpReduceCall{"scatter", 2, updates_dev, d, size, out_dev}.Keys(indices_dev, e));
 }
 
 int euler_gpu_scatter_max(void* stream, const float* updates_dev,
                           const int32_t* indices_dev, int64_t e, int64_t d,
                           int32_t size, float* out_dev) {
-  return ScatterImpl<1>((hipStream_t)stream, updates_dev, indices_dev, e, d,
-                        size, out_dev);
+  return RunMpReduce((hipStream_t)stream,
+                     MpReduceCall{"scatter", 1, updates_dev, d, size, out_dev}.Keys(indices_dev, e));
 }
 
 int euler_gpu_gather_segment_reduce(void* stream, int32_t mode, const float* params_dev,
                                     const int32_t* gather_indices_dev,
                                     const int64_t* seg_ptr_dev, int64_t count, int64_t d,
                                     int32_t size, float* out_dev) {
-  if (mode < 0 || mode > 2)
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce: mode is 0 add, 1 max, 2 mean");
-  if (d < 0 || size < 0 || (!seg_ptr_dev && count < 0))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce: bad shape");
-  if (size == 0 || d == 0) return EULER_GPU_OK;
-  if (!out_dev || !params_dev) return Fail(EULER_GPU_EINVAL, "gather_segment_reduce: null buffer");
-  if (!seg_ptr_dev && mode == 2 && count >= (1LL << 24))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce: mean needs segments shorter than 2^24");
-  hipStream_t st = (hipStream_t)stream;
-  if (mode == 0)
-    return SegmentReduceImpl<0>(st, params_dev, gather_indices_dev, seg_ptr_dev, count, d, size, out_dev);
-  if (mode == 1)
-    return SegmentReduceImpl<1>(st, params_dev, gather_indices_dev, seg_ptr_dev, count, d, size, out_dev);
-  return SegmentReduceImpl<2>(st, params_dev, gather_indices_dev, seg_ptr_dev, count, d, size, out_dev);
+  return RunMpReduce((hipStream_t)stream,
+                     MpReduceCall{"gather_segment_reduce", mode, params_dev, d, size, out_dev}
+                         .Gather(kGatherOrNull, gather_indices_dev).Segments(seg_ptr_dev, count));
 }
 
 int euler_gpu_gather_segment_reduce_ids(void* stream, int32_t mode, const float* params_dev,
                                         int64_t params_rows, const int64_t* gather_ids_dev,
                                         const int64_t* seg_ptr_dev, int64_t count, int64_t d,
                                         int32_t size, float* out_dev) {
-  if (mode < 0 || mode > 2)
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids: mode is 0 add, 1 max, 2 mean");
-  if (d < 0 || size < 0 || (!seg_ptr_dev && count < 0))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids: bad shape");
-  if (size == 0 || d == 0) return EULER_GPU_OK;
-  if (!out_dev || !params_dev || !gather_ids_dev)
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids: null buffer");
-  if (!seg_ptr_dev && mode == 2 && count >= (1LL << 24))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids: mean needs segments shorter than 2^24");
-  // the index is the low 32-bit word of the id: the table must be addressable by it, and an id
-  // past the table (a neighbour that is not a node of this graph, a dangling edge) reads the
-  // LAST row instead of memory outside the table
-  if (params_rows < 0 || params_rows >= ((int64_t)1 << 31))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids: the table must have fewer than 2^31 rows");
-  const uint32_t row_max = params_rows > 0 ? (uint32_t)(params_rows - 1) : 0xFFFFFFFFu;
-  hipStream_t st = (hipStream_t)stream;
-  const int32_t* lo = reinterpret_cast<const int32_t*>(gather_ids_dev);     // little endian: word 0 of every id
-  if (mode == 0) return SegmentReduceImpl<0>(st, params_dev, lo, seg_ptr_dev, count, d, size, out_dev, 2, row_max);
-  if (mode == 1) return SegmentReduceImpl<1>(st, params_dev, lo, seg_ptr_dev, count, d, size, out_dev, 2, row_max);
-  return SegmentReduceImpl<2>(st, params_dev, lo, seg_ptr_dev, count, d, size, out_dev, 2, row_max);
+  return RunMpReduce((hipStream_t)stream,
+                     MpReduceCall{"gather_segment_reduce_ids", mode, params_dev, d, size, out_dev}
+                         .Gather(kGatherIds, gather_ids_dev, params_rows).Segments(seg_ptr_dev, count));
 }
 
 int euler_gpu_gather_scatter(void* stream, int32_t mode, const float* params_dev,
                              const int32_t* gather_indices_dev,
                              const int32_t* scatter_indices_dev, int64_t e, int64_t d,
                              int32_t size, float* out_dev) {
-  if (mode < 0 || mode > 2) return Fail(EULER_GPU_EINVAL, "gather_scatter: mode is 0 add, 1 max, 2 mean");
-  if (e > 0 && !gather_indices_dev) return Fail(EULER_GPU_EINVAL, "gather_scatter: null buffer");
-  if (mode == 2 && e >= (1LL << 24))
-    return Fail(EULER_GPU_EINVAL, "gather_scatter: mean needs e < 2^24");
-  hipStream_t st = (hipStream_t)stream;
-  if (mode == 0)
-    return ScatterImpl<0>(st, params_dev, scatter_indices_dev, e, d, size, out_dev, gather_indices_dev);
-  if (mode == 1)
-    return ScatterImpl<1>(st, params_dev, scatter_indices_dev, e, d, size, out_dev, gather_indices_dev);
-  return ScatterImpl<2>(st, params_dev, scatter_indices_dev, e, d, size, out_dev, gather_indices_dev);
+  return RunMpReduce((hipStream_t)stream,
+                     MpReduceCall{"gather_scatter", mode, params_dev, d, size, out_dev}
+                         .Gather(kGatherNeeded, gather_indices_dev).Keys(scatter_indices_dev, e));
 }
 
 int euler_gpu_gather_scatter_w(void* stream, int32_t mode, const float* params_dev,
                                const int32_t* gather_indices_dev,
                                const int32_t* scatter_indices_dev, int64_t e, int64_t d,
                                int32_t size, float* out_dev, const float* w_dev, int32_t heads) {
-  const int rc = CheckWeightedShape("gather_scatter_w", mode, d, heads);
-  if (rc != EULER_GPU_OK) return rc;
-  if (e < 0 || size < 0) return Fail(EULER_GPU_EINVAL, "gather_scatter_w: bad shape");
-  if (size == 0 || d == 0) return EULER_GPU_OK;
-  if (!out_dev || (e > 0 && (!params_dev || !scatter_indices_dev || !w_dev)))
-    return Fail(EULER_GPU_EINVAL, "gather_scatter_w: null buffer");
-  if (e >= (1LL << 31)) return Fail(EULER_GPU_EINVAL, "gather_scatter_w: e >= 2^31");
-  if (mode == 2 && e >= (1LL << 24))
-    return Fail(EULER_GPU_EINVAL, "gather_scatter_w: mean needs e < 2^24");
-  hipStream_t st = (hipStream_t)stream;
-  const int32_t* keys = scatter_indices_dev;
-  const uint32_t* perm = nullptr;
-  StreamBuf scratch(st);
-  {
-    const int rg = GroupScatterKeys(st, scatter_indices_dev, e, &scratch, &keys, &perm);
-    if (rg != EULER_GPU_OK) return rg;
-  }
-  return DispatchWeightedReduce(st, mode, params_dev, SegSpec{keys, nullptr, 0, e, size},
-                                MpwIndex{perm, gather_indices_dev, 1, 0xFFFFFFFFu}, d, out_dev, w_dev,
-                                heads);
+  return RunMpReduce((hipStream_t)stream,
+                     MpReduceCall{"gather_scatter_w", mode, params_dev, d, size, out_dev}
+                         .Gather(kGatherOrNull, gather_indices_dev).Keys(scatter_indices_dev, e)
+                         .Weights(w_dev, heads));
 }
 
 int euler_gpu_gather_segment_reduce_w(void* stream, int32_t mode, const float* params_dev,
@@ -945,21 +900,10 @@ int euler_gpu_gather_segment_reduce_w(void* stream, int32_t mode, const float* p
                                       const int64_t* seg_ptr_dev, int64_t count, int64_t d,
                                       int32_t size, float* out_dev, const float* w_dev,
                                       int32_t heads) {
-  const int rc = CheckWeightedShape("gather_segment_reduce_w", mode, d, heads);
-  if (rc != EULER_GPU_OK) return rc;
-  if (size < 0 || (!seg_ptr_dev && count < 0))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_w: bad shape");
-  if (size == 0 || d == 0) return EULER_GPU_OK;
-  if (!out_dev || !params_dev || !w_dev)
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_w: null buffer");
-  if (!seg_ptr_dev && (int64_t)size * count >= (1LL << 31))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_w: e >= 2^31");
-  if (!seg_ptr_dev && mode == 2 && count >= (1LL << 24))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_w: mean needs segments shorter than 2^24");
-  return DispatchWeightedReduce((hipStream_t)stream, mode, params_dev,
-                                SegSpec{nullptr, seg_ptr_dev, count, 0, size},
-                                MpwIndex{nullptr, gather_indices_dev, 1, 0xFFFFFFFFu}, d, out_dev,
-                                w_dev, heads);
+  return RunMpReduce((hipStream_t)stream,
+                     MpReduceCall{"gather_segment_reduce_w", mode, params_dev, d, size, out_dev}
+                         .Gather(kGatherOrNull, gather_indices_dev).Segments(seg_ptr_dev, count)
+                         .Weights(w_dev, heads));
 }
 
 int euler_gpu_gather_segment_reduce_ids_w(void* stream, int32_t mode, const float* params_dev,
@@ -967,24 +911,10 @@ int euler_gpu_gather_segment_reduce_ids_w(void* stream, int32_t mode, const floa
                                           const int64_t* seg_ptr_dev, int64_t count, int64_t d,
                                           int32_t size, float* out_dev, const float* w_dev,
                                           int32_t heads) {
-  const int rc = CheckWeightedShape("gather_segment_reduce_ids_w", mode, d, heads);
-  if (rc != EULER_GPU_OK) return rc;
-  if (size < 0 || (!seg_ptr_dev && count < 0))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: bad shape");
-  if (size == 0 || d == 0) return EULER_GPU_OK;
-  if (!out_dev || !params_dev || !gather_ids_dev || !w_dev)
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: null buffer");
-  if (!seg_ptr_dev && (int64_t)size * count >= (1LL << 31))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: e >= 2^31");
-  if (!seg_ptr_dev && mode == 2 && count >= (1LL << 24))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: mean needs segments shorter than 2^24");
-  if (params_rows < 0 || params_rows >= ((int64_t)1 << 31))
-    return Fail(EULER_GPU_EINVAL, "gather_segment_reduce_ids_w: the table must have fewer than 2^31 rows");
-  const uint32_t row_max = params_rows > 0 ? (uint32_t)(params_rows - 1) : 0xFFFFFFFFu;
-  const int32_t* lo = reinterpret_cast<const int32_t*>(gather_ids_dev);     // little endian: word 0 of every id
-  return DispatchWeightedReduce((hipStream_t)stream, mode, params_dev,
-                                SegSpec{nullptr, seg_ptr_dev, count, 0, size},
-                                MpwIndex{nullptr, lo, 2, row_max}, d, out_dev, w_dev, heads);
+  return RunMpReduce((hipStream_t)stream,
+                     MpReduceCall{"gather_segment_reduce_ids_w", mode, params_dev, d, size, out_dev}
+                         .Gather(kGatherIds, gather_ids_dev, params_rows).Segments(seg_ptr_dev, count)
+                         .Weights(w_dev, heads));
 }
 
 int euler_gpu_neighbor_post_process(void* stream, int64_t n, int32_t* idx_dev,

@@ -1,5 +1,11 @@
-// Where the updates of a destination are, for the segment reduces of mp_kernels.hip (fp32) and
-// mp_half_kernels.hip (bf16 / fp16 storage): device functions shared by both.
+// The segment reduces of mp_kernels.hip (fp32) and mp_half_kernels.hip (bf16 / fp16 storage), shared
+// by both and by the ops built on them (edge_softmax, relation_reduce, top-k):
+//  - device: where the updates of a destination are (SegSpec / SegBounds);
+//  - host: the launch shape of a reduce with a wave-slot per destination row (RowLaneShape), the
+//    grouping of scatter keys (GroupScatterKeys), and the ONE path of the sixteen scatter_* /
+//    gather_scatter* / gather_segment_reduce* entries: each fills an MpReduceCall and calls
+//    RunMpReduce, which checks it (CheckMpReduce: the only argument ladder), groups the keys,
+//    builds SegSpec / MpwIndex once and picks the launcher by (weighted, dtype, mode).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -58,6 +64,72 @@ __device__ __forceinline__ void SegBounds(const SegSpec& s, int64_t r, int64_t* 
   }
 }
 
+// The launch shape of a reduce with blockDim = (64, 4) and a wave-slot per destination row.  The
+// vector form - a lane owns N adjacent columns (one 16-byte access), dv = d / N lanes a row,
+// 64 / dv rows a wave - serves d % N == 0 with dv a divisor of 64, rows on 16-byte boundaries and,
+// for the weighted kernels, N | dh so that a lane's columns share a head (dh = 0: no heads); every
+// other d takes the element form, a column per lane.  At most 256 * 32 blocks: the rows are strided.
+struct LaneShape {
+  bool vec;
+  int64_t dv;        // lanes of a row in the vector form
+  unsigned blocks;
+};
+
+inline LaneShape RowLaneShape(int32_t size, int64_t d, int n, int64_t dh, const void* params,
+                              const void* out) {
+  const int64_t dv = d / n;
+  const bool vec = d % n == 0 && dv <= 64 && 64 % dv == 0 && dh % n == 0 &&
+                   ((uintptr_t)params % 16 == 0) && ((uintptr_t)out % 16 == 0);
+  const int64_t rows_per_block = vec ? 4 * (64 / dv) : 4;
+  int64_t blocks = ((int64_t)size + rows_per_block - 1) / rows_per_block;
+  if (blocks > 256 * 32) blocks = 256 * 32;
+  return LaneShape{vec, dv, (unsigned)blocks};
+}
+
+struct MpwIndex;      // mp_weighted.h
+
+// One call of a scatter_* / gather_scatter* / gather_segment_reduce* entry, as its adapter in
+// mp_kernels.hip / mp_half_kernels.hip states it: {name, mode, params, d, size, out}, then what the
+// entry has beyond an fp32 reduce of consecutive rows.
+enum MpGather {
+  kNoGatherArg,     // scatter_*: update p is row p
+  kGatherOrNull,    // int32 indices; nullptr: update p is row p
+  kGatherNeeded,    // int32 indices, nullptr refused
+  kGatherIds,       // int64 ids read in place (index = low word, clamped to the last row), nullptr refused
+};
+
+struct MpReduceCall {
+  const char* name;          // of the entry, as its messages begin
+  int32_t mode;              // 0 add, 1 max, 2 mean
+  const void* params;        // the table, or the updates themselves
+  int64_t d;
+  int32_t size;
+  void* out;
+  bool typed = false;        // a `_t` entry: dtype codes, and weights whose alignment is not their C type's
+  int32_t in_dtype = EULER_GPU_F32, out_dtype = EULER_GPU_F32, w_dtype = EULER_GPU_F32;
+  MpGather gather_kind = kNoGatherArg;
+  const void* gather = nullptr;
+  int64_t params_rows = 0;   // kGatherIds: rows of the table
+  bool keyed = false;        // destinations by scatter key (keys, e); else by seg_ptr, or `count` each
+  const int32_t* keys = nullptr;
+  int64_t e = 0;
+  const int64_t* seg_ptr = nullptr;
+  int64_t count = 0;
+  bool weighted = false;
+  const void* w = nullptr;   // [E, heads]
+  int32_t heads = 1;
+
+  MpReduceCall& Typed(int32_t in, int32_t out_dt) { typed = true; in_dtype = in; out_dtype = out_dt; return *this; }
+  MpReduceCall& Gather(MpGather kind, const void* g, int64_t rows = 0) {
+    gather_kind = kind; gather = g; params_rows = rows; return *this;
+  }
+  MpReduceCall& Keys(const int32_t* k, int64_t n) { keyed = true; keys = k; e = n; return *this; }
+  MpReduceCall& Segments(const int64_t* ptr, int64_t n) { seg_ptr = ptr; count = n; return *this; }
+  MpReduceCall& Weights(const void* w_dev, int32_t h, int32_t dt = EULER_GPU_F32) {
+    weighted = true; w = w_dev; heads = h; w_dtype = dt; return *this;
+  }
+};
+
 #pragma GCC visibility push(hidden)
 // mp_kernels.hip: groups the e scatter keys by destination for the reduces.  Keys that are already
 // non-decreasing (one look, one host wait) are used as they are: *keys = idx, *perm = nullptr.
@@ -65,8 +137,16 @@ __device__ __forceinline__ void SegBounds(const SegSpec& s, int64_t r, int64_t* 
 // the original position of the p-th grouped update.
 int GroupScatterKeys(hipStream_t st, const int32_t* idx, int64_t e, StreamBuf* scratch,
                      const int32_t** keys, const uint32_t** perm);
-// mp_kernels.hip: the argument checks every weighted entry shares (mode 0..2, heads >= 1, heads | d)
-int CheckWeightedShape(const char* what, int32_t mode, int64_t d, int32_t heads);
+// mp_kernels.hip: the argument ladder, in its one order: dtype codes and weight alignment; mode,
+// heads, heads | d; negative shape; size == 0 || d == 0 (*nothing_to_do: OK, nothing is touched - the
+// callers hand over null for empty tensors, so the null check comes after); null buffers; e >= 2^31;
+// the 2^24 limits of a mean; the 2^31 rows of an id-addressed table; 2-byte alignment of 16-bit
+// data.  Host arithmetic and Fail() only: no HIP call.
+int CheckMpReduce(const MpReduceCall& c, bool* nothing_to_do);
+int RunMpReduce(hipStream_t st, const MpReduceCall& c);
+// mp_half_kernels.hip: the launchers over bf16 / fp16 rows (c checked, seg and ix built)
+int ReduceHalf(hipStream_t st, const MpReduceCall& c, const SegSpec& seg, const MpwIndex& ix);
+int WeightedReduceHalf(hipStream_t st, const MpReduceCall& c, const SegSpec& seg, const MpwIndex& ix);
 #pragma GCC visibility pop
 
 }  // namespace euler_gpu

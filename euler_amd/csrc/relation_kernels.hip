@@ -207,20 +207,12 @@ __global__ __launch_bounds__(256) void RelationReduceVecKernel(const RelArgs A, 
 template <int MODE, int DT, bool OUT16>
 int LaunchRelation(hipStream_t st, const RelArgs& A) {
   constexpr int N = DT == kF32 ? 4 : 8;
-  const dim3 block(64, 4);
-  const int64_t dv = A.d / N;
-  const int32_t size = A.seg.size;
-  if (A.d % N == 0 && dv <= 64 && 64 % dv == 0 && ((uintptr_t)A.params % 16 == 0) &&
-      ((uintptr_t)A.out % 16 == 0)) {
-    const int64_t rows_per_block = 4 * (64 / dv);
-    int64_t blocks = ((int64_t)size + rows_per_block - 1) / rows_per_block;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL((RelationReduceVecKernel<MODE, DT, OUT16, N>), dim3((unsigned)blocks), block, 0, st, A,
-                       (int32_t)dv);
+  const LaneShape s = RowLaneShape(A.seg.size, A.d, N, 0, A.params, A.out);
+  if (s.vec) {
+    hipLaunchKernelGGL((RelationReduceVecKernel<MODE, DT, OUT16, N>), dim3(s.blocks), dim3(64, 4), 0, st, A,
+                       (int32_t)s.dv);
   } else {
-    int64_t blocks = ((int64_t)size + 3) / 4;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL((RelationReduceKernel<MODE, DT, OUT16>), dim3((unsigned)blocks), block, 0, st, A);
+    hipLaunchKernelGGL((RelationReduceKernel<MODE, DT, OUT16>), dim3(s.blocks), dim3(64, 4), 0, st, A);
   }
   EG_HIP(hipGetLastError());
   return EULER_GPU_OK;

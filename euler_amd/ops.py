@@ -77,16 +77,9 @@ def _gather_raw(params, indices, out_dtype=None):
     e, d = indices.numel(), params.shape[1]
     out = torch.empty((e, d), dtype=od, device=params.device)
     with _on(params.device):
-        if code == _lib.F32:
-            check(lib().euler_gpu_gather(_stream(), _ptr(params), _ptr(indices), e, d,
-                                         params.shape[0], _ptr(out)))
-        else:
-            check(lib().euler_gpu_gather_t(_stream(), _ptr(params), code, _ptr(indices), e, d,
-                                           params.shape[0], _ptr(out), _DT[od]))
+        check(lib().euler_gpu_gather_t(_stream(), _ptr(params), code, _ptr(indices), e, d,
+                                       params.shape[0], _ptr(out), _DT[od]))
     return out
-
-
-_SCATTER_F32 = ("euler_gpu_scatter_add", "euler_gpu_scatter_max", "euler_gpu_scatter_mean")
 
 
 def _scatter_raw(mode, updates, indices, size, out_dtype=None):
@@ -99,12 +92,8 @@ def _scatter_raw(mode, updates, indices, size, out_dtype=None):
     e, d = updates.shape
     out = torch.empty((int(size), d), dtype=od, device=updates.device)
     with _on(updates.device):
-        if code == _lib.F32:
-            check(getattr(lib(), _SCATTER_F32[mode])(_stream(), _ptr(updates), _ptr(indices), e, d,
-                                                     int(size), _ptr(out)))
-        else:
-            check(lib().euler_gpu_scatter_t(_stream(), mode, _ptr(updates), code, _ptr(indices), e, d,
-                                            int(size), _ptr(out), _DT[od]))
+        check(lib().euler_gpu_scatter_t(_stream(), mode, _ptr(updates), code, _ptr(indices), e, d,
+                                        int(size), _ptr(out), _DT[od]))
     return out
 
 
@@ -274,12 +263,8 @@ def _gather_scatter_raw(mode, params, gather_indices, scatter_indices, size, val
     e, d = gi.numel(), params.shape[1]
     out = torch.empty((int(size), d), dtype=od, device=params.device)
     with _on(params.device):
-        if code == _lib.F32:
-            check(lib().euler_gpu_gather_scatter(_stream(), mode, _ptr(params), _ptr(gi), _ptr(si), e, d,
-                                                 int(size), _ptr(out)))
-        else:
-            check(lib().euler_gpu_gather_scatter_t(_stream(), mode, _ptr(params), code, _ptr(gi), _ptr(si),
-                                                   e, d, int(size), _ptr(out), _DT[od]))
+        check(lib().euler_gpu_gather_scatter_t(_stream(), mode, _ptr(params), code, _ptr(gi), _ptr(si),
+                                               e, d, int(size), _ptr(out), _DT[od]))
     return out
 
 
@@ -348,57 +333,56 @@ def _segment_dst(seg_ptr, count, size, device):
     return torch.repeat_interleave(torch.arange(size, device=device, dtype=torch.int32), lens)
 
 
+def _segment_args(params, gather_indices, seg_ptr, count, size, validate):
+    """the tensors of a segmented call -> (params, gi, as_ids, sp), contiguous and checked"""
+    params = params.contiguous()
+    # int64 ids (what the samplers return) are read in place: index = low word of the id,
+    # the int32 a cast would give, without the cast's pass (euler_gpu_gather_segment_reduce_ids_t)
+    as_ids = gather_indices.dtype == torch.int64 and not validate
+    gi = gather_indices.contiguous() if as_ids else gather_indices.to(torch.int32).contiguous()
+    _need_cuda(params, gi)
+    sp = None
+    if seg_ptr is not None:
+        sp = seg_ptr.to(torch.int64).contiguous()
+        _need_cuda(params, sp)
+        if sp.numel() != size + 1:
+            raise ValueError("gather_segment_reduce: seg_ptr has size + 1 entries")
+    elif gi.numel() != size * count:
+        raise ValueError("gather_segment_reduce: size * count gather indices")
+    if validate:
+        _check_rows("gather_segment_reduce", gi, params.shape[0])
+    return params, gi, as_ids, sp
+
+
+def _saved_rows(gi, n_rows):
+    """int64 ids as the int32 rows the forward kernel read, for the gradient kernels: an id past the
+    table - or a negative one, e.g. default_node = -1: unsigned there - reads the table's LAST row
+    (euler_gpu.h: min((uint32) low word, rows - 1)), and the gradient must flow to that same row
+    (the raw low word would be an out-of-range or negative scatter key)"""
+    return torch.clamp(gi & 0xFFFFFFFF, max=n_rows - 1).to(torch.int32)
+
+
 class _GatherSegmentReduce(torch.autograd.Function):
     @staticmethod
     def forward(ctx, params, gather_indices, seg_ptr, count, size, op, validate, out_dtype):
         code = _dt("gather_segment_reduce", params)
         od = _out_dt("gather_segment_reduce", params, out_dtype)
-        params = params.contiguous()
-        # int64 ids (what the samplers return) are read in place: index = low word of the id,
-        # the int32 a cast would give, without the cast's pass (euler_gpu_gather_segment_reduce_ids)
-        as_ids = gather_indices.dtype == torch.int64 and not validate
-        gi = gather_indices.contiguous() if as_ids else gather_indices.to(torch.int32).contiguous()
-        _need_cuda(params, gi)
-        sp = None
-        if seg_ptr is not None:
-            sp = seg_ptr.to(torch.int64).contiguous()
-            _need_cuda(params, sp)
-            if sp.numel() != size + 1:
-                raise ValueError("gather_segment_reduce: seg_ptr has size + 1 entries")
-        elif gi.numel() != size * count:
-            raise ValueError("gather_segment_reduce: size * count gather indices")
-        if validate:
-            _check_rows("gather_segment_reduce", gi, params.shape[0])
-        out = torch.empty((int(size), params.shape[1]), dtype=od, device=params.device)
-        sp_p = _ptr(sp) if sp is not None else None
+        params, gi, as_ids, sp = _segment_args(params, gather_indices, seg_ptr, count, size, validate)
+        rows, d = params.shape
+        out = torch.empty((size, d), dtype=od, device=params.device)
         with _on(params.device):
-            if code == _lib.F32:
-                if as_ids:      # (ids past the table read its last row: euler_gpu.h)
-                    check(lib().euler_gpu_gather_segment_reduce_ids(
-                        _stream(), _GS_MODE[op], _ptr(params), int(params.shape[0]), _ptr(gi),
-                        sp_p, int(count), params.shape[1], int(size), _ptr(out)))
-                else:
-                    check(lib().euler_gpu_gather_segment_reduce(
-                        _stream(), _GS_MODE[op], _ptr(params), _ptr(gi), sp_p,
-                        int(count), params.shape[1], int(size), _ptr(out)))
-            elif as_ids:
+            if as_ids:      # (ids past the table read its last row: euler_gpu.h)
                 check(lib().euler_gpu_gather_segment_reduce_ids_t(
-                    _stream(), _GS_MODE[op], _ptr(params), code, int(params.shape[0]), _ptr(gi),
-                    sp_p, int(count), params.shape[1], int(size), _ptr(out), _DT[od]))
+                    _stream(), _GS_MODE[op], _ptr(params), code, rows, _ptr(gi), _ptr(sp), count, d, size,
+                    _ptr(out), _DT[od]))
             else:
                 check(lib().euler_gpu_gather_segment_reduce_t(
-                    _stream(), _GS_MODE[op], _ptr(params), code, _ptr(gi), sp_p,
-                    int(count), params.shape[1], int(size), _ptr(out), _DT[od]))
+                    _stream(), _GS_MODE[op], _ptr(params), code, _ptr(gi), _ptr(sp), count, d, size,
+                    _ptr(out), _DT[od]))
         if as_ids and ctx.needs_input_grad[0]:
-            # the gradient kernels take int32 indices.  The forward kernel reads an id past the
-            # table - or a negative one, e.g. default_node = -1: unsigned there - from the table's
-            # LAST row (euler_gpu.h); the gradient must flow to that same row, so the saved
-            # indices get the same clamp (the raw low word would be an out-of-range or
-            # negative scatter key)
-            last = int(params.shape[0]) - 1            # min((uint32) low word, rows - 1), as the kernel
-            gi = torch.clamp(gi & 0xFFFFFFFF, max=last).to(torch.int32)
+            gi = _saved_rows(gi, rows)
         ctx.save_for_backward(params, gi, sp if sp is not None else torch.empty(0), out)
-        ctx.has_ptr, ctx.count, ctx.size, ctx.op = sp is not None, int(count), int(size), op
+        ctx.has_ptr, ctx.count, ctx.size, ctx.op = sp is not None, count, size, op
         return out
 
     @staticmethod
@@ -602,13 +586,9 @@ def _gather_scatter_w_raw(mode, params, gi, si, size, w2, heads, out_dtype=None,
     e, d = si.numel(), params.shape[1]
     out = torch.empty((int(size), d), dtype=od, device=params.device)
     with _on(params.device):
-        if code == _lib.F32:
-            check(lib().euler_gpu_gather_scatter_w(_stream(), mode, _ptr(params), _ptr(gi), _ptr(si), e, d,
-                                                   int(size), _ptr(out), _ptr(w2), heads))
-        else:
-            check(lib().euler_gpu_gather_scatter_w_t(_stream(), mode, _ptr(params), code, _ptr(gi), _ptr(si),
-                                                     e, d, int(size), _ptr(out), _DT[od], _ptr(w2),
-                                                     _DT[w2.dtype], heads))
+        check(lib().euler_gpu_gather_scatter_w_t(_stream(), mode, _ptr(params), code, _ptr(gi), _ptr(si),
+                                                 e, d, int(size), _ptr(out), _DT[od], _ptr(w2),
+                                                 _DT[w2.dtype], heads))
     return out
 
 
@@ -692,32 +672,21 @@ class _GatherScatterW(torch.autograd.Function):
 
 
 class _GatherSegmentReduceW(torch.autograd.Function):
-    """gather_segment_reduce with edge_weight (euler_gpu_gather_segment_reduce_w / _ids_w)"""
+    """gather_segment_reduce with edge_weight (euler_gpu_gather_segment_reduce_w_t / _ids_w_t)"""
 
     @staticmethod
     def _raw(mode, params, gi, as_ids, sp, count, size, w2, heads, od):
-        code = _lib.F32 if params.dtype == _F32 else _DT[params.dtype]
-        out = torch.empty((int(size), params.shape[1]), dtype=od, device=params.device)
-        sp_p = _ptr(sp) if sp is not None else None
-        d = params.shape[1]
+        rows, d = params.shape
+        out = torch.empty((size, d), dtype=od, device=params.device)
         with _on(params.device):
-            if code == _lib.F32:
-                if as_ids:
-                    check(lib().euler_gpu_gather_segment_reduce_ids_w(
-                        _stream(), mode, _ptr(params), int(params.shape[0]), _ptr(gi), sp_p, int(count), d,
-                        int(size), _ptr(out), _ptr(w2), heads))
-                else:
-                    check(lib().euler_gpu_gather_segment_reduce_w(
-                        _stream(), mode, _ptr(params), _ptr(gi), sp_p, int(count), d, int(size), _ptr(out),
-                        _ptr(w2), heads))
-            elif as_ids:
+            if as_ids:
                 check(lib().euler_gpu_gather_segment_reduce_ids_w_t(
-                    _stream(), mode, _ptr(params), code, int(params.shape[0]), _ptr(gi), sp_p, int(count), d,
-                    int(size), _ptr(out), _DT[od], _ptr(w2), _DT[w2.dtype], heads))
+                    _stream(), mode, _ptr(params), _DT[params.dtype], rows, _ptr(gi), _ptr(sp), count, d, size,
+                    _ptr(out), _DT[od], _ptr(w2), _DT[w2.dtype], heads))
             else:
                 check(lib().euler_gpu_gather_segment_reduce_w_t(
-                    _stream(), mode, _ptr(params), code, _ptr(gi), sp_p, int(count), d, int(size), _ptr(out),
-                    _DT[od], _ptr(w2), _DT[w2.dtype], heads))
+                    _stream(), mode, _ptr(params), _DT[params.dtype], _ptr(gi), _ptr(sp), count, d, size,
+                    _ptr(out), _DT[od], _ptr(w2), _DT[w2.dtype], heads))
         return out
 
     @staticmethod
@@ -725,28 +694,12 @@ class _GatherSegmentReduceW(torch.autograd.Function):
         _dt("gather_segment_reduce", params)
         od = _out_dt("gather_segment_reduce", params, out_dtype)
         w2, heads = _edge_weight("gather_segment_reduce", w, gather_indices.numel(), params)
-        params = params.contiguous()
-        as_ids = gather_indices.dtype == torch.int64 and not validate
-        gi = gather_indices.contiguous() if as_ids else gather_indices.to(torch.int32).contiguous()
-        _need_cuda(params, gi)
-        sp = None
-        if seg_ptr is not None:
-            sp = seg_ptr.to(torch.int64).contiguous()
-            _need_cuda(params, sp)
-            if sp.numel() != size + 1:
-                raise ValueError("gather_segment_reduce: seg_ptr has size + 1 entries")
-        elif gi.numel() != size * count:
-            raise ValueError("gather_segment_reduce: size * count gather indices")
-        if validate:
-            _check_rows("gather_segment_reduce", gi, params.shape[0])
+        params, gi, as_ids, sp = _segment_args(params, gather_indices, seg_ptr, count, size, validate)
         out = _GatherSegmentReduceW._raw(_GS_MODE[op], params, gi, as_ids, sp, count, size, w2, heads, od)
         if as_ids and (ctx.needs_input_grad[0] or ctx.needs_input_grad[8]):
-            # the clamp-to-last-row rule of the forward kernel for the saved indices
-            # (_GatherSegmentReduce.forward)
-            last = int(params.shape[0]) - 1
-            gi = torch.clamp(gi & 0xFFFFFFFF, max=last).to(torch.int32)
+            gi = _saved_rows(gi, params.shape[0])
         ctx.save_for_backward(params, gi, sp if sp is not None else torch.empty(0), w, out)
-        ctx.has_ptr, ctx.count, ctx.size, ctx.op = sp is not None, int(count), int(size), op
+        ctx.has_ptr, ctx.count, ctx.size, ctx.op = sp is not None, count, size, op
         return out
 
     @staticmethod
