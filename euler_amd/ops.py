@@ -1309,6 +1309,179 @@ def triple_score_proj(ent, rel, src, rel_id, dst, neg=None, proj="hyperplane", h
     return pos if neg is None else (pos, out)
 
 
+KG_MATRIX_MAX_DIM = 512
+
+
+def _matrix_grouping(rel_id, n_rel):
+    """The grouping of euler_gpu_triple_score_matrix, with torch and without a host wait:
+    -> (order [B]: the stable sort of the keys - rel_id, or n_rel where it names no relation -,
+    sorted_keys [B])"""
+    valid = (rel_id >= 0) & (rel_id < n_rel)
+    key = torch.where(valid, rel_id, torch.full_like(rel_id, n_rel))
+    sorted_keys, order = torch.sort(key, stable=True)
+    return order.contiguous(), sorted_keys
+
+
+def _matrix_segments(sorted_keys, n_rel, compact):
+    """-> (seg_ptr [nseg + 1], seg_rel [nseg]) over the sorted keys.  Not compact: one segment a
+    relation, any length may be 0 - fixed size, no host wait.  compact: the distinct relations
+    used (their segments are adjacent in the order); this one waits for the host."""
+    dev = sorted_keys.device
+    if compact:
+        seg_rel = torch.unique_consecutive(sorted_keys)
+        seg_rel = seg_rel[seg_rel < n_rel].contiguous()
+        edges = torch.cat([seg_rel, torch.full((1,), n_rel, dtype=torch.int64, device=dev)])
+    else:
+        seg_rel = torch.arange(n_rel, dtype=torch.int64, device=dev)
+        edges = torch.arange(n_rel + 1, dtype=torch.int64, device=dev)
+    return torch.searchsorted(sorted_keys, edges).contiguous(), seg_rel
+
+
+def _triple_matrix_head(ent, rel, matrix, src, rel_id, dst, neg, kind, corrupt, order):
+    """the arguments the two triple_score_matrix entries share, from prepared tensors"""
+    b, k = src.numel(), (neg.shape[1] if neg is not None else 0)
+    return (_stream(), _KG_KIND[kind], _KG_CORRUPT[corrupt], _ptr(ent), _DT[ent.dtype], ent.shape[0], ent.shape[1],
+            _ptr(rel), _DT[rel.dtype], rel.shape[0], rel.shape[1], _ptr(matrix), _DT[matrix.dtype],
+            _ptr(src), _ptr(rel_id), _ptr(dst), _ptr(neg), b, k, _ptr(order))
+
+
+def _triple_score_matrix_raw(ent, rel, matrix, src, rel_id, dst, neg, kind, corrupt, order):
+    """euler_gpu_triple_score_matrix on prepared tensors -> (pos [B], neg_out [B, K'])"""
+    b, k = src.numel(), (neg.shape[1] if neg is not None else 0)
+    kp = 2 * k if corrupt == "both" else k
+    if b == 0 or ent.shape[1] == 0 or rel.shape[1] == 0:
+        return torch.zeros(b, dtype=_F32, device=ent.device), torch.zeros((b, kp), dtype=_F32, device=ent.device)
+    pos = torch.empty(b, dtype=_F32, device=ent.device)
+    out = torch.empty((b, kp), dtype=_F32, device=ent.device)
+    with _on(ent.device):
+        check(lib().euler_gpu_triple_score_matrix(
+            *_triple_matrix_head(ent, rel, matrix, src, rel_id, dst, neg, kind, corrupt, order),
+            _ptr(pos), _ptr(out) if k else None))
+    return pos, out
+
+
+def _triple_score_matrix_grad_raw(ent, rel, matrix, src, rel_id, dst, neg, kind, corrupt, order, seg_ptr, seg_rel,
+                                  g_pos, g_neg):
+    """euler_gpu_triple_score_matrix_grad -> the fp32 gradients of the raw rows per occurrence
+    (G_src [B, de], G_rel [B, dr], G_dst [B, de], G_neg [B, K, de]), the gz rows (gz_src, gz_dst
+    [B, dr], gz_neg [B, K, dr]) and G_M [nseg, de * dr] in the matrix's dtype (None without
+    segments)"""
+    b, k, de, dr = src.numel(), (neg.shape[1] if neg is not None else 0), ent.shape[1], rel.shape[1]
+    nseg = 0 if seg_rel is None else seg_rel.numel()
+    empty = b == 0 or de == 0 or dr == 0
+    make = torch.zeros if empty else torch.empty
+    f = lambda *shape: make(shape, dtype=_F32, device=ent.device)                        # noqa: E731
+    gs, gr, gd, gn = f(b, de), f(b, dr), f(b, de), f(b, k, de)
+    zs, zd, zn = f(b, dr), f(b, dr), f(b, k, dr)
+    gm = None if seg_rel is None else make((nseg, de * dr), dtype=matrix.dtype, device=ent.device)
+    if empty:
+        return gs, gr, gd, gn, zs, zd, zn, gm
+    g_pos = g_pos.to(_F32).contiguous()
+    g_neg = g_neg.to(_F32).contiguous() if k else None
+    with _on(ent.device):
+        check(lib().euler_gpu_triple_score_matrix_grad(
+            *_triple_matrix_head(ent, rel, matrix, src, rel_id, dst, neg, kind, corrupt, order),
+            _ptr(seg_ptr) if nseg else None, _ptr(seg_rel) if nseg else None, nseg, _ptr(g_pos), _ptr(g_neg),
+            _ptr(gs), _ptr(gr), _ptr(gd), _ptr(gn) if k else None, _ptr(zs), _ptr(zd), _ptr(zn) if k else None,
+            _ptr(gm) if nseg else None))
+    return gs, gr, gd, gn, zs, zd, zn, gm
+
+
+class _TripleScoreMatrix(torch.autograd.Function):
+    """The fused scores with TransR's projection.  ent and rel take their gradients as
+    _TripleScore's do: the per-occurrence rows go through _table_grad at [src | dst | neg] and at
+    rel_id.  The gradient of `matrix` is the third kernel's ordered sum per relation: dense
+    [R, de * dr], or with sparse_grad a sparse_coo_tensor over the distinct relations used (that
+    compaction waits for the host, as _table_grad's does)."""
+
+    @staticmethod
+    def forward(ctx, ent, rel, matrix, src, rel_id, dst, neg, kind, corrupt, sparse_grad):
+        order, sorted_keys = _matrix_grouping(rel_id, rel.shape[0])
+        ctx.save_for_backward(ent, rel, matrix, src, rel_id, dst, neg, order, sorted_keys)
+        ctx.conf = (kind, corrupt, sparse_grad)
+        return _triple_score_matrix_raw(ent, rel, matrix, src, rel_id, dst, neg, kind, corrupt, order)
+
+    @staticmethod
+    def backward(ctx, g_pos, g_neg):
+        ent, rel, matrix, src, rel_id, dst, neg, order, sorted_keys = ctx.saved_tensors
+        kind, corrupt, sparse_grad = ctx.conf
+        seg_ptr = seg_rel = None
+        if ctx.needs_input_grad[2]:
+            seg_ptr, seg_rel = _matrix_segments(sorted_keys, rel.shape[0], sparse_grad)
+        gs, gr, gd, gn, _, _, _, gm = _triple_score_matrix_grad_raw(
+            ent, rel, matrix, src, rel_id, dst, neg, kind, corrupt, order, seg_ptr, seg_rel, g_pos, g_neg)
+        g_ent = g_rel = g_matrix = None
+        if ctx.needs_input_grad[0]:
+            rows, ids = [gs, gd], [src, dst]
+            if neg is not None:
+                rows.append(gn.reshape(-1, gn.shape[2]))
+                ids.append(neg.reshape(-1))
+            g_ent = _table_grad(torch.cat(rows), torch.cat(ids), ent.shape[0], ent.dtype, sparse_grad)
+        if ctx.needs_input_grad[1]:
+            g_rel = _table_grad(gr, rel_id, rel.shape[0], rel.dtype, sparse_grad)
+        if ctx.needs_input_grad[2]:
+            g_matrix = torch.sparse_coo_tensor(seg_rel.reshape(1, -1), gm, matrix.shape) if sparse_grad else gm
+        return (g_ent, g_rel, g_matrix) + (None,) * 7
+
+
+def triple_score_matrix(ent, rel, matrix, src, rel_id, dst, neg=None, kind="trans_l1", corrupt="both",
+                        sparse_grad=False):
+    """triple_score with TransR's per-relation matrix projection fused in (generate_embedding of
+    the reference's examples/TransX/transR.py:41-68): ent [rows, de], rel [relations, dr] and
+    matrix [relations, de * dr] (or [relations, de, dr]; row-major M_rho [de, dr]).  With
+    rho = rel_id an entity row x is not normalised and becomes N(x . M_rho), r = N(rel[rho]); N is
+    tf.nn.l2_normalize with its 1e-12 clamp.  The reference looks up one matrix per triple, tiles
+    it over the negatives and runs a batched product: a [B, K, de * dr] block forward and backward.
+    Here the triples are worked on grouped by relation (a stable sort of rel_id, built with torch,
+    no host wait), a matrix is staged once per group of triples and no triple owns a matrix.
+    kind is "trans_l1" or "trans_l2" ("distmult" takes no projection); corrupt, the returned
+    pos [B] and neg [B, K'] (pos alone when neg is None) and the rule for ids that name no row
+    are triple_score's; a rel_id that names no relation removes its rel row and its matrix.  The
+    three tables are fp32, bf16 or fp16, each its own dtype; de and dr are at most 512.  All
+    arithmetic is fp32 in a fixed order (euler_amd/csrc/kg_matrix.h) that does not depend on the
+    batch or its grouping; the same call returns the same bits.  Gradients: ent and rel as
+    triple_score's (scatter_add of the kernel's per-occurrence rows, rounded once); the matrix's
+    gradient is summed per relation over its occurrences in triple order, without atomics, and
+    rounded once to the matrix's dtype.  sparse_grad=True returns sparse_coo tensors over the
+    distinct rows / relations for all three tables (torch.optim.SparseAdam)."""
+    name = "triple_score_matrix"
+    if kind not in ("trans_l1", "trans_l2"):
+        raise ValueError("%s: kind is trans_l1 or trans_l2 (distmult takes no projection)" % name)
+    if corrupt not in _KG_CORRUPT:
+        raise ValueError("%s: corrupt is front, tail or both" % name)
+    for t in (ent, rel, matrix):
+        _dt(name, t)
+    if ent.dim() != 2 or rel.dim() != 2 or ent.shape[0] < 1 or rel.shape[0] < 1:
+        raise ValueError("%s: ent is [rows, de] and rel is [relations, dr], one row at least" % name)
+    de, dr = ent.shape[1], rel.shape[1]
+    if matrix.dim() not in (2, 3) or matrix.shape[0] != rel.shape[0] or \
+            (tuple(matrix.shape[1:]) != (de, dr) if matrix.dim() == 3 else matrix.shape[1] != de * dr):
+        raise ValueError("%s: matrix is [relations, de * dr] or [relations, de, dr]" % name)
+    if de > KG_MATRIX_MAX_DIM or dr > KG_MATRIX_MAX_DIM:
+        raise ValueError("%s: de and dr are at most %d" % (name, KG_MATRIX_MAX_DIM))
+    if sparse_grad and matrix.dim() == 3:
+        raise ValueError("%s: sparse_grad takes the matrix as [relations, de * dr]" % name)
+    src, rel_id, dst = (t.to(torch.int64).reshape(-1).contiguous() for t in (src, rel_id, dst))
+    b = src.numel()
+    if rel_id.numel() != b or dst.numel() != b:
+        raise ValueError("%s: one src, rel_id and dst per triple" % name)
+    if neg is not None:
+        neg = neg.to(torch.int64)
+        neg = (neg if neg.dim() == 2 else neg.reshape(b, -1)).contiguous()
+        if neg.shape[0] != b:
+            raise ValueError("%s: neg is [B, K]" % name)
+    _need_cuda(ent, rel, matrix, src, rel_id, dst, *(() if neg is None else (neg,)))
+    if b * max(1 if neg is None else neg.shape[1], 1) * 2 >= 2 ** 31 or ent.shape[0] >= 2 ** 31 \
+            or rel.shape[0] >= 2 ** 31:
+        raise ValueError("%s: B * max(K, 1) * 2 and the tables' rows must stay below 2^31" % name)
+    flat = matrix.contiguous()
+    if flat.dim() == 3:
+        flat = flat.reshape(rel.shape[0], de * dr)
+    pos, out = _TripleScoreMatrix.apply(ent.contiguous(), rel.contiguous(), flat, src, rel_id, dst, neg, kind,
+                                        corrupt, bool(sparse_grad))
+    return pos if neg is None else (pos, out)
+
+
 # ---- in-place embedding stores (tf_euler/python/utils/embedding.py:24-68) ---------------------
 # The stores of ScalableSageEncoder / ScalableGCNEncoder (utils/encoders.py:629-748, 294-409): a
 # non-trainable [max_id + 1, d] table per layer that lives in HBM across steps and is changed IN

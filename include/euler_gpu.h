@@ -1086,6 +1086,66 @@ int euler_gpu_triple_score_proj_grad(void* stream, int32_t proj, int32_t kind, i
                                      float* g_dst_dev, float* g_neg_rows_dev, float* g_rel_aux_dev,
                                      float* g_src_aux_dev, float* g_dst_aux_dev,
                                      float* g_neg_aux_rows_dev);
+/* triple_score_matrix: triple_score with TransR's per-relation matrix projection fused in
+ * (generate_embedding of examples/TransX/transR.py:41-68): tables ent [ent_rows, de],
+ * rel [rel_rows, dr] and matrix [rel_rows, de * dr], read row-major as M_rho [de, dr]; an entity
+ * row x is NOT normalised and becomes N(x . M_rho), r = N(rel[rho]), N = tf.nn.l2_normalize as in
+ * triple_score.  kind is 0 trans_l1 or 1 trans_l2 over the dr columns; corrupt, pos_out_dev [b]
+ * and neg_out_dev [b, K'] are triple_score's; the projection of n_j serves its front and its tail
+ * score.  No triple fetches a matrix of its own and no [b, k, de * dr] block exists: the triples
+ * are worked on grouped by relation and a workgroup stages M_rho once per run of equal relation.
+ * The three tables are fp32, bf16 or fp16, each its own type, widened exactly.  Ids are signed
+ * int64; an id outside [0, rows) names no row in any table it indexes (a rel_id removes rel[rho]
+ * AND M_rho): never dereferenced, reads as zeros, gets zero gradient rows.  All arithmetic is
+ * fp32 in the fixed orders stated in euler_amd/csrc/kg_matrix.h (they depend on de, dr, the types
+ * and the alignment of rel, never on b, k, the grouping or the launch).
+ * THE GROUPING is prepared by the caller, with key(t) = rel_id[t] if 0 <= rel_id[t] < rel_rows,
+ * else rel_rows:
+ *   order_dev [b]        a permutation of 0 .. b - 1 that sorts key(t) ascending and is STABLE
+ *                        (equal keys keep increasing t).
+ *   seg_ptr_dev [nseg+1] non-decreasing positions into order_dev; segment s is the positions
+ *   seg_rel_dev [nseg]   [seg_ptr[s], seg_ptr[s + 1]) and must hold exactly the triples whose key
+ *                        is seg_rel[s].  Lengths may be 0: nseg = rel_rows with seg_rel[s] = s is
+ *                        valid and needs no host wait.  Triples of key rel_rows belong to no
+ *                        segment.
+ * An order that is not a permutation, or wrong segments, are the caller's error and give wrong
+ * numbers only: an entry of order_dev outside [0, b) is skipped, seg_ptr is clamped to [0, b], a
+ * triple whose key is not its segment's relation and a segment whose seg_rel names no relation
+ * contribute nothing; no kernel reads or writes outside its buffers.
+ * triple_score_matrix_grad: from g_pos_dev [b] and g_neg_dev [b, K'] the fp32 gradients of the RAW
+ * rows per occurrence - g_src_dev, g_dst_dev [b, de], g_neg_rows_dev [b, k, de], g_rel_dev
+ * [b, dr]; a table's gradient is their scatter_add by id - the rows gz (the gradient of every
+ * projected row before its normalisation) gz_src_dev, gz_dst_dev [b, dr], gz_neg_rows_dev
+ * [b, k, dr], which the caller provides as scratch, and g_matrix_dev [nseg, de * dr] in the
+ * matrix's dtype: row s is the gradient of M_{seg_rel[s]}, summed over the segment's occurrences
+ * in the stated order (no float atomics) and written once; +0 for a segment without a term.
+ * nseg == 0 computes no matrix gradient (seg_ptr_dev, seg_rel_dev and g_matrix_dev may be NULL).
+ * Both only enqueue (the gradient three kernels): no allocation, no host wait; both can be
+ * captured into a graph.  EULER_GPU_EINVAL: the rules of triple_score_proj, de or dr above 512,
+ * ent_rows >= 2^31, order_dev null, nseg < 0 or >= 2^31, nseg > 0 with a null segment array or
+ * g_matrix_dev.  b == 0, de == 0 or dr == 0 returns EULER_GPU_OK and touches nothing; k == 0
+ * leaves the negative outputs untouched (neg_dev and they may be NULL). */
+int euler_gpu_triple_score_matrix(void* stream, int32_t kind, int32_t corrupt, const void* ent_dev,
+                                  int32_t ent_dtype, int64_t ent_rows, int64_t de,
+                                  const void* rel_dev, int32_t rel_dtype, int64_t rel_rows,
+                                  int64_t dr, const void* matrix_dev, int32_t matrix_dtype,
+                                  const int64_t* src_dev, const int64_t* rel_id_dev,
+                                  const int64_t* dst_dev, const int64_t* neg_dev, int64_t b,
+                                  int64_t k, const int64_t* order_dev, float* pos_out_dev,
+                                  float* neg_out_dev);
+int euler_gpu_triple_score_matrix_grad(void* stream, int32_t kind, int32_t corrupt,
+                                       const void* ent_dev, int32_t ent_dtype, int64_t ent_rows,
+                                       int64_t de, const void* rel_dev, int32_t rel_dtype,
+                                       int64_t rel_rows, int64_t dr, const void* matrix_dev,
+                                       int32_t matrix_dtype, const int64_t* src_dev,
+                                       const int64_t* rel_id_dev, const int64_t* dst_dev,
+                                       const int64_t* neg_dev, int64_t b, int64_t k,
+                                       const int64_t* order_dev, const int64_t* seg_ptr_dev,
+                                       const int64_t* seg_rel_dev, int64_t nseg,
+                                       const float* g_pos_dev, const float* g_neg_dev,
+                                       float* g_src_dev, float* g_rel_dev, float* g_dst_dev,
+                                       float* g_neg_rows_dev, float* gz_src_dev, float* gz_dst_dev,
+                                       float* gz_neg_rows_dev, void* g_matrix_dev);
 /* store_update / store_add / store_take: the in-place embedding stores of ScalableSage /
  * ScalableGCN (tf_euler/python/utils/embedding.py:24-68, encoders.py:713-748) - tf.scatter_update,
  * tf.scatter_add and embedding_lookup with the optional clearing update of encoders.py:738-743 -
