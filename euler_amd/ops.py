@@ -1482,6 +1482,149 @@ def triple_score_matrix(ent, rel, matrix, src, rel_id, dst, neg=None, kind="tran
     return pos if neg is None else (pos, out)
 
 
+# ---- the skip-gram loss head (tf_euler/python/solution/base_unsupervise.py) --------------------
+
+def _skipgram_head(target, context, src, pos, neg):
+    """the arguments the two skipgram_loss entries share, from prepared tensors"""
+    return (_stream(), _ptr(target), _DT[target.dtype], target.shape[0], _ptr(context), _DT[context.dtype],
+            context.shape[0], _ptr(src), _ptr(pos), _ptr(neg), src.numel(), pos.shape[1],
+            neg.shape[1] if neg is not None else 0, target.shape[1])
+
+
+def _skipgram_loss_raw(target, context, src, pos, neg):
+    """euler_gpu_skipgram_loss on prepared tensors -> (loss [1], rank [B] int32, logits [B, P + K],
+    row_loss [B])"""
+    b, n, dev = src.numel(), pos.shape[1] + (neg.shape[1] if neg is not None else 0), target.device
+    if b == 0:
+        return (torch.zeros(1, dtype=_F32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
+                torch.zeros((0, n), dtype=_F32, device=dev), torch.zeros(0, dtype=_F32, device=dev))
+    loss, row_loss = torch.empty(1, dtype=_F32, device=dev), torch.empty(b, dtype=_F32, device=dev)
+    rank = torch.empty(b, dtype=torch.int32, device=dev)
+    logits = torch.empty((b, n), dtype=_F32, device=dev)
+    with _on(dev):
+        check(lib().euler_gpu_skipgram_loss(*_skipgram_head(target, context, src, pos, neg), _ptr(logits), _ptr(rank),
+                                            _ptr(row_loss), _ptr(loss)))
+    return loss, rank, logits, row_loss
+
+
+def _skipgram_loss_grad_raw(target, context, src, pos, neg, logits, g):
+    """euler_gpu_skipgram_loss_grad -> the fp32 gradients of the raw rows per occurrence:
+    G_src [B, d], G_pos [B, P, d] and G_neg [B, K, d]; g is the gradient of the loss (one element)"""
+    b, p, k, d = src.numel(), pos.shape[1], (neg.shape[1] if neg is not None else 0), target.shape[1]
+    make = torch.zeros if b == 0 else torch.empty
+    gs = make((b, d), dtype=_F32, device=target.device)
+    gp = make((b, p, d), dtype=_F32, device=target.device)
+    gn = make((b, k, d), dtype=_F32, device=target.device)
+    if b == 0:
+        return gs, gp, gn
+    g = g.to(_F32).reshape(1).contiguous()
+    logits = logits.contiguous()
+    with _on(target.device):
+        check(lib().euler_gpu_skipgram_loss_grad(*_skipgram_head(target, context, src, pos, neg), _ptr(logits),
+                                                 _ptr(g), _ptr(gs), _ptr(gp), _ptr(gn) if k else None))
+    return gs, gp, gn
+
+
+class _SkipgramLoss(torch.autograd.Function):
+    """The fused loss head, in the shape of _TripleScore: the forward saves its logits, the kernel
+    of the backward returns the gradient of every looked-up row from them, and scatter_add adds
+    those rows at the keys src (target) and [pos | neg] (context).  rank and logits carry no
+    gradient; the index tensors get none."""
+
+    @staticmethod
+    def forward(ctx, target, context, src, pos, neg, sparse_grad):
+        loss, rank, logits, _ = _skipgram_loss_raw(target, context, src, pos, neg)
+        ctx.save_for_backward(target, context, src, pos, neg, logits)
+        ctx.sparse_grad = sparse_grad
+        ctx.mark_non_differentiable(rank, logits)
+        return loss.reshape(()), rank, logits
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_rank, _g_logits):
+        target, context, src, pos, neg, logits = ctx.saved_tensors
+        gs, gp, gn = _skipgram_loss_grad_raw(target, context, src, pos, neg, logits, g_loss)
+        d = target.shape[1]
+        g_target = g_context = None
+        if ctx.needs_input_grad[0]:
+            g_target = _table_grad(gs, src, target.shape[0], target.dtype, ctx.sparse_grad)
+        if ctx.needs_input_grad[1]:
+            rows, ids = [gp.reshape(-1, d)], [pos.reshape(-1)]
+            if neg is not None:
+                rows.append(gn.reshape(-1, d))
+                ids.append(neg.reshape(-1))
+            g_context = _table_grad(torch.cat(rows), torch.cat(ids), context.shape[0], context.dtype,
+                                    ctx.sparse_grad)
+        return g_target, g_context, None, None, None, None
+
+
+def skipgram_loss(target, context, src, pos, neg=None, sparse_grad=False, return_logits=False):
+    """The loss head of the walk-based models in one pass (DeepWalk, node2vec, LINE, unsupervised
+    GraphSAGE: the reference's solution/base_unsupervise.py with PosNegLogits of
+    solution/logits.py:30-34, xent_loss of solution/losses.py:27-33 and the rank behind mrr_score /
+    hitk_score / mr_score of utils/metrics.py:51-83).  target [Nt, d] and context [Nc, d] are the
+    two embedding tables (fp32, bf16 or fp16, each its own dtype; pass the same tensor twice to
+    share one table, LINE's first order); src [B], pos [B, P] (P >= 1) and neg [B, K] (or None)
+    are int64 ids.  With t = target[src] the logits are x_j = t . context[pos_j] and
+    t . context[neg_j]; the loss is the mean over all B * (P + K) logits of softplus(-x) of a
+    positive and softplus(x) of a negative; rank [B] (int32) counts the negatives and the first
+    P - 1 positives whose logit is >= the last positive's (tf.nn.top_k's tie rule on
+    concat([neg, pos]): a tie goes against the positive) - rank_metric turns it into mrr, mr
+    and hit@k.  Returns (loss, rank), loss a 0-d fp32 tensor, or (loss, rank, logits [B, P + K])
+    with return_logits; rank and logits carry no gradient.  No [B, 1 + K, d] block, no matmul
+    and no sort is built; an id outside [0, rows) names no row: it reads as a row of zeros (its
+    term, ln 2, still counts) and gets no gradient.  All arithmetic is fp32 in a fixed order,
+    exp and log1p included (euler_amd/csrc/skipgram.h); the same call returns the same bits.
+    Gradients: the kernel's per-row gradients are added at the keys src (target) and [pos | neg]
+    (context) by scatter_add and rounded once to the table's dtype; sparse_grad=True returns them
+    as torch.sparse_coo_tensor over the distinct rows (for torch.optim.SparseAdam); for a shared
+    table autograd adds the two.  NaN logits are outside the contract.  No host wait on the
+    forward path."""
+    name = "skipgram_loss"
+    _dt(name, target)
+    _dt(name, context)
+    if target.dim() != 2 or context.dim() != 2 or target.shape[1] != context.shape[1] or target.shape[1] < 1 \
+            or target.shape[0] < 1 or context.shape[0] < 1:
+        raise ValueError("%s: target is [rows, d] and context is [rows, d], one row and one column at least" % name)
+    src = src.to(torch.int64).reshape(-1).contiguous()
+    b = src.numel()
+    pos = pos.to(torch.int64)
+    pos = (pos if pos.dim() == 2 else pos.reshape(b, -1)).contiguous()
+    if pos.shape[0] != b or pos.shape[1] < 1:
+        raise ValueError("%s: pos is [B, P], P >= 1" % name)
+    if neg is not None:
+        neg = neg.to(torch.int64)
+        neg = (neg if neg.dim() == 2 else neg.reshape(b, -1)).contiguous()
+        if neg.shape[0] != b:
+            raise ValueError("%s: neg is [B, K]" % name)
+        if neg.shape[1] == 0:
+            neg = None
+    _need_cuda(target, context, src, pos, *(() if neg is None else (neg,)))
+    if b * (pos.shape[1] + (0 if neg is None else neg.shape[1])) >= 2 ** 31 or target.shape[0] >= 2 ** 31 \
+            or context.shape[0] >= 2 ** 31:
+        raise ValueError("%s: B * (P + K) and the tables' rows must stay below 2^31" % name)
+    tc = target.contiguous()
+    cc = tc if context is target else context.contiguous()
+    loss, rank, logits = _SkipgramLoss.apply(tc, cc, src, pos, neg, bool(sparse_grad))
+    return (loss, rank, logits) if return_logits else (loss, rank)
+
+
+_RANK_METRICS = ("mrr", "mr", "hit1", "hit3", "hit10")
+
+
+def rank_metric(name, rank):
+    """The reference's ranking metrics from skipgram_loss's integer ranks (utils/metrics.py:51-83):
+    "mrr" = mean 1 / (rank + 1), "mr" = mean rank + 1, "hit1" / "hit3" / "hit10" = the share of
+    rows with rank < k.  Plain torch in float64, for logging: a 0-d tensor, no bit contract."""
+    if name not in _RANK_METRICS:
+        raise ValueError("rank_metric: name is one of %s" % ", ".join(_RANK_METRICS))
+    r = rank.to(torch.float64)
+    if name == "mrr":
+        return (1.0 / (r + 1.0)).mean()
+    if name == "mr":
+        return (r + 1.0).mean()
+    return (r < float(name[3:])).to(torch.float64).mean()
+
+
 # ---- in-place embedding stores (tf_euler/python/utils/embedding.py:24-68) ---------------------
 # The stores of ScalableSageEncoder / ScalableGCNEncoder (utils/encoders.py:629-748, 294-409): a
 # non-trainable [max_id + 1, d] table per layer that lives in HBM across steps and is changed IN

@@ -1146,6 +1146,49 @@ int euler_gpu_triple_score_matrix_grad(void* stream, int32_t kind, int32_t corru
                                        float* g_src_dev, float* g_rel_dev, float* g_dst_dev,
                                        float* g_neg_rows_dev, float* gz_src_dev, float* gz_dst_dev,
                                        float* gz_neg_rows_dev, void* g_matrix_dev);
+/* skipgram_loss: the loss head of the walk-based models (DeepWalk, node2vec, LINE, unsupervised
+ * GraphSAGE: tf_euler/python/solution/base_unsupervise.py with PosNegLogits of
+ * solution/logits.py:30-34, xent_loss of solution/losses.py:27-33 and mrr_score / hitk_score /
+ * mr_score of utils/metrics.py:51-83) in one pass: the lookup of t = target[src[i]] and of the
+ * p + k context rows c_j = context[pos[i][j]] (j < p), context[neg[i][j - p]] (j >= p), the
+ * logits x_j = sum t * c_j, the sigmoid cross-entropy softplus(-x_j) of a positive and
+ * softplus(x_j) of a negative, and the rank of the LAST positive - 1 + p + k table rows read once
+ * each per pair row, no [b, 1 + k, d] block, no matmul, no sort.
+ * logits_dev [b, p + k] fp32, positives first.  rank_dev [b] int32: how many of the k negatives
+ * and the first p - 1 positives have a logit >= the last positive's (tf.nn.top_k's
+ * lower-index-first rule on concat([neg, pos]): a tie goes against the positive).  row_loss_dev
+ * [b]: the terms of a row added in the order j = 0 .. p + k - 1.  loss_dev [1]: the row sums
+ * reduced in a fixed order that is a function of b alone, divided once by float(b * (p + k)).
+ * The tables are fp32, bf16 or fp16, each its own type (they may be the same table), widened
+ * exactly; ids are signed int64; an id outside [0, rows) of its table names no row: it is never
+ * dereferenced, reads as a row of zeros (its term, ln 2, still counts) and gets a zero gradient
+ * row.  All arithmetic is correctly rounded fp32 in the order stated in
+ * euler_amd/csrc/skipgram.h, exp and log1p included: the same call returns the same bits, and no
+ * float atomic is used.  NaN logits are outside the contract.
+ * skipgram_loss_grad: from the forward's logits_dev and the scalar g_dev [1] (the gradient of
+ * the loss) the fp32 gradients of the RAW rows per occurrence - g_src_dev [b, d] (target),
+ * g_pos_dev [b, p, d] and g_neg_dev [b, k, d] (context); no dot product is taken again.  A
+ * table's gradient is their scatter_add by id.
+ * Both only enqueue (the forward two kernels): no allocation, no host wait; both can be captured
+ * into a graph.  EULER_GPU_EINVAL, checked before anything is enqueued, so every output is
+ * written entirely or not at all: an unknown dtype, b < 0, k < 0, p < 1, d < 1, d >= 2^31, a
+ * table with fewer than 1 or with 2^31 or more rows, b * (p + k) >= 2^31, a null required buffer,
+ * k > 0 with neg_dev or g_neg_dev null, a buffer not aligned to its type.  b == 0: the forward
+ * writes loss_dev = +0 and touches nothing else (every other buffer may be NULL), the gradient
+ * touches nothing.  k == 0: neg_dev and g_neg_dev may be NULL. */
+int euler_gpu_skipgram_loss(void* stream, const void* target_dev, int32_t target_dtype,
+                            int64_t target_rows, const void* context_dev, int32_t context_dtype,
+                            int64_t context_rows, const int64_t* src_dev, const int64_t* pos_dev,
+                            const int64_t* neg_dev, int64_t b, int64_t p, int64_t k, int64_t d,
+                            float* logits_dev, int32_t* rank_dev, float* row_loss_dev,
+                            float* loss_dev);
+int euler_gpu_skipgram_loss_grad(void* stream, const void* target_dev, int32_t target_dtype,
+                                 int64_t target_rows, const void* context_dev,
+                                 int32_t context_dtype, int64_t context_rows,
+                                 const int64_t* src_dev, const int64_t* pos_dev,
+                                 const int64_t* neg_dev, int64_t b, int64_t p, int64_t k,
+                                 int64_t d, const float* logits_dev, const float* g_dev,
+                                 float* g_src_dev, float* g_pos_dev, float* g_neg_dev);
 /* store_update / store_add / store_take: the in-place embedding stores of ScalableSage /
  * ScalableGCN (tf_euler/python/utils/embedding.py:24-68, encoders.py:713-748) - tf.scatter_update,
  * tf.scatter_add and embedding_lookup with the optional clearing update of encoders.py:738-743 -
