@@ -867,6 +867,228 @@ def edge_softmax(logits, indices=None, size=None, seg_ptr=None, count=None, out_
     return _EdgeSoftmax.apply(logits, si, sp, 0 if count is None else count, int(size), od)
 
 
+# ---- fused segment attention: logits, softmax and weighted sum in one pass ---------------------
+_ATT_KIND = {"dot": 0, "additive": 1}
+
+
+def _att_dst(si, sp, count, size, e, device):
+    """the destination of every update as int32 [E]; outside [0, size) where it has none"""
+    if si is not None:
+        return si
+    if sp is None:
+        return torch.arange(size, device=device, dtype=torch.int32).repeat_interleave(int(count))
+    pos = torch.arange(e, device=device, dtype=torch.int64)
+    dst = torch.searchsorted(sp, pos, right=True) - 1          # -1 before seg_ptr[0]
+    return torch.where(pos >= sp[-1], torch.full_like(dst, size), dst).to(torch.int32)
+
+
+def _att_rows(gi, n_rows):
+    """the int32 rows the kernels read: the low word as unsigned, clamped to the table's last row"""
+    return torch.clamp(gi.to(torch.int64) & 0xFFFFFFFF, max=n_rows - 1).to(torch.int32)
+
+
+def _att_call(fn, kind, q, qi, k, v, gi, si, sp, count, size, heads, scale, slope, tail):
+    d = k.shape[1]
+    dv = v.shape[1] if v is not None else d
+    with _on(k.device):
+        check(fn(_stream(), kind, _ptr(q), _DT[q.dtype] if q is not None else 0, q.shape[0] if q is not None else 0,
+                 _ptr(qi), _ptr(k), _DT[k.dtype], k.shape[0], _ptr(v), _DT[v.dtype] if v is not None else 0,
+                 v.shape[0] if v is not None else 0, _ptr(gi), int(gi.dtype == torch.int64), _ptr(si), _ptr(sp),
+                 int(count), gi.numel(), d, dv, heads, size, float(scale), float(slope), *tail))
+
+
+class _AttentionAggregate(torch.autograd.Function):
+    """euler_gpu_segment_attention, and for the backward euler_gpu_segment_attention_grad at the
+    destinations plus the weighted reduces grouped by source row"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, kind, qi, gi, si, sp, count, size, heads, scale, slope, od, want_logits):
+        e = gi.numel()
+        dv = v.shape[1] if v is not None else k.shape[1]
+        dev = k.device
+        alpha = torch.empty((e, heads), dtype=_F32, device=dev)
+        logits = torch.zeros((e, heads), dtype=_F32, device=dev) if want_logits else None
+        if e == 0 or size == 0:
+            out = torch.zeros((size, dv), dtype=od, device=dev)
+            alpha.zero_()
+        else:
+            out = torch.empty((size, dv), dtype=od, device=dev)
+            _att_call(lib().euler_gpu_segment_attention, kind, q, qi, k, v, gi, si, sp, count, size, heads,
+                      scale, slope, (_ptr(out), _DT[od], _ptr(alpha), _ptr(logits)))
+        ctx.save_for_backward(alpha, *[t for t in (q, k, v, qi, gi, si, sp) if t is not None])
+        ctx.has = [t is not None for t in (q, k, v, qi, gi, si, sp)]
+        ctx.conf = (kind, count, size, heads, scale, slope)
+        if want_logits:
+            ctx.mark_non_differentiable(alpha, logits)
+            return out, alpha, logits
+        ctx.mark_non_differentiable(alpha)
+        return out, alpha
+
+    @staticmethod
+    def backward(ctx, grad, *unused):
+        saved = list(ctx.saved_tensors)
+        alpha = saved.pop(0)
+        q, k, v, qi, gi, si, sp = [saved.pop(0) if h else None for h in ctx.has]
+        kind, count, size, heads, scale, slope = ctx.conf
+        e, d = gi.numel(), k.shape[1]
+        need_q = q is not None and ctx.needs_input_grad[0]
+        need_k, need_v = ctx.needs_input_grad[1], v is not None and ctx.needs_input_grad[2]
+        gq = gk = gv = None
+        if e == 0 or size == 0:
+            gq = torch.zeros_like(q) if need_q else None
+            gk = torch.zeros_like(k) if need_k else None
+            gv = torch.zeros_like(v) if need_v else None
+            return (gq, gk, gv) + (None,) * 12
+        g2 = grad.contiguous()
+        if g2.dtype not in _DT:
+            g2 = g2.float()
+        ds = torch.empty((e, heads), dtype=_F32, device=k.device)
+        dq_dst = torch.empty((size, d), dtype=_F32, device=k.device)
+        _att_call(lib().euler_gpu_segment_attention_grad, kind, q, qi, k, v, gi, si, sp, count, size, heads,
+                  scale, slope, (_ptr(alpha), _ptr(g2), _DT[g2.dtype], _ptr(ds), _ptr(dq_dst)))
+        # the source side: an update without a destination has alpha = ds = 0 and reads a row of zeros
+        dst = _att_dst(si, sp, count, size, e, k.device)
+        if si is not None or sp is not None:
+            valid, key = _keys_in_range(dst, size)
+            key = torch.where(valid.reshape(-1), key, torch.full_like(key, size))
+        else:
+            key = dst
+        rows_k = _att_rows(gi, k.shape[0])
+        if need_v or (v is None and need_k):
+            tv = v if v is not None else k
+            g32 = g2.float()                               # (fp32 already: no copy)
+            if si is not None or sp is not None:           # the zero row of updates without a destination
+                g32 = torch.cat([g32, g32.new_zeros((1, g32.shape[1]))])
+            gv = _gather_scatter_w_raw(_ADD, g32, key, rows_k if v is None else _att_rows(gi, v.shape[0]),
+                                       tv.shape[0], alpha, heads, _F32)
+        if need_k:
+            if kind == 0:
+                q_of_dst = torch.clamp(key, max=size - 1)
+                if qi is not None:
+                    q_of_dst = qi[q_of_dst.long()]
+                gk = _gather_scatter_w_raw(_ADD, q, q_of_dst, rows_k, k.shape[0], ds, heads, _F32)
+            else:
+                gk = _scatter_raw(_ADD, ds, rows_k, k.shape[0])
+            if v is None:
+                gk = gv + gk                               # (fp32, grad_v first)
+            gk = gk.to(k.dtype)
+        if need_q:
+            if qi is not None:
+                gq = _scatter_raw(_ADD, dq_dst, qi, q.shape[0])
+            elif q.shape[0] > size:
+                gq = torch.cat([dq_dst, dq_dst.new_zeros((q.shape[0] - size, d))])
+            else:
+                gq = dq_dst
+            gq = gq.to(q.dtype)
+        return (gq, gk, gv.to(v.dtype) if need_v else None) + (None,) * 12
+
+
+def attention_aggregate(kind, q, k, gather_indices, size, v=None, q_index=None, heads=1, scale=1.0,
+                        negative_slope=0.2, indices=None, seg_ptr=None, count=None, out_dtype=None,
+                        return_attention=False, validate=False, return_logits=False):
+    """Attention over the updates of every destination in ONE pass (euler_gpu_segment_attention):
+    a logit per (update, head), the softmax over the destination's updates, and the sum of the
+    gathered rows weighted by it - what GATConv, AGNNConv, AttentionPool and Set2SetPool compose from
+    `edge_dot` (or two gathers), `edge_softmax` and a weighted reduce.  For destination r (qr =
+    q_index[r], or r), update p with g = gather_indices[p] and head h:
+      kind "dot":       logit = scale * sum_c q[qr, h*dh+c] * k[g, h*dh+c]; q and k are [*, D],
+                        dh = D // heads.  AGNN: q = beta * l2norm(x), k = l2norm(x), v = x;
+                        Set2Set: q per graph, k = the inputs, v = None; dot-product attention.
+      kind "additive":  logit = leaky_relu(q[qr, h] + k[g, h], negative_slope); q and k are score
+                        tables [*, heads]; q = None means 0, negative_slope = 1.0 the identity.
+                        GAT; AttentionPool is q = None, slope 1, k = the gate.  Needs v.
+      alpha = softmax of the logits over the destination's updates (the bits of `edge_softmax`);
+      out[r, h*dv+c] = sum_p alpha[p, h] * v[g, h*dv+c], v [*, Dv], dv = Dv // heads (the bits of
+      gather_segment_reduce("add", v, gather_indices, size, edge_weight=alpha)).
+    v = None (dot only) means v is k: every gathered row is loaded once for the logit and the sum.
+    Tables are fp32, bf16 or fp16, each its own; gather_indices int32, or the int64 ids a sampler
+    returned (read in place); a row number past a table reads its last row.  The destinations come in
+    exactly one form - indices (scatter keys, any order, with size), seg_ptr or count - as for
+    `edge_softmax`.  Returns [size, Dv] in out_dtype (None: the dtype of v); an empty destination is
+    a zero row; updates that belong to no destination contribute nothing and get alpha = 0 and a
+    zero gradient.  return_attention=True also returns the fp32 alpha [E, heads] (not
+    differentiable on its own), return_logits=True the fp32 logits after it.
+    `scale` is a plain float and is not differentiated: a learnable temperature belongs in q
+    (q = beta * x).  Measured on a sampled block: the one-table dot form (v = None) is level
+    with or faster than edge_dot + edge_softmax + the weighted reduce, and so are the graph pools' forwards;
+    the additive kind and dot with a separate v are slower than those three ops today - prefer them there.
+    return_logits is an addition to the op's signature for checks that need the op's own logits.
+    Differentiable in q, k and v: the destination side in one pass
+    (euler_gpu_segment_attention_grad), the source side by the weighted reduces."""
+    if kind not in _ATT_KIND:
+        raise ValueError("attention_aggregate: kind is dot or additive")
+    if (indices is not None) + (seg_ptr is not None) + (count is not None) != 1:
+        raise ValueError("attention_aggregate: pass exactly one of indices, seg_ptr and count")
+    heads, size = int(heads), int(size)
+    if heads < 1 or size < 0:
+        raise ValueError("attention_aggregate: heads >= 1 and size >= 0")
+    _dt("attention_aggregate", k)
+    if k.dim() != 2 or (q is not None and q.dim() != 2) or (v is not None and v.dim() != 2):
+        raise ValueError("attention_aggregate: q, k and v are [rows, columns] tables")
+    if kind == "additive":
+        if v is None:
+            raise ValueError("attention_aggregate: additive attention needs v")
+        if k.shape[1] != heads or (q is not None and q.shape[1] != heads):
+            raise ValueError("attention_aggregate: additive q and k are [*, heads] score tables")
+    else:
+        if q is None:
+            raise ValueError("attention_aggregate: dot attention needs q")
+        if q.shape[1] != k.shape[1] or k.shape[1] % heads != 0:
+            raise ValueError("attention_aggregate: q and k are [*, D] with heads dividing D")
+    if q is not None:
+        _dt("attention_aggregate", q)
+    if v is not None:
+        _dt("attention_aggregate", v)
+        if v.shape[1] % heads != 0:
+            raise ValueError("attention_aggregate: heads must divide the columns of v")
+    tv = v if v is not None else k
+    od = tv.dtype if out_dtype is None else out_dtype
+    if od not in _DT:
+        raise TypeError("attention_aggregate: out_dtype is float32, bfloat16 or float16, not %s" % od)
+    if gather_indices.dtype not in (torch.int32, torch.int64):
+        raise TypeError("attention_aggregate: gather_indices are int32 or int64")
+    gi = gather_indices.reshape(-1).contiguous()
+    e = gi.numel()
+    tensors = [t.contiguous() if t is not None else None for t in (q, k, v)]
+    q, k, v = tensors
+    _need_cuda(k, gi, *[t for t in (q, v) if t is not None])
+    if e > 0 and (k.shape[0] < 1 or tv.shape[0] < 1):
+        raise ValueError("attention_aggregate: a gathered table has no rows")
+    si = sp = qi = None
+    if indices is not None:
+        si = indices.to(torch.int32).reshape(-1).contiguous()
+        _need_cuda(si)
+        if si.numel() != e:
+            raise ValueError("attention_aggregate: one scatter key per gather index (%d), not %d" % (e, si.numel()))
+    elif seg_ptr is not None:
+        sp = seg_ptr.to(torch.int64).contiguous()
+        _need_cuda(sp)
+        if sp.numel() != size + 1:
+            raise ValueError("attention_aggregate: seg_ptr has size + 1 entries")
+    else:
+        count = int(count)
+        if count < 1 or size * count != e:
+            raise ValueError("attention_aggregate: size * count gather indices, count >= 1")
+    if q_index is not None:
+        qi = q_index.to(torch.int32).reshape(-1).contiguous()
+        _need_cuda(qi)
+        if qi.numel() != size:
+            raise ValueError("attention_aggregate: one q_index per destination (%d), not %d" % (size, qi.numel()))
+    elif q is not None and q.shape[0] < size:
+        raise ValueError("attention_aggregate: q has fewer rows than there are destinations")
+    if q is not None and size > 0 and q.shape[0] < 1:
+        raise ValueError("attention_aggregate: q has no rows")
+    if validate:
+        _check_rows("attention_aggregate", gi, min(k.shape[0], tv.shape[0]))
+        if qi is not None:
+            _check_rows("attention_aggregate", qi, q.shape[0])
+    res = _AttentionAggregate.apply(q, k, v, _ATT_KIND[kind], qi, gi, si, sp, 0 if count is None else count, size,
+                                    heads, float(scale), float(negative_slope), od, bool(return_logits))
+    if not (return_attention or return_logits):
+        return res[0]
+    return tuple([res[0]] + ([res[1]] if return_attention else []) + ([res[2]] if return_logits else []))
+
+
 # ---- per-relation aggregation (RGCN) ----------------------------------------------------------
 _REL_MODE = {"add": 0, "max": 1, "mean": 2, "mean_rel": 3}
 

@@ -969,6 +969,57 @@ int euler_gpu_edge_softmax_grad(void* stream, const void* y_dev, int32_t y_dtype
                                 const int32_t* indices_dev, const int64_t* seg_ptr_dev,
                                 int64_t count, int64_t e, int32_t heads, int32_t size,
                                 void* out_dev, int32_t out_dtype);
+/* segment_attention: attention over the updates of every destination in one pass - a logit per
+ * (update, head), the softmax of euler_gpu_edge_softmax over the destination's updates, and the
+ * sum of the gathered rows weighted by it: GATConv (convolution/gat_conv.py:66-72), AGNNConv
+ * (convolution/agnn_conv.py:36-54), AttentionPool (graph_pool/attention_pool.py:36-40) and
+ * Set2SetPool (graph_pool/set2set_pool.py:45-49).  For destination r (qr = q_index_dev[r], or r),
+ * update p gathering row g = gather_dev[p] and head h:
+ *   kind 0 (dot):       logit = fl(scale * DOT_c q[qr][h dh + c] * k[g][h dh + c]), q and k [*, d],
+ *                       dh = d / heads, in the order euler_amd/csrc/mp_attention.h states (a
+ *                       function of dh alone);
+ *   kind 1 (additive):  a = fl(q[qr][h] + k[g][h]), logit = a < 0 ? fl(a * negative_slope) : a,
+ *                       q and k [*, heads] (d == heads), q_dev NULL: q = +0;
+ *   alpha = the bits euler_gpu_edge_softmax returns for these logits;
+ *   out[r][c] = +0, then fl(acc + fl(v[g][c] * alpha[p][c / (dv / heads)])) in increasing p: the
+ *   bits of euler_gpu_gather_segment_reduce_w_t (add) with alpha as the weights.
+ * v_dev NULL (dot only, dv == d): v is k, and each gathered row is loaded once for both uses.
+ * Tables fp32 / bf16 / fp16, each its own; gather_dev int32 indices (gather_is_ids == 0) or int64
+ * ids (index = low word); every row number is clamped to its table's last row.  The destinations
+ * come in exactly one of the three forms of euler_gpu_edge_softmax.  out_dev is [size, dv]
+ * (out_dtype: any of the three, one rounding); an empty destination is a zero row.  alpha_dev
+ * (fp32 [e, heads], may be NULL) receives alpha, 0 for updates that belong to no destination;
+ * logits_dev (may be NULL) the logits of the updates that have one.  A segment whose maximum
+ * logit is not finite is outside the contract, as for euler_gpu_edge_softmax.
+ * segment_attention_grad: the destination side of the backward in one pass, from the saved
+ * alpha_dev and the incoming grad_dev [size, dv]: da = DOT_c grad[r] * v[g] per head (the order
+ * above over dv / heads), dl = the gradient of euler_gpu_edge_softmax_grad,
+ *   dot:       ds = fl(scale * dl),  dq_dst[r] = the ordered fold of k[g] with ds   ([size, d]);
+ *   additive:  ds = a < 0 ? fl(dl * negative_slope) : dl,  dq_dst[r][h] = +0 + ds_0 + ds_1 ...
+ * ds_dev is fp32 [e, heads] (0 for updates without a destination), dq_dst_dev fp32 [size, d].
+ * The source-side gradients (grouped by gathered row) are euler_gpu_gather_scatter_w_t calls.
+ * No float atomics; explicit keys that are not grouped cost GroupScatterKeys' one host wait.
+ * EULER_GPU_EINVAL: unknown kind or dtype, heads < 1 or not dividing d / dv (additive: d !=
+ * heads), additive without v, not exactly one segment form, count with e != size * count,
+ * e >= 2^31, a null buffer, a table without rows.  size == 0 and e == 0 touches nothing. */
+int euler_gpu_segment_attention(void* stream, int32_t kind, const void* q_dev, int32_t q_dtype,
+                                int64_t q_rows, const int32_t* q_index_dev, const void* k_dev,
+                                int32_t k_dtype, int64_t k_rows, const void* v_dev, int32_t v_dtype,
+                                int64_t v_rows, const void* gather_dev, int32_t gather_is_ids,
+                                const int32_t* indices_dev, const int64_t* seg_ptr_dev,
+                                int64_t count, int64_t e, int64_t d, int64_t dv, int32_t heads,
+                                int32_t size, float scale, float negative_slope, void* out_dev,
+                                int32_t out_dtype, float* alpha_dev, float* logits_dev);
+int euler_gpu_segment_attention_grad(void* stream, int32_t kind, const void* q_dev, int32_t q_dtype,
+                                     int64_t q_rows, const int32_t* q_index_dev, const void* k_dev,
+                                     int32_t k_dtype, int64_t k_rows, const void* v_dev,
+                                     int32_t v_dtype, int64_t v_rows, const void* gather_dev,
+                                     int32_t gather_is_ids, const int32_t* indices_dev,
+                                     const int64_t* seg_ptr_dev, int64_t count, int64_t e, int64_t d,
+                                     int64_t dv, int32_t heads, int32_t size, float scale,
+                                     float negative_slope, const float* alpha_dev,
+                                     const void* grad_dev, int32_t grad_dtype, float* ds_dev,
+                                     float* dq_dst_dev);
 /* relation_reduce: the aggregation of RGCN's RelationConv (relation_conv.py:53-70) by linearity -
  * mean_e W[t_e] x_e = (sum_t W_t * sum_{e: t_e = t} x_e) / deg - as the reduce of gathered rows
  * per (destination, relation): out_dev is [size, num_relations, d], which one dense GEMM with the
