@@ -1,6 +1,9 @@
-// The lane helpers of the triple-scoring kernels (kg_score_kernels.hip, kg_proj_kernels.hip): what
-// one lane of a task sees of a table row, of an fp32 output row and of its gy, and the butterfly
-// over the lanes of a task.  Device code only; the arithmetic itself is in kg_score.h / kg_proj.h.
+// The lane helpers of the triple-scoring kernels (kg_score_kernels.hip, kg_proj_kernels.hip,
+// kg_matrix_kernels.hip): what one lane of a task sees of a table row, of an fp32 output row and
+// of its gy, the butterfly over the lanes of a task, and the steps every family's kernels take
+// the same way - ss and inv of a row, the slot of a negative's score and the
+// front / tail corruption of one negative, forward and gradient.  Device code only; the
+// arithmetic itself is in kg_score.h / kg_proj.h / kg_matrix.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -158,6 +161,52 @@ struct LaneAcc {
 __device__ __forceinline__ float KgCombine(float s, int32_t lanes) {
   for (int32_t off = lanes >> 1; off > 0; off >>= 1) s = __fadd_rn(s, __shfl_xor(s, off));
   return s;
+}
+
+// ss and inv of a row
+template <int V, typename Row>
+__device__ __forceinline__ void KgLaneNorm(const Row& x, bool normalize, int32_t l, int32_t lanes, int32_t chunks,
+                                           float* ss, float* inv) {
+  *ss = normalize ? KgCombine(KgLaneSumSq<V>(x, l, lanes, chunks), lanes) : 0.f;
+  *inv = KgInv(*ss, normalize);
+}
+
+// Where the score of negative k of triple t stands in neg_out / g_neg: [b, k_total] front or tail
+// scores, for corrupt "both" [b, 2 * k_total] with the tail scores behind the front ones
+__device__ __forceinline__ int64_t KgNegSlot(int32_t corrupt, int64_t k_total, int64_t t, int64_t k, bool tail) {
+  const int64_t kp = corrupt == kKgBoth ? 2 * k_total : k_total;
+  return t * kp + (tail && corrupt == kKgBoth ? k_total : 0) + k;
+}
+
+// The corruption of a triple (h, r, t) by one negative n: the front score s(n, r, t) and / or the
+// tail score s(h, r, n), as `corrupt` asks.  The caller stores them: put(tail, score), each as
+// soon as it is known.
+template <int V, typename Ent, typename Rel, typename Put>
+__device__ __forceinline__ void KgLaneCorrupt(int32_t kind, int32_t corrupt, const Ent& h, float ih, const Rel& r,
+                                              float ir, const Ent& t, float it, const Ent& n, float in, int32_t l,
+                                              int32_t lanes, int32_t chunks, Put put) {
+  if (corrupt != kKgTail)
+    put(false, KgFinish(kind, KgCombine(KgLaneScore<V>(kind, n, in, r, ir, t, it, l, lanes, chunks), lanes)));
+  if (corrupt != kKgFront)
+    put(true, KgFinish(kind, KgCombine(KgLaneScore<V>(kind, h, ih, r, ir, n, in, l, lanes, chunks), lanes)));
+}
+
+// Its gradient: g(tail), the incoming gradient of each of the two scores, into the gy of the rows
+// that score read.  trans_l2 needs the score again.
+template <int V, typename Ent, typename Rel, typename Acc, typename G>
+__device__ __forceinline__ void KgLaneCorruptGrad(int32_t kind, int32_t corrupt, G g, const Ent& h, float ih,
+                                                  const Rel& r, float ir, const Ent& t, float it, const Ent& n,
+                                                  float in, Acc& gh, Acc& gr, Acc& gt, Acc& gn, int32_t l,
+                                                  int32_t lanes, int32_t chunks) {
+  const bool l2 = kind == kKgTransL2;
+  if (corrupt != kKgTail) {
+    const float s = l2 ? KgCombine(KgLaneScore<V>(kind, n, in, r, ir, t, it, l, lanes, chunks), lanes) : 0.f;
+    KgLaneScoreGrad<V>(kind, KgScale(kind, g(false), s), n, in, r, ir, t, it, gn, gr, gt, l, lanes, chunks);
+  }
+  if (corrupt != kKgFront) {
+    const float s = l2 ? KgCombine(KgLaneScore<V>(kind, h, ih, r, ir, n, in, l, lanes, chunks), lanes) : 0.f;
+    KgLaneScoreGrad<V>(kind, KgScale(kind, g(true), s), h, ih, r, ir, n, in, gh, gr, gn, l, lanes, chunks);
+  }
 }
 
 }  // namespace

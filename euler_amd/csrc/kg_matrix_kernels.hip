@@ -6,6 +6,8 @@
 // its rows c, once per run of equal relation in its share.  The arithmetic, the range rule and
 // every summation order are stated in kg_matrix.h and kg_score.h, which the host check compiles
 // too; no order depends on the grouping, the tiling or the grid.  No float atomics, no MFMA.
+// The argument ladder is kg_entry.h's (MatrixCall states what this family adds); the entries keep
+// the rules of the segments and of the gz / G_M buffers.
 //
 //   TripleScoreMatrixKernel          forward.  A triple is a task of L lanes of a wave, as in
 //       kg_score_kernels.hip; a lane owns the columns of its chunks of the dr columns (at most 8,
@@ -32,6 +34,7 @@
 #include "device_fns.h"
 #include "device_mem.h"
 #include "half_cvt.h"
+#include "kg_entry.h"
 #include "kg_lanes.h"
 #include "kg_matrix.h"
 
@@ -46,20 +49,14 @@ constexpr int kKgmGmC = 16, kKgmGmJ = 64;         // the tile of G_M of a grid c
 constexpr int kKgmGmBatch = 128;                  // occurrence rows staged at a time
 constexpr int64_t kKgmMaxBlocks = 2048;           // 8 workgroups a CU
 
-struct KgmArgs {
-  int32_t kind, corrupt, log_l, ent_dt, rel_dt, mat_dt;
-  const void* ent; int64_t ent_rows, de;
-  const void* rel; int64_t rel_rows, dr;
+struct KgmArgs : KgTripleArgs {                   // out_vec: g_rel and the gz buffers start on 16 bytes
+  int32_t ent_dt, rel_dt, mat_dt;
+  int64_t de, dr;
   const void* matrix;
-  const int64_t* src; const int64_t* rel_id; const int64_t* dst; const int64_t* neg;
-  int64_t b, k;
-  const int64_t* order; const int64_t* seg_ptr; const int64_t* seg_rel; int64_t nseg;
-  float* pos_out; float* neg_out;                 // forward
-  const float* g_pos; const float* g_neg;         // gradient
-  float* g_src; float* g_rel; float* g_dst; float* g_neg_rows;
+  const int64_t* order;
+  const int64_t* seg_ptr; const int64_t* seg_rel; int64_t nseg;                  // gradient
   float* gz_src; float* gz_dst; float* gz_neg_rows;
   void* g_matrix;
-  int32_t out_vec;                                // g_rel and the gz buffers start on 16 bytes
   int32_t gx_share;                               // triples of a workgroup's share of the gx kernel
 };
 
@@ -235,13 +232,6 @@ __device__ __forceinline__ void KgmProject(const KgmArgs& a, int32_t n, int32_t 
   }
 }
 
-// ss and inv of a row
-template <int V, typename Row>
-__device__ __forceinline__ void KgmNorm(const Row& x, int32_t l, int32_t lanes, int32_t chunks, float* ss, float* inv) {
-  *ss = KgCombine(KgLaneSumSq<V>(x, l, lanes, chunks), lanes);
-  *inv = KgInv(*ss, true);
-}
-
 // What the two per-triple kernels share of a task: its place, its rel row and z of h and t.  The
 // entity rows of a task are numbered h, t, n_0 .. n_{K-1} and projected kKgmRows at a time, so
 // h and t share their pass over M with the first two negatives.
@@ -266,7 +256,7 @@ struct KgmTask {
     R.dt = a.rel_dt;
     R.ok = KgInRange(rid, a.rel_rows);
     R.at = R.ok ? rid * a.dr : 0;
-    KgmNorm<V>(R, l, lanes, chunks, &ssr, &ir);
+    KgLaneNorm<V>(R, true, l, lanes, chunks, &ssr, &ir);
   }
   // z of the entity rows r0 .. r0 + kKgmRows - 1 (those below 2 + K)
   __device__ __forceinline__ void Rows(const KgmArgs& a, int32_t n, const int64_t* s_key, float* sm, int64_t r0,
@@ -286,8 +276,8 @@ struct KgmTask {
   __device__ __forceinline__ void Keep(const KgmRegs<V> z[kKgmRows]) {
     zh = z[0];
     zt = z[1];
-    KgmNorm<V>(zh, l, lanes, chunks, &ssh, &ih);
-    KgmNorm<V>(zt, l, lanes, chunks, &sst, &it);
+    KgLaneNorm<V>(zh, true, l, lanes, chunks, &ssh, &ih);
+    KgLaneNorm<V>(zt, true, l, lanes, chunks, &sst, &it);
   }
   template <typename RowA, typename RowC>
   __device__ __forceinline__ float Terms(int32_t kind, const RowA& x, float ix, const RowC& c, float ic) const {
@@ -301,7 +291,6 @@ __global__ __launch_bounds__(256) void TripleScoreMatrixKernel(const KgmArgs a) 
   __shared__ int32_t s_idx[kKgmMaxShare];
   __shared__ int64_t s_key[kKgmMaxShare];
   const int32_t share = (int32_t)blockDim.x >> a.log_l;
-  const int64_t kp = a.corrupt == kKgBoth ? 2 * a.k : a.k;
   for (int64_t p0 = (int64_t)blockIdx.x * share; p0 < a.b; p0 += (int64_t)gridDim.x * share) {
     const int32_t n = a.b - p0 < share ? (int32_t)(a.b - p0) : share;
     __syncthreads();
@@ -323,15 +312,11 @@ __global__ __launch_bounds__(256) void TripleScoreMatrixKernel(const KgmArgs a) 
         const int64_t k = r0 + i - 2;
         if (k >= 0 && k < a.k) {
           float ssn, in;
-          KgmNorm<V>(z[i], T.l, T.lanes, T.chunks, &ssn, &in);
-          if (a.corrupt != kKgTail) {
-            const float s = KgFinish(a.kind, T.Terms(a.kind, z[i], in, T.zt, T.it));
-            if (put) a.neg_out[(int64_t)T.t * kp + k] = s;
-          }
-          if (a.corrupt != kKgFront) {
-            const float s = KgFinish(a.kind, T.Terms(a.kind, T.zh, T.ih, z[i], in));
-            if (put) a.neg_out[(int64_t)T.t * kp + (a.corrupt == kKgBoth ? a.k : 0) + k] = s;
-          }
+          KgLaneNorm<V>(z[i], true, T.l, T.lanes, T.chunks, &ssn, &in);
+          KgLaneCorrupt<V>(a.kind, a.corrupt, T.zh, T.ih, T.R, T.ir, T.zt, T.it, z[i], in, T.l, T.lanes, T.chunks,
+                           [&](bool tail, float s) {
+                             if (put) a.neg_out[KgNegSlot(a.corrupt, a.k, T.t, k, tail)] = s;
+                           });
         }
       }
     }
@@ -352,7 +337,6 @@ __global__ __launch_bounds__(256) void TripleScoreMatrixGradKernel(const KgmArgs
   __shared__ int32_t s_idx[kKgmMaxShare];
   __shared__ int64_t s_key[kKgmMaxShare];
   const int32_t share = (int32_t)blockDim.x >> a.log_l;
-  const int64_t kp = a.corrupt == kKgBoth ? 2 * a.k : a.k;
   const bool vec = a.out_vec != 0, l2 = a.kind == kKgTransL2;
   for (int64_t p0 = (int64_t)blockIdx.x * share; p0 < a.b; p0 += (int64_t)gridDim.x * share) {
     const int32_t n = a.b - p0 < share ? (int32_t)(a.b - p0) : share;
@@ -381,19 +365,12 @@ __global__ __launch_bounds__(256) void TripleScoreMatrixGradKernel(const KgmArgs
         const int64_t k = r0 + i - 2;
         if (k >= 0 && k < a.k) {
           float ssn, in;
-          KgmNorm<V>(z[i], T.l, T.lanes, T.chunks, &ssn, &in);
+          KgLaneNorm<V>(z[i], true, T.l, T.lanes, T.chunks, &ssn, &in);
           KgmRegs<V> gn;
           gn.Clear(a.log_l);
-          if (a.corrupt != kKgTail) {
-            const float s = l2 ? T.Terms(a.kind, z[i], in, T.zt, T.it) : 0.f;
-            const float gs = KgScale(a.kind, live ? a.g_neg[tt * kp + k] : 0.f, s);
-            KgLaneScoreGrad<V>(a.kind, gs, z[i], in, T.R, T.ir, T.zt, T.it, gn, gr, gt, T.l, T.lanes, T.chunks);
-          }
-          if (a.corrupt != kKgFront) {
-            const float s = l2 ? T.Terms(a.kind, T.zh, T.ih, z[i], in) : 0.f;
-            const float gs = KgScale(a.kind, live ? a.g_neg[tt * kp + (a.corrupt == kKgBoth ? a.k : 0) + k] : 0.f, s);
-            KgLaneScoreGrad<V>(a.kind, gs, T.zh, T.ih, T.R, T.ir, z[i], in, gh, gr, gn, T.l, T.lanes, T.chunks);
-          }
+          const auto g = [&](bool tail) { return live ? a.g_neg[KgNegSlot(a.corrupt, a.k, tt, k, tail)] : 0.f; };
+          KgLaneCorruptGrad<V>(a.kind, a.corrupt, g, T.zh, T.ih, T.R, T.ir, T.zt, T.it, z[i], in, gh, gr, gt, gn, T.l,
+                               T.lanes, T.chunks);
           KgmThrough<V>(T, z[i], ssn, in, gn, LaneOut<V>{a.gz_neg_rows + (tt * a.k + k) * a.dr, live, vec});
         }
       }
@@ -581,7 +558,7 @@ unsigned Blocks(int64_t b, int64_t share) {
 // changes no bit.
 int Launch(hipStream_t st, KgmArgs a, bool grad) {
   const int32_t v = KgMatrixChunkWidth(a.dr, (uintptr_t)a.rel, a.rel_dt == kF32);
-  a.log_l = KgLogLanes(a.dr / v);
+  a.log_l = KgTaskLaunch(a.b, a.dr / v).log_l;
   const bool few = a.b * 4 < a.rel_rows * (256 >> a.log_l);
   const int threads = few ? 64 : 256;
   a.gx_share = few ? 2 : kKgmGxShare;
@@ -602,32 +579,14 @@ int Launch(hipStream_t st, KgmArgs a, bool grad) {
   return EULER_GPU_OK;
 }
 
-bool KnownDtype(int32_t t) { return t == EULER_GPU_F32 || t == EULER_GPU_BF16 || t == EULER_GPU_F16; }
-
-// The checks both entries share.  -> EULER_GPU_OK with *run = false when there is nothing to do.
-int CheckMatrixArgs(const char* what, const KgmArgs& a, bool* run) {
-  *run = false;
-  const std::string w(what);
-  if (a.kind < 0 || a.kind > 1) return Fail(EULER_GPU_EINVAL, w + ": kind outside 0..1 (distmult takes no projection)");
-  if (a.corrupt < 0 || a.corrupt > 2) return Fail(EULER_GPU_EINVAL, w + ": corrupt outside 0..2");
-  if (!KnownDtype(a.ent_dt) || !KnownDtype(a.rel_dt) || !KnownDtype(a.mat_dt))
-    return Fail(EULER_GPU_EINVAL, w + ": unknown dtype (0 fp32, 1 bf16, 2 fp16)");
-  if (a.k < 0 || a.b < 0 || a.de < 0 || a.dr < 0) return Fail(EULER_GPU_EINVAL, w + ": b, k, de or dr < 0");
-  if (a.ent_rows < 1 || a.rel_rows < 1) return Fail(EULER_GPU_EINVAL, w + ": a table with fewer than 1 row");
-  if (a.de > kKgMatrixMaxDim || a.dr > kKgMatrixMaxDim) return Fail(EULER_GPU_EINVAL, w + ": de or dr above 512");
-  if (a.ent_rows >= (1LL << 31)) return Fail(EULER_GPU_EINVAL, w + ": ent_rows >= 2^31");
-  if (a.b >= (1LL << 31) || a.k >= (1LL << 31) || a.b * (a.k > 1 ? a.k : 1) * 2 >= (1LL << 31))
-    return Fail(EULER_GPU_EINVAL, w + ": b * max(k, 1) * 2 >= 2^31");
-  if (a.b == 0 || a.de == 0 || a.dr == 0) return EULER_GPU_OK;
-  if (!a.ent || !a.rel || !a.matrix || !a.src || !a.rel_id || !a.dst || !a.order)
-    return Fail(EULER_GPU_EINVAL, w + ": null buffer");
-  if (a.k > 0 && !a.neg) return Fail(EULER_GPU_EINVAL, w + ": k > 0 without negatives");
-  const uintptr_t ea = a.ent_dt == EULER_GPU_F32 ? 4 : 2, ra = a.rel_dt == EULER_GPU_F32 ? 4 : 2,
-                  ma = a.mat_dt == EULER_GPU_F32 ? 4 : 2;
-  if ((uintptr_t)a.ent % ea != 0 || (uintptr_t)a.rel % ra != 0 || (uintptr_t)a.matrix % ma != 0)
-    return Fail(EULER_GPU_EINVAL, w + ": a table is not aligned to its type");
-  *run = true;
-  return EULER_GPU_OK;
+// what the matrix family adds to the shared ladder
+KgCall MatrixCall(const char* what, const KgmArgs& a) {
+  KgCall c{what, kKgMatrixFamily, a.ent_dt, a.rel_dt, a.de};
+  c.dr = a.dr;
+  c.matrix = a.matrix;
+  c.matrix_dtype = a.mat_dt;
+  c.order = a.order;
+  return c;
 }
 
 }  // namespace
@@ -643,16 +602,11 @@ int euler_gpu_triple_score_matrix(void* stream, int32_t kind, int32_t corrupt, c
                                   const int64_t* src_dev, const int64_t* rel_id_dev, const int64_t* dst_dev,
                                   const int64_t* neg_dev, int64_t b, int64_t k, const int64_t* order_dev,
                                   float* pos_out_dev, float* neg_out_dev) {
-  KgmArgs a{};
-  a.kind = kind; a.corrupt = corrupt; a.ent_dt = ent_dtype; a.rel_dt = rel_dtype; a.mat_dt = matrix_dtype;
-  a.ent = ent_dev; a.ent_rows = ent_rows; a.de = de;
-  a.rel = rel_dev; a.rel_rows = rel_rows; a.dr = dr;
-  a.matrix = matrix_dev;
-  a.src = src_dev; a.rel_id = rel_id_dev; a.dst = dst_dev; a.neg = neg_dev;
-  a.b = b; a.k = k; a.order = order_dev;
-  a.pos_out = pos_out_dev; a.neg_out = neg_out_dev;
+  KgmArgs a{KgShared(kind, corrupt, ent_dev, ent_rows, rel_dev, rel_rows, src_dev, rel_id_dev, dst_dev, neg_dev, b, k,
+                     pos_out_dev, neg_out_dev),
+            ent_dtype, rel_dtype, matrix_dtype, de, dr, matrix_dev, order_dev};
   bool run;
-  const int rc = CheckMatrixArgs("triple_score_matrix", a, &run);
+  const int rc = CheckKgCall(MatrixCall("triple_score_matrix", a), a, &run);
   if (rc != EULER_GPU_OK || !run) return rc;
   if (!pos_out_dev || (k > 0 && !neg_out_dev)) return Fail(EULER_GPU_EINVAL, "triple_score_matrix: null output buffer");
   return Launch((hipStream_t)stream, a, false);
@@ -668,19 +622,12 @@ int euler_gpu_triple_score_matrix_grad(void* stream, int32_t kind, int32_t corru
                                        const float* g_neg_dev, float* g_src_dev, float* g_rel_dev, float* g_dst_dev,
                                        float* g_neg_rows_dev, float* gz_src_dev, float* gz_dst_dev,
                                        float* gz_neg_rows_dev, void* g_matrix_dev) {
-  KgmArgs a{};
-  a.kind = kind; a.corrupt = corrupt; a.ent_dt = ent_dtype; a.rel_dt = rel_dtype; a.mat_dt = matrix_dtype;
-  a.ent = ent_dev; a.ent_rows = ent_rows; a.de = de;
-  a.rel = rel_dev; a.rel_rows = rel_rows; a.dr = dr;
-  a.matrix = matrix_dev;
-  a.src = src_dev; a.rel_id = rel_id_dev; a.dst = dst_dev; a.neg = neg_dev;
-  a.b = b; a.k = k; a.order = order_dev; a.seg_ptr = seg_ptr_dev; a.seg_rel = seg_rel_dev; a.nseg = nseg;
-  a.g_pos = g_pos_dev; a.g_neg = g_neg_dev;
-  a.g_src = g_src_dev; a.g_rel = g_rel_dev; a.g_dst = g_dst_dev; a.g_neg_rows = g_neg_rows_dev;
-  a.gz_src = gz_src_dev; a.gz_dst = gz_dst_dev; a.gz_neg_rows = gz_neg_rows_dev;
-  a.g_matrix = g_matrix_dev;
+  KgmArgs a{KgShared(kind, corrupt, ent_dev, ent_rows, rel_dev, rel_rows, src_dev, rel_id_dev, dst_dev, neg_dev, b, k,
+                     nullptr, nullptr, g_pos_dev, g_neg_dev, g_src_dev, g_rel_dev, g_dst_dev, g_neg_rows_dev),
+            ent_dtype, rel_dtype, matrix_dtype, de, dr, matrix_dev, order_dev, seg_ptr_dev, seg_rel_dev, nseg,
+            gz_src_dev, gz_dst_dev, gz_neg_rows_dev, g_matrix_dev};
   bool run;
-  const int rc = CheckMatrixArgs("triple_score_matrix_grad", a, &run);
+  const int rc = CheckKgCall(MatrixCall("triple_score_matrix_grad", a), a, &run);
   if (rc == EULER_GPU_OK && (nseg < 0 || nseg >= (1LL << 31)))
     return Fail(EULER_GPU_EINVAL, "triple_score_matrix_grad: nseg outside 0 .. 2^31 - 1");
   if (rc != EULER_GPU_OK || !run) return rc;

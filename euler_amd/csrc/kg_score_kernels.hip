@@ -3,7 +3,9 @@
 // [b, k] negatives, their l2 normalisation and the 1 + K' scores of a triple in one pass - 3 + k
 // table rows read and 1 + K' floats written per triple, where the composition from gather and
 // element-wise ops builds about a dozen [b, k, d] blocks.  The arithmetic, the range rule and
-// the summation order are stated in kg_score.h, which the host check compiles too.
+// the summation order are stated in kg_score.h, which the host check compiles too.  The argument
+// ladder, the dtype fan-out and the launch shape are kg_entry.h's, shared with the two projected
+// families; the corruption step of a negative is kg_lanes.h's.
 //
 // A triple is a task of L lanes of a wave (64 / L triples a wave), as in edge_dot_kernels.hip;
 // partial sums stay in registers and are combined inside the wave (__shfl_xor) - no LDS, no
@@ -17,31 +19,17 @@
 #include "device_fns.h"
 #include "device_mem.h"
 #include "half_cvt.h"
+#include "kg_entry.h"
 #include "kg_lanes.h"
 #include "kg_score.h"
 
 namespace euler_gpu {
 namespace {
 
-struct KgArgs {
-  int32_t kind, normalize, corrupt, log_l;
-  const void* ent; int64_t ent_rows;
-  const void* rel; int64_t rel_rows;
-  const int64_t* src; const int64_t* rel_id; const int64_t* dst; const int64_t* neg;
-  int64_t b, k, d;
-  float* pos_out; float* neg_out;                 // forward
-  const float* g_pos; const float* g_neg;         // gradient
-  float* g_src; float* g_rel; float* g_dst; float* g_neg_rows;
-  int32_t out_vec;                                // the four gradient buffers start on 16 bytes
+struct KgArgs : KgTripleArgs {
+  int32_t normalize;
+  int64_t d;
 };
-
-// ss and inv of a row
-template <int V, typename Row>
-__device__ __forceinline__ void KgNorm(const Row& x, bool normalize, int32_t l, int32_t lanes, int32_t chunks,
-                                       float* ss, float* inv) {
-  *ss = normalize ? KgCombine(KgLaneSumSq<V>(x, l, lanes, chunks), lanes) : 0.f;
-  *inv = KgInv(*ss, normalize);
-}
 
 template <int DE, int DR, int V, bool REG>
 __global__ __launch_bounds__(256) void TripleScoreKernel(const KgArgs a) {
@@ -53,7 +41,6 @@ __global__ __launch_bounds__(256) void TripleScoreKernel(const KgArgs a) {
   const int64_t waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
   const int32_t chunks = (int32_t)(a.d / V);
   const bool normalize = a.normalize != 0;
-  const int64_t kp = a.corrupt == kKgBoth ? 2 * a.k : a.k;
   for (int64_t t0 = wave * tasks_per_wave; t0 < a.b; t0 += waves * tasks_per_wave) {
     const int64_t t = t0 + sub;
     const bool live = t < a.b;
@@ -63,22 +50,17 @@ __global__ __launch_bounds__(256) void TripleScoreKernel(const KgArgs a) {
     R.Open(a.rel, live ? a.rel_id[t] : -1, a.rel_rows, a.d, l, chunks);
     T.Open(a.ent, live ? a.dst[t] : -1, a.ent_rows, a.d, l, chunks);
     float ss, ih, ir, it, in;
-    KgNorm<V>(H, normalize, l, lanes, chunks, &ss, &ih);
-    KgNorm<V>(R, normalize, l, lanes, chunks, &ss, &ir);
-    KgNorm<V>(T, normalize, l, lanes, chunks, &ss, &it);
+    KgLaneNorm<V>(H, normalize, l, lanes, chunks, &ss, &ih);
+    KgLaneNorm<V>(R, normalize, l, lanes, chunks, &ss, &ir);
+    KgLaneNorm<V>(T, normalize, l, lanes, chunks, &ss, &it);
     const float pos = KgFinish(a.kind, KgCombine(KgLaneScore<V>(a.kind, H, ih, R, ir, T, it, l, lanes, chunks), lanes));
     if (live && l == 0) a.pos_out[t] = pos;
     for (int64_t k = 0; k < a.k; ++k) {
       N.Open(a.ent, live ? a.neg[t * a.k + k] : -1, a.ent_rows, a.d, l, chunks);
-      KgNorm<V>(N, normalize, l, lanes, chunks, &ss, &in);
-      if (a.corrupt != kKgTail) {
-        const float s = KgFinish(a.kind, KgCombine(KgLaneScore<V>(a.kind, N, in, R, ir, T, it, l, lanes, chunks), lanes));
-        if (live && l == 0) a.neg_out[t * kp + k] = s;
-      }
-      if (a.corrupt != kKgFront) {
-        const float s = KgFinish(a.kind, KgCombine(KgLaneScore<V>(a.kind, H, ih, R, ir, N, in, l, lanes, chunks), lanes));
-        if (live && l == 0) a.neg_out[t * kp + (a.corrupt == kKgBoth ? a.k : 0) + k] = s;
-      }
+      KgLaneNorm<V>(N, normalize, l, lanes, chunks, &ss, &in);
+      KgLaneCorrupt<V>(a.kind, a.corrupt, H, ih, R, ir, T, it, N, in, l, lanes, chunks, [&](bool tail, float s) {
+        if (live && l == 0) a.neg_out[KgNegSlot(a.corrupt, a.k, t, k, tail)] = s;
+      });
     }
   }
 }
@@ -101,8 +83,6 @@ __global__ __launch_bounds__(256) void TripleScoreGradKernel(const KgArgs a) {
   const int64_t waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
   const int32_t chunks = (int32_t)(a.d / V);
   const bool normalize = a.normalize != 0, vec = a.out_vec != 0;
-  const bool l2 = a.kind == kKgTransL2;
-  const int64_t kp = a.corrupt == kKgBoth ? 2 * a.k : a.k;
   for (int64_t t0 = wave * tasks_per_wave; t0 < a.b; t0 += waves * tasks_per_wave) {
     const int64_t t = t0 + sub;
     const bool live = t < a.b;
@@ -113,9 +93,9 @@ __global__ __launch_bounds__(256) void TripleScoreGradKernel(const KgArgs a) {
     R.Open(a.rel, live ? a.rel_id[t] : -1, a.rel_rows, a.d, l, chunks);
     T.Open(a.ent, live ? a.dst[t] : -1, a.ent_rows, a.d, l, chunks);
     float ssh, ssr, sst, ssn, ih, ir, it, in;
-    KgNorm<V>(H, normalize, l, lanes, chunks, &ssh, &ih);
-    KgNorm<V>(R, normalize, l, lanes, chunks, &ssr, &ir);
-    KgNorm<V>(T, normalize, l, lanes, chunks, &sst, &it);
+    KgLaneNorm<V>(H, normalize, l, lanes, chunks, &ssh, &ih);
+    KgLaneNorm<V>(R, normalize, l, lanes, chunks, &ssr, &ir);
+    KgLaneNorm<V>(T, normalize, l, lanes, chunks, &sst, &it);
     const LaneOut<V> oh{a.g_src + tt * a.d, live, vec}, orl{a.g_rel + tt * a.d, live, vec},
         ot{a.g_dst + tt * a.d, live, vec};
     LaneAcc<V, REG> gh, gr, gt, gn;
@@ -123,25 +103,18 @@ __global__ __launch_bounds__(256) void TripleScoreGradKernel(const KgArgs a) {
     gr.Open(orl, l, lanes, chunks);
     gt.Open(ot, l, lanes, chunks);
     {
-      const float s = l2 ? KgCombine(KgLaneScore<V>(a.kind, H, ih, R, ir, T, it, l, lanes, chunks), lanes) : 0.f;
+      const float s =
+          a.kind == kKgTransL2 ? KgCombine(KgLaneScore<V>(a.kind, H, ih, R, ir, T, it, l, lanes, chunks), lanes) : 0.f;
       const float gs = KgScale(a.kind, live ? a.g_pos[t] : 0.f, s);
       KgLaneScoreGrad<V>(a.kind, gs, H, ih, R, ir, T, it, gh, gr, gt, l, lanes, chunks);
     }
     for (int64_t k = 0; k < a.k; ++k) {
       N.Open(a.ent, live ? a.neg[t * a.k + k] : -1, a.ent_rows, a.d, l, chunks);
-      KgNorm<V>(N, normalize, l, lanes, chunks, &ssn, &in);
+      KgLaneNorm<V>(N, normalize, l, lanes, chunks, &ssn, &in);
       const LaneOut<V> on{a.g_neg_rows + (tt * a.k + k) * a.d, live, vec};
       gn.Open(on, l, lanes, chunks);
-      if (a.corrupt != kKgTail) {
-        const float s = l2 ? KgCombine(KgLaneScore<V>(a.kind, N, in, R, ir, T, it, l, lanes, chunks), lanes) : 0.f;
-        const float gs = KgScale(a.kind, live ? a.g_neg[t * kp + k] : 0.f, s);
-        KgLaneScoreGrad<V>(a.kind, gs, N, in, R, ir, T, it, gn, gr, gt, l, lanes, chunks);
-      }
-      if (a.corrupt != kKgFront) {
-        const float s = l2 ? KgCombine(KgLaneScore<V>(a.kind, H, ih, R, ir, N, in, l, lanes, chunks), lanes) : 0.f;
-        const float gs = KgScale(a.kind, live ? a.g_neg[t * kp + (a.corrupt == kKgBoth ? a.k : 0) + k] : 0.f, s);
-        KgLaneScoreGrad<V>(a.kind, gs, H, ih, R, ir, N, in, gh, gr, gn, l, lanes, chunks);
-      }
+      const auto g = [&](bool tail) { return live ? a.g_neg[KgNegSlot(a.corrupt, a.k, t, k, tail)] : 0.f; };
+      KgLaneCorruptGrad<V>(a.kind, a.corrupt, g, H, ih, R, ir, T, it, N, in, gh, gr, gt, gn, l, lanes, chunks);
       KgRowGrad<V>(N, normalize, ssn, in, gn, on, l, lanes, chunks);
     }
     KgRowGrad<V>(H, normalize, ssh, ih, gh, oh, l, lanes, chunks);
@@ -159,14 +132,10 @@ void LaunchOne(hipStream_t st, const KgArgs& a, bool grad, dim3 grid) {
 template <int DE, int DR>
 int LaunchTripleScore(hipStream_t st, KgArgs a, bool grad) {
   const int32_t v = KgChunkWidth(a.d, (uintptr_t)a.ent, DE == kF32, (uintptr_t)a.rel, DR == kF32);
-  const int64_t chunks = a.d / v;
-  a.log_l = KgLogLanes(chunks);
-  const bool reg = chunks <= 64;                  // a lane owns at most one chunk
-  const int64_t tasks_per_wave = 64 >> a.log_l;
-  const int64_t waves = (a.b + tasks_per_wave - 1) / tasks_per_wave;
-  int64_t blocks = (waves + 3) / 4;
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  const dim3 grid((unsigned)blocks);
+  const KgLaunchShape shape = KgTaskLaunch(a.b, a.d / v);
+  a.log_l = shape.log_l;
+  const bool reg = shape.reg;
+  const dim3 grid(shape.grid);
   if (v == 8) reg ? LaunchOne<DE, DR, 8, true>(st, a, grad, grid) : LaunchOne<DE, DR, 8, false>(st, a, grad, grid);
   else if (v == 4) reg ? LaunchOne<DE, DR, 4, true>(st, a, grad, grid) : LaunchOne<DE, DR, 4, false>(st, a, grad, grid);
   else reg ? LaunchOne<DE, DR, 1, true>(st, a, grad, grid) : LaunchOne<DE, DR, 1, false>(st, a, grad, grid);
@@ -174,41 +143,9 @@ int LaunchTripleScore(hipStream_t st, KgArgs a, bool grad) {
   return EULER_GPU_OK;
 }
 
-template <int DE>
-int DispatchRel(hipStream_t st, const KgArgs& a, int32_t rel_dtype, bool grad) {
-  if (rel_dtype == EULER_GPU_F32) return LaunchTripleScore<DE, kF32>(st, a, grad);
-  if (rel_dtype == EULER_GPU_BF16) return LaunchTripleScore<DE, kBF16>(st, a, grad);
-  return LaunchTripleScore<DE, kF16>(st, a, grad);
-}
-
-bool KgKnownDtype(int32_t t) { return t == EULER_GPU_F32 || t == EULER_GPU_BF16 || t == EULER_GPU_F16; }
-
-// The checks both entries share.  -> EULER_GPU_OK with *run = false when there is nothing to do.
-int CheckTripleArgs(const char* what, const KgArgs& a, int32_t ent_dtype, int32_t rel_dtype, bool* run) {
-  *run = false;
-  if (a.kind < 0 || a.kind > 2) return Fail(EULER_GPU_EINVAL, std::string(what) + ": kind outside 0..2");
-  if (a.corrupt < 0 || a.corrupt > 2) return Fail(EULER_GPU_EINVAL, std::string(what) + ": corrupt outside 0..2");
-  if (!KgKnownDtype(ent_dtype) || !KgKnownDtype(rel_dtype))
-    return Fail(EULER_GPU_EINVAL, std::string(what) + ": unknown dtype (0 fp32, 1 bf16, 2 fp16)");
-  if (a.k < 0 || a.b < 0 || a.d < 0) return Fail(EULER_GPU_EINVAL, std::string(what) + ": b, k or d < 0");
-  if (a.ent_rows < 1 || a.rel_rows < 1) return Fail(EULER_GPU_EINVAL, std::string(what) + ": a table with fewer than 1 row");
-  if (a.d >= (1LL << 31)) return Fail(EULER_GPU_EINVAL, std::string(what) + ": d >= 2^31");
-  if (a.b >= (1LL << 31) || a.k >= (1LL << 31) || a.b * (a.k > 1 ? a.k : 1) * 2 >= (1LL << 31))
-    return Fail(EULER_GPU_EINVAL, std::string(what) + ": b * max(k, 1) * 2 >= 2^31");
-  if (a.b == 0 || a.d == 0) return EULER_GPU_OK;
-  if (!a.ent || !a.rel || !a.src || !a.rel_id || !a.dst) return Fail(EULER_GPU_EINVAL, std::string(what) + ": null buffer");
-  if (a.k > 0 && !a.neg) return Fail(EULER_GPU_EINVAL, std::string(what) + ": k > 0 without negatives");
-  if ((uintptr_t)a.ent % (ent_dtype == EULER_GPU_F32 ? 4 : 2) != 0 ||
-      (uintptr_t)a.rel % (rel_dtype == EULER_GPU_F32 ? 4 : 2) != 0)
-    return Fail(EULER_GPU_EINVAL, std::string(what) + ": a table is not aligned to its type");
-  *run = true;
-  return EULER_GPU_OK;
-}
-
-int DispatchEnt(hipStream_t st, const KgArgs& a, int32_t ent_dtype, int32_t rel_dtype, bool grad) {
-  if (ent_dtype == EULER_GPU_F32) return DispatchRel<kF32>(st, a, rel_dtype, grad);
-  if (ent_dtype == EULER_GPU_BF16) return DispatchRel<kBF16>(st, a, rel_dtype, grad);
-  return DispatchRel<kF16>(st, a, rel_dtype, grad);
+int Dispatch(hipStream_t st, const KgArgs& a, int32_t ent_dtype, int32_t rel_dtype, bool grad) {
+  return KgDispatchTables(ent_dtype, rel_dtype,
+                          [&](auto de, auto dr) { return LaunchTripleScore<de, dr>(st, a, grad); });
 }
 
 }  // namespace
@@ -224,17 +161,14 @@ int euler_gpu_triple_score(void* stream, int32_t kind, int32_t normalize, int32_
                            const int64_t* src_dev, const int64_t* rel_id_dev, const int64_t* dst_dev,
                            const int64_t* neg_dev, int64_t b, int64_t k, int64_t d,
                            float* pos_out_dev, float* neg_out_dev) {
-  KgArgs a{};
-  a.kind = kind; a.normalize = normalize; a.corrupt = corrupt;
-  a.ent = ent_dev; a.ent_rows = ent_rows; a.rel = rel_dev; a.rel_rows = rel_rows;
-  a.src = src_dev; a.rel_id = rel_id_dev; a.dst = dst_dev; a.neg = neg_dev;
-  a.b = b; a.k = k; a.d = d;
-  a.pos_out = pos_out_dev; a.neg_out = neg_out_dev;
+  const KgArgs a{KgShared(kind, corrupt, ent_dev, ent_rows, rel_dev, rel_rows, src_dev, rel_id_dev, dst_dev, neg_dev,
+                          b, k, pos_out_dev, neg_out_dev),
+                 normalize, d};
   bool run;
-  const int rc = CheckTripleArgs("triple_score", a, ent_dtype, rel_dtype, &run);
+  const int rc = CheckKgCall({"triple_score", kKgScoreFamily, ent_dtype, rel_dtype, d}, a, &run);
   if (rc != EULER_GPU_OK || !run) return rc;
   if (!pos_out_dev || (k > 0 && !neg_out_dev)) return Fail(EULER_GPU_EINVAL, "triple_score: null output buffer");
-  return DispatchEnt((hipStream_t)stream, a, ent_dtype, rel_dtype, false);
+  return Dispatch((hipStream_t)stream, a, ent_dtype, rel_dtype, false);
 }
 
 int euler_gpu_triple_score_grad(void* stream, int32_t kind, int32_t normalize, int32_t corrupt,
@@ -244,22 +178,18 @@ int euler_gpu_triple_score_grad(void* stream, int32_t kind, int32_t normalize, i
                                 const int64_t* neg_dev, int64_t b, int64_t k, int64_t d,
                                 const float* g_pos_dev, const float* g_neg_dev,
                                 float* g_src_dev, float* g_rel_dev, float* g_dst_dev, float* g_neg_rows_dev) {
-  KgArgs a{};
-  a.kind = kind; a.normalize = normalize; a.corrupt = corrupt;
-  a.ent = ent_dev; a.ent_rows = ent_rows; a.rel = rel_dev; a.rel_rows = rel_rows;
-  a.src = src_dev; a.rel_id = rel_id_dev; a.dst = dst_dev; a.neg = neg_dev;
-  a.b = b; a.k = k; a.d = d;
-  a.g_pos = g_pos_dev; a.g_neg = g_neg_dev;
-  a.g_src = g_src_dev; a.g_rel = g_rel_dev; a.g_dst = g_dst_dev; a.g_neg_rows = g_neg_rows_dev;
+  KgArgs a{KgShared(kind, corrupt, ent_dev, ent_rows, rel_dev, rel_rows, src_dev, rel_id_dev, dst_dev, neg_dev, b, k,
+                    nullptr, nullptr, g_pos_dev, g_neg_dev, g_src_dev, g_rel_dev, g_dst_dev, g_neg_rows_dev),
+           normalize, d};
   bool run;
-  const int rc = CheckTripleArgs("triple_score_grad", a, ent_dtype, rel_dtype, &run);
+  const int rc = CheckKgCall({"triple_score_grad", kKgScoreFamily, ent_dtype, rel_dtype, d}, a, &run);
   if (rc != EULER_GPU_OK || !run) return rc;
   if (!g_pos_dev || !g_src_dev || !g_rel_dev || !g_dst_dev || (k > 0 && (!g_neg_dev || !g_neg_rows_dev)))
     return Fail(EULER_GPU_EINVAL, "triple_score_grad: null gradient buffer");
-  if (((uintptr_t)g_src_dev | (uintptr_t)g_rel_dev | (uintptr_t)g_dst_dev | (uintptr_t)g_neg_rows_dev) % 4 != 0)
-    return Fail(EULER_GPU_EINVAL, "triple_score_grad: a gradient buffer is not aligned to its type");
-  a.out_vec = ((uintptr_t)g_src_dev | (uintptr_t)g_rel_dev | (uintptr_t)g_dst_dev | (uintptr_t)g_neg_rows_dev) % 16 == 0;
-  return DispatchEnt((hipStream_t)stream, a, ent_dtype, rel_dtype, true);
+  const uintptr_t all = (uintptr_t)g_src_dev | (uintptr_t)g_rel_dev | (uintptr_t)g_dst_dev | (uintptr_t)g_neg_rows_dev;
+  if (all % 4 != 0) return Fail(EULER_GPU_EINVAL, "triple_score_grad: a gradient buffer is not aligned to its type");
+  a.out_vec = all % 16 == 0;
+  return Dispatch((hipStream_t)stream, a, ent_dtype, rel_dtype, true);
 }
 
 }  // extern "C"

@@ -1258,6 +1258,48 @@ _KG_KIND = {"trans_l1": 0, "trans_l2": 1, "distmult": 2}
 _KG_CORRUPT = {"front": 0, "tail": 1, "both": 2}
 
 
+def _kg_ids(name, src, rel_id, dst, neg):
+    """the ids of a triple-scoring op -> int64 contiguous src, rel_id, dst [B], neg [B, K] or None, and B"""
+    src, rel_id, dst = (t.to(torch.int64).reshape(-1).contiguous() for t in (src, rel_id, dst))
+    b = src.numel()
+    if rel_id.numel() != b or dst.numel() != b:
+        raise ValueError("%s: one src, rel_id and dst per triple" % name)
+    if neg is not None:
+        neg = neg.to(torch.int64)
+        neg = (neg if neg.dim() == 2 else neg.reshape(b, -1)).contiguous()
+        if neg.shape[0] != b:
+            raise ValueError("%s: neg is [B, K]" % name)
+    return src, rel_id, dst, neg, b
+
+
+def _kg_limits(name, b, neg, *row_counts):
+    """the kernels' 32-bit limits: the scores of a batch and the rows of every table given"""
+    if b * max(1 if neg is None else neg.shape[1], 1) * 2 >= 2 ** 31 or max(row_counts) >= 2 ** 31:
+        raise ValueError("%s: B * max(K, 1) * 2 and the %s rows must stay below 2^31"
+                         % (name, "table's" if len(row_counts) == 1 else "tables'"))
+
+
+def _kg_scores_out(b, k, corrupt, empty, device):
+    """-> (pos [B], neg_out [B, K']) for a forward entry to fill; zeros when it has nothing to do"""
+    make = torch.zeros if empty else torch.empty
+    return (make(b, dtype=_F32, device=device),
+            make((b, 2 * k if corrupt == "both" else k), dtype=_F32, device=device))
+
+
+def _kg_incoming(g_pos, g_neg, k):
+    """the incoming gradients as a gradient entry reads them: fp32, contiguous, no g_neg without negatives"""
+    return g_pos.to(_F32).contiguous(), g_neg.to(_F32).contiguous() if k else None
+
+
+def _kg_ent_grad(rows_src, rows_dst, rows_neg, src, dst, neg, table, sparse_grad):
+    """the gradient of an entity table from its occurrences' rows, at the keys [src | dst | neg]"""
+    rows, ids = [rows_src, rows_dst], [src, dst]
+    if neg is not None:
+        rows.append(rows_neg.reshape(-1, rows_neg.shape[2]))
+        ids.append(neg.reshape(-1))
+    return _table_grad(torch.cat(rows), torch.cat(ids), table.shape[0], table.dtype, sparse_grad)
+
+
 def _triple_head(ent, rel, src, rel_id, dst, neg, kind, corrupt, normalize):
     """the arguments the two triple_score entries share, from prepared tensors"""
     b, k = src.numel(), (neg.shape[1] if neg is not None else 0)
@@ -1269,11 +1311,9 @@ def _triple_head(ent, rel, src, rel_id, dst, neg, kind, corrupt, normalize):
 def _triple_score_raw(ent, rel, src, rel_id, dst, neg, kind, corrupt, normalize):
     """euler_gpu_triple_score on prepared tensors -> (pos [B], neg_out [B, K'])"""
     b, k, d = src.numel(), (neg.shape[1] if neg is not None else 0), ent.shape[1]
-    kp = 2 * k if corrupt == "both" else k
+    pos, out = _kg_scores_out(b, k, corrupt, b == 0 or d == 0, ent.device)
     if b == 0 or d == 0:
-        return torch.zeros(b, dtype=_F32, device=ent.device), torch.zeros((b, kp), dtype=_F32, device=ent.device)
-    pos = torch.empty(b, dtype=_F32, device=ent.device)
-    out = torch.empty((b, kp), dtype=_F32, device=ent.device)
+        return pos, out
     with _on(ent.device):
         check(lib().euler_gpu_triple_score(*_triple_head(ent, rel, src, rel_id, dst, neg, kind, corrupt, normalize),
                                            _ptr(pos), _ptr(out) if k else None))
@@ -1289,8 +1329,7 @@ def _triple_score_grad_raw(ent, rel, src, rel_id, dst, neg, kind, corrupt, norma
     gn = make((b, k, d), dtype=_F32, device=ent.device)
     if b == 0 or d == 0:
         return gs, gr, gd, gn
-    g_pos = g_pos.to(_F32).contiguous()
-    g_neg = g_neg.to(_F32).contiguous() if k else None
+    g_pos, g_neg = _kg_incoming(g_pos, g_neg, k)
     with _on(ent.device):
         check(lib().euler_gpu_triple_score_grad(
             *_triple_head(ent, rel, src, rel_id, dst, neg, kind, corrupt, normalize), _ptr(g_pos), _ptr(g_neg),
@@ -1336,11 +1375,7 @@ class _TripleScore(torch.autograd.Function):
                                                 g_pos, g_neg)
         g_ent = g_rel = None
         if ctx.needs_input_grad[0]:
-            rows, ids = [gs, gd], [src, dst]
-            if neg is not None:
-                rows.append(gn.reshape(-1, gn.shape[2]))
-                ids.append(neg.reshape(-1))
-            g_ent = _table_grad(torch.cat(rows), torch.cat(ids), ent.shape[0], ent.dtype, sparse_grad)
+            g_ent = _kg_ent_grad(gs, gd, gn, src, dst, neg, ent, sparse_grad)
         if ctx.needs_input_grad[1]:
             g_rel = _table_grad(gr, rel_id, rel.shape[0], rel.dtype, sparse_grad)
         return (g_ent, g_rel) + (None,) * 8
@@ -1373,18 +1408,9 @@ def triple_score(ent, rel, src, rel_id, dst, neg=None, kind="trans_l1", corrupt=
     _dt("triple_score", rel)
     if ent.dim() != 2 or rel.dim() != 2 or ent.shape[1] != rel.shape[1] or ent.shape[0] < 1 or rel.shape[0] < 1:
         raise ValueError("triple_score: ent is [rows, d] and rel is [relations, d], one row at least")
-    src, rel_id, dst = (t.to(torch.int64).reshape(-1).contiguous() for t in (src, rel_id, dst))
-    b = src.numel()
-    if rel_id.numel() != b or dst.numel() != b:
-        raise ValueError("triple_score: one src, rel_id and dst per triple")
-    if neg is not None:
-        neg = neg.to(torch.int64)
-        neg = (neg if neg.dim() == 2 else neg.reshape(b, -1)).contiguous()
-        if neg.shape[0] != b:
-            raise ValueError("triple_score: neg is [B, K]")
+    src, rel_id, dst, neg, b = _kg_ids("triple_score", src, rel_id, dst, neg)
     _need_cuda(ent, rel, src, rel_id, dst, *(() if neg is None else (neg,)))
-    if b * max(1 if neg is None else neg.shape[1], 1) * 2 >= 2 ** 31 or ent.shape[0] >= 2 ** 31:
-        raise ValueError("triple_score: B * max(K, 1) * 2 and the table's rows must stay below 2^31")
+    _kg_limits("triple_score", b, neg, ent.shape[0])
     pos, out = _TripleScore.apply(ent.contiguous(), rel.contiguous(), src, rel_id, dst, neg, kind, corrupt,
                                   bool(normalize), bool(sparse_grad))
     return pos if neg is None else (pos, out)
@@ -1404,11 +1430,9 @@ def _triple_proj_head(proj, ent, ent_aux, rel, rel_aux, src, rel_id, dst, neg, k
 def _triple_score_proj_raw(proj, ent, ent_aux, rel, rel_aux, src, rel_id, dst, neg, kind, corrupt):
     """euler_gpu_triple_score_proj on prepared tensors -> (pos [B], neg_out [B, K'])"""
     b, k, d = src.numel(), (neg.shape[1] if neg is not None else 0), ent.shape[1]
-    kp = 2 * k if corrupt == "both" else k
+    pos, out = _kg_scores_out(b, k, corrupt, b == 0 or d == 0, ent.device)
     if b == 0 or d == 0:
-        return torch.zeros(b, dtype=_F32, device=ent.device), torch.zeros((b, kp), dtype=_F32, device=ent.device)
-    pos = torch.empty(b, dtype=_F32, device=ent.device)
-    out = torch.empty((b, kp), dtype=_F32, device=ent.device)
+        return pos, out
     with _on(ent.device):
         check(lib().euler_gpu_triple_score_proj(
             *_triple_proj_head(proj, ent, ent_aux, rel, rel_aux, src, rel_id, dst, neg, kind, corrupt),
@@ -1428,8 +1452,7 @@ def _triple_score_proj_grad_raw(proj, ent, ent_aux, rel, rel_aux, src, rel_id, d
     gsa, gda, gna = (flat(), flat(), block()) if proj == "transfer" else (None, None, None)
     if b == 0 or d == 0:
         return gs, gr, gd, gn, gra, gsa, gda, gna
-    g_pos = g_pos.to(_F32).contiguous()
-    g_neg = g_neg.to(_F32).contiguous() if k else None
+    g_pos, g_neg = _kg_incoming(g_pos, g_neg, k)
     with _on(ent.device):
         check(lib().euler_gpu_triple_score_proj_grad(
             *_triple_proj_head(proj, ent, ent_aux, rel, rel_aux, src, rel_id, dst, neg, kind, corrupt),
@@ -1455,14 +1478,9 @@ class _TripleScoreProj(torch.autograd.Function):
         proj, kind, corrupt, sparse_grad = ctx.conf
         gs, gr, gd, gn, gra, gsa, gda, gna = _triple_score_proj_grad_raw(
             proj, ent, ent_aux, rel, rel_aux, src, rel_id, dst, neg, kind, corrupt, g_pos, g_neg)
-        ids = torch.cat([src, dst] + ([neg.reshape(-1)] if neg is not None else []))
-
-        def ent_grad(a, c, n, table):
-            rows = [a, c] + ([n.reshape(-1, n.shape[2])] if neg is not None else [])
-            return _table_grad(torch.cat(rows), ids, table.shape[0], table.dtype, sparse_grad)
-
-        g_ent = ent_grad(gs, gd, gn, ent) if ctx.needs_input_grad[0] else None
-        g_ent_aux = ent_grad(gsa, gda, gna, ent_aux) if ent_aux is not None and ctx.needs_input_grad[1] else None
+        g_ent = _kg_ent_grad(gs, gd, gn, src, dst, neg, ent, sparse_grad) if ctx.needs_input_grad[0] else None
+        g_ent_aux = _kg_ent_grad(gsa, gda, gna, src, dst, neg, ent_aux, sparse_grad) \
+            if ent_aux is not None and ctx.needs_input_grad[1] else None
         g_rel = _table_grad(gr, rel_id, rel.shape[0], rel.dtype, sparse_grad) if ctx.needs_input_grad[2] else None
         g_rel_aux = _table_grad(gra, rel_id, rel_aux.shape[0], rel_aux.dtype, sparse_grad) \
             if ctx.needs_input_grad[3] else None
@@ -1512,19 +1530,10 @@ def triple_score_proj(ent, rel, src, rel_id, dst, neg=None, proj="hyperplane", h
         raise ValueError("%s: ent_transfer has ent's shape, hyper / rel_transfer have rel's" % name)
     if rel_aux.dtype != rel.dtype or (ent_aux is not None and ent_aux.dtype != ent.dtype):
         raise TypeError("%s: ent_transfer has ent's dtype, hyper / rel_transfer have rel's" % name)
-    src, rel_id, dst = (t.to(torch.int64).reshape(-1).contiguous() for t in (src, rel_id, dst))
-    b = src.numel()
-    if rel_id.numel() != b or dst.numel() != b:
-        raise ValueError("%s: one src, rel_id and dst per triple" % name)
-    if neg is not None:
-        neg = neg.to(torch.int64)
-        neg = (neg if neg.dim() == 2 else neg.reshape(b, -1)).contiguous()
-        if neg.shape[0] != b:
-            raise ValueError("%s: neg is [B, K]" % name)
+    src, rel_id, dst, neg, b = _kg_ids(name, src, rel_id, dst, neg)
     _need_cuda(ent, rel, rel_aux, src, rel_id, dst, *(() if neg is None else (neg,)),
                *(() if ent_aux is None else (ent_aux,)))
-    if b * max(1 if neg is None else neg.shape[1], 1) * 2 >= 2 ** 31 or ent.shape[0] >= 2 ** 31:
-        raise ValueError("%s: B * max(K, 1) * 2 and the table's rows must stay below 2^31" % name)
+    _kg_limits(name, b, neg, ent.shape[0])
     pos, out = _TripleScoreProj.apply(ent.contiguous(), None if ent_aux is None else ent_aux.contiguous(),
                                       rel.contiguous(), rel_aux.contiguous(), src, rel_id, dst, neg, proj, kind,
                                       corrupt, bool(sparse_grad))
@@ -1570,11 +1579,10 @@ def _triple_matrix_head(ent, rel, matrix, src, rel_id, dst, neg, kind, corrupt, 
 def _triple_score_matrix_raw(ent, rel, matrix, src, rel_id, dst, neg, kind, corrupt, order):
     """euler_gpu_triple_score_matrix on prepared tensors -> (pos [B], neg_out [B, K'])"""
     b, k = src.numel(), (neg.shape[1] if neg is not None else 0)
-    kp = 2 * k if corrupt == "both" else k
-    if b == 0 or ent.shape[1] == 0 or rel.shape[1] == 0:
-        return torch.zeros(b, dtype=_F32, device=ent.device), torch.zeros((b, kp), dtype=_F32, device=ent.device)
-    pos = torch.empty(b, dtype=_F32, device=ent.device)
-    out = torch.empty((b, kp), dtype=_F32, device=ent.device)
+    empty = b == 0 or ent.shape[1] == 0 or rel.shape[1] == 0
+    pos, out = _kg_scores_out(b, k, corrupt, empty, ent.device)
+    if empty:
+        return pos, out
     with _on(ent.device):
         check(lib().euler_gpu_triple_score_matrix(
             *_triple_matrix_head(ent, rel, matrix, src, rel_id, dst, neg, kind, corrupt, order),
@@ -1598,8 +1606,7 @@ def _triple_score_matrix_grad_raw(ent, rel, matrix, src, rel_id, dst, neg, kind,
     gm = None if seg_rel is None else make((nseg, de * dr), dtype=matrix.dtype, device=ent.device)
     if empty:
         return gs, gr, gd, gn, zs, zd, zn, gm
-    g_pos = g_pos.to(_F32).contiguous()
-    g_neg = g_neg.to(_F32).contiguous() if k else None
+    g_pos, g_neg = _kg_incoming(g_pos, g_neg, k)
     with _on(ent.device):
         check(lib().euler_gpu_triple_score_matrix_grad(
             *_triple_matrix_head(ent, rel, matrix, src, rel_id, dst, neg, kind, corrupt, order),
@@ -1634,11 +1641,7 @@ class _TripleScoreMatrix(torch.autograd.Function):
             ent, rel, matrix, src, rel_id, dst, neg, kind, corrupt, order, seg_ptr, seg_rel, g_pos, g_neg)
         g_ent = g_rel = g_matrix = None
         if ctx.needs_input_grad[0]:
-            rows, ids = [gs, gd], [src, dst]
-            if neg is not None:
-                rows.append(gn.reshape(-1, gn.shape[2]))
-                ids.append(neg.reshape(-1))
-            g_ent = _table_grad(torch.cat(rows), torch.cat(ids), ent.shape[0], ent.dtype, sparse_grad)
+            g_ent = _kg_ent_grad(gs, gd, gn, src, dst, neg, ent, sparse_grad)
         if ctx.needs_input_grad[1]:
             g_rel = _table_grad(gr, rel_id, rel.shape[0], rel.dtype, sparse_grad)
         if ctx.needs_input_grad[2]:
@@ -1683,19 +1686,9 @@ def triple_score_matrix(ent, rel, matrix, src, rel_id, dst, neg=None, kind="tran
         raise ValueError("%s: de and dr are at most %d" % (name, KG_MATRIX_MAX_DIM))
     if sparse_grad and matrix.dim() == 3:
         raise ValueError("%s: sparse_grad takes the matrix as [relations, de * dr]" % name)
-    src, rel_id, dst = (t.to(torch.int64).reshape(-1).contiguous() for t in (src, rel_id, dst))
-    b = src.numel()
-    if rel_id.numel() != b or dst.numel() != b:
-        raise ValueError("%s: one src, rel_id and dst per triple" % name)
-    if neg is not None:
-        neg = neg.to(torch.int64)
-        neg = (neg if neg.dim() == 2 else neg.reshape(b, -1)).contiguous()
-        if neg.shape[0] != b:
-            raise ValueError("%s: neg is [B, K]" % name)
+    src, rel_id, dst, neg, b = _kg_ids(name, src, rel_id, dst, neg)
     _need_cuda(ent, rel, matrix, src, rel_id, dst, *(() if neg is None else (neg,)))
-    if b * max(1 if neg is None else neg.shape[1], 1) * 2 >= 2 ** 31 or ent.shape[0] >= 2 ** 31 \
-            or rel.shape[0] >= 2 ** 31:
-        raise ValueError("%s: B * max(K, 1) * 2 and the tables' rows must stay below 2^31" % name)
+    _kg_limits(name, b, neg, ent.shape[0], rel.shape[0])
     flat = matrix.contiguous()
     if flat.dim() == 3:
         flat = flat.reshape(rel.shape[0], de * dr)
