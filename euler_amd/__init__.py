@@ -7,4 +7,5 @@ the C ABI of include/euler_gpu.h.  There is no CPU fallback."""
 from .graph import Graph, synth_params            # noqa: F401
 from . import ops                                 # noqa: F401
 from . import dataflow                            # noqa: F401
+from . import optim                               # noqa: F401
 from .euler_ops import *                          # noqa: F401,F403

@@ -12,72 +12,12 @@
 // other task reads or writes that table row.  Nothing here waits on the host: the three entries
 // only enqueue, scratch comes from StreamBuf and goes back in stream order on every exit, and
 // every check precedes the first write to the table.  take without clear needs no grouping: it is
-// a plain lookup per occurrence.
-#include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
-
-#include "device_fns.h"
-#include "device_mem.h"
-#include "embed_store.h"
+// a plain lookup per occurrence.  The chunk loads and stores, the key kernel, the sort and the
+// eight-ahead walk live in embed_group.h, which the sparse-row optimiser steps share.
+#include "embed_group.h"
 
 namespace euler_gpu {
 namespace {
-
-constexpr int kBytes[3] = {4, 2, 2};
-
-// V adjacent elements as their bits: 16-byte (8-byte) accesses where the type and V allow
-template <int DT, int V>
-__device__ __forceinline__ void EsLoad(const void* base, int64_t at, uint32_t r[V]) {
-  if constexpr (DT == kF32) {
-    const uint32_t* p = static_cast<const uint32_t*>(base) + at;
-    if constexpr (V == 1) {
-      r[0] = *p;
-    } else {
-#pragma unroll
-      for (int q = 0; q < V / 4; ++q) {
-        const uint4 v = reinterpret_cast<const uint4*>(p)[q];
-        r[4 * q] = v.x; r[4 * q + 1] = v.y; r[4 * q + 2] = v.z; r[4 * q + 3] = v.w;
-      }
-    }
-  } else {
-    const uint16_t* p = static_cast<const uint16_t*>(base) + at;
-    if constexpr (V == 1) {
-      r[0] = *p;
-    } else if constexpr (V == 4) {
-      const uint2 v = *reinterpret_cast<const uint2*>(p);
-      r[0] = v.x & 0xffffu; r[1] = v.x >> 16; r[2] = v.y & 0xffffu; r[3] = v.y >> 16;
-    } else {
-      const uint4 v = *reinterpret_cast<const uint4*>(p);
-      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { r[2 * q] = w[q] & 0xffffu; r[2 * q + 1] = w[q] >> 16; }
-    }
-  }
-}
-
-template <int DT, int V>
-__device__ __forceinline__ void EsStore(void* base, int64_t at, const uint32_t r[V]) {
-  if constexpr (DT == kF32) {
-    uint32_t* p = static_cast<uint32_t*>(base) + at;
-    if constexpr (V == 1) {
-      *p = r[0];
-    } else {
-#pragma unroll
-      for (int q = 0; q < V / 4; ++q)
-        reinterpret_cast<uint4*>(p)[q] = make_uint4(r[4 * q], r[4 * q + 1], r[4 * q + 2], r[4 * q + 3]);
-    }
-  } else {
-    uint16_t* p = static_cast<uint16_t*>(base) + at;
-    if constexpr (V == 1) {
-      *p = (uint16_t)r[0];
-    } else if constexpr (V == 4) {
-      *reinterpret_cast<uint2*>(p) = make_uint2(r[0] | (r[1] << 16), r[2] | (r[3] << 16));
-    } else {
-      *reinterpret_cast<uint4*>(p) =
-          make_uint4(r[0] | (r[1] << 16), r[2] | (r[3] << 16), r[4] | (r[5] << 16), r[6] | (r[7] << 16));
-    }
-  }
-}
 
 struct EsArgs {
   void* table; int64_t rows, d;
@@ -87,27 +27,6 @@ struct EsArgs {
   const uint64_t* keys; const uint32_t* perm;                                  // the sorted pairs
   int32_t log_l;
 };
-
-__global__ __launch_bounds__(256) void EsKeysKernel(const int64_t* __restrict__ ids, int64_t e, int64_t rows,
-                                                    const int32_t* __restrict__ row_index, int64_t m,
-                                                    uint64_t* __restrict__ keys, uint32_t* __restrict__ pos) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < e; p += stride) {
-    keys[p] = EsKey(ids[p], rows, EsSourceLive(p, row_index, m));
-    pos[p] = (uint32_t)p;
-  }
-}
-
-// K sorted entries from q on: which of them belong to the segment of `key` (ok), and their
-// positions.  An entry past the segment stands in as entry i (the head), which is always valid.
-template <int K>
-__device__ __forceinline__ void EsAhead(const EsArgs& a, uint64_t key, int64_t i, int64_t q, bool ok[K],
-                                        int64_t pos[K]) {
-#pragma unroll
-  for (int x = 0; x < K; ++x) ok[x] = q + x < a.e && a.keys[q + x < a.e ? q + x : i] == key;
-#pragma unroll
-  for (int x = 0; x < K; ++x) pos[x] = a.perm[ok[x] ? q + x : i];
-}
 
 // The task that sorted entry i starts (update: ends), run by the L lanes of a group; l = the
 // lane's number in its group.  DV: the dtype of values (update, add) or of out (take).
@@ -249,8 +168,6 @@ int DispatchTable(hipStream_t st, const EsArgs& a, int32_t table_dtype, const vo
   return DispatchOther<OP, kF16>(st, a, other, other_dtype);
 }
 
-bool EsKnownDtype(int32_t t) { return t == EULER_GPU_F32 || t == EULER_GPU_BF16 || t == EULER_GPU_F16; }
-
 // The checks the three entries share: the table, the ids and the other data buffer (values / out).
 // -> EULER_GPU_OK with *run = false when there is nothing to do.
 int CheckStoreArgs(const std::string& what, const EsArgs& a, int32_t table_dtype, const void* other,
@@ -269,32 +186,6 @@ int CheckStoreArgs(const std::string& what, const EsArgs& a, int32_t table_dtype
       (uintptr_t)a.ids % 8 != 0)
     return Fail(EULER_GPU_EINVAL, what + ": a buffer is not aligned to its type");
   *run = true;
-  return EULER_GPU_OK;
-}
-
-// (key, position) of every occurrence, stably sorted by key, into `pairs` (released by its owner)
-int GroupOccurrences(hipStream_t st, EsArgs* a, StreamBuf* pairs) {
-  const size_t n = (size_t)a->e;
-  EG_HIP(pairs->alloc(n * (8 + 8 + 4 + 4) + 64));
-  uint64_t* keys_in = pairs->as<uint64_t>();
-  uint64_t* keys_out = keys_in + n;
-  uint32_t* pos_in = reinterpret_cast<uint32_t*>(keys_out + n);
-  uint32_t* pos_out = pos_in + n;
-  int64_t blocks = ((int64_t)n + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  hipLaunchKernelGGL(EsKeysKernel, dim3((unsigned)blocks), dim3(256), 0, st, a->ids, a->e, a->rows, a->row_index,
-                     a->m, keys_in, pos_in);
-  EG_HIP(hipGetLastError());
-  const int bits = EsKeyBits(a->rows);
-  size_t tmp_bytes = 0;
-  EG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys_in, keys_out, pos_in, pos_out, (int)n, 0, bits,
-                                            st));
-  StreamBuf tmp(st);          // (the library's scratch goes back before the store kernel runs)
-  EG_HIP(tmp.alloc(tmp_bytes + 16));
-  EG_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.as(), tmp_bytes, keys_in, keys_out, pos_in, pos_out, (int)n, 0, bits,
-                                            st));
-  a->keys = keys_out;
-  a->perm = pos_out;
   return EULER_GPU_OK;
 }
 

@@ -5,6 +5,7 @@ ops.  All tensors must live on a CUDA (ROCm) device; nothing here has a CPU
 path."""
 import contextlib
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -1942,6 +1943,114 @@ def embedding_take(table, ids, clear=False, out_dtype=None):
         if clear:
             torch.autograd.graph.increment_version(table)
     return out.reshape(shape)
+
+
+# ---- fused sparse-row optimiser steps ------------------------------------------------------------
+# One call applies one optimiser step to the table rows a list of ids names, from the gradient
+# rows of the OCCURRENCES: duplicates are summed in input order inside the kernel, the table and
+# its state rows change in place.  The contract is stated in euler_amd/csrc/sparse_optim.h;
+# euler_amd/optim.py wraps this in torch.optim.Optimizer classes.
+
+_ROW_STEP_KINDS = {"sgd": 0, "momentum": 1, "adagrad": 2, "adam": 3}
+_ROW_STEP_STATES = {"sgd": 0, "momentum": 1, "adagrad": 1, "adam": 2}
+
+
+def _storage_overlap(a, b):
+    """do two contiguous tensors share bytes?"""
+    if a.numel() == 0 or b.numel() == 0 or a.device != b.device:
+        return False
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def sparse_row_step(kind, table, ids, grad, state=(), lr=None, momentum=0.0, eps=None, betas=(0.9, 0.999), step=1,
+                    row_index=None, count=None):
+    """One optimiser step - kind "sgd", "momentum", "adagrad" or "adam", the four of the
+    reference's utils/optimizers.py - IN PLACE on the rows of `table` ([rows, d], contiguous; fp32,
+    bf16 or fp16; a leaf that requires grad is accepted: a parameter is one) that `ids` names.
+    `grad` holds the gradient rows of the occurrences, in the three forms of embedding_add: grad[p],
+    grad[row_index[p]] or grad[p // count]; fp32 or of the table's dtype.  Per distinct in-range id
+    the rows of its occurrences are summed IN INPUT ORDER in fp32 (no coalesce, no float atomics),
+    then the step runs in correctly rounded fp32 operations and the row is rounded once:
+      sgd       p -= lr * g                                     state ()
+      momentum  a = momentum * a + g;  p -= lr * a              state (a,)      touched rows only
+      adagrad   s += g * g;  p -= lr * g / (sqrt(s) + eps)      state (s,)      eps default 1e-10
+      adam      m += (g - m) * (1 - beta1);  v += (g * g - v) * (1 - beta2);
+                p -= lr * sqrt(1 - beta2^step) / (1 - beta1^step) * m / (sqrt(v) + eps)
+                                                                state (m, v)    eps default 1e-8
+    (adam is lazy: torch.optim.SparseAdam's formula).  `state` tensors are fp32, contiguous, of the
+    table's shape, modified in place, and share no storage with the table or grad.  The scalars
+    are computed here in double and rounded once to fp32; `step` (>= 1) is the caller's count.
+    Rows no live id names keep their bits.  Returns `table`; the version counters of the table and
+    of every state tensor advance.  The same call gives the same bits; no host wait."""
+    name = "sparse_row_step"
+    if kind not in _ROW_STEP_KINDS:
+        raise ValueError("%s: kind is one of %s, not %r" % (name, ", ".join(_ROW_STEP_KINDS), kind))
+    if not torch.is_tensor(table) or table.dtype not in _DT:
+        raise ValueError("%s: table must be float32, bfloat16 or float16" % name)
+    if table.dim() != 2 or table.shape[0] < 1 or not table.is_contiguous():
+        raise ValueError("%s: table is a contiguous [rows, d] tensor, one row at least (it is modified in place)" % name)
+    if table.requires_grad and not table.is_leaf:
+        raise RuntimeError("%s: table is not a leaf: only a parameter (or a tensor without grad) is stepped in place"
+                           % name)
+    if ids.dtype.is_floating_point or ids.dtype == torch.bool:
+        raise ValueError("%s: ids are integers, not %s" % (name, ids.dtype))
+    flat = ids.to(torch.int64).reshape(-1).contiguous()
+    e, d = flat.numel(), table.shape[1]
+    if e >= 2 ** 31 or d >= 2 ** 31:
+        raise ValueError("%s: the number of ids and d must stay below 2^31" % name)
+    if not torch.is_tensor(grad) or grad.dim() != 2 or grad.shape[1] != d:
+        raise ValueError("%s: grad is [M, d] with the table's d" % name)
+    if grad.dtype != _F32 and grad.dtype != table.dtype:
+        raise ValueError("%s: grad is float32 or of the table's dtype (%s), not %s" % (name, table.dtype, grad.dtype))
+    if row_index is not None and count is not None:
+        raise ValueError("%s: pass row_index or count, not both" % name)
+    m = grad.shape[0]
+    if row_index is not None:
+        if row_index.dtype.is_floating_point or row_index.numel() != e:
+            raise ValueError("%s: row_index holds one integer per id" % name)
+        row_index = row_index.to(torch.int32).reshape(-1).contiguous()
+    elif count is not None:
+        count = int(count)
+        if count <= 0 or e % count != 0 or m != e // count:
+            raise ValueError("%s: count > 0 divides the number of ids and grad is [ids / count, d]" % name)
+    elif m != e:
+        raise ValueError("%s: grad holds one row per id (or pass row_index / count)" % name)
+    grad = grad.detach().contiguous()
+    state = tuple(state)
+    if len(state) != _ROW_STEP_STATES[kind]:
+        raise ValueError("%s: %s takes %d state tensor(s), not %d" % (name, kind, _ROW_STEP_STATES[kind], len(state)))
+    for n, s in enumerate(state):
+        if not torch.is_tensor(s) or s.dtype != _F32 or s.shape != table.shape:
+            raise ValueError("%s: state[%d] is a float32 tensor of the table's shape" % (name, n))
+        if not s.is_contiguous():
+            raise ValueError("%s: state[%d] is not contiguous (it is modified in place)" % (name, n))
+        if s.requires_grad:
+            raise RuntimeError("%s: state[%d] requires grad" % (name, n))
+        if _storage_overlap(s, table) or _storage_overlap(s, grad) or any(_storage_overlap(s, o) for o in state[:n]):
+            raise ValueError("%s: state[%d] shares storage with the table, grad or another state tensor" % (name, n))
+    _need_cuda(table, flat, grad, *state, *(() if row_index is None else (row_index,)))
+    if lr is None:
+        raise ValueError("%s: lr is required" % name)
+    if eps is None:
+        eps = {"adagrad": 1e-10, "adam": 1e-8}.get(kind, 0.0)
+    beta1, beta2 = betas
+    step = int(step)
+    if step < 1 or not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0):
+        raise ValueError("%s: step >= 1 and betas in [0, 1)" % name)
+    scalars = (float(lr), float(momentum), float(eps), 1.0 - beta1, 1.0 - beta2,
+               float(lr) * math.sqrt(1.0 - beta2 ** step) / (1.0 - beta1 ** step))
+    if not all(np.isfinite(x) and x >= 0 for x in scalars):
+        raise ValueError("%s: lr, momentum and eps are finite and not negative" % name)
+    with torch.no_grad(), _on(table.device):
+        check(lib().euler_gpu_sparse_optim_step(
+            _stream(), _ROW_STEP_KINDS[kind], _ptr(table), _DT[table.dtype], table.shape[0], d,
+            _ptr(state[0]) if len(state) > 0 else None, _ptr(state[1]) if len(state) > 1 else None, _ptr(flat), e,
+            _ptr(grad), _DT[grad.dtype], m, _ptr(row_index), count or 0, *scalars))
+        torch.autograd.graph.increment_version(table)
+        for s in state:
+            torch.autograd.graph.increment_version(s)
+    return table
 
 
 def scatter_softmax(updates, indices, size, out_dtype=None):

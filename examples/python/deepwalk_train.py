@@ -17,10 +17,11 @@ tensors over the rows that were looked up, for SparseAdam.  --composed runs the 
 softplus formulation in plain torch instead, for comparison.  The two tables are
 [max_id + 2, dim]: random_walk fills a walk that cannot go on with default_node = max_id + 1,
 which has a row of its own as in the reference.  --order 1 shares one table between target and
-context (LINE's first order, examples/line/line.py:52-53).
+context (LINE's first order, examples/line/line.py:52-53).  --fused-optimizer steps with
+euler_amd.optim.SparseAdam (one fused call per table) instead of torch.optim.SparseAdam.
 
     python examples/python/deepwalk_train.py [--data DIR] [--batch 1024] [--steps 20] [--dim 128]
-                                             [--composed] [--order 1|2]
+                                             [--composed] [--order 1|2] [--fused-optimizer]
 """
 import argparse
 import os
@@ -32,8 +33,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import euler_amd                                   # noqa: E402
-from euler_amd import euler_ops, ops               # noqa: E402
+from euler_amd import euler_ops, ops, optim        # noqa: E402
 from deepwalk_minibatch import to_sample           # noqa: E402
+from fused_optimizer_check import moved_only_looked_up_rows          # noqa: E402
 
 
 def composed_loss(target, context, src, pos, negs):
@@ -91,6 +93,8 @@ def main():
     ap.add_argument("--order", type=int, default=2, choices=[1, 2])
     ap.add_argument("--composed", action="store_true", help="the torch composition instead of ops.skipgram_loss")
     ap.add_argument("--nodes", type=int, default=200_000)
+    ap.add_argument("--fused-optimizer", action="store_true",
+                    help="euler_amd.optim.SparseAdam - one fused kernel per table - instead of torch.optim.SparseAdam")
     a = ap.parse_args()
     if a.data:
         euler_ops.initialize_graph({"mode": "local", "data_path": a.data})       # euler_ops/base.py
@@ -103,14 +107,18 @@ def main():
         max_id = a.nodes
     G.set_seed(42)
     target, context = make_tables(max_id, a.dim, a.order)
-    opt = torch.optim.SparseAdam([target] if context is target else [target, context], lr=a.lr)
+    params = [target] if context is target else [target, context]
+    opt = (optim.SparseAdam if a.fused_optimizer else torch.optim.SparseAdam)(params, lr=a.lr)
     mode = "composed" if a.composed else "fused"
     for step in range(a.steps):
         src, pos, negs = sample_step(a.batch, max_id, a.walk_len, a.num_negs)
         loss, rank, _ = loss_of(target, context, src, pos, negs, a.composed)
         opt.zero_grad()
         loss.backward()
+        before = [p.detach().clone() for p in params] if a.fused_optimizer and step == 0 else None
         opt.step()
+        if before is not None:
+            print("fused optimizer: %d rows moved, all of them looked up" % moved_only_looked_up_rows(params, before))
         print("step %d (%s, order %d): loss %.6f  mrr %.4f  pairs %d"
               % (step, mode, a.order, float(loss), float(ops.rank_metric("mrr", rank)), src.numel()))
         assert torch.isfinite(loss)

@@ -23,8 +23,10 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import euler_amd                                   # noqa: E402
-from euler_amd import ops                          # noqa: E402
+from euler_amd import ops, optim                   # noqa: E402
+from fused_optimizer_check import moved_only_looked_up_rows          # noqa: E402
 
 
 def ring_graph(n, vocab, seed):
@@ -58,13 +60,15 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--dim", type=int, default=16)
     ap.add_argument("--fanout", type=int, default=5)
+    ap.add_argument("--fused-optimizer", action="store_true",
+                    help="euler_amd.optim.SparseAdam - one fused kernel per table - instead of torch.optim.SparseAdam")
     a = ap.parse_args()
     torch.manual_seed(0)
     G = ring_graph(a.nodes, a.vocab, 1)
     G.set_seed(42)
     id_table = (torch.randn(a.nodes + 1, a.dim, device="cuda") * 0.1).requires_grad_(True)
     feat_table = (torch.randn(a.vocab, a.dim, device="cuda") * 0.1).requires_grad_(True)
-    opt_sparse = torch.optim.SparseAdam([feat_table], lr=0.01)
+    opt_sparse = (optim.SparseAdam if a.fused_optimizer else torch.optim.SparseAdam)([feat_table], lr=0.01)
     opt_dense = torch.optim.SGD([id_table], lr=0.01)
 
     roots = torch.randint(1, a.nodes + 1, (a.batch,), device="cuda")
@@ -85,6 +89,8 @@ def main():
     opt_dense.step()
     torch.cuda.synchronize()
     moved = int((feat_table.detach() != before).any(dim=1).sum())
+    if a.fused_optimizer:
+        print("fused optimizer: %d rows moved, all of them looked up" % moved_only_looked_up_rows([feat_table], [before]))
     print("ShallowEncoder step: %d roots x fanout %d, dim %d, loss %.6f; sparse gradient over %d of %d "
           "table rows, %d rows updated by SparseAdam"
           % (a.batch, a.fanout, a.dim, float(loss.detach()), rows_read, a.vocab, moved))

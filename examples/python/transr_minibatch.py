@@ -28,8 +28,10 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import euler_amd                                   # noqa: E402
-from euler_amd import ops                          # noqa: E402
+from euler_amd import ops, optim                   # noqa: E402
+from fused_optimizer_check import moved_only_looked_up_rows          # noqa: E402
 
 FIXTURE = os.path.join(ROOT, "tests", "golden", "fixture_dat")
 
@@ -100,6 +102,8 @@ def main():
     ap.add_argument("--ent-dim", type=int, default=32)
     ap.add_argument("--rel-dim", type=int, default=24)
     ap.add_argument("--margin", type=float, default=1.0)
+    ap.add_argument("--fused-optimizer", action="store_true",
+                    help="euler_amd.optim.SparseAdam - one fused kernel per table - instead of torch.optim.SparseAdam")
     ap.add_argument("--data", default=FIXTURE, help="a graph directory (euler.meta + .dat); default: the fixture graph")
     a = ap.parse_args()
     torch.manual_seed(0)
@@ -107,13 +111,17 @@ def main():
     G.set_seed(7)
     n_ent, n_rel = G.id_range()[0] + 1, G.num_edge_types          # row = node id / edge type
     tables = make_tables(n_ent, n_rel, a.ent_dim, a.rel_dim)
-    opt = torch.optim.SparseAdam(list(tables.values()), lr=0.01)
+    opt = (optim.SparseAdam if a.fused_optimizer else torch.optim.SparseAdam)(list(tables.values()), lr=0.01)
     src, rel_id, dst, neg = sample_batch(G, a.batch, a.negs)
     pos, scores = energies(tables, src, rel_id, dst, neg, a.kind, a.composed)
     loss = margin_loss(pos, scores, a.margin)
     opt.zero_grad()
     loss.backward()
+    before = [t.detach().clone() for t in tables.values()] if a.fused_optimizer else None
     opt.step()
+    if a.fused_optimizer:
+        print("fused optimizer: %d rows moved, all of them looked up"
+              % moved_only_looked_up_rows(list(tables.values()), before))
     rows = int(tables["ent"].grad.coalesce().indices().numel())
     mats = int(tables["matrix"].grad.coalesce().indices().numel())
     print("transr %s (%s): loss %.6f  rows updated %d of %d, matrices %d of %d"

@@ -1274,6 +1274,36 @@ int euler_gpu_store_add(void* stream, void* table_dev, int32_t table_dtype, int6
 int euler_gpu_store_take(void* stream, void* table_dev, int32_t table_dtype, int64_t rows,
                          int64_t d, const int64_t* ids_dev, int64_t e, int32_t clear,
                          void* out_dev, int32_t out_dtype);
+/* sparse_optim_step: ONE optimiser step - kind 0 sgd, 1 momentum, 2 adagrad, 3 adam, the four of
+ * the reference's tf_euler/python/utils/optimizers.py - on the rows of table_dev [rows, d] (fp32 /
+ * bf16 / fp16, contiguous) that ids_dev names, IN PLACE, from the gradient rows of the
+ * occurrences: no coalesce, no [distinct, d] temporary, no float atomics.  The contract, every
+ * formula included, is stated in euler_amd/csrc/sparse_optim.h.
+ * state0_dev / state1_dev: fp32 [rows, d], contiguous, modified in place - sgd: both NULL;
+ * momentum: the accumulator, NULL; adagrad: the sum of squares, NULL; adam: exp_avg, exp_avg_sq.
+ * ids_dev, grad_dev / grad_dtype / m, row_index_dev and count are values_dev & co. of store_add:
+ * an id outside [0, rows) names no row, the gradient row of occurrence p is grad[p],
+ * grad[row_index_dev[p]] or grad[p / count], grad is fp32 or the table's dtype.  Per distinct
+ * live id and column: g = the sum of its occurrences in increasing p (fp32, one rounding per add,
+ * starting from the first occurrence), then the step in correctly rounded fp32 operations, then
+ * ONE rounding to the table's dtype.  The same call gives the same bits, for every launch
+ * geometry.  The scalars are fp32 values the caller computed in double and rounded once: lr, mu
+ * (momentum), eps, om1 = 1 - beta1, om2 = 1 - beta2, step_size = lr * sqrt(1 - beta2^t) /
+ * (1 - beta1^t); those the kind does not use are ignored but checked.  Rows no live id names keep
+ * their bits in the table and the state.
+ * Only enqueues (three launches): no host wait; scratch is stream-ordered and released on every
+ * exit; every check precedes the first write, so an error leaves the table and the state
+ * untouched.  EULER_GPU_EINVAL: an unknown kind or dtype, a grad dtype that is neither fp32 nor
+ * the table's, a scalar that is negative or not finite, a state pointer missing for the kind or
+ * given where the kind has none, rows < 1, e or d >= 2^31 (or < 0), the count / row_index / m
+ * rules of store_add, a null required buffer, a buffer not aligned to its element type.  e == 0
+ * or d == 0 returns EULER_GPU_OK and touches nothing. */
+int euler_gpu_sparse_optim_step(void* stream, int32_t kind, void* table_dev, int32_t table_dtype,
+                                int64_t rows, int64_t d, float* state0_dev, float* state1_dev,
+                                const int64_t* ids_dev, int64_t e, const void* grad_dev,
+                                int32_t grad_dtype, int64_t m, const int32_t* row_index_dev,
+                                int64_t count, float lr, float mu, float eps, float om1, float om2,
+                                float step_size);
 /* gather_segment_topk: the step of the reference's LGCEncoder (LGCN,
  * tf_euler/python/utils/encoders.py:911-914: get_dense_feature, reshape [B, nb, d], transpose,
  * tf.nn.top_k, transpose) in one pass - for every destination r and every column c the k largest
