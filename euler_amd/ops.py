@@ -771,6 +771,219 @@ def edge_dot(a, a_index, b, b_index, heads=1, out_dtype=None):
     return _EdgeDot.apply(a, a_index, b, b_index, heads, out_dtype)
 
 
+# ---- GCN-normalised aggregation (norm_i * norm_j * x_j) -----------------------------------------
+def _gcn_edges(name, edge_index, size, seg_ptr, count):
+    """the edge arguments of gcn_norm / gcn_aggregate -> (dst keys | None, src, seg_ptr | None, count,
+    n_dst, n_src): destinations by key (edge_index is [2, E] or a pair (dst, src)) or by segment
+    (edge_index is the source column, with seg_ptr or count)"""
+    try:
+        n_dst, n_src = (int(s) for s in size)
+    except (TypeError, ValueError):
+        raise ValueError("%s: size is (n_dst, n_src)" % name)
+    if n_dst < 0 or n_src < 0:
+        raise ValueError("%s: size is (n_dst, n_src), both >= 0" % name)
+    if seg_ptr is not None and count is not None:
+        raise ValueError("%s: pass seg_ptr or count, not both" % name)
+    pair = isinstance(edge_index, (tuple, list)) or edge_index.dim() == 2
+    segmented = seg_ptr is not None or count is not None
+    if pair and segmented:
+        raise ValueError("%s: destinations come as keys (edge_index [2, E]) or as seg_ptr / count with "
+                         "the source column alone, not both" % name)
+    if not pair and not segmented:
+        raise ValueError("%s: a source column alone needs seg_ptr or count" % name)
+    if pair:
+        if len(edge_index) != 2:
+            raise ValueError("%s: edge_index is [2, E] or (dst, src)" % name)
+        dst, src = edge_index[0], edge_index[1]
+        if dst.dim() != 1 or src.dim() != 1 or dst.numel() != src.numel():
+            raise ValueError("%s: one destination and one source per edge" % name)
+    else:
+        dst, src = None, edge_index
+        if src.dim() != 1:
+            raise ValueError("%s: the source column is [E]" % name)
+    for t in (dst, src):
+        if t is not None and (t.dtype.is_floating_point or t.dtype == torch.bool):
+            raise ValueError("%s: indices are integers, not %s" % (name, t.dtype))
+    if dst is not None:
+        dst = dst.to(torch.int32).contiguous()
+    src = src.to(torch.int32).contiguous()
+    _need_cuda(src)
+    if src.numel() >= 2 ** 31:
+        raise ValueError("%s: fewer than 2^31 edges" % name)
+    sp = None
+    if seg_ptr is not None:
+        sp = seg_ptr.to(torch.int64).contiguous()
+        _need_cuda(sp)
+        if sp.numel() != n_dst + 1:
+            raise ValueError("%s: seg_ptr has n_dst + 1 entries" % name)
+        count = 0
+    elif count is not None:
+        count = int(count)
+        if count < 1:
+            raise ValueError("%s: count >= 1" % name)
+        if src.numel() != n_dst * count:
+            raise ValueError("%s: n_dst * count source indices (%d), not %d" % (name, n_dst * count, src.numel()))
+    else:
+        _need_cuda(dst)
+        count = 0
+    return dst, src, sp, count, n_dst, n_src
+
+
+def _gcn_dst(name, dst, src, sp, count, n_dst):
+    """the destination key of every edge; a segmented block's are built (_segment_dst)"""
+    if dst is not None:
+        return dst
+    dst = _segment_dst(sp, count, n_dst, src.device)
+    if dst.numel() != src.numel():
+        raise ValueError("%s: seg_ptr must span the %d source indices, not %d" % (name, src.numel(), dst.numel()))
+    return dst
+
+
+def _gcn_norm_raw(dst, src, n_dst, n_src):
+    norm_dst = torch.empty(n_dst, dtype=_F32, device=src.device)
+    norm_src = torch.empty(n_src, dtype=_F32, device=src.device)
+    with _on(src.device):
+        check(lib().euler_gpu_gcn_norm(_stream(), _ptr(dst), _ptr(src), src.numel(), n_dst, n_src,
+                                       _ptr(norm_dst), _ptr(norm_src)))
+    return norm_dst, norm_src
+
+
+def gcn_norm(edge_index, size, seg_ptr=None, count=None):
+    """(norm_dst [n_dst], norm_src [n_src]) of a block, fp32: norm = 1 / sqrt(degree), the symmetric
+    normalisation of GCN / APPNP / SGCN / TAG / ARMA / DNA (gcn_conv.py:33-51), the degree of a node
+    being the number of the block's edges at it on its side.  edge_index is [2, E] or a pair
+    (dst, src) - row 0 the destinations, as Block.edge_index - and size = (n_dst, n_src); with
+    seg_ptr or count (the forms of gather_segment_reduce) edge_index is the source column alone.
+    An edge counts iff both its indices are in range; a node without an edge gets 0, not inf (it
+    is never multiplied into anything).  A histogram with integer atomics (euler_gpu_gcn_norm): no
+    sort, no host wait, the same bits on every call - those of numpy's
+    float32(1) / sqrt(float32(deg)).  No gradient flows through the tables."""
+    dst, src, sp, count, n_dst, n_src = _gcn_edges("gcn_norm", edge_index, size, seg_ptr, count)
+    dst = _gcn_dst("gcn_norm", dst, src, sp, count, n_dst)
+    return _gcn_norm_raw(dst, src, n_dst, n_src)
+
+
+def _gather_reduce_norm_raw(mode, x, gi, si, sp, count, size, norm_dst, norm_src, root, agg_scale, root_scale,
+                            od):
+    """euler_gpu_gather_reduce_norm_t on checked, contiguous tensors -> [size, D] of dtype od"""
+    rows, d = x.shape
+    out = torch.empty((size, d), dtype=od, device=x.device)
+    with _on(x.device):
+        check(lib().euler_gpu_gather_reduce_norm_t(
+            _stream(), mode, _ptr(x), _DT[x.dtype], rows, _ptr(gi), _ptr(si), _ptr(sp), int(count), gi.numel(), d,
+            size, _ptr(norm_dst), _ptr(norm_src), _ptr(root), _DT[root.dtype] if root is not None else _lib.F32,
+            float(agg_scale), float(root_scale), _ptr(out), _DT[od]))
+    return out
+
+
+class _GcnAggregate(torch.autograd.Function):
+    """gcn_aggregate.  grad_x is the same entry with the roles swapped: rows of G (grad * agg_scale;
+    for mean divided by count + 1e-7, as _weighted_backward) gathered by dst and scattered by src,
+    the two norm tables exchanged - the operand pairs and the stable grouping by src of the
+    composition's gradient, so its bits.  A destination key outside the block gathers nothing (the
+    entry gives such an update the weight 0)."""
+
+    @staticmethod
+    def forward(ctx, x, root, dst, src, sp, count, n_dst, norm_dst, norm_src, op, agg_scale, root_scale, od):
+        out = _gather_reduce_norm_raw(_GS_MODE[op], x, src, dst, sp, count, n_dst, norm_dst, norm_src, root,
+                                      agg_scale, root_scale, od)
+        ctx.save_for_backward(src, norm_dst, norm_src, *[t for t in (dst, sp) if t is not None])
+        ctx.has = (dst is not None, sp is not None)
+        ctx.args = (count, n_dst, x.shape[0], op, agg_scale, root_scale, x.dtype,
+                    root.dtype if root is not None else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        src, norm_dst, norm_src = ctx.saved_tensors[:3]
+        rest = list(ctx.saved_tensors[3:])
+        dst = rest.pop(0) if ctx.has[0] else None
+        sp = rest.pop(0) if ctx.has[1] else None
+        count, n_dst, n_src, op, agg_scale, root_scale, x_dtype, root_dtype = ctx.args
+        g32 = grad.float().contiguous()
+        grad_x = grad_root = None
+        if ctx.needs_input_grad[0]:
+            g = g32 if agg_scale == 1.0 else g32 * agg_scale
+            keys = _gcn_dst("gcn_aggregate", dst, src, sp, count, n_dst)
+            if op == "mean":
+                if dst is not None:
+                    cnt = _count(dst, n_dst, g.device)
+                elif sp is not None:
+                    cnt = (sp[1:] - sp[:-1]).to(_F32).reshape(-1, 1) + 1e-7
+                else:
+                    cnt = torch.full((n_dst, 1), float(count), dtype=_F32, device=g.device) + 1e-7
+                g = g / cnt
+            grad_x = _gather_reduce_norm_raw(_ADD, g.contiguous(), keys, src, None, 0, n_src, norm_src, norm_dst,
+                                             None, 1.0, 1.0, _F32).to(x_dtype)
+        if root_dtype is not None and ctx.needs_input_grad[1]:
+            grad_root = (g32 if root_scale == 1.0 else g32 * root_scale).to(root_dtype)
+        return (grad_x, grad_root) + (None,) * 11
+
+
+def gcn_aggregate(x, edge_index, size, norm=None, op="add", root=None, alpha=None, root_scale=None,
+                  seg_ptr=None, count=None, out_dtype=None, validate=False):
+    """The aggregation of GCNConv / SGCNConv / TAGConv (op "add"), DNAConv (op "mean"), and with a
+    root term a whole APPNPConv / ARMAConv step, in one pass (euler_gpu_gather_reduce_norm_t):
+        out[i] = reduce over the edges (i, j) of norm_dst[i] * norm_src[j] * x[j]
+    x is the source-side table [n_src, D] (fp32 / bf16 / fp16), size = (n_dst, n_src), edge_index
+    [2, E] or a pair (dst, src); with seg_ptr or count edge_index is the source column alone (see
+    gcn_norm).  norm is gcn_norm's pair of tables (fp32); None computes them here, once, and keeps
+    them for the backward pass.  The weight norm_dst[i] * norm_src[j], the message and the sum are
+    separate fp32 roundings in input order: the bits of
+    gather_scatter(op, x, src, dst, n_dst, edge_weight=norm_dst[dst] * norm_src[src]) without the
+    [E] weight, its two gathers and its multiply.  mean divides by (edges of i + 1e-7).
+    root ([n_dst, D], the dtype of x or fp32) adds the destination's own row in the same pass:
+    out = agg * a + root * b, three fp32 roundings before the one to out_dtype.  alpha is shorthand
+    for (a, b) = (1 - alpha, alpha) (appnp_conv.py:57-60); root without alpha uses (1, 1)
+    (arma_conv.py:72-75); root_scale overrides b.
+    An edge whose destination is outside [0, n_dst) or whose source is outside [0, n_src) contributes
+    nothing, and its gradient is exactly 0; validate=True checks the source indices first (one
+    host wait).  out_dtype as gather_scatter.  Gradients flow to x and root (the same fused entry
+    with the roles swapped: no [E] or [E, D] tensor in either direction), none through norm."""
+    if op not in ("add", "mean"):
+        raise ValueError("gcn_aggregate: op is add or mean")
+    _dt("gcn_aggregate", x)
+    od = _out_dt("gcn_aggregate", x, out_dtype)
+    dst, src, sp, count, n_dst, n_src = _gcn_edges("gcn_aggregate", edge_index, size, seg_ptr, count)
+    _need_cuda(x)
+    if x.dim() != 2 or x.shape[0] != n_src:
+        raise ValueError("gcn_aggregate: x is the source-side table [n_src, D]")
+    if op == "mean" and src.numel() >= (1 << 24):
+        raise ValueError("gcn_aggregate: a mean needs fewer than 2^24 edges")
+    if validate:
+        _check_rows("gcn_aggregate", src, n_src)
+    if norm is None:
+        norm = _gcn_norm_raw(_gcn_dst("gcn_aggregate", dst, src, sp, count, n_dst), src, n_dst, n_src)
+    norm_dst, norm_src = norm
+    for t, n, side in ((norm_dst, n_dst, "norm_dst"), (norm_src, n_src, "norm_src")):
+        if t.dtype != _F32:
+            raise TypeError("gcn_aggregate: %s is float32, not %s" % (side, t.dtype))
+        if t.dim() != 1 or t.numel() != n:
+            raise ValueError("gcn_aggregate: %s has %d entries, not %s" % (side, n, tuple(t.shape)))
+        _need_cuda(t)
+    agg_scale, b = 1.0, 1.0
+    if alpha is not None:
+        if root is None:
+            raise ValueError("gcn_aggregate: alpha needs root")
+        agg_scale, b = 1.0 - float(alpha), float(alpha)
+    if root_scale is not None:
+        if root is None:
+            raise ValueError("gcn_aggregate: root_scale needs root")
+        b = float(root_scale)
+    if root is not None:
+        if root.dtype != _F32 and root.dtype != x.dtype:
+            raise TypeError("gcn_aggregate: root is float32 or the dtype of x (%s), not %s" % (x.dtype, root.dtype))
+        if root.dim() != 2 or tuple(root.shape) != (n_dst, x.shape[1]):
+            raise ValueError("gcn_aggregate: root is [n_dst, D] = %s, not %s"
+                             % ((n_dst, x.shape[1]), tuple(root.shape)))
+        _need_cuda(root)
+        root = root.contiguous()
+        # the scales as the fp32 numbers the kernel multiplies by
+        agg_scale, b = float(np.float32(agg_scale)), float(np.float32(b))
+    return _GcnAggregate.apply(x.contiguous(), root, dst, src, sp, count, n_dst, norm_dst.detach().contiguous(),
+                               norm_src.detach().contiguous(), op, agg_scale, b, od)
+
+
 # ---- fused softmax over the updates of a destination ------------------------------------------
 def _edge_softmax_raw(x2, grad2, si, sp, count, size, od):
     """euler_gpu_edge_softmax (grad2 None) / euler_gpu_edge_softmax_grad (x2 = the forward's

@@ -937,6 +937,53 @@ int euler_gpu_edge_dot_t(void* stream, const void* a_dev, int32_t a_dtype,
                          const int32_t* a_index_dev, const void* b_dev, int32_t b_dtype,
                          const int32_t* b_index_dev, int64_t e, int64_t d, int32_t heads,
                          void* out_dev, int32_t out_dtype);
+/* gcn_norm: the two tables of the symmetric degree normalisation of GCN / APPNP / SGCN / TAG /
+ * ARMA / DNA (gcn_conv.py:33-51: norm = deg ** -0.5 on both sides of a block).  dst_keys_dev and
+ * src_keys_dev are int32 [e]; an edge counts if and only if BOTH keys are in range (dst in
+ * [0, size_dst), src in [0, size_src)): an edge the reduce below leaves out changes nobody's
+ * degree.  norm_dst_out_dev [size_dst] and norm_src_out_dev [size_src] get
+ * 1 / sqrt((float)deg) - a correctly rounded fp32 square root and a correctly rounded fp32 divide:
+ * the bits of numpy's float32(1) / sqrt(float32(deg)) - and exactly 0 where deg == 0 (the
+ * reference's inf there is never multiplied into anything; 0 keeps the tables finite).  The
+ * degrees are counted with int32 atomics into stream-ordered scratch: no grouping of the keys, no
+ * sort, no host wait, and the same bits on every call.  One kernel writes both tables: both or
+ * neither.  EULER_GPU_EINVAL: a negative shape, a null buffer, e >= 2^31, a buffer that is not
+ * 4-byte aligned.  size_dst == 0 and size_src == 0 returns EULER_GPU_OK and touches nothing. */
+int euler_gpu_gcn_norm(void* stream, const int32_t* dst_keys_dev, const int32_t* src_keys_dev,
+                       int64_t e, int32_t size_dst, int32_t size_src, float* norm_dst_out_dev,
+                       float* norm_src_out_dev);
+/* gather_reduce_norm: the weighted fused reduce above whose weight is formed from two node
+ * tables instead of read from an [e] array:
+ *   out[r][c] = reduce over the updates p of r, in input order, of
+ *               fl(x[g(p)][c] * fl(norm_dst[r] * norm_src[g(p)])),   g = gather_indices_dev
+ * - three separate fp32 roundings, in the order of norm_i * norm_j * x_j: the bits of
+ * euler_gpu_gather_scatter_w_t with w[p] = norm_dst[dst[p]] * norm_src[g(p)] (fp32).  mode is 0
+ * (add) or 2 (mean: divided by segment length + 1e-7f); max is refused.  x_dev is [rows, d] in
+ * fp32 / bf16 / fp16, the norm tables are fp32 ([size] and [rows]), out_dtype is fp32 or in_dtype
+ * (one rounding at the store).  The destinations come in exactly one of the three forms of
+ * euler_gpu_edge_softmax (indices_dev, seg_ptr_dev, count > 0); e is the number of gather indices.
+ * An update whose gather index lies outside [0, rows) contributes nothing: weight 0, row clamped
+ * to the last one - for finite tables every bit of the result is that of the reduce without it
+ * (euler_amd/csrc/mp_gcn.h).  A backward pass can therefore gather by a destination key that is
+ * out of range, without an appended zero row.
+ * root_dev (NULL: no epilogue, the scales are not read) is [size, d] in root_dtype (fp32 or
+ * in_dtype): out = fl(fl(agg * agg_scale) + fl(root[r] * root_scale)), formed in fp32 before the
+ * one rounding to out_dtype - APPNP's (1 - alpha, alpha), ARMA's (1, 1).
+ * 16-byte-aligned x, root and out with the vector shapes of the weighted entries take the
+ * 16-byte-lane kernels.  EULER_GPU_EINVAL, in this order: an unknown dtype, out_dtype / root_dtype
+ * neither fp32 nor in_dtype; mode not 0 or 2; a negative shape, not exactly one segment form, count
+ * with e != size * count; (size == 0 or d == 0 returns EULER_GPU_OK and touches nothing;) a null
+ * buffer - out and norm_dst whenever there is a destination; x, the gather indices and norm_src when
+ * e > 0 and rows > 0 (an empty table may be null: nothing of it is read); e or rows >= 2^31; mean
+ * with e (keys, seg_ptr) or count >= 2^24; a buffer not aligned to its type.  A refused call writes
+ * nothing. */
+int euler_gpu_gather_reduce_norm_t(void* stream, int32_t mode, const void* x_dev, int32_t in_dtype,
+                                   int64_t rows, const int32_t* gather_indices_dev,
+                                   const int32_t* indices_dev, const int64_t* seg_ptr_dev,
+                                   int64_t count, int64_t e, int64_t d, int32_t size,
+                                   const float* norm_dst_dev, const float* norm_src_dev,
+                                   const void* root_dev, int32_t root_dtype, float agg_scale,
+                                   float root_scale, void* out_dev, int32_t out_dtype);
 /* edge_softmax: the softmax of the [e, heads] logits over the updates of every destination -
  * what GATConv and AGNNConv run between the logit and the aggregate (gat_conv.py:66-72), the
  * reference's scatter_softmax (tf_euler/python/euler_ops/mp_ops.py:76-79) - in one read and one
