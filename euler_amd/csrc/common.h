@@ -465,4 +465,11 @@ inline int GridFor(int64_t work_items, int block) {
   return (int)blocks;
 }
 
+// The largest item count a grid-stride loop with a uint32_t counter may cover on a GridFor
+// grid of `block` threads: past it, `s += stride` of the last pass wraps below `total` and the
+// loop never ends.  (stride <= 4096 * block.)
+inline int64_t GridForU32Limit(int block) {
+  return 0xffffffffLL - 256LL * 16 * block;
+}
+
 }  // namespace euler_gpu

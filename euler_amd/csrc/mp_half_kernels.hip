@@ -636,7 +636,7 @@ int euler_gpu_get_dense_feature_t(const euler_gpu_graph* g, void* stream, const 
     const bool out16 = out_dtype != EULER_GPU_F32;
     const bool vec8 = v.feat_uniform && fid >= 0 && fid < v.n_float && dim % 8 == 0 &&
                       g->feat_slot_aligned8 && ((uintptr_t)out_dev % 16 == 0) &&
-                      n * (int64_t)(dim / 8) < 0xffffffffLL;
+                      n * (int64_t)(dim / 8) < GridForU32Limit(block);  // its loop counts in uint32_t
     const uint16_t* t16 = static_cast<const uint16_t*>(g->feat16);
     if (vec8) {
       const dim3 vgrid(GridFor(n * (int64_t)(dim / 8), block));

@@ -1084,7 +1084,8 @@ int euler_gpu_get_dense_feature(const euler_gpu_graph* g, void* stream,
   const GraphView& v = g->view;
   const bool vec4 = g_feature_vec4 != 0 && v.feat_uniform && fid >= 0 && fid < v.n_float && dim % 4 == 0 &&
                     v.feat_stride % 4 == 0 && g->feat_slot_aligned &&
-                    ((uintptr_t)out_dev % 16 == 0) && n * (int64_t)(dim / 4) < 0xffffffffLL;
+                    ((uintptr_t)out_dev % 16 == 0) &&
+                    n * (int64_t)(dim / 4) < GridForU32Limit(block);  // its loop counts in uint32_t
   if (vec4) {
     hipLaunchKernelGGL(DenseFeatureVec4Kernel, dim3(GridFor(n * (int64_t)(dim / 4), block)),
                        dim3(block), 0, (hipStream_t)stream, v, nodes_dev, n, fid, dim / 4,
