@@ -4,7 +4,11 @@
 // read.  The HOST forms are plain integer C++ (tests/csrc/half_cvt_check.cc pins them against
 // torch's CPU conversions); the DEVICE forms are casts the compiler lowers to the gfx950
 // convert instructions (v_cvt_pk_bf16_f32, v_cvt_f16_f32, v_cvt_f32_f16), which round the same
-// way - finite values and infinities have the same bits on both sides.
+// way - finite values and infinities have the same bits on both sides, and a NaN comes out
+// quiet with its sign.  tests/test_half_cvt_gpu.py pins the device forms against the same CPU
+// conversions on the same patterns (tests/half_edges.py: every 16-bit pattern widened; ties,
+// subnormals of both formats, overflow, inf and NaN narrowed), and
+// tests/test_half_store_edges_gpu.py every op's own 16-bit store at those edges.
 // No HIP header is needed: a host-only program may include this file on its own.
 #pragma once
 

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from conftest import ROOT
+from half_edges import classes, edge_bits, narrow_set
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 u16p, f32p = C.POINTER(C.c_uint16), C.POINTER(C.c_float)
@@ -78,43 +79,12 @@ def test_every_16_bit_pattern_widens_to_torchs_float(HCV, dtype):
         assert np.array_equal(got.view(np.uint32)[nan] >> 31, (bits[nan] >> 15).astype(np.uint32))
 
 
-def _edge_bits(dtype):
-    """fp32 bit patterns around every rounding decision of the format"""
-    out = [0x00000000, 0x80000000, 0x7f800000, 0xff800000, 0x7fc00000, 0xffc00000, 0x7f800001,
-           0xff800001, 0x7fffffff, 0x00000001, 0x80000001, 0x007fffff, 0x00800000, 0x7f7fffff,
-           0xff7fffff]
-    drop = 16 if dtype == torch.bfloat16 else 13          # mantissa bits that leave
-    half = 1 << (drop - 1)
-    for base in (0x3f800000, 0x3f810000, 0x40490000, 0xbf800000, 0xc2f70000, 0x00800000, 0x3effe000):
-        base &= ~((1 << drop) - 1)
-        for odd in (0, 1):                                  # ties towards an even and an odd neighbour
-            b = base + (odd << drop)
-            out += [b + half, b + half - 1, b + half + 1, b, b + (1 << drop) - 1]
-    if dtype == torch.bfloat16:
-        # the largest finite bf16 is 0x7f7f: 0x7f7f7fff stays, 0x7f7f8000 is the first to reach inf
-        out += [0x7f7f0000, 0x7f7f7fff, 0x7f7f8000, 0x7f7f8001, 0xff7f7fff, 0xff7f8000]
-    else:
-        # 65504 = 0x477fe000 is the largest finite fp16; 65520 = 0x477ff000 the first to reach inf
-        out += [0x477fe000, 0x477fefff, 0x477ff000, 0x477ff001, 0x47800000, 0xc77fefff, 0xc77ff000,
-                0x4b000000, 0x7f000000]
-        # subnormal range: 2^-14 = 0x38800000 (smallest normal), 2^-24 = 0x33800000 (smallest
-        # subnormal), 2^-25 = 0x33000000 (its tie with zero)
-        for b in (0x38800000, 0x387fffff, 0x387fe000, 0x387ff000, 0x387ff001, 0x38000000, 0x33800000,
-                  0x33000000, 0x33000001, 0x32ffffff, 0x33c00000, 0x33bfffff, 0x33c00001, 0x34200000,
-                  0x34600000, 0x32000000, 0x37000000, 0x37001000, 0x37003000):
-            out += [b, b | 0x80000000]
-        rng = np.random.default_rng(5)
-        sub = rng.integers(0x32800000, 0x38900000, 4096, dtype=np.int64)      # 2^-26 .. 2^-14
-        out += sub.tolist() + (sub | 0x80000000).tolist()
-    return np.array(out, dtype=np.uint32)
-
-
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 def test_narrowing_equals_torchs_to(HCV, dtype):
-    rng = np.random.default_rng(20)
-    rand = rng.integers(0, 1 << 32, 1 << 20, dtype=np.uint64).astype(np.uint32)
-    f_bits = np.concatenate([_edge_bits(dtype), rand])
-    f_bits = np.concatenate([f_bits, np.zeros((-f_bits.size) % 8, np.uint32)])
+    # the edge list, 2^20 uniform patterns, 2^18 with a uniform binade, 2^14 exact ties with their
+    # fp32 neighbours (a multiple of 8 patterns)
+    f_bits = narrow_set(dtype)
+    assert f_bits[:edge_bits(dtype).size].tolist() == edge_bits(dtype).tolist() and f_bits.size % 8 == 0
     want = _torch_narrow(dtype, f_bits)
     exp_mask, man_mask = (0x7f80, 0x007f) if dtype == torch.bfloat16 else (0x7c00, 0x03ff)
     want_nan = ((want & exp_mask) == exp_mask) & ((want & man_mask) != 0)
@@ -138,3 +108,15 @@ def test_round_trip_is_the_identity_on_16_bit_values(HCV, dtype):
     keep = ~np.isnan(wide)
     back = _narrow(HCV, "hcv_narrow", dtype, wide.view(np.uint32))
     assert np.array_equal(back[keep], bits[keep])
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_the_patterns_reach_every_class(dtype):
+    """A condition on the INPUTS, against the CPU reference alone: the set every narrowing path is
+    checked on (here and on the GPU) holds at least 1000 results of each class.  bf16 alone has
+    few finite values that round to inf - the edge list, the ties at the top binade and what the
+    uniform draws give - and needs 10."""
+    got = classes(narrow_set(dtype), dtype)
+    for name in ("normal", "subnormal", "zero", "nan", "tie"):
+        assert got[name] >= 1000, (name, got)
+    assert got["to_inf"] >= (10 if dtype == torch.bfloat16 else 1000), got
