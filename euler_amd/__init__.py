@@ -8,4 +8,5 @@ from .graph import Graph, synth_params            # noqa: F401
 from . import ops                                 # noqa: F401
 from . import dataflow                            # noqa: F401
 from . import optim                               # noqa: F401
+from . import metrics                             # noqa: F401
 from .euler_ops import *                          # noqa: F401,F403

@@ -70,3 +70,11 @@ def sparse_feature_embedding(nodes, feature_names, tables, combiner="sum", defau
     g = base.get_default_graph()
     return g.sparse_feature_embedding(nodes, _slots(g, feature_names, "sparse", False), tables, combiner,
                                       default_values, out_dtype, sparse_grad)
+
+
+def supervise_loss(nodes, logits, label_name, label_dim, metric=None, return_prob=False):
+    """SuperviseModel.__call__ after out_fc (mp_utils/base.py:35-47) on the default graph: the mean
+    sigmoid cross-entropy of logits [n, label_dim] against the dense feature `label_name` of the
+    nodes, read straight from the feature table, plus a streaming metric: Graph.supervise_loss."""
+    g = base.get_default_graph()
+    return g.supervise_loss(nodes, logits, _slots(g, [label_name], "dense", False)[0], label_dim, metric, return_prob)

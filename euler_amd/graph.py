@@ -1019,6 +1019,20 @@ class Graph:
                 outs.append(out)
         return outs
 
+    def supervise_loss(self, nodes, logits, label_fid, label_dim, metric=None, return_prob=False):
+        """SuperviseModel.__call__ after out_fc (tf_euler/python/mp_utils/base.py:35-47) in one
+        kernel: nodes [B] int64 and logits [B, label_dim] -> the mean sigmoid cross-entropy against
+        the float feature slot label_fid of the nodes, read straight from the feature table with
+        get_dense_feature's semantics (an unknown node or slot: zeros; a slot shorter than
+        label_dim: zero filled; a longer one: truncated; a 16-bit table: widened) - no [B, C]
+        label block is built.  metric, return_prob, the arithmetic and the gradient:
+        ops.supervise_loss."""
+        from . import ops
+        nodes = _as_i64_cuda(nodes, self.device).reshape(-1)
+        if logits.dim() != 2 or logits.shape[0] != nodes.numel() or logits.shape[1] != int(label_dim):
+            raise ValueError("supervise_loss: logits is [len(nodes), label_dim]")
+        return ops._supervise_call("supervise_loss", logits, None, self, nodes, int(label_fid), metric, return_prob)
+
     def num_u64_features(self):
         return lib().euler_gpu_graph_num_u64_features(self._h)
 

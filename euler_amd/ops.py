@@ -2054,6 +2054,103 @@ def rank_metric(name, rank):
     return (r < float(name[3:])).to(torch.float64).mean()
 
 
+# ---- the supervised loss head (tf_euler/python/mp_utils/base.py:24-47) -------------------------
+
+_SV_SCRATCH = {}
+
+
+def _supervise_scratch(device):
+    """counters of a call without a metric: added to and never read, one block per device"""
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    if key not in _SV_SCRATCH:
+        _SV_SCRATCH[key] = torch.zeros(5, dtype=torch.int64, device=device)
+    return _SV_SCRATCH[key]
+
+
+def _supervise_loss_raw(logits, labels, graph, nodes, fid, counts, hist, thresholds, want_prob, want_diff):
+    """euler_gpu_supervise_loss on prepared tensors -> (loss [1], prob [B, C] | None, diff [B, C] |
+    None, row_loss [B]); counts [5] and hist [2, T + 1] | None (int64) are added to"""
+    b, c, dev = logits.shape[0], logits.shape[1], logits.device
+    loss, row_loss = torch.empty(1, dtype=_F32, device=dev), torch.empty(b, dtype=_F32, device=dev)
+    prob = torch.empty((b, c), dtype=_F32, device=dev) if want_prob else None
+    diff = torch.empty((b, c), dtype=_F32, device=dev) if want_diff else None
+    with _on(dev):
+        check(lib().euler_gpu_supervise_loss(
+            _stream(), _ptr(logits), _DT[logits.dtype], b, c, _ptr(labels), _DT[labels.dtype] if labels is not None else 0,
+            graph._h if graph is not None else None, _ptr(nodes), int(fid), int(thresholds), _ptr(prob), _ptr(diff),
+            _ptr(row_loss), _ptr(loss), _ptr(counts), _ptr(hist)))
+    return loss, prob, diff, row_loss
+
+
+def _supervise_loss_grad_raw(diff, g, dtype):
+    """euler_gpu_supervise_loss_grad -> the gradient of the logits [B, C] in `dtype`"""
+    b, c = diff.shape
+    out = torch.empty((b, c), dtype=dtype, device=diff.device)
+    g = g.to(_F32).reshape(1).contiguous()
+    with _on(diff.device):
+        check(lib().euler_gpu_supervise_loss_grad(_stream(), _ptr(diff), _ptr(g), b, c, _ptr(out), _DT[dtype]))
+    return out
+
+
+class _SuperviseLoss(torch.autograd.Function):
+    """The fused head: the forward keeps diff = p - z only when the logits need a gradient, and the
+    backward is one kernel on it.  prob carries no gradient; the labels get none."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, graph, nodes, fid, metric, return_prob):
+        need = ctx.needs_input_grad[0]
+        if metric is not None:
+            counts, hist, t = metric._buffers(logits.device)
+        else:
+            counts, hist, t = _supervise_scratch(logits.device), None, 0
+        loss, prob, diff, _ = _supervise_loss_raw(logits, labels, graph, nodes, fid, counts, hist, t, return_prob, need)
+        if need:
+            ctx.save_for_backward(diff)
+        ctx.dtype = logits.dtype
+        if prob is not None:
+            ctx.mark_non_differentiable(prob)
+        return loss.reshape(()), prob
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_prob):
+        diff, = ctx.saved_tensors
+        return _supervise_loss_grad_raw(diff, g_loss, ctx.dtype), None, None, None, None, None, None
+
+
+def _supervise_call(name, logits, labels, graph, nodes, fid, metric, return_prob):
+    _dt(name, logits)
+    if logits.dim() != 2 or logits.shape[1] < 1:
+        raise ValueError("%s: logits is [B, C], C >= 1" % name)
+    _need_cuda(logits)
+    if logits.numel() >= 2 ** 31:
+        raise ValueError("%s: B * C must stay below 2^31" % name)
+    if metric is not None and not hasattr(metric, "_buffers"):
+        raise TypeError("%s: metric is a metrics.Streaming object (f1, acc or auc)" % name)
+    loss, prob = _SuperviseLoss.apply(logits.contiguous(), labels, graph, nodes, fid, metric, bool(return_prob))
+    return (loss, prob) if return_prob else loss
+
+
+def supervise_loss(logits, labels, metric=None, return_prob=False):
+    """The loss head of the supervised models in one pass (the reference's SuperviseModel.__call__
+    after out_fc, mp_utils/base.py:24-47; SuperviseSolution; GraphModel): logits [B, C] and labels
+    [B, C] (fp32, bf16 or fp16 each; soft labels allowed) -> the mean over all B * C elements of
+    tf.nn.sigmoid_cross_entropy_with_logits, a 0-d fp32 tensor, or (loss, prob [B, C] fp32 =
+    sigmoid(logits)) with return_prob.  metric: a metrics.Streaming object ("f1", "acc" or "auc")
+    whose device counters the same kernel adds to - the prediction is floor(p + 0.5) in fp32, the
+    AUC buckets are those of tf.metrics.auc's threshold table; no host wait, and metric.value() is a
+    device tensor.  All arithmetic is fp32 in a fixed order (euler_amd/csrc/supervise.h): the same
+    call returns the same bits.  The logits receive the gradient g / (B C) * (p - labels), rounded
+    once to their dtype, from one kernel on p - labels, which the forward keeps only when the
+    logits require a gradient; the labels receive none.  NaN logits are outside the contract.
+    Graph.supervise_loss reads the labels straight from a graph's feature table instead."""
+    name = "supervise_loss"
+    _dt(name, labels)
+    if labels.shape != logits.shape:
+        raise ValueError("%s: labels has the shape of logits, [B, C]" % name)
+    _need_cuda(labels)
+    return _supervise_call(name, logits, labels.detach().contiguous(), None, None, 0, metric, return_prob)
+
+
 # ---- in-place embedding stores (tf_euler/python/utils/embedding.py:24-68) ---------------------
 # The stores of ScalableSageEncoder / ScalableGCNEncoder (utils/encoders.py:629-748, 294-409): a
 # non-trainable [max_id + 1, d] table per layer that lives in HBM across steps and is changed IN

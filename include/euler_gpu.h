@@ -1287,6 +1287,45 @@ int euler_gpu_skipgram_loss_grad(void* stream, const void* target_dev, int32_t t
                                  const int64_t* neg_dev, int64_t b, int64_t p, int64_t k,
                                  int64_t d, const float* logits_dev, const float* g_dev,
                                  float* g_src_dev, float* g_pos_dev, float* g_neg_dev);
+/* supervise_loss: the loss head of the supervised models (GraphSAGE, GCN, GAT, ... and the graph
+ * classifiers: SuperviseModel.__call__ after out_fc, tf_euler/python/mp_utils/base.py:24-47,
+ * SuperviseSolution of solution/base_supervise.py, GraphModel of mp_utils/base_graph.py:24-47,
+ * with f1_score / acc_score / auc_score of utils/metrics.py:29-48) in ONE read of the logits and
+ * the labels: p = sigmoid(x), sigmoid_cross_entropy_with_logits(z, x) (soft labels allowed), its
+ * mean, the prediction floor(p + 0.5), the streaming counts tp / fp / fn / correct / total and the
+ * two histograms behind tf.metrics.auc.  The contract is stated in euler_amd/csrc/supervise.h.
+ * logits_dev [b, c]: fp32, bf16 or fp16, widened exactly.  The labels come in ONE of two forms:
+ * labels_dev [b, c] (fp32, bf16 or fp16; graph and nodes_dev NULL), or the graph form (labels_dev
+ * NULL): nodes_dev [b] and the float feature slot fid of `graph`, read straight from the graph's
+ * feature table as euler_gpu_get_dense_feature_t reads it (an unknown node or slot: zeros; a
+ * slot shorter than c: zero filled; a longer one: truncated; a 16-bit table: widened) - no [b, c]
+ * label block exists.
+ * prob_dev [b, c] fp32 (may be NULL): p.  diff_dev [b, c] fp32 (may be NULL): p - z, what the
+ * gradient needs.  row_loss_dev [b]: the terms of a row added in the order 0 .. c - 1.  loss_dev
+ * [1]: the row sums reduced in the fixed order of skipgram_loss, a function of b alone, divided
+ * once by float(b * c).  These are WRITTEN.  counts_dev [5] int64 (tp, fp, fn, correct, total)
+ * and hist_dev [2][thresholds + 1] int64 (may be NULL; row 0: label != 0, row 1: label == 0; bucket
+ * = the number of thresholds of tf.metrics.auc's table strictly below p) are ADDED TO - they
+ * stream across calls - with integer atomics only: the same bits on every run, and no float
+ * atomic anywhere.
+ * supervise_loss_grad: from diff_dev and the scalar g_dev [1] (the gradient of the loss)
+ * g_logits_dev [b, c] = (g / float(b * c)) * diff, rounded once to logits_dtype.
+ * Both only enqueue (the forward two kernels): no allocation, no host wait; both can be captured
+ * into a graph.  EULER_GPU_EINVAL, checked before anything is enqueued, so every output is
+ * written entirely or not at all: an unknown dtype, b < 0, c < 1, b * c >= 2^31, thresholds < 2
+ * with hist_dev given, both label forms or neither, a null required buffer, a buffer not aligned
+ * to its element type.  b == 0: the forward writes loss_dev = +0 and touches nothing else (every
+ * buffer but loss_dev and counts_dev may be NULL, the labels of both forms included), the gradient
+ * touches nothing.  NaN logits are
+ * outside the contract. */
+int euler_gpu_supervise_loss(void* stream, const void* logits_dev, int32_t logits_dtype, int64_t b,
+                             int64_t c, const void* labels_dev, int32_t labels_dtype,
+                             const euler_gpu_graph* graph, const uint64_t* nodes_dev, int32_t fid,
+                             int32_t thresholds, float* prob_dev, float* diff_dev,
+                             float* row_loss_dev, float* loss_dev, int64_t* counts_dev,
+                             int64_t* hist_dev);
+int euler_gpu_supervise_loss_grad(void* stream, const float* diff_dev, const float* g_dev, int64_t b,
+                                  int64_t c, void* g_logits_dev, int32_t logits_dtype);
 /* store_update / store_add / store_take: the in-place embedding stores of ScalableSage /
  * ScalableGCN (tf_euler/python/utils/embedding.py:24-68, encoders.py:713-748) - tf.scatter_update,
  * tf.scatter_add and embedding_lookup with the optional clearing update of encoders.py:738-743 -
