@@ -14,6 +14,7 @@
 
 #include "device_fns.h"
 #include "device_mem.h"
+#include "mp_fp8.h"
 #include "mp_segments.h"
 #include "mp_weighted.h"
 
@@ -377,16 +378,18 @@ int CheckMpReduce(const MpReduceCall& c, bool* nothing_to_do) {
     return Fail(EULER_GPU_EINVAL, std::string(c.name) + ": " + why);
   };
   const char* const not_in = " is neither fp32 nor the input's dtype";
-  if (c.typed) {
-    if (c.in_dtype != EULER_GPU_F32 && c.in_dtype != EULER_GPU_BF16 && c.in_dtype != EULER_GPU_F16)
-      return fail("unknown dtype " + std::to_string(c.in_dtype) + " (0 fp32, 1 bf16, 2 fp16)");
+  if (c.fp8) {      // an Fp8Rows table: the output and the weights each in any of the three types
+    if (!MpKnownDtype(c.out_dtype)) return fail("unknown out_dtype " + std::to_string(c.out_dtype) + kMpDtypeCodes);
+    if (c.weighted && !MpKnownDtype(c.w_dtype)) return fail("unknown w_dtype " + std::to_string(c.w_dtype) + kMpDtypeCodes);
+  } else if (c.typed) {
+    if (!MpKnownDtype(c.in_dtype)) return fail("unknown dtype " + std::to_string(c.in_dtype) + kMpDtypeCodes);
     if (c.out_dtype != EULER_GPU_F32 && c.out_dtype != c.in_dtype)
       return fail("out_dtype " + std::to_string(c.out_dtype) + not_in);
     if (c.weighted && c.w_dtype != EULER_GPU_F32 && c.w_dtype != c.in_dtype)
       return fail("w_dtype " + std::to_string(c.w_dtype) + not_in);
-    if (c.weighted && (uintptr_t)c.w % (c.w_dtype == EULER_GPU_F32 ? 4 : 2) != 0)
-      return fail("the weights are not aligned to their type");
   }
+  if ((c.fp8 || c.typed) && c.weighted && (uintptr_t)c.w % (c.w_dtype == EULER_GPU_F32 ? 4 : 2) != 0)
+    return fail("the weights are not aligned to their type");
   if (c.mode < 0 || c.mode > 2) return fail("mode is 0 add, 1 max, 2 mean");
   if (c.weighted && c.heads < 1) return fail("heads < 1");
   if (c.weighted && (c.d < 0 || c.d % c.heads != 0)) return fail("heads must divide d");
@@ -397,6 +400,7 @@ int CheckMpReduce(const MpReduceCall& c, bool* nothing_to_do) {
   }
   // (a keyed call without updates reads nothing, and still fills `out`)
   if (!c.out || ((!c.keyed || c.e > 0) && (!c.params || (c.keyed && !c.keys) || (c.weighted && !c.w) ||
+                                           (c.fp8 && !c.fp8_scale) ||
                                            (c.gather_kind >= kGatherNeeded && !c.gather))))
     return fail("null buffer");
   // the sort of the keys and the weights' positions are 32-bit; the unweighted kernels walk seg_ptr /
@@ -415,6 +419,8 @@ int CheckMpReduce(const MpReduceCall& c, bool* nothing_to_do) {
     return fail("the table must have fewer than 2^31 rows");
   if (c.in_dtype != EULER_GPU_F32 && ((uintptr_t)c.params % 2 != 0 || (uintptr_t)c.out % 2 != 0))
     return fail("16-bit data must be 2-byte aligned");
+  if (c.fp8 && ((uintptr_t)c.out % (c.out_dtype == EULER_GPU_F32 ? 4 : 2) != 0 || (uintptr_t)c.fp8_scale % 4 != 0))
+    return fail("a buffer is not aligned to its type");
   return EULER_GPU_OK;
 }
 
@@ -436,6 +442,7 @@ int RunMpReduce(hipStream_t st, const MpReduceCall& c) {
   const bool ids = c.gather_kind == kGatherIds;
   const MpwIndex ix{perm, static_cast<const int32_t*>(c.gather), ids ? 2 : 1,
                     ids && c.params_rows > 0 ? (uint32_t)(c.params_rows - 1) : 0xFFFFFFFFu};
+  if (c.fp8) return ReduceFp8(st, c, seg, ix);
   if (c.in_dtype != EULER_GPU_F32)
     return c.weighted ? WeightedReduceHalf(st, c, seg, ix) : ReduceHalf(st, c, seg, ix);
   const float* params = static_cast<const float*>(c.params);

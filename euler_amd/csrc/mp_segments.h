@@ -88,6 +88,10 @@ inline LaneShape RowLaneShape(int32_t size, int64_t d, int n, int64_t dh, const 
 
 struct MpwIndex;      // mp_weighted.h
 
+// the storage type codes of a typed entry point (EULER_GPU_F32 / _BF16 / _F16), and how a message lists them
+inline bool MpKnownDtype(int32_t dt) { return dt == EULER_GPU_F32 || dt == EULER_GPU_BF16 || dt == EULER_GPU_F16; }
+constexpr const char* kMpDtypeCodes = " (0 fp32, 1 bf16, 2 fp16)";
+
 // One call of a scatter_* / gather_scatter* / gather_segment_reduce* entry, as its adapter in
 // mp_kernels.hip / mp_half_kernels.hip states it: {name, mode, params, d, size, out}, then what the
 // entry has beyond an fp32 reduce of consecutive rows.
@@ -118,8 +122,12 @@ struct MpReduceCall {
   bool weighted = false;
   const void* w = nullptr;   // [E, heads]
   int32_t heads = 1;
+  const float* fp8_scale = nullptr;   // fp8: params is the q [rows, d] of an Fp8Rows table, this its [d] scales
+  bool fp8 = false;                   // (an internal storage kind: no dtype code of the C ABI names it)
 
   MpReduceCall& Typed(int32_t in, int32_t out_dt) { typed = true; in_dtype = in; out_dtype = out_dt; return *this; }
+  // an fp8_* entry: out_dtype (and w_dtype) any of the three codes
+  MpReduceCall& Fp8(const float* scale, int32_t out_dt) { fp8 = true; fp8_scale = scale; out_dtype = out_dt; return *this; }
   MpReduceCall& Gather(MpGather kind, const void* g, int64_t rows = 0) {
     gather_kind = kind; gather = g; params_rows = rows; return *this;
   }
@@ -141,7 +149,7 @@ int GroupScatterKeys(hipStream_t st, const int32_t* idx, int64_t e, StreamBuf* s
 // heads, heads | d; negative shape; size == 0 || d == 0 (*nothing_to_do: OK, nothing is touched - the
 // callers hand over null for empty tensors, so the null check comes after); null buffers; e >= 2^31;
 // the 2^24 limits of a mean; the 2^31 rows of an id-addressed table; 2-byte alignment of 16-bit
-// data.  Host arithmetic and Fail() only: no HIP call.
+// data (fp8: the output's alignment to its type).  Host arithmetic and Fail() only: no HIP call.
 int CheckMpReduce(const MpReduceCall& c, bool* nothing_to_do);
 int RunMpReduce(hipStream_t st, const MpReduceCall& c);
 // mp_half_kernels.hip: the launchers over bf16 / fp16 rows (c checked, seg and ix built)

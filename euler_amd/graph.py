@@ -1019,6 +1019,31 @@ class Graph:
                 outs.append(out)
         return outs
 
+    def fp8_dense_feature(self, fid, dim, chunk_rows=1 << 20):
+        """The float feature slot `fid` of every id 0 .. max_id as an id-indexed ops.Fp8Rows table
+        of max_id + 1 rows and `dim` columns (an id that is no node, or a short slot: zeros, as
+        get_dense_feature) - the constant input features of a GNN at a quarter of their fp32
+        bytes, read by ops.gather / ops.gather_segment_reduce with the sampled ids as they are.
+        Two passes of get_dense_feature in chunks of chunk_rows ids - the column absmax, then the
+        store - so no more than one fp32 chunk is alive at a time: the result equals
+        Fp8Rows.quantize(get_dense_feature(all ids)).  Plain Python over those primitives; the
+        graph's own table and everything that reads it are untouched."""
+        from . import ops
+        rows, dim, chunk_rows = int(self.id_range()[0]) + 1, int(dim), max(1, int(chunk_rows))
+
+        def chunks():
+            for first in range(0, rows, chunk_rows):
+                ids = torch.arange(first, min(first + chunk_rows, rows), dtype=torch.int64, device=self.device)
+                yield first, self.get_dense_feature(ids, [fid], [dim], out_dtype=torch.float32)[0]
+
+        absmax = torch.zeros(dim, dtype=torch.float32, device=self.device)
+        for _, x in chunks():
+            ops.column_absmax(x, out=absmax)
+        table = ops.Fp8Rows.empty(rows, dim, ops.Fp8Rows.scale_of(absmax), self.device)
+        for first, x in chunks():
+            table.store(first, x)
+        return table
+
     def supervise_loss(self, nodes, logits, label_fid, label_dim, metric=None, return_prob=False):
         """SuperviseModel.__call__ after out_fc (tf_euler/python/mp_utils/base.py:35-47) in one
         kernel: nodes [B] int64 and logits [B, label_dim] -> the mean sigmoid cross-entropy against

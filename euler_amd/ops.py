@@ -186,7 +186,10 @@ class _ScatterMax(torch.autograd.Function):
 def gather(params, indices, out_dtype=None):
     """MPGather: out[i,:] = params[indices[i],:] (fp32, bf16 or fp16 rows, int32 indices).
     out_dtype: None = the dtype of params, or torch.float32 for 16-bit params (the rows widened,
-    which is exact)."""
+    which is exact).  params may be an Fp8Rows table: the rows of its dequantize(), out_dtype None
+    (fp32), float32, bfloat16 or float16; no gradient."""
+    if isinstance(params, Fp8Rows):
+        return _fp8_gather(params, indices, out_dtype)
     return _Gather.apply(params, indices, out_dtype)
 
 
@@ -404,7 +407,15 @@ def gather_segment_reduce(op, params, gather_indices, size, seg_ptr=None, count=
     with dst = the destination of every index, in one pass and without the scatter's
     look at its key column (no host wait; validate=True checks the gather indices first,
     which is one).  out_dtype as scatter_add.  edge_weight as gather_scatter - e.g. the weights
-    sample_neighbor returns next to the ids."""
+    sample_neighbor returns next to the ids.
+
+    params may be an Fp8Rows table (the constant input features of a GNN, a quarter of their fp32
+    bytes): the result has the bits of this op on params.dequantize(), out_dtype None (fp32),
+    float32, bfloat16 or float16; edge_weight float32, bfloat16 or float16.  No gradient flows to
+    an Fp8Rows, and an edge_weight that requires grad raises NotImplementedError there."""
+    if isinstance(params, Fp8Rows):
+        return _fp8_gather_segment_reduce(op, params, gather_indices, size, seg_ptr, count, validate,
+                                          out_dtype, edge_weight)
     if op not in _GS_MODE:
         raise ValueError("gather_segment_reduce: op is add, max or mean")
     if (seg_ptr is None) == (count is None):
@@ -415,6 +426,181 @@ def gather_segment_reduce(op, params, gather_indices, size, seg_ptr=None, count=
                                            int(size), op, bool(validate), out_dtype, edge_weight)
     return _GatherSegmentReduce.apply(params, gather_indices, seg_ptr, 0 if count is None else int(count),
                                       int(size), op, bool(validate), out_dtype)
+
+
+# ---- quantised (fp8) feature row tables --------------------------------------------------------
+FP8_MAX = 448.0     # the largest finite e4m3fn value
+
+
+def _fp8_out_dt(name, out_dtype):
+    if out_dtype is None:
+        return _F32
+    if out_dtype not in _DT:
+        raise TypeError("%s: out_dtype of an Fp8Rows op is float32, bfloat16 or float16, not %s"
+                        % (name, out_dtype))
+    return out_dtype
+
+
+def column_absmax(x, out=None):
+    """absmax[c] = the largest |x[r, c]| over the FINITE values of column c of x [n, d] (fp32, bf16
+    or fp16; NaN and +-inf are skipped), as fp32 [d].  Exact.  With `out` (fp32 [d], non-negative):
+    out = max(out, absmax(x)) in place, so that a table is scanned in chunks."""
+    code = _dt("column_absmax", x)
+    if x.dim() != 2:
+        raise ValueError("column_absmax: x is [n, d]")
+    x = x.contiguous()
+    _need_cuda(x)
+    n, d = x.shape
+    if out is None:
+        out = torch.zeros(d, dtype=_F32, device=x.device)
+    elif out.dtype != _F32 or out.dim() != 1 or out.numel() != d or not out.is_contiguous() \
+            or out.device != x.device:
+        raise ValueError("column_absmax: out is a contiguous float32 [d] tensor on the device of x")
+    with _on(x.device):
+        check(lib().euler_gpu_column_absmax(_stream(), _ptr(x), code, n, d, _ptr(out)))
+    return out
+
+
+class Fp8Rows(object):
+    """A quantised row table: q [N, d] uint8 codes of OCP e4m3fn (q.view(torch.float8_e4m3fn) is a
+    view of the same bytes) and scale [d] fp32, finite and positive, one per column.  Its value is
+    x^[r, c] = float32(q[r, c]) * scale[c] (one fp32 multiply); ops.gather and
+    ops.gather_segment_reduce read it in place and return the bits of the fp32 op on
+    dequantize().  Forward only: no gradient flows to a table."""
+
+    def __init__(self, q, scale):
+        if q.dtype == getattr(torch, "float8_e4m3fn", None):
+            q = q.view(torch.uint8)
+        if q.dtype != torch.uint8 or q.dim() != 2:
+            raise TypeError("Fp8Rows: q is a [N, d] uint8 (or float8_e4m3fn) tensor")
+        if scale.dtype != _F32 or scale.dim() != 1 or scale.numel() != q.shape[1]:
+            raise TypeError("Fp8Rows: scale is a float32 [d] tensor")
+        _need_cuda(q, scale)
+        if q.device != scale.device:
+            raise ValueError("Fp8Rows: q and scale live on different devices")
+        self.q = q.contiguous()
+        self.scale = scale.detach().contiguous()
+
+    @property
+    def shape(self):
+        return self.q.shape
+
+    @property
+    def device(self):
+        return self.q.device
+
+    @staticmethod
+    def scale_of(absmax):
+        """the column scales of a column absmax: absmax / 448, and 1 where the column is all zero.
+        The d divisions are done on the host (one wait, once per table): IEEE fp32, whatever a
+        device library makes of a division by a constant."""
+        a = absmax.detach().to(_F32).cpu().numpy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            s = np.where(a > 0, a / np.float32(FP8_MAX), np.float32(1)).astype(np.float32)
+        return torch.from_numpy(s).to(absmax.device)
+
+    @staticmethod
+    def empty(n, d, scale, device=None):
+        """an uninitialised table of n rows with the given column scales (fill it with store())"""
+        device = scale.device if device is None else torch.device(device)
+        scale = scale.to(device=device, dtype=_F32)
+        return Fp8Rows(torch.empty((int(n), int(d)), dtype=torch.uint8, device=device), scale)
+
+    def store(self, first_row, x):
+        """quantises x [m, d] (fp32, bf16 or fp16) into rows [first_row, first_row + m) in place,
+        with the table's scale: q = Enc(x / scale), an fp32 division, round to nearest even, values
+        past the scale saturate at +-448"""
+        code = _dt("Fp8Rows.store", x)
+        first_row = int(first_row)
+        if x.dim() != 2 or x.shape[1] != self.q.shape[1]:
+            raise ValueError("Fp8Rows.store: x is [m, %d]" % self.q.shape[1])
+        if first_row < 0 or first_row + x.shape[0] > self.q.shape[0]:
+            raise IndexError("Fp8Rows.store: rows [%d, %d) are not inside the table's %d"
+                             % (first_row, first_row + x.shape[0], self.q.shape[0]))
+        x = x.detach().contiguous()
+        _need_cuda(x)
+        if x.device != self.q.device:
+            raise ValueError("Fp8Rows.store: x lives on %s, the table on %s" % (x.device, self.q.device))
+        m, d = x.shape
+        with _on(self.q.device):
+            check(lib().euler_gpu_fp8_quantize_rows(_stream(), _ptr(x), code, m, d, _ptr(self.scale),
+                                                    _ptr(self.q[first_row:first_row + m])))
+        return self
+
+    @staticmethod
+    def quantize(x, scale=None):
+        """the table of x [N, d]; scale None: from x's own columns (absmax over the finite values /
+        448, 1 for a column of zeros), else the caller's (e.g. one that clips outliers)"""
+        if scale is None:
+            scale = Fp8Rows.scale_of(column_absmax(x.detach()))
+        return Fp8Rows.empty(x.shape[0], x.shape[1], scale, x.device).store(0, x)
+
+    def dequantize(self, out_dtype=_F32):
+        """x^ [N, d] in fp32 (exact), or rounded once to bf16 / fp16"""
+        n = self.q.shape[0]
+        if n >= 1 << 31:
+            raise ValueError("Fp8Rows.dequantize: the table has 2^31 rows or more")
+        return _fp8_gather(self, torch.arange(n, dtype=torch.int32, device=self.q.device), out_dtype)
+
+
+def _fp8_gather(table, indices, out_dtype):
+    od = _fp8_out_dt("gather", out_dtype)
+    indices = indices.to(torch.int32).contiguous()
+    _need_cuda(indices)
+    e, d = indices.numel(), table.q.shape[1]
+    out = torch.empty((e, d), dtype=od, device=table.q.device)
+    with _on(table.q.device):
+        check(lib().euler_gpu_fp8_gather(_stream(), _ptr(table.q), _ptr(table.scale), _ptr(indices), e, d,
+                                         table.q.shape[0], _ptr(out), _DT[od]))
+    return out
+
+
+def _fp8_gather_segment_reduce(op, table, gather_indices, size, seg_ptr, count, validate, out_dtype,
+                               edge_weight):
+    if op not in _GS_MODE:
+        raise ValueError("gather_segment_reduce: op is add, max or mean")
+    if (seg_ptr is None) == (count is None):
+        raise ValueError("gather_segment_reduce: pass seg_ptr or count")
+    od = _fp8_out_dt("gather_segment_reduce", out_dtype)
+    size, count = int(size), 0 if count is None else int(count)
+    rows, d = table.q.shape
+    w2, heads = None, 1
+    if edge_weight is not None:
+        if edge_weight.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("gather_segment_reduce: no gradient to edge_weight through an Fp8Rows "
+                                      "table")
+        if edge_weight.dtype not in _DT:
+            raise TypeError("gather_segment_reduce: edge_weight is float32, bfloat16 or float16, not %s"
+                            % edge_weight.dtype)
+        w2, heads = _fp8_edge_weight(edge_weight.detach(), gather_indices.numel(), d)
+    _, gi, as_ids, sp = _segment_args(table.q, gather_indices, seg_ptr, count, size, bool(validate))
+    out = torch.empty((size, d), dtype=od, device=table.q.device)
+    wd = _DT[w2.dtype] if w2 is not None else _lib.F32
+    with _on(table.q.device):
+        if as_ids:
+            check(lib().euler_gpu_fp8_gather_segment_reduce_ids(
+                _stream(), _GS_MODE[op], _ptr(table.q), _ptr(table.scale), rows, _ptr(gi), _ptr(sp), count, d,
+                size, _ptr(out), _DT[od], _ptr(w2), wd, heads))
+        else:
+            check(lib().euler_gpu_fp8_gather_segment_reduce(
+                _stream(), _GS_MODE[op], _ptr(table.q), _ptr(table.scale), _ptr(gi), _ptr(sp), count, d, size,
+                _ptr(out), _DT[od], _ptr(w2), wd, heads))
+    return out
+
+
+def _fp8_edge_weight(w, e, d):
+    """the shape rules of _edge_weight for a quantised table -> ([E, H] contiguous, H)"""
+    name = "gather_segment_reduce"
+    _need_cuda(w)
+    if w.dim() not in (1, 2):
+        raise ValueError("%s: edge_weight is [E], [E, 1] or [E, H]" % name)
+    w2 = w.reshape(-1, 1) if w.dim() == 1 else w
+    if w2.shape[0] != e:
+        raise ValueError("%s: one weight row per edge (%d), not %d" % (name, e, w2.shape[0]))
+    heads = int(w2.shape[1])
+    if heads < 1 or d % heads != 0:
+        raise ValueError("%s: the %d weights of an edge do not divide the %d columns" % (name, heads, d))
+    return w2.contiguous(), heads
 
 
 # ---- per-column top-k of a sampled block (LGCN: utils/encoders.py:872-922) --------------------

@@ -937,6 +937,60 @@ int euler_gpu_edge_dot_t(void* stream, const void* a_dev, int32_t a_dtype,
                          const int32_t* a_index_dev, const void* b_dev, int32_t b_dtype,
                          const int32_t* b_index_dev, int64_t e, int64_t d, int32_t heads,
                          void* out_dev, int32_t out_dtype);
+
+/* ---- quantised (FP8) feature row tables -------------------------------------------
+ * A table is q_dev, [rows, d] uint8 codes of OCP e4m3fn (what torch.float8_e4m3fn and gfx950's
+ * converts use: 0x7f / 0xff NaN, no inf, largest finite value 448, subnormals m * 2^-9), plus
+ * scale_dev, [d] fp32 finite positive values, one per COLUMN.  Its value is
+ *   x^[r][c] = fl(Dec(q[r][c]) * scale[c])          (one correctly rounded fp32 multiply)
+ * and an entry below that reads a table is the fp32 entry above on x^: the same fp32 adds in
+ * input order, the same compares for max and the -1e9 empty row, mean = sum / (length + 1e-7f),
+ * the same min((uint32) low word, rows - 1) treatment of int64 ids, the weighted product formed
+ * as the _w entries form it - stored as fp32 unchanged or rounded once, to nearest even, to
+ * bf16 / fp16 (out_dtype: any of EULER_GPU_F32 / _BF16 / _F16).  Nothing is accumulated below
+ * fp32, so the result has the bits of the fp32 entry on the dequantised table.  These are new
+ * entries: no `_t` entry accepts a code for this storage.
+ *
+ * euler_gpu_column_absmax: absmax_dev[c] = max(absmax_dev[c], max |x[r][c]|) over the FINITE
+ * values of column c of x_dev ([n, d] of `dtype`; NaN and +-inf are skipped) - in/out, so that a
+ * table is scanned in chunks; the caller zeroes it first.  Exact (a max has no order).  The scale
+ * of a column is absmax / 448.0f, or 1.0f where absmax is 0 (the caller's arithmetic).
+ * euler_gpu_fp8_quantize_rows: q_dev[r][c] = Enc(x[r][c] / scale[c]) for the n rows of x_dev - an
+ * IEEE fp32 division, then round to nearest even into e4m3fn with subnormals, after a clamp to
+ * [-448, 448]: +-inf and everything past the scale saturate to +-448, NaN gives 0x7f | sign, -0
+ * gives 0x80.  16-bit x is widened exactly first.  q_dev may point into a larger table.
+ * euler_gpu_fp8_gather: out[i][:] = x^[indices[i]][:], e rows of out_dtype; indices are trusted.
+ * euler_gpu_fp8_gather_segment_reduce / _ids: euler_gpu_gather_segment_reduce_t / _ids_t over x^
+ * (mode 0 add, 1 max, 2 mean; seg_ptr_dev or `count`; gather_indices_dev NULL: update p is row p),
+ * and with w_dev != NULL their _w_t forms: w_dev [e, heads] of w_dtype (any of the three), heads
+ * dividing d.  w_dev == NULL: unweighted, w_dtype and heads are not looked at.
+ * 16-byte aligned q_dev / out_dev with d % 16 == 0, d <= 1024, d / 16 a divisor of 64 (and
+ * (d / heads) % 16 == 0) take the 16-byte-lane reduce kernels - a 128-d row is one 128-byte line -,
+ * every other shape a column per lane; the gather reads four codes a lane into fp32 rows (d % 4 == 0,
+ * q_dev 4-byte and out_dev 16-byte aligned) and sixteen into 16-bit rows (d % 16 == 0, both 16-byte
+ * aligned), else one.  A table may be larger than 2^32 bytes.
+ * EULER_GPU_EINVAL, checked in this order: an unknown dtype code, weights not aligned to their
+ * type; mode, heads < 1, heads not dividing d; a negative shape; [size == 0 or d == 0 (e, n):
+ * EULER_GPU_OK, nothing is touched]; a null buffer; e >= 2^31 (weighted); mean with count >= 2^24;
+ * params_rows outside [0, 2^31); a buffer not aligned to its type. */
+int euler_gpu_column_absmax(void* stream, const void* x_dev, int32_t dtype, int64_t n, int64_t d,
+                            float* absmax_dev);
+int euler_gpu_fp8_quantize_rows(void* stream, const void* x_dev, int32_t dtype, int64_t n, int64_t d,
+                                const float* scale_dev, uint8_t* q_dev);
+int euler_gpu_fp8_gather(void* stream, const uint8_t* q_dev, const float* scale_dev,
+                         const int32_t* indices_dev, int64_t e, int64_t d, int64_t n_rows,
+                         void* out_dev, int32_t out_dtype);
+int euler_gpu_fp8_gather_segment_reduce(void* stream, int32_t mode, const uint8_t* q_dev,
+                                        const float* scale_dev, const int32_t* gather_indices_dev,
+                                        const int64_t* seg_ptr_dev, int64_t count, int64_t d,
+                                        int32_t size, void* out_dev, int32_t out_dtype,
+                                        const void* w_dev, int32_t w_dtype, int32_t heads);
+int euler_gpu_fp8_gather_segment_reduce_ids(void* stream, int32_t mode, const uint8_t* q_dev,
+                                            const float* scale_dev, int64_t params_rows,
+                                            const int64_t* gather_ids_dev,
+                                            const int64_t* seg_ptr_dev, int64_t count, int64_t d,
+                                            int32_t size, void* out_dev, int32_t out_dtype,
+                                            const void* w_dev, int32_t w_dtype, int32_t heads);
 /* gcn_norm: the two tables of the symmetric degree normalisation of GCN / APPNP / SGCN / TAG /
  * ARMA / DNA (gcn_conv.py:33-51: norm = deg ** -0.5 on both sides of a block).  dst_keys_dev and
  * src_keys_dev are int32 [e]; an edge counts if and only if BOTH keys are in range (dst in
