@@ -29,6 +29,10 @@ int Fail(int code, const std::string& msg);
                                    hipGetErrorString(_e));                  \
   } while (0)
 
+// the storage type codes of a typed entry point (EULER_GPU_F32 / _BF16 / _F16), and how a message lists them
+inline bool KnownDtype(int32_t dt) { return dt == EULER_GPU_F32 || dt == EULER_GPU_BF16 || dt == EULER_GPU_F16; }
+constexpr const char* kDtypeCodes = " (0 fp32, 1 bf16, 2 fp16)";
+
 // ------------------------------------------------------------ HBM layout
 //
 // The reference keeps one heap object per node (unordered_map<id, Node*> ->

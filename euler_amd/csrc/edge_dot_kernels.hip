@@ -136,8 +136,6 @@ int DispatchEdgeDotB(hipStream_t st, const void* a, const int32_t* ai, const voi
   return LaunchEdgeDot<DTA, kF16>(st, a, ai, b, bi, e, heads, dh, out, out_dtype);
 }
 
-bool KnownDtype(int32_t t) { return t == EULER_GPU_F32 || t == EULER_GPU_BF16 || t == EULER_GPU_F16; }
-
 }  // namespace
 }  // namespace euler_gpu
 
@@ -149,7 +147,7 @@ int euler_gpu_edge_dot_t(void* stream, const void* a_dev, int32_t a_dtype, const
                          const void* b_dev, int32_t b_dtype, const int32_t* b_index_dev, int64_t e,
                          int64_t d, int32_t heads, void* out_dev, int32_t out_dtype) {
   if (!KnownDtype(a_dtype) || !KnownDtype(b_dtype) || !KnownDtype(out_dtype))
-    return Fail(EULER_GPU_EINVAL, "edge_dot: unknown dtype (0 fp32, 1 bf16, 2 fp16)");
+    return Fail(EULER_GPU_EINVAL, std::string("edge_dot: unknown dtype") + kDtypeCodes);
   if (heads < 1) return Fail(EULER_GPU_EINVAL, "edge_dot: heads < 1");
   if (e < 0 || d < 0 || d % heads != 0) return Fail(EULER_GPU_EINVAL, "edge_dot: heads must divide d");
   if (e == 0 || d == 0) return EULER_GPU_OK;

@@ -192,8 +192,6 @@ __global__ __launch_bounds__(kSmxBlock) void EdgeSoftmaxLongKernel(const SmxArgs
   }
 }
 
-bool KnownDtype(int32_t t) { return t == EULER_GPU_F32 || t == EULER_GPU_BF16 || t == EULER_GPU_F16; }
-
 template <bool GRAD>
 int Launch(hipStream_t st, const SmxArgs& A, bool uniform, int64_t count) {
   const int64_t tasks = (int64_t)A.seg.size * A.heads;
@@ -207,12 +205,9 @@ int Launch(hipStream_t st, const SmxArgs& A, bool uniform, int64_t count) {
     EG_HIP(hipGetLastError());
   }
   if ((!uniform || count > kSmxShort) && A.seg.size > 0) {
-    int64_t chunks = ((int64_t)A.seg.size + kSmxBlock - 1) / kSmxBlock;
-    if (chunks > 256 * 32) chunks = 256 * 32;
-    int64_t share = 2048 / chunks;                      // few destinations: more blocks a chunk
-    share = share < 1 ? 1 : (share > 16 ? 16 : share);
-    hipLaunchKernelGGL((EdgeSoftmaxLongKernel<GRAD>), dim3((unsigned)chunks, (unsigned)share), dim3(kSmxBlock),
-                       0, st, A, SmxHeadsPerWave(A.heads));
+    const SmxLongGrid g = SmxLongGridFor(A.seg.size);
+    hipLaunchKernelGGL((EdgeSoftmaxLongKernel<GRAD>), dim3(g.chunks, g.share), dim3(kSmxBlock), 0, st, A,
+                       SmxHeadsPerWave(A.heads));
     EG_HIP(hipGetLastError());
   }
   return EULER_GPU_OK;
@@ -224,25 +219,18 @@ int EdgeSoftmaxImpl(const char* what, void* stream, const void* a, int32_t a_dt,
                     int32_t size, void* out, int32_t out_dt) {
   const std::string w(what);
   if (!KnownDtype(a_dt) || !KnownDtype(b_dt) || !KnownDtype(out_dt))
-    return Fail(EULER_GPU_EINVAL, w + ": unknown dtype (0 fp32, 1 bf16, 2 fp16)");
+    return Fail(EULER_GPU_EINVAL, w + ": unknown dtype" + kDtypeCodes);
   if (heads < 1) return Fail(EULER_GPU_EINVAL, w + ": heads < 1");
   if (e < 0 || size < 0 || count < 0) return Fail(EULER_GPU_EINVAL, w + ": bad shape");
-  if ((indices != nullptr) + (seg_ptr != nullptr) + (count > 0) != 1)
-    return Fail(EULER_GPU_EINVAL, w + ": pass exactly one of indices, seg_ptr and count");
-  if (count > 0 && e != (int64_t)size * count)
-    return Fail(EULER_GPU_EINVAL, w + ": e is not size * count");
+  hipStream_t st = (hipStream_t)stream;
+  SegDest dst(st, indices, seg_ptr, count, e, size);
+  if (const char* why = dst.FormError()) return Fail(EULER_GPU_EINVAL, w + ": " + why);
   if (e == 0) return EULER_GPU_OK;
   if (!a || !out || (GRAD && !b)) return Fail(EULER_GPU_EINVAL, w + ": null buffer");
-  if (e >= (1LL << 31)) return Fail(EULER_GPU_EINVAL, w + ": e >= 2^31");
-  hipStream_t st = (hipStream_t)stream;
-  const int32_t* keys = indices;
-  const uint32_t* perm = nullptr;
-  StreamBuf scratch(st);                // the grouped keys of the unsorted path: one sort a call
-  if (indices) {
-    const int rc = GroupScatterKeys(st, indices, e, &scratch, &keys, &perm);
-    if (rc != EULER_GPU_OK) return rc;
-  }
-  const SmxArgs A{a, a_dt, b, b_dt, SegSpec{keys, seg_ptr, count, e, size}, perm, e, heads, out, out_dt};
+  if (const char* why = dst.LengthError()) return Fail(EULER_GPU_EINVAL, w + ": " + why);
+  const int rc = dst.Resolve();
+  if (rc != EULER_GPU_OK) return rc;
+  const SmxArgs A{a, a_dt, b, b_dt, dst.seg(), dst.perm(), e, heads, out, out_dt};
   return Launch<GRAD>(st, A, count > 0, count);
 }
 

@@ -96,8 +96,6 @@ __device__ __forceinline__ void EsAhead(const Args& a, uint64_t key, int64_t i, 
   for (int x = 0; x < K; ++x) pos[x] = a.perm[ok[x] ? q + x : i];
 }
 
-bool EsKnownDtype(int32_t t) { return t == EULER_GPU_F32 || t == EULER_GPU_BF16 || t == EULER_GPU_F16; }
-
 // (key, position) of every occurrence, stably sorted by key, into `pairs` (released by its owner)
 template <typename Args>
 int GroupOccurrences(hipStream_t st, Args* a, StreamBuf* pairs) {

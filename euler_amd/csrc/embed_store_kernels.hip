@@ -173,8 +173,8 @@ int DispatchTable(hipStream_t st, const EsArgs& a, int32_t table_dtype, const vo
 int CheckStoreArgs(const std::string& what, const EsArgs& a, int32_t table_dtype, const void* other,
                    int32_t other_dtype, bool* run) {
   *run = false;
-  if (!EsKnownDtype(table_dtype) || !EsKnownDtype(other_dtype))
-    return Fail(EULER_GPU_EINVAL, what + ": unknown dtype (0 fp32, 1 bf16, 2 fp16)");
+  if (!KnownDtype(table_dtype) || !KnownDtype(other_dtype))
+    return Fail(EULER_GPU_EINVAL, what + ": unknown dtype" + kDtypeCodes);
   if (other_dtype != EULER_GPU_F32 && other_dtype != table_dtype)
     return Fail(EULER_GPU_EINVAL, what + ": values / out are fp32 or of the table's dtype");
   if (a.rows < 1) return Fail(EULER_GPU_EINVAL, what + ": a table with fewer than 1 row");

@@ -356,7 +356,7 @@ extern "C" {
 int euler_gpu_column_absmax(void* stream, const void* x_dev, int32_t dtype, int64_t n, int64_t d,
                             float* absmax_dev) {
   const auto fail = [](const std::string& why) { return Fail(EULER_GPU_EINVAL, "column_absmax: " + why); };
-  if (!MpKnownDtype(dtype)) return fail("unknown dtype " + std::to_string(dtype) + kMpDtypeCodes);
+  if (!KnownDtype(dtype)) return fail("unknown dtype " + std::to_string(dtype) + kDtypeCodes);
   if (n < 0 || d < 0) return fail("bad shape");
   if (n == 0 || d == 0) return EULER_GPU_OK;
   if (!x_dev || !absmax_dev) return fail("null buffer");
@@ -377,7 +377,7 @@ int euler_gpu_column_absmax(void* stream, const void* x_dev, int32_t dtype, int6
 int euler_gpu_fp8_quantize_rows(void* stream, const void* x_dev, int32_t dtype, int64_t n, int64_t d,
                                 const float* scale_dev, uint8_t* q_dev) {
   const auto fail = [](const std::string& why) { return Fail(EULER_GPU_EINVAL, "fp8_quantize_rows: " + why); };
-  if (!MpKnownDtype(dtype)) return fail("unknown dtype " + std::to_string(dtype) + kMpDtypeCodes);
+  if (!KnownDtype(dtype)) return fail("unknown dtype " + std::to_string(dtype) + kDtypeCodes);
   if (n < 0 || d < 0) return fail("bad shape");
   if (n == 0 || d == 0) return EULER_GPU_OK;
   if (!x_dev || !scale_dev || !q_dev) return fail("null buffer");
@@ -401,7 +401,7 @@ int euler_gpu_fp8_gather(void* stream, const uint8_t* q_dev, const float* scale_
                          int32_t out_dtype) {
   (void)n_rows;      // (as euler_gpu_gather: the indices are trusted)
   const auto fail = [](const std::string& why) { return Fail(EULER_GPU_EINVAL, "fp8_gather: " + why); };
-  if (!MpKnownDtype(out_dtype)) return fail("unknown out_dtype " + std::to_string(out_dtype) + kMpDtypeCodes);
+  if (!KnownDtype(out_dtype)) return fail("unknown out_dtype " + std::to_string(out_dtype) + kDtypeCodes);
   if (e < 0 || d < 0) return fail("bad shape");
   if (e == 0 || d == 0) return EULER_GPU_OK;
   if (!q_dev || !scale_dev || !indices_dev || !out_dev) return fail("null buffer");

@@ -265,8 +265,6 @@ int LaunchMode(hipStream_t st, const GcnCall& c, int32_t in_dtype, bool out16) {
   return out16 ? LaunchH16<MODE, kF16, true>(st, c) : LaunchH16<MODE, kF16, false>(st, c);
 }
 
-bool KnownDtype(int32_t t) { return t == EULER_GPU_F32 || t == EULER_GPU_BF16 || t == EULER_GPU_F16; }
-
 // a failing exit after work was enqueued: the stream is drained before the scratch goes back
 int Drained(hipStream_t st, int rc) {
   if (rc != EULER_GPU_OK) (void)hipStreamSynchronize(st);
@@ -321,8 +319,7 @@ int euler_gpu_gather_reduce_norm_t(void* stream, int32_t mode, const void* x_dev
                                    int32_t out_dtype) {
   const auto fail = [](const std::string& why) { return Fail(EULER_GPU_EINVAL, "gather_reduce_norm: " + why); };
   // the ladder, in the order of CheckMpReduce
-  if (!KnownDtype(in_dtype))
-    return fail("unknown dtype " + std::to_string(in_dtype) + " (0 fp32, 1 bf16, 2 fp16)");
+  if (!KnownDtype(in_dtype)) return fail("unknown dtype " + std::to_string(in_dtype) + kDtypeCodes);
   if (out_dtype != EULER_GPU_F32 && out_dtype != in_dtype)
     return fail("out_dtype " + std::to_string(out_dtype) + " is neither fp32 nor the input's dtype");
   if (root_dev && root_dtype != EULER_GPU_F32 && root_dtype != in_dtype)
@@ -330,10 +327,10 @@ int euler_gpu_gather_reduce_norm_t(void* stream, int32_t mode, const void* x_dev
   if (mode == 1) return fail("max is not supported (mode is 0 add, 2 mean)");
   if (mode != 0 && mode != 2) return fail("mode is 0 add, 2 mean");
   if (e < 0 || d < 0 || size < 0 || rows < 0 || count < 0) return fail("bad shape");
+  hipStream_t st = (hipStream_t)stream;
+  SegDest dst(st, indices_dev, seg_ptr_dev, count, e, size);
   // (a block without edges may come with no form at all: the keys of an empty tensor are null)
-  const int forms = (indices_dev != nullptr) + (seg_ptr_dev != nullptr) + (count > 0);
-  if (forms > 1 || (forms == 0 && e > 0)) return fail("pass exactly one of indices, seg_ptr and count");
-  if (count > 0 && e != (int64_t)size * count) return fail("e is not size * count");
+  if (const char* why = dst.FormError(SegDest::kNoFormWhenEmpty)) return fail(why);
   if (size == 0 || d == 0) return EULER_GPU_OK;
   // what the kernels read: out and norm_dst[r] for every destination, whatever its segment; x, the gather
   // indices and norm_src only where an update can contribute (e > 0 and rows > 0: an empty table has no
@@ -341,7 +338,7 @@ int euler_gpu_gather_reduce_norm_t(void* stream, int32_t mode, const void* x_dev
   const bool live = e > 0 && rows > 0;
   if (!out_dev || !norm_dst_dev || (live && (!x_dev || !gather_indices_dev || !norm_src_dev)))
     return fail("null buffer");
-  if (e >= (1LL << 31)) return fail("e >= 2^31");
+  if (const char* why = dst.LengthError()) return fail(why);
   if (rows >= (1LL << 31)) return fail("the table must have fewer than 2^31 rows");
   // a destination could collect 2^24 or more updates: its f32 count would no longer be its length
   // (keys or seg_ptr: no segment is longer than e)
@@ -355,20 +352,15 @@ int euler_gpu_gather_reduce_norm_t(void* stream, int32_t mode, const void* x_dev
       (uintptr_t)gather_indices_dev % 4 != 0 || (uintptr_t)indices_dev % 4 != 0 || (uintptr_t)seg_ptr_dev % 8 != 0)
     return fail("norm tables and indices must be aligned to their type");
 
-  hipStream_t st = (hipStream_t)stream;
-  SegSpec seg{nullptr, seg_ptr_dev, count, e, size};
-  const uint32_t* perm = nullptr;
-  StreamBuf scratch(st);                // the grouped keys of the unsorted path: one sort a call
-  if (!live) {
-    // no update can contribute: every destination reduces an empty segment (add and mean give 0)
-    seg = SegSpec{nullptr, nullptr, 0, 0, size};
-  } else if (indices_dev) {
-    seg = SegSpec{indices_dev, nullptr, 0, e, size};
-    const int rc = GroupScatterKeys(st, indices_dev, e, &scratch, &seg.keys, &perm);
+  // !live: no update can contribute, every destination reduces an empty segment (add and mean give 0)
+  SegSpec seg{nullptr, nullptr, 0, 0, size};
+  if (live) {
+    const int rc = dst.Resolve();
     if (rc != EULER_GPU_OK) return Drained(st, rc);
+    seg = dst.seg();
   }
   const GcnCall c{x_dev, d, out_dev, seg,
-                  MpwIndex{perm, gather_indices_dev, 1, rows > 0 ? (uint32_t)(rows - 1) : 0u},
+                  MpwIndex{dst.perm(), gather_indices_dev, 1, rows > 0 ? (uint32_t)(rows - 1) : 0u},
                   GcnTables{norm_dst_dev, norm_src_dev, (uint32_t)rows},
                   GcnRoot{root_dev, root_dtype == EULER_GPU_F32, agg_scale, root_scale}};
   const bool out16 = out_dtype != EULER_GPU_F32;

@@ -42,7 +42,6 @@ inline KgTripleArgs KgShared(int32_t kind, int32_t corrupt, const void* ent, int
                       pos_out, neg_out, g_pos, g_neg, g_src, g_rel, g_dst, g_neg_rows, /*out_vec=*/0};
 }
 
-inline bool KgKnownDtype(int32_t t) { return t == EULER_GPU_F32 || t == EULER_GPU_BF16 || t == EULER_GPU_F16; }
 inline bool KgAligned(const void* p, int32_t dtype) { return (uintptr_t)p % (dtype == EULER_GPU_F32 ? 4 : 2) == 0; }
 
 // What a family adds to the ladder.  score: d.  proj: d, proj and its two aux tables.  matrix:
@@ -73,8 +72,8 @@ inline int CheckKgCall(const KgCall& c, const KgTripleArgs& a, bool* run) {
     return Fail(EULER_GPU_EINVAL, w + ": kind outside 0..1 (distmult takes no projection)");
   }
   if (a.corrupt < 0 || a.corrupt > 2) return Fail(EULER_GPU_EINVAL, w + ": corrupt outside 0..2");
-  if (!KgKnownDtype(c.ent_dtype) || !KgKnownDtype(c.rel_dtype) || !KgKnownDtype(c.matrix_dtype))
-    return Fail(EULER_GPU_EINVAL, w + ": unknown dtype (0 fp32, 1 bf16, 2 fp16)");
+  if (!KnownDtype(c.ent_dtype) || !KnownDtype(c.rel_dtype) || !KnownDtype(c.matrix_dtype))
+    return Fail(EULER_GPU_EINVAL, w + ": unknown dtype" + kDtypeCodes);
   if (a.k < 0 || a.b < 0 || c.d < 0 || c.dr < 0)
     return Fail(EULER_GPU_EINVAL, w + (matrix ? ": b, k, de or dr < 0" : ": b, k or d < 0"));
   if (a.ent_rows < 1 || a.rel_rows < 1) return Fail(EULER_GPU_EINVAL, w + ": a table with fewer than 1 row");

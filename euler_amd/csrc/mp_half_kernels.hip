@@ -427,8 +427,8 @@ extern "C" {
 int euler_gpu_gather_t(void* stream, const void* params_dev, int32_t in_dtype,
                        const int32_t* indices_dev, int64_t e, int64_t d, int64_t n_params,
                        void* out_dev, int32_t out_dtype) {
-  if (in_dtype != EULER_GPU_F32 && in_dtype != EULER_GPU_BF16 && in_dtype != EULER_GPU_F16)
-    return Fail(EULER_GPU_EINVAL, "gather: unknown dtype " + std::to_string(in_dtype) + " (0 fp32, 1 bf16, 2 fp16)");
+  if (!KnownDtype(in_dtype))
+    return Fail(EULER_GPU_EINVAL, "gather: unknown dtype " + std::to_string(in_dtype) + kDtypeCodes);
   if (out_dtype != EULER_GPU_F32 && out_dtype != in_dtype)
     return Fail(EULER_GPU_EINVAL, "gather: out_dtype " + std::to_string(out_dtype) +
                                       " is neither fp32 nor the input's dtype");
@@ -550,9 +550,8 @@ int32_t euler_gpu_graph_dense_feature_dtype(const euler_gpu_graph* g) {
 
 int euler_gpu_graph_set_dense_feature_dtype(euler_gpu_graph* g, void* stream, int32_t dtype) {
   if (!g) return Fail(EULER_GPU_ENOGRAPH, "set_dense_feature_dtype: null graph");
-  if (dtype != EULER_GPU_F32 && dtype != EULER_GPU_BF16 && dtype != EULER_GPU_F16)
-    return Fail(EULER_GPU_EINVAL, "set_dense_feature_dtype: unknown dtype " + std::to_string(dtype) +
-                                      " (0 fp32, 1 bf16, 2 fp16)");
+  if (!KnownDtype(dtype))
+    return Fail(EULER_GPU_EINVAL, "set_dense_feature_dtype: unknown dtype " + std::to_string(dtype) + kDtypeCodes);
   if (g->feat_dtype == dtype) return EULER_GPU_OK;
   if (g->feat_dtype != EULER_GPU_F32)
     return Fail(EULER_GPU_EINVAL, "set_dense_feature_dtype: the table is already stored in 16 bits "
@@ -610,9 +609,8 @@ int euler_gpu_get_dense_feature_t(const euler_gpu_graph* g, void* stream, const 
                                   int64_t n, int32_t fid, int32_t dim, void* out_dev, int32_t out_dtype) {
   if (!g) return Fail(EULER_GPU_ENOGRAPH, "get_dense_feature: null graph");
   const int32_t in_dtype = g->feat_dtype;
-  if (out_dtype != EULER_GPU_F32 && out_dtype != EULER_GPU_BF16 && out_dtype != EULER_GPU_F16)
-    return Fail(EULER_GPU_EINVAL, "get_dense_feature: unknown dtype " + std::to_string(out_dtype) +
-                                      " (0 fp32, 1 bf16, 2 fp16)");
+  if (!KnownDtype(out_dtype))
+    return Fail(EULER_GPU_EINVAL, "get_dense_feature: unknown dtype " + std::to_string(out_dtype) + kDtypeCodes);
   // an fp32 table serves every output type (one rounding at the store); a 16-bit one fp32 or its own
   if (in_dtype != EULER_GPU_F32 && out_dtype != EULER_GPU_F32 && out_dtype != in_dtype)
     return Fail(EULER_GPU_EINVAL, "get_dense_feature: out_dtype " + std::to_string(out_dtype) +

@@ -222,8 +222,12 @@ __global__ __launch_bounds__(256) void SegmentReduceVec4Kernel(
   }
 }
 
-int GroupScatterKeys(hipStream_t st, const int32_t* idx, int64_t e, StreamBuf* scratch,
-                     const int32_t** keys, const uint32_t** perm) {
+// Groups the e scatter keys by destination for the reduces.  Keys that are already non-decreasing
+// (one look, one host wait) are used as they are: *keys = idx, *perm = nullptr.  Otherwise a stable
+// sort of (key, position) into `scratch`: *keys = the grouped keys, (*perm)[p] = the original
+// position of the p-th grouped update.
+static int GroupScatterKeys(hipStream_t st, const int32_t* idx, int64_t e, StreamBuf* scratch,
+                            const int32_t** keys, const uint32_t** perm) {
   *keys = idx;
   *perm = nullptr;
   if (e > 1) {
@@ -260,6 +264,11 @@ int GroupScatterKeys(hipStream_t st, const int32_t* idx, int64_t e, StreamBuf* s
     }
   }
   return EULER_GPU_OK;
+}
+
+int SegDest::Resolve() {
+  if (indices_ == nullptr) return EULER_GPU_OK;
+  return GroupScatterKeys(st_, indices_, seg_.e, &scratch_, &seg_.keys, &perm_);
 }
 
 // the fp32 reduce of the destinations of `seg`: update p is row ix.Row(ix.Pos(p)) of `upd`
@@ -379,10 +388,10 @@ int CheckMpReduce(const MpReduceCall& c, bool* nothing_to_do) {
   };
   const char* const not_in = " is neither fp32 nor the input's dtype";
   if (c.fp8) {      // an Fp8Rows table: the output and the weights each in any of the three types
-    if (!MpKnownDtype(c.out_dtype)) return fail("unknown out_dtype " + std::to_string(c.out_dtype) + kMpDtypeCodes);
-    if (c.weighted && !MpKnownDtype(c.w_dtype)) return fail("unknown w_dtype " + std::to_string(c.w_dtype) + kMpDtypeCodes);
+    if (!KnownDtype(c.out_dtype)) return fail("unknown out_dtype " + std::to_string(c.out_dtype) + kDtypeCodes);
+    if (c.weighted && !KnownDtype(c.w_dtype)) return fail("unknown w_dtype " + std::to_string(c.w_dtype) + kDtypeCodes);
   } else if (c.typed) {
-    if (!MpKnownDtype(c.in_dtype)) return fail("unknown dtype " + std::to_string(c.in_dtype) + kMpDtypeCodes);
+    if (!KnownDtype(c.in_dtype)) return fail("unknown dtype " + std::to_string(c.in_dtype) + kDtypeCodes);
     if (c.out_dtype != EULER_GPU_F32 && c.out_dtype != c.in_dtype)
       return fail("out_dtype " + std::to_string(c.out_dtype) + not_in);
     if (c.weighted && c.w_dtype != EULER_GPU_F32 && c.w_dtype != c.in_dtype)
@@ -428,19 +437,17 @@ int RunMpReduce(hipStream_t st, const MpReduceCall& c) {
   bool nothing_to_do;
   int rc = CheckMpReduce(c, &nothing_to_do);
   if (rc != EULER_GPU_OK || nothing_to_do) return rc;
-  SegSpec seg{nullptr, c.seg_ptr, c.count, 0, c.size};
-  const uint32_t* perm = nullptr;
-  StreamBuf scratch(st);      // stream-ordered scratch of the unsorted path, released on every exit
-  if (c.keyed) {
-    seg = SegSpec{c.keys, nullptr, 0, c.e, c.size};
-    rc = GroupScatterKeys(st, c.keys, c.e, &scratch, &seg.keys, &perm);
-    if (rc != EULER_GPU_OK) return rc;
-  }
+  // (an adapter states keys and e, or seg_ptr and count, never both: which form an entry takes is
+  // in its name, so CheckMpReduce has no form rule)
+  SegDest dst(st, c.keys, c.seg_ptr, c.count, c.e, c.size);
+  rc = dst.Resolve();
+  if (rc != EULER_GPU_OK) return rc;
+  const SegSpec& seg = dst.seg();
   // int64 ids: the index is word 0 of every id (little endian), and an id past the table (a
   // neighbour that is not a node of this graph, a dangling edge) reads the LAST row instead of
   // memory outside the table
   const bool ids = c.gather_kind == kGatherIds;
-  const MpwIndex ix{perm, static_cast<const int32_t*>(c.gather), ids ? 2 : 1,
+  const MpwIndex ix{dst.perm(), static_cast<const int32_t*>(c.gather), ids ? 2 : 1,
                     ids && c.params_rows > 0 ? (uint32_t)(c.params_rows - 1) : 0xFFFFFFFFu};
   if (c.fp8) return ReduceFp8(st, c, seg, ix);
   if (c.in_dtype != EULER_GPU_F32)

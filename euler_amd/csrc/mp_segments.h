@@ -1,11 +1,13 @@
 // The segment reduces of mp_kernels.hip (fp32) and mp_half_kernels.hip (bf16 / fp16 storage), shared
-// by both and by the ops built on them (edge_softmax, relation_reduce, top-k):
+// by both and by the ops built on them (edge_softmax, segment_attention, relation_reduce,
+// gather_reduce_norm):
 //  - device: where the updates of a destination are (SegSpec / SegBounds);
-//  - host: the launch shape of a reduce with a wave-slot per destination row (RowLaneShape), the
-//    grouping of scatter keys (GroupScatterKeys), and the ONE path of the sixteen scatter_* /
-//    gather_scatter* / gather_segment_reduce* entries: each fills an MpReduceCall and calls
-//    RunMpReduce, which checks it (CheckMpReduce: the only argument ladder), groups the keys,
-//    builds SegSpec / MpwIndex once and picks the launcher by (weighted, dtype, mode).
+//  - host: the launch shape of a reduce with a wave-slot per destination row (RowLaneShape); the
+//    destinations of a call (SegDest): the rule on its three forms, the grouping of scatter keys and
+//    the SegSpec, for every op above; and the ONE path of the sixteen scatter_* / gather_scatter* /
+//    gather_segment_reduce* entries: each fills an MpReduceCall and calls RunMpReduce, which checks
+//    it (CheckMpReduce: the only argument ladder), resolves its SegDest, builds the MpwIndex once and
+//    picks the launcher by (weighted, dtype, mode).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -88,9 +90,45 @@ inline LaneShape RowLaneShape(int32_t size, int64_t d, int n, int64_t dh, const 
 
 struct MpwIndex;      // mp_weighted.h
 
-// the storage type codes of a typed entry point (EULER_GPU_F32 / _BF16 / _F16), and how a message lists them
-inline bool MpKnownDtype(int32_t dt) { return dt == EULER_GPU_F32 || dt == EULER_GPU_BF16 || dt == EULER_GPU_F16; }
-constexpr const char* kMpDtypeCodes = " (0 fp32, 1 bf16, 2 fp16)";
+#pragma GCC visibility push(hidden)      // from here on: helpers of the host code, not names of the library
+// The destinations of one call as an entry point receives them - `indices` (a scatter key per update),
+// `seg_ptr` ([size + 1] offsets) or `count` (updates per destination) - from the rule on which forms
+// may come together to the SegSpec the kernels read.  An entry declares one where its `scratch` used to
+// be: it owns the grouped keys of the unsorted path, so it lives as long as the launches that read them.
+class SegDest {
+ public:
+  enum Forms {
+    kOneForm,           // exactly one of the three
+    kNoFormWhenEmpty,   // ... or none when e == 0: the keys of an empty tensor are null (gather_reduce_norm)
+  };
+  SegDest(hipStream_t st, const int32_t* indices, const int64_t* seg_ptr, int64_t count, int64_t e, int32_t size)
+      : st_(st), scratch_(st), indices_(indices), seg_{indices, seg_ptr, count, e, size} {}
+  // The two shared rules of a ladder, host arithmetic only: nullptr, or what the entry's message says
+  // after its own name.  Two calls, because every ladder has its empty case (and some their null
+  // checks) between them.
+  const char* FormError(Forms allowed = kOneForm) const {
+    const int forms = (indices_ != nullptr) + (seg_.ptr != nullptr) + (seg_.count > 0);
+    if (forms != 1 && !(forms == 0 && allowed == kNoFormWhenEmpty && seg_.e == 0))
+      return "pass exactly one of indices, seg_ptr and count";
+    if (seg_.count > 0 && seg_.e != (int64_t)seg_.size * seg_.count) return "e is not size * count";
+    return nullptr;
+  }
+  // (the sort of the keys and the positions of the updates are 32-bit)
+  const char* LengthError() const { return seg_.e >= (1LL << 31) ? "e >= 2^31" : nullptr; }
+  // mp_kernels.hip: groups the keys of the `indices` form (GroupScatterKeys: one look when they are
+  // sorted already, one host wait); nothing to do for the other two.  Before it, seg() has the keys as
+  // they came and perm() is null.
+  int Resolve();
+  const SegSpec& seg() const { return seg_; }
+  const uint32_t* perm() const { return perm_; }   // the original position of the p-th grouped update, or null
+
+ private:
+  hipStream_t st_;
+  StreamBuf scratch_;
+  const int32_t* indices_;
+  SegSpec seg_;
+  const uint32_t* perm_ = nullptr;
+};
 
 // One call of a scatter_* / gather_scatter* / gather_segment_reduce* entry, as its adapter in
 // mp_kernels.hip / mp_half_kernels.hip states it: {name, mode, params, d, size, out}, then what the
@@ -138,13 +176,6 @@ struct MpReduceCall {
   }
 };
 
-#pragma GCC visibility push(hidden)
-// mp_kernels.hip: groups the e scatter keys by destination for the reduces.  Keys that are already
-// non-decreasing (one look, one host wait) are used as they are: *keys = idx, *perm = nullptr.
-// Otherwise a stable sort of (key, position) into `scratch`: *keys = the grouped keys, (*perm)[p] =
-// the original position of the p-th grouped update.
-int GroupScatterKeys(hipStream_t st, const int32_t* idx, int64_t e, StreamBuf* scratch,
-                     const int32_t** keys, const uint32_t** perm);
 // mp_kernels.hip: the argument ladder, in its one order: dtype codes and weight alignment; mode,
 // heads, heads | d; negative shape; size == 0 || d == 0 (*nothing_to_do: OK, nothing is touched - the
 // callers hand over null for empty tensors, so the null check comes after); null buffers; e >= 2^31;

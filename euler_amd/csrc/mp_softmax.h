@@ -45,6 +45,20 @@ constexpr float kSmxExpFloor = -86.0f;
 
 EG_MPW_HD int32_t SmxHeadsPerWave(int32_t heads) { return (heads <= 64 && 64 % heads == 0) ? heads : 1; }
 
+// The grid of a kernel over the segments longer than kSmxShort (host; size > 0): x = chunks of kSmxBlock
+// destinations, at most 256 * 32 (the chunks are strided); y = blocks that share the long
+// destinations of a chunk - few destinations: more blocks a chunk.  edge_softmax and
+// segment_attention both launch by it: the two walk the long segments with the same lanes, and the
+// summation order above must stay a function of n and heads alone in both.
+struct SmxLongGrid { unsigned chunks, share; };
+inline SmxLongGrid SmxLongGridFor(int32_t size) {
+  int64_t chunks = ((int64_t)size + kSmxBlock - 1) / kSmxBlock;
+  if (chunks > 256 * 32) chunks = 256 * 32;
+  int64_t share = 2048 / chunks;
+  share = share < 1 ? 1 : (share > 16 ? 16 : share);
+  return SmxLongGrid{(unsigned)chunks, (unsigned)share};
+}
+
 EG_MPW_HD float SmxSub(float a, float b) { return MpwAdd(a, -b); }       // fl(a - b)
 EG_MPW_HD float SmxMax(float m, float x) { return x > m ? x : m; }
 EG_MPW_HD float SmxNegInf() { return BitsF32(0xff800000u); }

@@ -228,7 +228,7 @@ int DispatchRelation(hipStream_t st, int32_t in_dtype, int32_t out_dtype, const 
                                     : LaunchRelation<MODE, kF16, true>(st, A);
 }
 
-int RelFail(const char* why) { return Fail(EULER_GPU_EINVAL, std::string("relation_reduce: ") + why); }
+int RelFail(const std::string& why) { return Fail(EULER_GPU_EINVAL, "relation_reduce: " + why); }
 
 }  // namespace
 }  // namespace euler_gpu
@@ -244,13 +244,11 @@ extern "C" int euler_gpu_relation_reduce(void* stream, int32_t mode, const void*
   if (mode < 0 || mode > 3) return RelFail("mode is 0 add, 1 max, 2 mean over the destination, 3 mean over the bucket");
   if (num_relations < 1) return RelFail("num_relations < 1");
   if (e < 0 || d < 0 || size < 0 || count < 0 || params_rows < 0) return RelFail("bad shape");
-  if (in_dtype != EULER_GPU_F32 && in_dtype != EULER_GPU_BF16 && in_dtype != EULER_GPU_F16)
-    return RelFail("unknown dtype (0 fp32, 1 bf16, 2 fp16)");
+  if (!KnownDtype(in_dtype)) return RelFail(std::string("unknown dtype") + kDtypeCodes);
   if (out_dtype != EULER_GPU_F32 && out_dtype != in_dtype) return RelFail("out_dtype is fp32 or in_dtype");
-  if ((indices_dev != nullptr) + (seg_ptr_dev != nullptr) + (count > 0) != 1)
-    return RelFail("pass exactly one of indices, seg_ptr and count");
-  if (count > 0 && e != (int64_t)size * count) return RelFail("e is not size * count");
-  if (e >= (1LL << 31)) return RelFail("e >= 2^31");
+  SegDest dst((hipStream_t)stream, indices_dev, seg_ptr_dev, count, e, size);
+  if (const char* why = dst.FormError()) return RelFail(why);
+  if (const char* why = dst.LengthError()) return RelFail(why);
   if ((int64_t)size * num_relations >= (1LL << 31)) return RelFail("size * num_relations >= 2^31");
   if (mode >= 2 && (e >= (1LL << 24) || count >= (1LL << 24)))
     return RelFail("a mean needs fewer than 2^24 updates (its counts are exact fp32)");
@@ -261,20 +259,14 @@ extern "C" int euler_gpu_relation_reduce(void* stream, int32_t mode, const void*
     if (params_rows < 1 || (gather_dev == nullptr && params_rows < e))
       return RelFail("the table has fewer rows than the updates read");
   }
+  const int rc = dst.Resolve();
+  if (rc != EULER_GPU_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  const int32_t* keys = indices_dev;
-  const uint32_t* perm = nullptr;
-  StreamBuf scratch(st);                // the grouped keys of the unsorted path: one sort a call
-  if (indices_dev) {
-    const int rc = GroupScatterKeys(st, indices_dev, e, &scratch, &keys, &perm);
-    if (rc != EULER_GPU_OK) return rc;
-  }
   // every index is clamped to the table's last row (int64 ids: the low word, as
   // euler_gpu_gather_segment_reduce_ids): no update reads outside the table
   const uint32_t row_max = (uint32_t)std::min<int64_t>(params_rows > 0 ? params_rows - 1 : 0, 0x7FFFFFFF);
-  const MpwIndex ix{perm, static_cast<const int32_t*>(gather_dev), gather_is_ids ? 2 : 1, row_max};
-  const RelArgs A{params_dev, SegSpec{keys, seg_ptr_dev, count, e, size}, ix, edge_type_dev, num_relations,
-                  e, d, out_dev, counts_dev};
+  const MpwIndex ix{dst.perm(), static_cast<const int32_t*>(gather_dev), gather_is_ids ? 2 : 1, row_max};
+  const RelArgs A{params_dev, dst.seg(), ix, edge_type_dev, num_relations, e, d, out_dev, counts_dev};
   if (mode == 0) return DispatchRelation<kRelAdd>(st, in_dtype, out_dtype, A);
   if (mode == 1) return DispatchRelation<kRelMax>(st, in_dtype, out_dtype, A);
   if (mode == 2) return DispatchRelation<kRelMeanDst>(st, in_dtype, out_dtype, A);

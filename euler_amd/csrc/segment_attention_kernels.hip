@@ -618,8 +618,6 @@ __global__ __launch_bounds__(kSmxBlock) void SegAttLongKernel(const AttArgs A, c
   ZeroOutside(A, block * kSmxBlock + threadIdx.x, (int64_t)gridDim.x * gridDim.y * kSmxBlock);
 }
 
-bool KnownDtype(int32_t t) { return t == EULER_GPU_F32 || t == EULER_GPU_BF16 || t == EULER_GPU_F16; }
-
 Table MakeTable(const void* p, int32_t dt, int64_t rows) {
   const uintptr_t align = dt == EULER_GPU_F32 ? 16 : 8;
   return Table{p, dt, (uint32_t)(rows > 0 ? rows - 1 : 0), (uintptr_t)p % align == 0};
@@ -699,11 +697,8 @@ int Launch(hipStream_t st, AttArgs A, bool uniform, int64_t count) {
     EG_HIP(hipGetLastError());
   }
   if (run_long) {
-    int64_t chunks = ((int64_t)A.seg.size + kSmxBlock - 1) / kSmxBlock;
-    if (chunks > 256 * 32) chunks = 256 * 32;
-    int64_t share = 2048 / chunks;                      // few destinations: more blocks a chunk
-    share = share < 1 ? 1 : (share > 16 ? 16 : share);
-    const dim3 grid((unsigned)chunks, (unsigned)share);
+    const SmxLongGrid g = SmxLongGridFor(A.seg.size);
+    const dim3 grid(g.chunks, g.share);
     const int32_t hc = SmxHeadsPerWave(A.heads);
     switch (ShortMode(A, dot_a, rows_c)) {                // (the same load modes)
       case 1: hipLaunchKernelGGL((SegAttLongKernel<GRAD, 1>), grid, dim3(kSmxBlock), 0, st, A, hc, !run_short); break;
@@ -723,18 +718,18 @@ struct AttCall {
   const void* k; int32_t k_dt; int64_t k_rows;
   const void* v; int32_t v_dt; int64_t v_rows;
   const void* gather; int32_t gather_is_ids;
-  const int32_t* indices; const int64_t* seg_ptr; int64_t count, e, d, dv;
+  int64_t count, e, d, dv;
   int32_t heads, size;
   float scale, slope;
 };
 
-// the argument ladder both entries share; *nothing: OK and nothing to launch
-int CheckCall(const AttCall& c, bool* nothing) {
+// the argument ladder both entries share (dst: the call's destinations); *nothing: OK and nothing to launch
+int CheckCall(const AttCall& c, const SegDest& dst, bool* nothing) {
   const std::string w(c.name);
   *nothing = false;
   if (c.kind != kAttDot && c.kind != kAttAdditive) return Fail(EULER_GPU_EINVAL, w + ": kind is 0 (dot) or 1 (additive)");
   if (!KnownDtype(c.k_dt) || (c.q && !KnownDtype(c.q_dt)) || (c.v && !KnownDtype(c.v_dt)))
-    return Fail(EULER_GPU_EINVAL, w + ": unknown dtype (0 fp32, 1 bf16, 2 fp16)");
+    return Fail(EULER_GPU_EINVAL, w + ": unknown dtype" + kDtypeCodes);
   if (c.heads < 1) return Fail(EULER_GPU_EINVAL, w + ": heads < 1");
   if (c.e < 0 || c.size < 0 || c.count < 0 || c.d < 0 || c.dv < 0) return Fail(EULER_GPU_EINVAL, w + ": bad shape");
   if (c.kind == kAttAdditive ? c.d != c.heads : c.d % c.heads != 0)
@@ -742,11 +737,9 @@ int CheckCall(const AttCall& c, bool* nothing) {
   if (c.dv % c.heads != 0) return Fail(EULER_GPU_EINVAL, w + ": heads must divide dv");
   if (c.kind == kAttAdditive && !c.v) return Fail(EULER_GPU_EINVAL, w + ": additive attention needs v");
   if (!c.v && c.dv != c.d) return Fail(EULER_GPU_EINVAL, w + ": without v, dv is d");
-  if ((c.indices != nullptr) + (c.seg_ptr != nullptr) + (c.count > 0) != 1)
-    return Fail(EULER_GPU_EINVAL, w + ": pass exactly one of indices, seg_ptr and count");
-  if (c.count > 0 && c.e != (int64_t)c.size * c.count) return Fail(EULER_GPU_EINVAL, w + ": e is not size * count");
+  if (const char* why = dst.FormError()) return Fail(EULER_GPU_EINVAL, w + ": " + why);
   if (c.size == 0 && c.e == 0) { *nothing = true; return EULER_GPU_OK; }
-  if (c.e >= (1LL << 31)) return Fail(EULER_GPU_EINVAL, w + ": e >= 2^31");
+  if (const char* why = dst.LengthError()) return Fail(EULER_GPU_EINVAL, w + ": " + why);
   if (c.e > 0 && (!c.k || !c.gather)) return Fail(EULER_GPU_EINVAL, w + ": null buffer");
   if (c.e > 0 && (c.k_rows < 1 || (c.v && c.v_rows < 1) || c.k_rows >= (1LL << 31) || c.v_rows >= (1LL << 31)))
     return Fail(EULER_GPU_EINVAL, w + ": a table has no rows, or 2^31 or more");
@@ -771,21 +764,16 @@ int euler_gpu_segment_attention(void* stream, int32_t kind, const void* q_dev, i
                                 float scale, float negative_slope, void* out_dev, int32_t out_dtype,
                                 float* alpha_dev, float* logits_dev) {
   const AttCall c{"segment_attention", kind, q_dev, q_dtype, q_rows, q_index_dev, k_dev, k_dtype, k_rows,
-                  v_dev, v_dtype, v_rows, gather_dev, gather_is_ids, indices_dev, seg_ptr_dev, count, e, d, dv,
-                  heads, size, scale, negative_slope};
+                  v_dev, v_dtype, v_rows, gather_dev, gather_is_ids, count, e, d, dv, heads, size, scale, negative_slope};
+  hipStream_t st = (hipStream_t)stream;
+  SegDest dst(st, indices_dev, seg_ptr_dev, count, e, size);
   bool nothing;
-  const int rc = CheckCall(c, &nothing);
+  int rc = CheckCall(c, dst, &nothing);
   if (rc != EULER_GPU_OK || nothing) return rc;
   if (!KnownDtype(out_dtype)) return Fail(EULER_GPU_EINVAL, "segment_attention: unknown out_dtype");
   if (size > 0 && dv > 0 && !out_dev) return Fail(EULER_GPU_EINVAL, "segment_attention: null buffer");
-  hipStream_t st = (hipStream_t)stream;
-  const int32_t* keys = indices_dev;
-  const uint32_t* perm = nullptr;
-  StreamBuf scratch(st), stage(st);
-  if (indices_dev && e > 0) {
-    const int g = GroupScatterKeys(st, indices_dev, e, &scratch, &keys, &perm);
-    if (g != EULER_GPU_OK) return g;
-  }
+  if ((rc = dst.Resolve()) != EULER_GPU_OK) return rc;
+  StreamBuf stage(st);
   AttArgs A{};
   A.kind = kind;
   A.qa = MakeTable(q_dev, q_dtype, q_rows); A.qa_index = q_index_dev; A.da = d;
@@ -793,7 +781,7 @@ int euler_gpu_segment_attention(void* stream, int32_t kind, const void* q_dev, i
   A.sq = A.qa; A.sq_index = q_index_dev; A.sk = A.ka;
   A.vc = v_dev ? MakeTable(v_dev, v_dtype, v_rows) : A.ka; A.dc = dv;
   A.gsrc = static_cast<const int32_t*>(gather_dev); A.gstride = gather_is_ids ? 2 : 1;
-  A.seg = SegSpec{keys, seg_ptr_dev, count, e, size}; A.perm = perm; A.e = e; A.heads = heads;
+  A.seg = dst.seg(); A.perm = dst.perm(); A.e = e; A.heads = heads;
   A.scale = scale; A.slope = negative_slope;
   A.buf = alpha_dev; A.logits = logits_dev;
   A.out = out_dev; A.out_dt = out_dtype;
@@ -818,22 +806,16 @@ int euler_gpu_segment_attention_grad(void* stream, int32_t kind, const void* q_d
                                      const float* alpha_dev, const void* grad_dev, int32_t grad_dtype,
                                      float* ds_dev, float* dq_dst_dev) {
   const AttCall c{"segment_attention_grad", kind, q_dev, q_dtype, q_rows, q_index_dev, k_dev, k_dtype, k_rows,
-                  v_dev, v_dtype, v_rows, gather_dev, gather_is_ids, indices_dev, seg_ptr_dev, count, e, d, dv,
-                  heads, size, scale, negative_slope};
+                  v_dev, v_dtype, v_rows, gather_dev, gather_is_ids, count, e, d, dv, heads, size, scale, negative_slope};
+  hipStream_t st = (hipStream_t)stream;
+  SegDest dst(st, indices_dev, seg_ptr_dev, count, e, size);
   bool nothing;
-  const int rc = CheckCall(c, &nothing);
+  int rc = CheckCall(c, dst, &nothing);
   if (rc != EULER_GPU_OK || nothing) return rc;
   if (!KnownDtype(grad_dtype)) return Fail(EULER_GPU_EINVAL, "segment_attention_grad: unknown grad dtype");
   if ((e > 0 && (!alpha_dev || !ds_dev)) || (size > 0 && d > 0 && !dq_dst_dev) || (size > 0 && dv > 0 && !grad_dev))
     return Fail(EULER_GPU_EINVAL, "segment_attention_grad: null buffer");
-  hipStream_t st = (hipStream_t)stream;
-  const int32_t* keys = indices_dev;
-  const uint32_t* perm = nullptr;
-  StreamBuf scratch(st);
-  if (indices_dev && e > 0) {
-    const int g = GroupScatterKeys(st, indices_dev, e, &scratch, &keys, &perm);
-    if (g != EULER_GPU_OK) return g;
-  }
+  if ((rc = dst.Resolve()) != EULER_GPU_OK) return rc;
   const Table tk = MakeTable(k_dev, k_dtype, k_rows);
   AttArgs A{};
   A.kind = kind;
@@ -842,7 +824,7 @@ int euler_gpu_segment_attention_grad(void* stream, int32_t kind, const void* q_d
   A.sq = MakeTable(q_dev, q_dtype, q_rows); A.sq_index = q_index_dev; A.sk = tk;
   A.vc = tk; A.dc = d;
   A.gsrc = static_cast<const int32_t*>(gather_dev); A.gstride = gather_is_ids ? 2 : 1;
-  A.seg = SegSpec{keys, seg_ptr_dev, count, e, size}; A.perm = perm; A.e = e; A.heads = heads;
+  A.seg = dst.seg(); A.perm = dst.perm(); A.e = e; A.heads = heads;
   A.scale = scale; A.slope = negative_slope;
   A.alpha_in = alpha_dev; A.buf = ds_dev; A.logits = nullptr;
   A.out = dq_dst_dev; A.out_dt = EULER_GPU_F32;

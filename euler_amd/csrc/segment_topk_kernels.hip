@@ -226,8 +226,6 @@ __global__ __launch_bounds__(256) void TkGradKernel(const void* __restrict__ gra
   }
 }
 
-bool TkKnownDtype(int32_t t) { return t == EULER_GPU_F32 || t == EULER_GPU_BF16 || t == EULER_GPU_F16; }
-
 }  // namespace
 }  // namespace euler_gpu
 
@@ -241,8 +239,8 @@ int euler_gpu_gather_segment_topk(void* stream, const void* params_dev, int32_t 
                                   void* out_dev, int32_t out_dtype, int32_t* sel_dev) {
   const std::string what("gather_segment_topk");
   if (k < 1 || k > kTkMaxK) return Fail(EULER_GPU_EINVAL, what + ": k outside 1..16");
-  if (!TkKnownDtype(in_dtype) || !TkKnownDtype(out_dtype))
-    return Fail(EULER_GPU_EINVAL, what + ": unknown dtype (0 fp32, 1 bf16, 2 fp16)");
+  if (!KnownDtype(in_dtype) || !KnownDtype(out_dtype))
+    return Fail(EULER_GPU_EINVAL, what + ": unknown dtype" + kDtypeCodes);
   if (out_dtype != EULER_GPU_F32 && out_dtype != in_dtype)
     return Fail(EULER_GPU_EINVAL, what + ": out is fp32 or of the input's dtype");
   if (size < 0 || e < 0 || d < 0 || count < 0) return Fail(EULER_GPU_EINVAL, what + ": size, e, d or count < 0");
@@ -271,7 +269,7 @@ int euler_gpu_segment_topk_grad(void* stream, const void* grad_dev, int32_t grad
                                 int64_t e, int64_t d, int32_t size, int32_t k, float* per_edge_dev) {
   const std::string what("segment_topk_grad");
   if (k < 1 || k > kTkMaxK) return Fail(EULER_GPU_EINVAL, what + ": k outside 1..16");
-  if (!TkKnownDtype(grad_dtype)) return Fail(EULER_GPU_EINVAL, what + ": unknown dtype (0 fp32, 1 bf16, 2 fp16)");
+  if (!KnownDtype(grad_dtype)) return Fail(EULER_GPU_EINVAL, what + ": unknown dtype" + kDtypeCodes);
   if (size < 0 || e < 0 || d < 0) return Fail(EULER_GPU_EINVAL, what + ": size, e or d < 0");
   if (e >= (1LL << 31) || d >= (1LL << 31)) return Fail(EULER_GPU_EINVAL, what + ": e or d >= 2^31");
   if (e == 0 || d == 0) return EULER_GPU_OK;

@@ -160,14 +160,12 @@ int DispatchTarget(hipStream_t st, const SgArgs& a, int32_t target_dtype, int32_
   return DispatchContext<kF16>(st, a, context_dtype, grad);
 }
 
-bool SgKnownDtype(int32_t t) { return t == EULER_GPU_F32 || t == EULER_GPU_BF16 || t == EULER_GPU_F16; }
-
 // The checks both entries share.  -> EULER_GPU_OK with *run = false when b == 0.
 int CheckSkipgramArgs(const char* what, const SgArgs& a, int32_t target_dtype, int32_t context_dtype, bool* run) {
   *run = false;
   const std::string w(what);
-  if (!SgKnownDtype(target_dtype) || !SgKnownDtype(context_dtype))
-    return Fail(EULER_GPU_EINVAL, w + ": unknown dtype (0 fp32, 1 bf16, 2 fp16)");
+  if (!KnownDtype(target_dtype) || !KnownDtype(context_dtype))
+    return Fail(EULER_GPU_EINVAL, w + ": unknown dtype" + kDtypeCodes);
   if (a.b < 0 || a.k < 0) return Fail(EULER_GPU_EINVAL, w + ": b or k < 0");
   if (a.p < 1 || a.d < 1) return Fail(EULER_GPU_EINVAL, w + ": p < 1 or d < 1");
   if (a.target_rows < 1 || a.context_rows < 1) return Fail(EULER_GPU_EINVAL, w + ": a table with fewer than 1 row");

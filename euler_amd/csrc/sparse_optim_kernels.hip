@@ -144,8 +144,8 @@ extern "C" int euler_gpu_sparse_optim_step(void* stream, int32_t kind, void* tab
   const std::string what("sparse_optim_step");
   if (kind < kSoSgd || kind > kSoAdam)
     return Fail(EULER_GPU_EINVAL, what + ": unknown kind (0 sgd, 1 momentum, 2 adagrad, 3 adam)");
-  if (!EsKnownDtype(table_dtype) || !EsKnownDtype(grad_dtype))
-    return Fail(EULER_GPU_EINVAL, what + ": unknown dtype (0 fp32, 1 bf16, 2 fp16)");
+  if (!KnownDtype(table_dtype) || !KnownDtype(grad_dtype))
+    return Fail(EULER_GPU_EINVAL, what + ": unknown dtype" + kDtypeCodes);
   if (grad_dtype != EULER_GPU_F32 && grad_dtype != table_dtype)
     return Fail(EULER_GPU_EINVAL, what + ": grad is fp32 or of the table's dtype");
   if (!SoScalarOk(lr) || !SoScalarOk(mu) || !SoScalarOk(eps) || !SoScalarOk(om1) || !SoScalarOk(om2) ||

@@ -184,7 +184,6 @@ __global__ __launch_bounds__(256) void SuperviseLossGradKernel(const float* __re
   }
 }
 
-bool SvKnownDtype(int32_t t) { return t == EULER_GPU_F32 || t == EULER_GPU_BF16 || t == EULER_GPU_F16; }
 uintptr_t SvElemSize(int32_t t) { return t == EULER_GPU_F32 ? 4 : 2; }
 
 // b and c of both entries
@@ -209,8 +208,8 @@ int euler_gpu_supervise_loss(void* stream, const void* logits_dev, int32_t logit
                              int64_t* hist_dev) {
   const std::string w("supervise_loss");
   const bool tensor_form = labels_dev != nullptr, graph_form = graph != nullptr;
-  if (!SvKnownDtype(logits_dtype) || (tensor_form && !SvKnownDtype(labels_dtype)))
-    return Fail(EULER_GPU_EINVAL, w + ": unknown dtype (0 fp32, 1 bf16, 2 fp16)");
+  if (!KnownDtype(logits_dtype) || (tensor_form && !KnownDtype(labels_dtype)))
+    return Fail(EULER_GPU_EINVAL, w + ": unknown dtype" + kDtypeCodes);
   const int rs = CheckSuperviseShape(w, b, c);
   if (rs != EULER_GPU_OK) return rs;
   if (hist_dev && thresholds < 2) return Fail(EULER_GPU_EINVAL, w + ": fewer than 2 thresholds");
@@ -271,7 +270,7 @@ int euler_gpu_supervise_loss(void* stream, const void* logits_dev, int32_t logit
 int euler_gpu_supervise_loss_grad(void* stream, const float* diff_dev, const float* g_dev, int64_t b, int64_t c,
                                   void* g_logits_dev, int32_t logits_dtype) {
   const std::string w("supervise_loss_grad");
-  if (!SvKnownDtype(logits_dtype)) return Fail(EULER_GPU_EINVAL, w + ": unknown dtype (0 fp32, 1 bf16, 2 fp16)");
+  if (!KnownDtype(logits_dtype)) return Fail(EULER_GPU_EINVAL, w + ": unknown dtype" + kDtypeCodes);
   const int rs = CheckSuperviseShape(w, b, c);
   if (rs != EULER_GPU_OK) return rs;
   if (b == 0) return EULER_GPU_OK;
