@@ -2240,6 +2240,101 @@ def rank_metric(name, rank):
     return (r < float(name[3:])).to(torch.float64).mean()
 
 
+# ---- exact search over a whole table (knn/knn.py:35-77; utils/metrics.py:51-83 over every row) --
+
+_TS_METRIC = {"ip": 0, "cos": 1, "l2": 2, "l1": 3}
+_TS_MAX_K = 64
+
+
+def _table_search_args(name, table, queries, metric, exclude, target=None):
+    """checks and prepares what table_topk and table_rank share -> (table, queries, metric code,
+    exclude | None, target | None), contiguous"""
+    if metric not in _TS_METRIC:
+        raise ValueError("%s: metric is one of %s" % (name, ", ".join(_TS_METRIC)))
+    _dt(name, table)
+    _dt(name, queries)
+    if table.dim() != 2 or queries.dim() != 2 or table.shape[1] != queries.shape[1] or table.shape[1] < 1:
+        raise ValueError("%s: table is [N, d] and queries is [Q, d], one column at least" % name)
+    q = queries.shape[0]
+    if table.shape[0] >= 2 ** 31 or q >= 2 ** 31:
+        raise ValueError("%s: N and Q must stay below 2^31" % name)
+    ids = []
+    for what, t in (("exclude", exclude), ("target", target)):
+        if t is not None:
+            if t.dtype != torch.int64 or t.dim() != 1 or t.shape[0] != q:
+                raise ValueError("%s: %s is [Q] int64" % (name, what))
+            t = t.contiguous()
+        ids.append(t)
+    _need_cuda(table, queries, *[t for t in ids if t is not None])
+    for t in [queries] + [t for t in ids if t is not None]:
+        if t.device != table.device:
+            raise ValueError("%s: every tensor must be on the table's device" % name)
+    return table.detach().contiguous(), queries.detach().contiguous(), _TS_METRIC[metric], ids[0], ids[1]
+
+
+def table_topk(table, queries, k, metric="ip", exclude=None, ids=None):
+    """The k best rows of a whole embedding table for each query, exactly and in one pass (the
+    step of the reference's knn/knn.py:35-77, which returns (distance, idx) through a faiss
+    index).  table [N, d] and queries [Q, d] are fp32, bf16 or fp16, each its own dtype, widened
+    exactly.  metric: "ip" = sum q_c x_c and "cos" = (ip * inv_q) * inv_x with
+    inv = 1 / sqrt(max(sum x_c^2, 1e-12)) - larger is better; "l2" = sum (q_c - x_c)^2 (the
+    squared distance, as faiss METRIC_L2 returns it) and "l1" = sum |q_c - x_c| (TransE's energy
+    with q = h + r) - smaller is better.  Row a precedes row b iff its score is better, or b's is
+    NaN and a's is not, or the two compare equal and a < b: a total order, so equal scores come out
+    in row order on every run.  exclude [Q] int64 (optional) is a row the query must not return -
+    its own row when the queries come from the table; a value outside [0, N) excludes nothing.
+    Returns (scores [Q, k] fp32, rows [Q, k] int64), best first; past the number of candidates
+    rows = -1 and scores = -inf (ip, cos) or +inf (l2, l1).  With ids ([N] int64, the node id of
+    every row, as knn.py maps I through its id file) the second output is ids[rows], -1 kept.
+    1 <= k <= 64.  No [Q, N] block is built: scratch is O(Q * k * slabs).  All arithmetic is fp32
+    in a fixed order (euler_amd/csrc/table_search.h): a score depends on the two rows, their dtypes
+    and the rows' alignment alone, never on Q, N, k or the grid, and the same call returns the same
+    bits.  Forward only: the outputs carry no gradient.  No host wait."""
+    name = "table_topk"
+    if not isinstance(k, int) or isinstance(k, bool) or k < 1 or k > _TS_MAX_K:
+        raise ValueError("%s: k is an int in 1..%d" % (name, _TS_MAX_K))
+    table, queries, code, exclude, _ = _table_search_args(name, table, queries, metric, exclude)
+    n, d, q, dev = table.shape[0], table.shape[1], queries.shape[0], table.device
+    if ids is not None:
+        if ids.dtype != torch.int64 or ids.dim() != 1 or ids.shape[0] != n or ids.device != dev:
+            raise ValueError("%s: ids is [N] int64 on the table's device" % name)
+    scores = torch.empty((q, k), dtype=_F32, device=dev)
+    rows = torch.empty((q, k), dtype=torch.int64, device=dev)
+    if q > 0:
+        with _on(dev):
+            check(lib().euler_gpu_table_topk(_stream(), code, _ptr(table) if n else None, _DT[table.dtype], n, d,
+                                             _ptr(queries), _DT[queries.dtype], q, k, _ptr(exclude), _ptr(scores),
+                                             _ptr(rows)))
+    if ids is not None and n > 0:
+        rows = torch.where(rows >= 0, ids[rows.clamp(min=0)], rows)
+    return scores, rows
+
+
+def table_rank(table, queries, target, metric="ip", exclude=None):
+    """The rank of row target[q] among ALL rows of the table for each query - the evaluation
+    TransE / DistMult / DeepWalk results are reported with, where skipgram_loss's rank (the
+    reference's utils/metrics.py:51-83) counts sampled negatives only.  table, queries, metric
+    and exclude as in table_topk; target [Q] int64.  rank[q] (int32) is the number of rows r,
+    r != target[q] and r != exclude[q], whose score is better than or EQUAL to that of row
+    target[q]: a tie goes against the target, as in skipgram_loss, so rank_metric applies
+    unchanged (mrr, mr, hit@k).  A NaN score is never counted; a target outside [0, N) gives -1.
+    The target's score comes from the same lane arithmetic as every other row's (bit-equal to the
+    score table_topk returns for it).  No [Q, N] block, integer partial counts per slab of rows;
+    forward only; no host wait."""
+    name = "table_rank"
+    if target is None:
+        raise ValueError("%s: target is [Q] int64" % name)
+    table, queries, code, exclude, target = _table_search_args(name, table, queries, metric, exclude, target)
+    n, d, q = table.shape[0], table.shape[1], queries.shape[0]
+    rank = torch.empty(q, dtype=torch.int32, device=table.device)
+    if q > 0:
+        with _on(table.device):
+            check(lib().euler_gpu_table_rank(_stream(), code, _ptr(table) if n else None, _DT[table.dtype], n, d,
+                                             _ptr(queries), _DT[queries.dtype], q, _ptr(target), _ptr(exclude),
+                                             _ptr(rank)))
+    return rank
+
+
 # ---- the supervised loss head (tf_euler/python/mp_utils/base.py:24-47) -------------------------
 
 _SV_SCRATCH = {}

@@ -1341,6 +1341,42 @@ int euler_gpu_skipgram_loss_grad(void* stream, const void* target_dev, int32_t t
                                  const int64_t* neg_dev, int64_t b, int64_t p, int64_t k,
                                  int64_t d, const float* logits_dev, const float* g_dev,
                                  float* g_src_dev, float* g_pos_dev, float* g_neg_dev);
+/* table_topk / table_rank: exact search over a whole embedding table - what a user does with a
+ * trained table.  table_topk is the step of the reference's knn/knn.py:35-77 (the nearest
+ * embeddings of a set of queries, returned as (distance, idx) through faiss) without an index and
+ * without a [q, n] score block; table_rank is the rank behind mrr_score / mr_score / hitk_score of
+ * utils/metrics.py:51-83, taken over EVERY row of the table where the reference ranks a positive
+ * against sampled negatives only.
+ * table_dev [n, d] and queries_dev [q, d]: fp32, bf16 or fp16, each its own type, widened exactly.
+ * metric: 0 ip (sum q_c x_c, larger is better), 1 cos ((ip * inv_q) * inv_x,
+ * inv = 1 / sqrt(max(sum x_c^2, 1e-12)), larger is better), 2 l2 (sum (q_c - x_c)^2, the squared
+ * distance as faiss METRIC_L2 returns it, smaller is better), 3 l1 (sum |q_c - x_c|, smaller is
+ * better: TransE's energy with q = h + r).  All arithmetic is correctly rounded fp32 in the
+ * summation order stated in euler_amd/csrc/table_search.h: a score is a function of the two rows,
+ * their types and the chunk width alone; the same call returns the same bits.
+ * Row a precedes row b for a query iff its score is better, or b's is NaN and a's is not, or the
+ * two compare equal (+0 == -0, any two NaNs) and a < b.
+ * exclude_dev [q] int64, or NULL: a row the query neither returns nor counts (its own row when
+ * the queries come from the table); a value outside [0, n) excludes nothing.
+ * table_topk: rows_out [q, k] int64 = the first min(k, candidates) rows in that order,
+ * scores_out [q, k] fp32 their scores; past the candidates rows = -1 and scores = -inf (ip, cos)
+ * or +inf (l2, l1).
+ * table_rank: rank_out [q] int32 = the number of rows r != target[q], r != exclude[q] whose score
+ * is better than or EQUAL to that of row target_dev[q] (a tie goes against the target, the rule of
+ * skipgram_loss's rank; a NaN score is never counted); -1 for a target outside [0, n).
+ * Both enqueue two kernels and take their scratch (O(q * k * slabs), slabs <= 512 a function of n
+ * and q alone) from the stream's pool: no host wait.  The outputs are written by the last kernel
+ * alone.  EULER_GPU_EINVAL, checked before anything is enqueued: a metric outside 0..3, an unknown
+ * dtype, d < 1, d >= 2^31, n or q outside 0 .. 2^31 - 1, k outside 1..64, a null required buffer
+ * (table_dev may be NULL when n == 0), a buffer not aligned to its type.  q == 0 touches nothing
+ * (every buffer may be NULL); n == 0 writes the fills (top-k) or -1 (rank). */
+int euler_gpu_table_topk(void* stream, int32_t metric, const void* table_dev, int32_t table_dtype,
+                         int64_t n, int64_t d, const void* queries_dev, int32_t q_dtype, int64_t q,
+                         int64_t k, const int64_t* exclude_dev, float* scores_out,
+                         int64_t* rows_out);
+int euler_gpu_table_rank(void* stream, int32_t metric, const void* table_dev, int32_t table_dtype,
+                         int64_t n, int64_t d, const void* queries_dev, int32_t q_dtype, int64_t q,
+                         const int64_t* target_dev, const int64_t* exclude_dev, int32_t* rank_out);
 /* supervise_loss: the loss head of the supervised models (GraphSAGE, GCN, GAT, ... and the graph
  * classifiers: SuperviseModel.__call__ after out_fc, tf_euler/python/mp_utils/base.py:24-47,
  * SuperviseSolution of solution/base_supervise.py, GraphModel of mp_utils/base_graph.py:24-47,
