@@ -112,6 +112,41 @@ def named_twice(rng, probe, extra=(), repeat=2, total=None):
     return ids
 
 
+SEARCH_Q, SEARCH_K = 33, 64               # two query tiles; more entries than probe rows: zero rows fill the tail
+
+
+def boundary_rows(n_elems, d, elem_bytes):
+    """the probe rows that straddle a boundary, then the last row"""
+    rows = n_elems // d
+    return np.array([straddling_row(b, d) for b in boundaries(elem_bytes) if b < rows * d] + [rows - 1], np.int64)
+
+
+def zero_rows(probe, rows):
+    """three rows that are no probe row: the lowest (the first to fill the tail of a list), one a
+    third into the table, one just before the last two"""
+    low = int(np.setdiff1d(np.arange(len(probe) + 1), probe)[0])
+    out = [low, rows // 3, rows - 3]
+    assert not np.isin(out, probe).any() and low < rows // 3 < rows - 3
+    return out
+
+
+def search_case(rng, probe, values, n_elems, d, elem_bytes):
+    """what table_topk / table_rank are asked over the big table -> (queries [33, d] float32, exclude
+    [33], target [33]).  Queries: every probe row (the rows at the boundaries among them), a zero row,
+    random rows.  exclude: a probe query's own row (every second one), else in turn a boundary row, a
+    zero row, -1 and rows + 5.  target: in turn a boundary row, a zero row, -1 and rows."""
+    rows, p, q = n_elems // d, len(probe), SEARCH_Q
+    edge, zero = boundary_rows(n_elems, d, elem_bytes).tolist(), zero_rows(probe, rows)
+    assert p + 2 <= q and set(edge) <= set(int(x) for x in probe)
+    queries = np.concatenate([values, np.zeros((1, d), np.float32),
+                              rng.standard_normal((q - p - 1, d)).astype(np.float32)])
+    turn_e, turn_t = edge + zero + [-1, rows + 5], edge + zero[:2] + [-1, rows]
+    exclude = np.array([turn_e[i % len(turn_e)] for i in range(q)], np.int64)
+    exclude[:p:2] = probe[::2]
+    target = np.array([turn_t[(i + 3) % len(turn_t)] for i in range(q)], np.int64)
+    return queries, exclude, target
+
+
 def wrapped_read(values, probe, d, row, elem_bytes):
     """what a read of `row` through each narrowed offset of its first element returns, on a table
     whose probe rows hold `values` and whose other rows are zero -> one [d] array per modulus"""

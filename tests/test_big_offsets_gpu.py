@@ -22,7 +22,12 @@ Covered, each over bf16 / fp16 / fp32 and the three d:
   read by row    gather; gather_scatter and gather_segment_reduce (add, max, mean; count, seg_ptr,
                  int64 ids; edge weights); gather_segment_topk with indices; edge_dot; gcn_aggregate;
                  attention_aggregate; relation_reduce; embedding_take; sparse_feature_embedding
-  sparse grads   triple_score, triple_score_proj (TransD with a second big table), triple_score_matrix,
+  scanned whole  table_topk (k = 64; the four metrics at d = 136, ip and l2 at 132 and 129; with and
+                 without exclude, once with ids=) and table_rank over all 31.6 M rows (the three
+                 dtypes, the three d): 33 queries in a second dtype - two query tiles, the
+                 cap of 512 slabs and the merge over 512 * 64 entries a query; expected values from
+                 table_search_ref.sparse_topk / sparse_rank on the probe rows
+  sparse grads  triple_score, triple_score_proj (TransD with a second big table), triple_score_matrix,
                  skipgram_loss (the big table as target, then as context)
   written        embedding_update / _add / _take(clear) in the plain, row_index and count forms, once
                  on a side stream; sparse_row_step sgd / momentum / adagrad with a 16 GiB state tensor
@@ -48,6 +53,7 @@ import segment_topk_ref as TK
 import skipgram_ref as SG
 import sparse_embed_ref as SE
 import sparse_optim_ref as SO
+import table_search_ref as SR
 import triple_score_matrix_ref as TM
 import triple_score_proj_ref as TP
 import triple_score_ref as TS
@@ -732,6 +738,62 @@ def test_sparse_feature_embedding(big, EA, O, d):
         finally:
             graph.close()
         assert big.count() == t.nnz
+
+
+# ---- the whole table searched -------------------------------------------------------------------
+QUERY_DT = {"f32": "bf16", "bf16": "f16", "f16": "f32"}                # the queries in a second dtype
+
+
+# the four metrics at d = 136; ip and l2 (one per direction of the order) at d = 132 and 129: with all four
+# there too these cases took 15.7 s a dtype on an MI355X, more than the module's other 16-bit cases together
+SEARCH_CASES = [(metric, d) for d in bo.DIMS for metric in SR.METRICS if d == bo.DIMS[0] or metric in ("ip", "l2")]
+
+
+@pytest.mark.parametrize("metric,d", SEARCH_CASES)
+def test_table_search(big, ops, metric, d):
+    """table_topk and table_rank over all 31.6 M rows: the offsets (int64_t)row * d + j * V of the
+    scan, the slabs' lists at * k + lane and the merge's ((i / k) * q + qq) * k + i % k.  33 queries
+    (two tiles): every probe row, a zero row, random rows in a second dtype.  k = 64 is more than
+    the probe rows, so zero rows fill the tail of every list in row order - and precede the probe
+    rows that score worse than a zero row.  Expected: table_search_ref.sparse_topk / sparse_rank on
+    the small table (test_table_search_host.py holds them against the dense restatement).  This is the
+    one shape that runs 512 slabs with every slab full-length: the cap and the long merge."""
+    torch, dt = big.torch, big.dt
+    dq, k = QUERY_DT[dt], bo.SEARCH_K
+    rng = np.random.default_rng(9500 + d)
+    with big.table(d) as t:
+        q32, exclude, target = bo.search_case(rng, t.probe, t.values, bo.BIG, d, bo.ELEM_BYTES[dt])
+        q32 = SR.to_dtype(q32, dq)
+        assert np.array_equal(q32[:len(t.probe)], t.values) and len(q32) == bo.SEARCH_Q and len(t.probe) < k
+        queries = dev(torch, store_ref.narrow(q32, dq), dq)
+        # the launch shape, from the restatement: two tiles, the cap of 512 slabs, an item a block
+        tiles = SR.tiles_of(len(q32), d)
+        slabs = SR.slabs_of(t.rows, tiles)
+        slab_rows = -(-t.rows // slabs)
+        assert (tiles, slabs) == (2, SR.MAX_SLABS) and tiles * slabs <= SR.BLOCK_CAP
+        assert (slabs - 1) * slab_rows < t.rows <= slabs * slab_rows and slab_rows > 60000
+        v = SR.chunk_width(d, t.t.data_ptr(), t.t.element_size(), queries.data_ptr(), queries.element_size())
+        assert v == (8 if d % 8 == 0 else 4 if d % 4 == 0 else 1)
+        for exc in (None, exclude):
+            got_s, got_r = ops.table_topk(t.t, queries, k, metric=metric, exclude=None if exc is None else dev(torch, exc))
+            want_s, want_r = SR.sparse_topk(t.probe, t.values, t.rows, q32, k, metric, v, exc)
+            assert np.all(want_r >= 0) and want_r.max() < t.rows
+            assert SR.same_scores(got_s.cpu().numpy(), want_s), (metric, d, exc is None, "scores")
+            assert np.array_equal(got_r.cpu().numpy(), want_r), (metric, d, exc is None, "rows")
+            assert big.count() == t.nnz
+        if metric == "l2":                                # once more with ids=: the second output is ids[rows]
+            ids = torch.arange(t.rows, device="cuda") * 3 + 7
+            got_s, got_r = ops.table_topk(t.t, queries, k, metric=metric, exclude=dev(torch, exclude), ids=ids)
+            assert SR.same_scores(got_s.cpu().numpy(), want_s) and np.array_equal(got_r.cpu().numpy(), want_r * 3 + 7)
+            del ids
+            assert big.count() == t.nnz
+        for exc in (None, exclude):
+            got = ops.table_rank(t.t, queries, dev(torch, target), metric=metric,
+                                 exclude=None if exc is None else dev(torch, exc))
+            want = SR.sparse_rank(t.probe, t.values, t.rows, q32, target, metric, v, exc)
+            assert got.dtype == torch.int32 and np.array_equal(got.cpu().numpy(), want), (metric, d, exc is None, "rank")
+            assert big.count() == t.nnz
+        assert want.min() == -1 and want.max() > t.rows - 2 * len(t.probe)
 
 
 def kg_batch(t, rng, b=32, k=3, n_rel=7):

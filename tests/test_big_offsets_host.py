@@ -12,7 +12,11 @@ are probe rows, and the rows just past 2^32 wrap to the offsets just past 0 (d =
 31580642 begins at element 2^32 + 16, which wraps to element 16 of row 0); likewise the rows at
 2^32 taken modulo 2^31 land in the probe rows at 2^31.  Such a read returns another probe row's
 values, shifted by some columns, which differ from the row's own:
-test_a_wrapped_read_is_never_the_rows_own_values asserts exactly that, on the values the GPU tests write."""
+test_a_wrapped_read_is_never_the_rows_own_values asserts exactly that, on the values the GPU tests write.
+
+The table search scans every row instead of reading named ones: its queries are the probe rows
+themselves, and a query equal to a row scores l2 = 0 and the largest ip against that row alone
+(test_another_row_scores_differently), so a scan that reads another row shows in the lists."""
 import numpy as np
 import pytest
 
@@ -123,3 +127,82 @@ def test_compact_round_trips():
         assert np.array_equal(ids[:, None] == ids[None, :], small[:, None] == small[None, :])
     with pytest.raises(ValueError):
         bo.compact(np.array([2]), probe, rows)
+
+
+# ---- the table search over the big table ------------------------------------------------------------
+import table_search_ref as SR                                             # noqa: E402
+
+SEARCH_CASES = [(d, dt) for d in bo.DIMS for dt in store_ref.DTYPES]
+
+
+@pytest.mark.parametrize("d,dt", SEARCH_CASES)
+def test_search_case_names_the_boundary_rows_and_runs_512_slabs(d, dt):
+    """what test_big_offsets_gpu.py::test_table_search asks: at most 33 queries (two tiles), every
+    probe row among them; exclude and target name boundary rows, zero rows and no row; the launch
+    shape is 2 tiles x 512 slabs, each item a block of its own, every slab non-empty"""
+    eb = bo.ELEM_BYTES[dt]
+    rows = bo.BIG // d
+    probe = bo.probe_rows(bo.BIG, d, eb)
+    values = bo.probe_values(np.random.default_rng(d), len(probe), d)
+    queries, exclude, target = bo.search_case(np.random.default_rng(9500 + d), probe, values, bo.BIG, d, eb)
+    assert queries.shape == (bo.SEARCH_Q, d) and bo.SEARCH_Q <= 33 and len(probe) < bo.SEARCH_K <= SR.MAX_K
+    edge, zero = bo.boundary_rows(bo.BIG, d, eb), bo.zero_rows(probe, rows)
+    assert len(edge) == len(bo.boundaries(eb)) + 1 and edge[-1] == rows - 1 and zero[0] == 2
+    for b, r in zip(bo.boundaries(eb), edge):
+        assert r * d < b < (r + 1) * d
+    assert np.array_equal(queries[:len(probe)], values) and not queries[len(probe)].any()
+    for ids, none in ((exclude, rows + 5), (target, rows)):
+        assert set(edge.tolist()) <= set(ids.tolist()) and zero[0] in ids and zero[1] in ids and -1 in ids and none in ids
+    own = exclude[:len(probe)] == probe
+    assert own[::2].all() and not own[1::2].any()
+    tiles = SR.tiles_of(bo.SEARCH_Q, d)
+    slabs = SR.slabs_of(rows, tiles)
+    slab_rows = -(-rows // slabs)
+    assert (tiles, slabs) == (2, 512) and tiles * slabs <= SR.BLOCK_CAP and (slabs - 1) * slab_rows < rows < 1 << 31
+    assert slabs * bo.SEARCH_Q * bo.SEARCH_K * 8 < 10 << 20                # the scratch the cases add
+
+
+@pytest.mark.parametrize("d,dt", SEARCH_CASES)
+def test_another_row_scores_differently(d, dt):
+    """why a scan that reads a wrong row shows: a query equal to a probe row scores l2 = 0 and the
+    largest ip against that row alone - no other probe row, no zero row, and nothing a narrowed offset
+    of the row returns gives either; so a wrong read moves the row in the list or changes its score"""
+    eb = bo.ELEM_BYTES[dt]
+    probe = bo.probe_rows(bo.BIG, d, eb)
+    values = bo.probe_values(np.random.default_rng(d), len(probe), d)
+    v = SR.chunk_width(d, 0, eb, 0, 4)
+    table = np.concatenate([values, np.zeros((1, d), np.float32)])         # the probe rows and a zero row
+    l2, ip = SR.scores(table, values, "l2", v), SR.scores(table, values, "ip", v)
+    here = np.arange(len(probe))
+    assert np.all(l2[here, here] == 0) and np.count_nonzero(l2 == 0) == len(probe)
+    assert np.array_equal(np.argmax(ip, 1), here) and np.all(np.sort(ip, 1)[:, -1] > np.sort(ip, 1)[:, -2])
+    wrapped = 0
+    for n, r in enumerate(probe.tolist()):
+        for w, got in zip(bo.wrapped_offsets(r * d, eb), bo.wrapped_read(values, probe, d, r, eb)):
+            if w != r * d:
+                wrapped += 1
+                assert SR.scores(got[None, :], values[n:n + 1], "l2", v)[0, 0] > 0
+                assert SR.scores(got[None, :], values[n:n + 1], "ip", v)[0, 0] < ip[n, n]
+    assert wrapped >= 3
+
+
+def test_sparse_expectations_at_the_big_shape():
+    """sparse_topk / sparse_rank at n = 31.6 M rows, without a table: the zero rows that fill the
+    tail are the lowest rows that are no probe row, in row order, and a zero-row target ranks behind
+    every other zero row"""
+    d, dt = 136, "bf16"
+    rows = bo.BIG // d
+    probe = bo.probe_rows(bo.BIG, d, 2)
+    values = bo.probe_values(np.random.default_rng(d), len(probe), d)
+    queries, exclude, target = bo.search_case(np.random.default_rng(9500 + d), probe, values, bo.BIG, d, 2)
+    for metric in SR.METRICS:
+        sc, got = SR.sparse_topk(probe, values, rows, queries, bo.SEARCH_K, metric, 8, exclude)
+        z = SR.scores(np.zeros((1, d), np.float32), queries, metric, 8)[:, 0]
+        for i in range(len(queries)):
+            zero = got[i][~np.isin(got[i], probe)]
+            want = [r for r in range(2, 2 + bo.SEARCH_K + 1) if r != exclude[i]][:len(zero)]
+            assert zero.tolist() == want and len(zero) >= bo.SEARCH_K - len(probe)
+            assert np.all(sc[i][~np.isin(got[i], probe)] == z[i]) and exclude[i] not in got[i]
+        rank = SR.sparse_rank(probe, values, rows, queries, target, metric, 8, exclude)
+        at_zero = np.isin(target, bo.zero_rows(probe, rows))
+        assert np.all(rank[at_zero] >= rows - len(probe) - 2) and np.all(rank[(target < 0) | (target >= rows)] == -1)

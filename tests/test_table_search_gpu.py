@@ -8,6 +8,13 @@ table_search_ref: a block takes one (query tile, slab) item a trip; a tile is 4 
 of up to 1024 rows is one slab, slabs = min(ceil(2048 / tiles), ceil(N / 1024), 512); the grid is
 capped at 8192 blocks; the merge runs a wave per query, four a block, under the same cap.
 
+After the feature's own cases: each term of the slab rule (the clamp by the tiles, the shortest last
+slab, the cap of 512), every branch of the chunk-width rule on views off a 16-byte boundary, the
+wave list under chosen arrival orders, all-NaN queries, rows that score the fill value, and
+table_rank against the float64 count.  What can be evaluated without a GPU - V per case, slab
+counts, the separation of the float64 scores, the helpers for many queries - is asserted in
+test_table_search_host.py as well.  (Offsets past 2^31: test_big_offsets_gpu.py.)
+
 A NaN score is compared as "NaN on both sides"."""
 import ctypes as C
 
@@ -259,3 +266,230 @@ def test_empty_shapes(torch_cuda, EA, metric):
     assert s.shape == (0, 4) and r.shape == (0, 4)
     assert ops.table_rank(torch.ones(5, 8, device="cuda"), queries[:0], torch.zeros(0, dtype=torch.int64, device="cuda"),
                           metric=metric).shape == (0,)
+
+
+# ---- the slab rule: the clamp by the tiles, the shortest last slab, the cap ------------------------
+def check_block(torch, ops, table, queries, s, metric, k, exclude, target, tag):
+    """check() for many queries: against topk_of_scores / rank_of_scores of the block of scores s
+    (test_table_search_host.py holds them against topk / rank)"""
+    got_s, got_r = ops.table_topk(table, queries, k, metric=metric, exclude=ids_dev(torch, exclude))
+    want = ref.topk_of_scores(s, k, metric, exclude)
+    assert same_scores(got_s.cpu().numpy(), want[0]), tag + ("scores",)
+    assert np.array_equal(got_r.cpu().numpy(), want[1]), tag + ("rows",)
+    got = ops.table_rank(table, queries, ids_dev(torch, target), metric=metric, exclude=ids_dev(torch, exclude))
+    assert got.dtype == torch.int32
+    assert np.array_equal(got.cpu().numpy(), ref.rank_of_scores(s, target, metric, exclude)), tag + ("rank",)
+
+
+@pytest.mark.parametrize("metric", ("ip", "l2"))
+def test_slabs_clamped_by_the_number_of_tiles(torch_cuda, EA, metric):
+    """Q = 32 * 100 + 1 is 101 tiles, so slabs = ceil(2048 / 101) = 21 although N = 30000 has 30
+    slabs' worth of rows; N = 21 * 1024 - 1, 21 * 1024 and 21 * 1024 + 1 straddle the row count at
+    which the clamp starts to bind (21 slabs of 1024, 1024 and 1025 rows, the last one shorter)"""
+    torch, ops = torch_cuda, EA.ops
+    d, q, k = 4, 32 * 100 + 1, 10
+    tiles = ref.tiles_of(q, d)
+    assert tiles == 101 and ref.slabs_of(30000, tiles) == 21 < -(-30000 // ref.MIN_SLAB_ROWS)
+    ns = (21 * 1024 - 1, 21 * 1024, 21 * 1024 + 1)
+    rng = np.random.default_rng(101)
+    t_np = tie_table(rng, ns[-1], d, "bf16")
+    q_np = np.array([-2, -1, -0.0, 0, 1, 2], F)[rng.integers(0, 6, (q, d))]
+    q_np[1::3] = rng.standard_normal((len(q_np[1::3]), d)).astype(F)
+    q_np[2::9] = t_np[rng.integers(0, ns[0], len(q_np[2::9]))]
+    table, queries = dev(torch, t_np, "bf16"), dev(torch, q_np)
+    assert width(table, queries) == 4
+    s_all = ref.scores(t_np, q_np, metric, 4)
+    for n in ns:
+        assert ref.slabs_of(n, tiles) == 21
+        exc, target = rng.integers(-2, n + 2, q), rng.integers(-1, n + 1, q)
+        check_block(torch, ops, table[:n], queries, s_all[:, :n], metric, k, exc, target, (metric, n))
+
+
+def big_flat_case(torch, n, seed, q=5):
+    """a tie-heavy bf16 table [n, 4] (4 MiB at n = 2^19) with fp32 queries: small integers, rows of
+    the table, random rows"""
+    rng = np.random.default_rng(seed)
+    t_np = tie_table(rng, n, 4, "bf16")
+    small = np.array([-2, -1, -0.0, 0, 1, 2], F)
+    q_np = np.concatenate([small[rng.integers(0, 6, (2, 4))], t_np[[n - 1, n // 2 + 7]],
+                           rng.standard_normal((q - 4, 4))]).astype(F)
+    return rng, t_np, q_np, dev(torch, t_np, "bf16"), dev(torch, q_np)
+
+
+def test_shortest_last_slab(torch_cuda, EA):
+    """N = 511 * 1024 + 1 with one tile: slabs = 512, slab_rows = ceil(N / 512) = 1023 and the last slab
+    holds N - 511 * 1023 = 512 rows, the shortest against the others that the rule allows
+    (test_table_search_host.py searches every N and tile count).  The best rows of two queries lie in
+    the last slab, and the last row is a target."""
+    torch, ops = torch_cuda, EA.ops
+    n = 511 * 1024 + 1
+    slabs = ref.slabs_of(n, 1)
+    slab_rows = -(-n // slabs)
+    assert (slabs, slab_rows, n - (slabs - 1) * slab_rows) == (512, 1023, 512)
+    rng, t_np, q_np, table, queries = big_flat_case(torch, n, 511)
+    assert ref.tiles_of(len(q_np), 4) == 1 and width(table, queries) == 4
+    last = (slabs - 1) * slab_rows
+    t_np[last + 5], t_np[n - 1], t_np[last - 1] = 64 * np.sign(q_np[0]) + (q_np[0] == 0), 64 * q_np[1], 32 * q_np[1]
+    table = dev(torch, t_np, "bf16")
+    exc = np.array([-1, n - 1, last, n, 5])
+    target = np.array([last + 5, n - 1, last, n - 1, -1])
+    for metric in ("ip", "l1"):
+        s = ref.scores(t_np, q_np, metric, 4)
+        if metric == "ip":
+            fin = np.where(np.isfinite(s), s, -np.inf)                 # (the table has a NaN row and a row with an inf)
+            assert np.argmax(fin[0]) == last + 5 and np.argmax(fin[1]) == n - 1 and np.argsort(fin[1])[-2] == last - 1
+        check_block(torch, ops, table, queries, s, metric, 10, exc, target, (metric,))
+
+
+def test_cap_of_512_slabs(torch_cuda, EA):
+    """N = 512 * 1024 + 1 (a 4 MiB bf16 table), Q = 5, k = 64, tie-heavy: slabs = 512, the cap, for
+    this and any larger N; the merge walks 512 * 64 entries a query, most of which tie"""
+    torch, ops = torch_cuda, EA.ops
+    n, k = 512 * 1024 + 1, 64
+    assert ref.slabs_of(n, 1) == ref.MAX_SLABS == 512 and -(-n // ref.MIN_SLAB_ROWS) == 513
+    assert all(ref.slabs_of(m, 1) == 512 for m in (n + 1, 2 * n, 10 ** 7, 2 ** 31 - 1))
+    rng, t_np, q_np, table, queries = big_flat_case(torch, n, 512)
+    assert ref.tiles_of(len(q_np), 4) == 1 and width(table, queries) == 4
+    exc, target = rng.integers(0, n, 5), rng.integers(0, n, 5)
+    exc[0], target[0], target[1] = -1, n - 1, 3
+    for metric in ("ip", "cos", "l2"):
+        s = ref.scores(t_np, q_np, metric, 4)
+        top = ref.topk_of_scores(s, k, metric, exc)[0]
+        assert min(len(np.unique(x[~np.isnan(x)])) for x in top) < k // 2, "the table must make ties among the best k"
+        check_block(torch, ops, table, queries, s, metric, k, exc, target, (metric,))
+
+
+# ---- views off a 16-byte boundary: the chunk width rule -----------------------------------------------
+def view_at(torch, x_np, dt, off_bytes):
+    """the values x_np in a device tensor of type dt that starts off_bytes past a 16-byte boundary"""
+    item = ITEM[dt]
+    assert off_bytes % item == 0
+    base = torch.empty(x_np.size + 16 // item, dtype=_torch_dt(torch, dt), device="cuda")
+    assert base.data_ptr() % 16 == 0
+    at = off_bytes // item
+    view = base[at:at + x_np.size].view(x_np.shape)
+    view.copy_(dev(torch, x_np, dt))
+    assert view.data_ptr() % 16 == off_bytes and view.is_contiguous()
+    return view
+
+
+@pytest.mark.parametrize("case", ref.ALIGN_CASES, ids=lambda c: "%s+%d-%s+%d-d%d-V%d" % c)
+def test_views_off_a_16_byte_boundary(torch_cuda, EA, case):
+    """every branch of KgChunkWidth a pair of aligned tables never takes, and V = 1 / 4 where the
+    queries are read from memory (d > 3072): N = 1100 (two slabs), Q = 33 (two tiles), the four
+    metrics, both ops"""
+    torch, ops = torch_cuda, EA.ops
+    dtt, off_t, dq, off_q, d, v = case
+    n, q = ref.ALIGN_N, ref.ALIGN_Q
+    rng = np.random.default_rng(1000 * d + off_t + off_q)
+    t_np = tie_table(rng, n, d, dtt)
+    q_np, own = queries_for(rng, t_np, dq, q=q)
+    table, queries = view_at(torch, t_np, dtt, off_t), view_at(torch, q_np, dq, off_q)
+    assert width(table, queries) == v == ref.align_case_width(case)
+    assert ref.tiles_of(q, d) == 2 and ref.slabs_of(n, 2) == 2 and ref.wave_queries(d)[1] == (d <= 3072)
+    exc = np.concatenate([own, rng.integers(-2, n + 2, q - len(own))])
+    target = rng.integers(-1, n + 1, q)
+    for metric in METRICS:
+        check(torch, ops, table, queries, t_np, q_np, metric, 10, exc, target, tag=case + (metric,))
+
+
+# ---- the list under chosen arrival orders -----------------------------------------------------------
+@pytest.mark.parametrize("metric", ("ip", "l2"))
+@pytest.mark.parametrize("kind", ref.ARRIVAL_ORDERS)
+def test_arrival_orders(torch_cuda, EA, kind, metric):
+    """scores chosen row by row (table_search_ref.arrival_case): every row entering at position 0,
+    no row entering a full list, all rows tied, a sawtooth, +0 / -0; N = 2049 is three slabs;
+    d = 1 offers 256 candidates a step, d = 64 four; k = 1, 63 and 64"""
+    torch, ops = torch_cuda, EA.ops
+    n = ref.ARRIVAL_N
+    assert ref.slabs_of(n, 1) == 3
+    exc = np.array([-1, n - 1, 0])
+    target = np.array([0, 683, n - 1])
+    for d in ref.ARRIVAL_DIMS:
+        t_np, q_np = ref.arrival_case(kind, metric, d)
+        table, queries = dev(torch, t_np), dev(torch, q_np)
+        s = None
+        for k in ref.ARRIVAL_KS:
+            s = check(torch, ops, table, queries, t_np, q_np, metric, k, None, target if k == 1 else None, s=s,
+                      tag=(kind, metric, d, k))
+            check(torch, ops, table, queries, t_np, q_np, metric, k, exc, target if k == 64 else None, s=s,
+                  tag=(kind, metric, d, k, "exclude"))
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_query_with_a_nan(torch_cuda, EA, metric):
+    """every score of the query is NaN: its list is rows 0 .. k - 1 in row order (without the
+    excluded one), its rank 0; the query beside it in the same wave is not disturbed"""
+    torch, ops = torch_cuda, EA.ops
+    n = ref.ARRIVAL_N
+    for d in ref.ARRIVAL_DIMS:
+        rng = np.random.default_rng(d)
+        t_np = rng.standard_normal((n, d)).astype(F)
+        q_np = rng.standard_normal((3, d)).astype(F)
+        q_np[0, d // 2], q_np[2, 0] = np.nan, np.nan
+        table, queries = dev(torch, t_np), dev(torch, q_np)
+        s = ref.scores(t_np, q_np, metric, width(table, queries))
+        assert np.all(np.isnan(s[[0, 2]])) and not np.any(np.isnan(s[1]))
+        for k in (1, 64):
+            got_s, got_r = ops.table_topk(table, queries, k, metric=metric, exclude=ids_dev(torch, [-1, 0, 3]))
+            got_s, got_r = got_s.cpu().numpy(), got_r.cpu().numpy()
+            assert got_r[0].tolist() == list(range(k)) and got_r[2].tolist() == [r for r in range(k + 1) if r != 3][:k]
+            assert np.all(np.isnan(got_s[[0, 2]]))
+            check(torch, ops, table, queries, t_np, q_np, metric, k, [-1, 0, 3], [5, 700, n - 1], s=s, tag=(metric, d, k))
+        got = ops.table_rank(table, queries, ids_dev(torch, [5, 700, n - 1]), metric=metric).cpu().numpy()
+        assert got[0] == 0 and got[2] == 0 and got[1] == ref.rank(t_np, q_np, [5, 700, n - 1], metric, 0, s=s)[1]
+
+
+@pytest.mark.parametrize("metric", ("ip", "l1"))
+def test_row_that_scores_the_fill_value(torch_cuda, EA, metric):
+    """a row holding -inf under ip (+inf under l1) against positive queries scores the fill value: it
+    is a candidate like any other - returned with its own row number behind every other row and ahead
+    of the -1 entries when N < k; when every row scores the fill, the list is the rows in order"""
+    torch, ops = torch_cuda, EA.ops
+    worst = F(-np.inf) if metric == "ip" else F(np.inf)
+    rng = np.random.default_rng(6)
+    for d in (1, 4, 64):
+        n, k = 5, 8
+        t_np = (np.abs(rng.standard_normal((n, d))) + 1).astype(F)
+        q_np = (np.abs(rng.standard_normal((2, d))) + 1).astype(F)
+        t_np[2, d // 2] = worst
+        table, queries = dev(torch, t_np), dev(torch, q_np)
+        s = check(torch, ops, table, queries, t_np, q_np, metric, k, None, [2, 0], tag=(metric, d, "one"))
+        assert np.all(s[:, 2] == worst) and np.all(np.isfinite(np.delete(s, 2, 1)))
+        got_s, got_r = (x.cpu().numpy() for x in ops.table_topk(table, queries, k, metric=metric))
+        assert np.all(got_r[:, 4] == 2) and np.all(got_s[:, 4:] == worst) and np.all(got_r[:, 5:] == -1)
+        # every row of three slabs scores the fill value
+        n = ref.ARRIVAL_N
+        t_np = (np.abs(rng.standard_normal((n, d))) + 1).astype(F)
+        t_np[:, d // 2] = worst
+        t_np[1000, :] = 1
+        table = dev(torch, t_np)
+        for k in (1, 64):
+            s = check(torch, ops, table, queries, t_np, q_np, metric, k, [1000, 0], [1000, 7], tag=(metric, d, k, "all"))
+            check(torch, ops, table, queries, t_np, q_np, metric, k, None, [1000, 7], s=s, tag=(metric, d, k, "all"))
+        assert np.count_nonzero(s[0] == worst) == n - 1
+        got_r = ops.table_topk(table, queries, 64, metric=metric)[1].cpu().numpy()
+        assert got_r[0].tolist() == [1000] + list(range(63))
+
+
+# ---- table_rank against float64 -----------------------------------------------------------------
+@pytest.mark.parametrize("metric", METRICS)
+def test_rank_equals_the_float64_count(torch_cuda, EA, metric):
+    """well-separated random fp32 rows (N = 3073, d = 64, Q = 33): no row's float64 score lies within
+    2 * bound of a target's (scores64's bound of the fp32 arithmetic), so the rank is the float64
+    count - a check that shares no arithmetic with the kernels or the restatement.  The metrics of
+    rank_metric follow from it."""
+    torch, ops = torch_cuda, EA.ops
+    t_np, q_np, target, count, margin = ref.separated_rank_case(metric, **ref.SEPARATED)
+    assert margin > 1 and count.min() == 0 and count.max() == 3072
+    exact, _ = ref.scores64(t_np, q_np, metric)
+    st = np.take_along_axis(exact, target[:, None], 1)
+    assert np.array_equal(count, ((exact >= st) if ref.larger_is_better(metric) else (exact <= st)).sum(1) - 1)
+    rank = ops.table_rank(dev(torch, t_np), dev(torch, q_np), ids_dev(torch, target), metric=metric)
+    assert np.array_equal(rank.cpu().numpy(), count)
+    want = torch.from_numpy(count)
+    for name in ("mrr", "mr", "hit1", "hit10"):
+        assert float(ops.rank_metric(name, rank.cpu())) == float(ops.rank_metric(name, want)), name
+    # mr and hit@k are sums of integers and one division: the same on the device and in numpy
+    assert float(ops.rank_metric("mr", rank)) == (count.astype(np.float64) + 1).sum() / len(count)
+    assert float(ops.rank_metric("hit10", rank)) == np.count_nonzero(count < 10) / len(count)

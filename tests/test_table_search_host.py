@@ -3,7 +3,11 @@ calls, against the numpy restatement tests/table_search_ref.py: bit equality of 
 rows and the ranks; the order rule on tie-heavy tables; the fills; exclude and target in and out of
 range; the restatement within the derived bound of float64; the C-ABI entries exported and bound,
 and every rule of their argument ladder (driven through the C ABI in a child process that sees no
-GPU: every row stops in front of the first HIP call).  CPU only.
+GPU: every row stops in front of the first HIP call).  Then what the GPU cases rest on: the slab
+rule at its clamps and its shortest last slab, V of every alignment case, sparse_topk / sparse_rank
+(a mostly-zero table that is never built) against the dense restatement, the chosen arrival orders,
+NaN queries and fill-valued rows through the host build, the separation behind the float64 rank
+check.  CPU only.
 
 A NaN score is compared as "NaN on both sides": its sign and payload are the hardware's."""
 import ctypes as C
@@ -288,6 +292,230 @@ def test_launch_shape_restated(TS):
             assert TS.ts_slabs(n, tiles) == ref.slabs_of(n, tiles), (n, tiles)
     assert ref.slabs_of(1024, 1) == 1 and ref.slabs_of(1025, 1) == 2 and ref.slabs_of(3073, 1) == 4
     assert ref.slabs_of(10 ** 7, 1) == ref.MAX_SLABS and ref.slabs_of(10 ** 7, 32) == 64
+
+
+def test_slab_clamps_and_the_shortest_last_slab(TS):
+    """the three terms of TsSlabs at the shapes test_table_search_gpu.py and test_big_offsets_gpu.py
+    run, and the shortest last slab the rule allows: over every N up to 2^20 and every tile count, a
+    last slab is never empty and never shorter than 512 rows, and is shortest against the other
+    slabs at N = 511 * 1024 + 1 - 512 slabs of 1023 rows, the last of 512"""
+    # the clamp by the number of tiles: 101 tiles, ceil(2048 / 101) = 21 < ceil(30000 / 1024) = 30
+    q = 32 * 100 + 1
+    assert ref.tiles_of(q, 4) == 101 and -(-2048 // 101) == 21 and -(-30000 // 1024) == 30
+    assert ref.slabs_of(30000, 101) == 21 == TS.ts_slabs(30000, 101)
+    for n in (21 * 1024 - 1, 21 * 1024, 21 * 1024 + 1):
+        assert ref.slabs_of(n, 101) == 21 == TS.ts_slabs(n, 101), n
+    assert ref.slabs_of(20 * 1024, 101) == 20                       # (below it the rows decide)
+    # the cap
+    for n in (512 * 1024 + 1, 10 ** 6, 10 ** 8, 2 ** 31 - 1):
+        assert ref.slabs_of(n, 1) == 512 == TS.ts_slabs(n, 1) and ref.slabs_of(n, 4) == 512, n
+    assert ref.slabs_of(511 * 1024, 1) == 511 and ref.slabs_of(512 * 1024 + 1, 5) == 410
+    # every (N, tiles): the last slab
+    n = np.arange(1, 1 << 20, dtype=np.int64)
+    by_rows = -(-n // ref.MIN_SLAB_ROWS)
+    worst = (2.0, None)
+    first_tiles = {}                          # the rule sees the tiles through min(ceil(2048 / tiles), 512) alone
+    for tiles in range(2050, 0, -1):
+        first_tiles[min(-(-ref.TARGET_BLOCKS // tiles), ref.MAX_SLABS)] = tiles
+    for cap, tiles in sorted(first_tiles.items(), reverse=True):
+        s = np.maximum(1, np.minimum(by_rows, cap))
+        assert s[-1] == ref.slabs_of(int(n[-1]), tiles) and s[2000] == ref.slabs_of(2001, tiles)
+        slab_rows = -(-n // s)
+        last = n - (s - 1) * slab_rows
+        assert last.min() >= 1 and last[s > 1].min(initial=512) >= 512, tiles
+        share = np.where(s > 1, last / slab_rows, 2.0)
+        at = int(np.argmin(share))
+        if share[at] < worst[0]:
+            worst = (float(share[at]), (int(n[at]), tiles, int(s[at]), int(slab_rows[at]), int(last[at])))
+    assert worst[1] == (511 * 1024 + 1, 1, 512, 1023, 512)
+
+
+@pytest.mark.parametrize("case", ref.ALIGN_CASES, ids=lambda c: "%s+%d-%s+%d-d%d-V%d" % c)
+def test_alignment_cases_take_the_width_they_are_meant_for(TS, case):
+    """the case table of test_table_search_gpu.py::test_views_off_a_16_byte_boundary: V as stated,
+    by the header's rule and by the restatement; the host build over that V == the restatement"""
+    dtt, off_t, dq, off_q, d, v = case
+    assert off_t % ITEM[dtt] == 0 and off_q % ITEM[dq] == 0 and d % v == 0
+    assert ref.align_case_width(case) == v == TS.ts_chunk_width(d, 4096 + off_t, dtt == "f32", 8192 + off_q, dq == "f32")
+    aligned = ref.chunk_width(d, 0, ITEM[dtt], 0, ITEM[dq])
+    assert aligned == v or off_t or off_q                                # only an offset moves V
+    assert ref.wave_queries(d)[1] == (d <= 3072)
+    assert ref.slabs_of(ref.ALIGN_N, ref.tiles_of(ref.ALIGN_Q, d)) == 2 and ref.tiles_of(ref.ALIGN_Q, d) == 2
+    rng = np.random.default_rng(d + off_t + off_q)
+    n = 40 if d > 3072 else 120
+    table = tie_table(rng, n, d, dtt)
+    queries, own = queries_for(rng, table, dq)
+    for metric in METRICS if d <= 3072 else ("cos", "l1"):
+        check_case(TS, table, queries, metric, v, (10,), (n,), own, case + (metric,))
+
+
+# ---- a mostly-zero table: sparse_topk / sparse_rank == the dense restatement ---------------------
+SPARSE_N = 3000
+SPARSE_PROBE = np.array([0, 1, 3, 700, 701, 1499, 1500, 2047, 2048, 2990, SPARSE_N - 2, SPARSE_N - 1])
+
+
+def sparse_case(rng, d, dtt, dq):
+    """-> (values [12, d], the dense table, queries [18, d], target [18], exclude [18]): queries equal
+    to probe rows, to the zero row, and random; every pair of (target kind, exclude kind) out of
+    probe row / zero row / -1 / n + 5, then target == exclude on a zero row and on a probe row"""
+    n, probe = SPARSE_N, SPARSE_PROBE
+    values = to_dtype(np.round(rng.standard_normal((len(probe), d)) * 16) / 16, dtt)
+    values[4] = values[3]                                                 # two probe rows that tie
+    dense = np.zeros((n, d), F)
+    dense[probe] = values
+    base = np.concatenate([values[[0, 3, 11]], np.zeros((1, d), F), -values[[5]], rng.standard_normal((3, d)).astype(F)])
+    queries = to_dtype(base[np.arange(18) % 8], dq)
+    kinds = {"probe": (0, 701, n - 1, 1500), "zero": (2, 4, 1600, n - 3), "none": (-1,) * 4, "past": (n + 5,) * 4}
+    target, exclude = [], []
+    for a, ka in enumerate(kinds):
+        for b, kb in enumerate(kinds):
+            target.append(kinds[ka][b])
+            exclude.append(kinds[kb][(a + 1) % 4])
+    target += [2, 701]
+    exclude += [2, 701]
+    return values, dense, queries, np.array(target, np.int64), np.array(exclude, np.int64)
+
+
+@pytest.mark.parametrize("dtt", DTYPES)
+@pytest.mark.parametrize("d", (129, 132, 136))
+def test_sparse_helpers_equal_the_dense_restatement(d, dtt):
+    """sparse_topk / sparse_rank (which never build the table) against topk / rank on the table
+    built explicitly: n = 3000, 12 probe rows with rows 0, 1, n - 2, n - 1 among them; the four
+    metrics, k = 1 / 10 / 64, with and without exclude.  Zero rows enter the lists ahead of probe
+    rows and behind them."""
+    n, probe = SPARSE_N, SPARSE_PROBE
+    assert {0, 1, n - 2, n - 1} <= set(probe.tolist()) and len(probe) == 12
+    dq = DTYPES[(DTYPES.index(dtt) + 1) % 3]
+    rng = np.random.default_rng(7 * d + DTYPES.index(dtt))
+    values, dense, queries, target, exclude = sparse_case(rng, d, dtt, dq)
+    assert np.count_nonzero(dense.any(1)) == len(probe)
+    v = ref.chunk_width(d, 0, ITEM[dtt], 0, ITEM[dq])
+    assert v == (8 if d % 8 == 0 else 4 if d % 4 == 0 else 1)
+    is_probe = np.zeros(n + 1, bool)
+    is_probe[probe] = True
+    ahead = behind = 0
+    for metric in METRICS:
+        s = ref.scores(dense, queries, metric, v)
+        for exc in (None, exclude):
+            for k in (1, 10, 64):
+                got = ref.sparse_topk(probe, values, n, queries, k, metric, v, exc)
+                want = ref.topk(dense, queries, k, metric, v, exc, s=s)
+                assert same_scores(got[0], want[0]) and np.array_equal(got[1], want[1]), (metric, k, exc is None)
+                if k == 64:
+                    assert np.all(want[1] >= 0)
+                    p = is_probe[want[1]]
+                    ahead += np.count_nonzero(~p[:, :-1] & p[:, 1:])          # a zero row, then a probe row
+                    behind += np.count_nonzero(p[:, :-1] & ~p[:, 1:])
+            got = ref.sparse_rank(probe, values, n, queries, target, metric, v, exc)
+            assert got.dtype == np.int32
+            assert np.array_equal(got, ref.rank(dense, queries, target, metric, v, exc, s=s)), (metric, exc is None)
+            assert np.array_equal(got, ref.rank_of_scores(s, target, metric, exc)), (metric, exc is None)
+        assert np.array_equal(ref.topk_of_scores(s, 10, metric, exclude)[1],
+                              ref.topk(dense, queries, 10, metric, v, exclude, s=s)[1])
+    assert ahead > 0 and behind > 0
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_block_forms_of_topk_and_rank_equal_the_loops(metric):
+    """topk_of_scores / rank_of_scores (what the many-query GPU cases are compared with) == topk /
+    rank on the tie-heavy table with its NaN and inf rows, exclude and targets in and out of range"""
+    rng = np.random.default_rng(21)
+    table = tie_table(rng, 300, 4, "f32")
+    queries, _ = queries_for(rng, table, "f32", q=40)
+    s = ref.scores(table, queries, metric, 4)
+    for n in (1, 9, 10, 11, 300):
+        exc, target = rng.integers(-2, n + 2, 40), rng.integers(-1, n + 1, 40)
+        for k in (1, 10, 64):
+            for e in (None, exc):
+                got = ref.topk_of_scores(s[:, :n], k, metric, e)
+                want = ref.topk(table[:n], queries, k, metric, 4, e, s=s[:, :n])
+                assert same_scores(got[0], want[0]) and np.array_equal(got[1], want[1]), (n, k)
+        assert np.array_equal(ref.rank_of_scores(s[:, :n], target, metric, exc),
+                              ref.rank(table[:n], queries, target, metric, 4, exc, s=s[:, :n])), n
+
+
+# ---- the list under chosen arrival orders ---------------------------------------------------------
+@pytest.mark.parametrize("metric", ("ip", "l2"))
+@pytest.mark.parametrize("kind", ref.ARRIVAL_ORDERS)
+def test_arrival_orders_host_build_equals_the_restatement(TS, kind, metric):
+    """the cases of test_table_search_gpu.py::test_arrival_orders through the host build, which
+    inserts row by row, forwards and backwards; and the scores are the chosen ones"""
+    n = ref.ARRIVAL_N
+    assert ref.slabs_of(n, 1) == 3
+    for d in ref.ARRIVAL_DIMS:
+        table, queries = ref.arrival_case(kind, metric, d)
+        v = ref.chunk_width(d, 0, 4, 0, 4)
+        s = ref.scores(table, queries, metric, v)
+        col = table[:, 0].astype(np.float64)
+        assert np.array_equal(s[0], col if metric == "ip" else col * col)
+        best = ref.order(s[0], metric)
+        if kind == "improving":
+            assert best.tolist() == list(range(n - 1, -1, -1))
+        elif kind == "worsening" or kind == "equal" or kind == "zeros":
+            assert best.tolist() == list(range(n))
+        else:
+            assert best[:4].tolist() == ([6, 13, 20, 27] if metric == "ip" else [0, 7, 14, 21])
+        for k in ref.ARRIVAL_KS if d == 4 else (63,):
+            want = ref.topk(table, queries, k, metric, v, s=s)
+            for backwards in (False, True):
+                got = host_topk(TS, table, queries, k, metric, v, backwards=backwards)
+                assert same_scores(got[0], want[0]) and np.array_equal(got[1], want[1]), (d, k, backwards)
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_nan_queries_and_rows_that_score_the_fill(TS, metric):
+    """table_search.h lines 30-35 on the restatement and the host build: a query with a NaN makes
+    every score NaN - rows 0 .. k - 1 in row order, every rank 0; a real row whose score is the
+    fill value comes back with its row number, behind every other row and ahead of the -1 entries"""
+    larger = ref.larger_is_better(metric)
+    rng = np.random.default_rng(5)
+    table = rng.standard_normal((70, 4)).astype(F)
+    queries = rng.standard_normal((2, 4)).astype(F)
+    queries[0, 2] = np.nan
+    s = ref.scores(table, queries, metric, 4)
+    assert np.all(np.isnan(s[0])) and not np.any(np.isnan(s[1]))
+    for fn in (lambda k: ref.topk(table, queries, k, metric, 4), lambda k: host_topk(TS, table, queries, k, metric, 4)):
+        sc, rows = fn(64)
+        assert rows[0].tolist() == list(range(64)) and np.all(np.isnan(sc[0]))
+    target = np.array([33, 33])
+    for got in (ref.rank(table, queries, target, metric, 4), host_rank(TS, table, queries, target, metric, 4)):
+        assert got[0] == 0 and got[1] == np.count_nonzero((s[1] >= s[1][33]) if larger else (s[1] <= s[1][33])) - 1
+    # a row that scores the fill value: -inf under ip / cos, +inf under l2 / l1 (positive queries)
+    worst = F(-np.inf) if larger else F(np.inf)
+    table, queries = np.abs(table[:5]) + F(1), np.abs(queries) + F(1)
+    queries[0, 2] = 1
+    table[2, 1] = worst
+    if metric == "cos":                       # (an inf in a row makes its cos NaN: plant the score instead)
+        s = ref.scores(table[[0, 1, 1, 3, 4]], queries, metric, 4)
+        s[:, 2] = worst
+    else:
+        s = ref.scores(table, queries, metric, 4)
+    assert np.all(s[:, 2] == worst) and np.all(np.isfinite(np.delete(s, 2, 1)))
+    sc, rows = ref.topk(table, queries, 8, metric, 4, s=s)
+    assert np.all(rows[:, 4] == 2) and np.all(sc[:, 4] == worst) and np.all(rows[:, 5:] == -1) and np.all(sc[:, 5:] == worst)
+    assert np.all(np.sort(rows[:, :4], 1) == [0, 1, 3, 4])
+    if metric != "cos":
+        got = host_topk(TS, table, queries, 8, metric, 4)
+        assert same_scores(got[0], sc) and np.array_equal(got[1], rows)
+        # every row scores the fill value: the list is still rows 0 .. in order, each with its number
+        table[:, 1] = worst
+        for fn in (lambda: ref.topk(table, queries, 8, metric, 4), lambda: host_topk(TS, table, queries, 8, metric, 4)):
+            sc, rows = fn()
+            assert rows.tolist() == [[0, 1, 2, 3, 4, -1, -1, -1]] * 2 and np.all(sc == worst)
+        assert ref.rank(table, queries, [2, 4], metric, 4).tolist() == [4, 4]
+        assert host_rank(TS, table, queries, [2, 4], metric, 4).tolist() == [4, 4]
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_separated_rank_case_holds_its_precondition(metric):
+    """test_table_search_gpu.py::test_rank_equals_the_float64_count: no row's float64 score lies within
+    2 * bound of a target's, the targets cover the best row, the last and the middle, and the
+    restatement (fp32, in the stated order) already returns the float64 count"""
+    table, queries, target, count, margin = ref.separated_rank_case(metric, **ref.SEPARATED)
+    assert table.shape == (3073, 64) and queries.shape == (33, 64) and table.dtype == queries.dtype == F
+    assert margin > 1
+    assert count.min() == 0 and count.max() == 3072 and np.count_nonzero((count > 100) & (count < 2900)) >= 5
+    assert np.array_equal(ref.rank(table, queries, target, metric, 8), count)
 
 
 def test_new_entries_are_exported_and_bound():
