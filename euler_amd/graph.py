@@ -285,6 +285,51 @@ class _SparseFeatureEmbedding(torch.autograd.Function):
         return (torch.sparse_coo_tensor(distinct.reshape(1, -1), values, (n_rows, dim)),) + none
 
 
+_NB_MODE = {"add": 0, "max": 1, "mean": 2}
+_NB_KIND = {None: 0, "edge": 1, "norm": 2}
+
+
+class _NeighborAggregate(torch.autograd.Function):
+    """Graph.neighbor_aggregate: the fused forward (euler_gpu_neighbor_reduce).  The backward
+    pass rebuilds the neighbour list and differentiates the composition of the existing ops
+    (Graph.neighbor_aggregate_composed), so the gradients of table and root have its bits."""
+
+    @staticmethod
+    def forward(ctx, table, root, graph, nodes, edge_types, op, kind, self_loop, norm, a, b, od):
+        from . import ops
+        n, d = nodes.numel(), table.shape[1]
+        out = torch.empty((n, d), dtype=od, device=table.device)
+        et, et_p, k = _i32_array(edge_types)
+        nd, ns = norm if norm is not None else (None, None)
+        with graph._on_device():
+            check(lib().euler_gpu_neighbor_reduce(
+                graph._h, _stream(), _NB_MODE[op], _ptr(nodes), n, et_p, k, _NB_KIND[kind], 1 if self_loop else 0,
+                _ptr(table), ops._DT[table.dtype], table.shape[0], d, _ptr(nd), _ptr(ns), _ptr(root),
+                ops._DT[root.dtype] if root is not None else _lib.F32, a, b, _ptr(out), ops._DT[od]))
+        ctx.save_for_backward(table, nodes, *[t for t in (root, nd, ns) if t is not None])
+        ctx.has_root, ctx.has_norm = root is not None, norm is not None
+        ctx.args = (graph, edge_types, op, kind, self_loop, a, b, od)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        table, nodes = ctx.saved_tensors[:2]
+        rest = list(ctx.saved_tensors[2:])
+        root = rest.pop(0) if ctx.has_root else None
+        norm = (rest[0], rest[1]) if ctx.has_norm else None
+        graph, edge_types, op, kind, self_loop, a, b, od = ctx.args
+        need_t, need_r = ctx.needs_input_grad[0], root is not None and ctx.needs_input_grad[1]
+        with torch.enable_grad():
+            t = table.detach().requires_grad_(need_t)
+            r = root.detach().requires_grad_(need_r) if root is not None else None
+            out = graph._aggregate_composed(op, t, nodes, edge_types, kind, norm, self_loop, r, a, b, od)
+            wanted = [x for x, need in ((t, need_t), (r, need_r)) if need]
+            got = list(torch.autograd.grad(out, wanted, grad)) if wanted else []
+        grad_t = got.pop(0) if need_t else None
+        grad_r = got.pop(0) if need_r else None
+        return (grad_t, grad_r) + (None,) * 10
+
+
 class Graph:
     """Immutable graph in HBM (CSR + row metadata + alias tables)."""
 
@@ -1475,6 +1520,159 @@ class Graph:
                 m = int(new_total.value)
                 ids, w, t = ids[:m], w[:m], t[:m]
         return idx, ids, w, t
+
+    # ------------------------------------------------- full-neighbour aggregation
+    def _neighbor_degree(self, nodes, edge_types, self_loop, as_norm):
+        nodes = _as_i64_cuda(nodes, self.device).reshape(-1)
+        n = nodes.numel()
+        et, et_p, k = _i32_array(edge_types)
+        out = torch.empty(n, dtype=torch.float32 if as_norm else torch.int32, device=self.device)
+        with self._on_device():
+            check(lib().euler_gpu_neighbor_degree(self._h, _stream(), _ptr(nodes), n, et_p, k,
+                                                  1 if self_loop else 0, 1 if as_norm else 0, _ptr(out)))
+        return out
+
+    def neighbor_degree(self, nodes, edge_types, self_loop=False):
+        """int32 [n]: the number of stored neighbours of every node over the listed edge types,
+        as get_full_neighbor lists them (a type listed twice counts twice, an unknown id has
+        none); self_loop adds 1.  One small kernel, no host wait."""
+        return self._neighbor_degree(nodes, edge_types, self_loop, False)
+
+    def neighbor_norm(self, nodes, edge_types, self_loop=False):
+        """float32 [n]: 1 / sqrt(neighbor_degree), 0 at degree 0 - ops.gcn_norm's rule and bits."""
+        return self._neighbor_degree(nodes, edge_types, self_loop, True)
+
+    def full_neighbor_segments(self, nodes, edge_types, self_loop=False):
+        """(seg_ptr int64 [n + 1], ids int64, weights float32) of get_full_neighbor's lists as the
+        segment ops take them; self_loop appends every node's own id with weight 1 to its
+        segment.  The list neighbor_aggregate does NOT build: 16 bytes per listed edge and a
+        host wait, fewer than 2^31 entries a call."""
+        nodes = _as_i64_cuda(nodes, self.device).reshape(-1)
+        n = nodes.numel()
+        idx, ids, w, _t = self.get_full_neighbor(nodes, edge_types)
+        lens = (idx[:, 1] - idx[:, 0]).to(torch.int64)
+        seg_ptr = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        if not self_loop:
+            torch.cumsum(lens, 0, out=seg_ptr[1:])
+            return seg_ptr, ids, w
+        torch.cumsum(lens + 1, 0, out=seg_ptr[1:])
+        owner = torch.repeat_interleave(torch.arange(n, device=self.device), lens)
+        place = torch.arange(ids.numel(), device=self.device) + owner
+        all_ids = torch.empty(ids.numel() + n, dtype=torch.int64, device=self.device)
+        all_w = torch.ones(ids.numel() + n, dtype=torch.float32, device=self.device)
+        all_ids[place] = ids
+        all_w[place] = w
+        all_ids[seg_ptr[1:] - 1] = nodes
+        return seg_ptr, all_ids, all_w
+
+    def _aggregate_composed(self, op, table, nodes, edge_types, kind, norm, self_loop, root, a, b, od):
+        from . import ops
+        n, rows = nodes.numel(), table.shape[0]
+        seg_ptr, ids, w = self.full_neighbor_segments(nodes, edge_types, self_loop)
+        if kind == "norm" and op != "max":
+            # ops.gcn_aggregate with the scales (a, b) already formed (it refuses max: below)
+            if op == "mean" and ids.numel() >= (1 << 24):
+                raise ValueError("neighbor_aggregate_composed: a mean needs fewer than 2^24 listed edges")
+            return ops._GcnAggregate.apply(table, root, None, ids.to(torch.int32).contiguous(), seg_ptr, 0, n,
+                                           norm[0], norm[1], op, a, b, od)
+        if kind == "norm":
+            g = ids & 0xFFFFFFFF
+            owner = torch.repeat_interleave(torch.arange(n, device=self.device), seg_ptr[1:] - seg_ptr[:-1])
+            w = torch.where(g < rows, norm[0][owner] * norm[1][torch.clamp(g, max=rows - 1)],
+                            torch.zeros((), dtype=torch.float32, device=self.device))
+        mid = od if root is None else torch.float32
+        agg = ops.gather_segment_reduce(op, table, ids, n, seg_ptr=seg_ptr, out_dtype=mid,
+                                        edge_weight=None if kind is None else w)
+        if root is None:
+            return agg
+        return (agg * a + root.float() * b).to(od)
+
+    def neighbor_aggregate_composed(self, op, table, nodes, edge_types, weight=None, norm=None, self_loop=False,
+                                    root=None, alpha=None, root_scale=None, out_dtype=None):
+        """neighbor_aggregate as the composition of the existing ops - get_full_neighbor (two calls
+        and a host wait), the list with the self ids appended, then ops.gather_segment_reduce or
+        ops.gcn_aggregate: what neighbor_aggregate equals bit for bit, and what its backward pass
+        runs.  Same arguments; the list must have fewer than 2^31 entries."""
+        table, nodes, norm, root, a, b, od = self._aggregate_args(
+            "neighbor_aggregate_composed", op, table, nodes, edge_types, weight, norm, self_loop, root, alpha,
+            root_scale, out_dtype)
+        return self._aggregate_composed(op, table, nodes, edge_types, weight, norm, self_loop, root, a, b, od)
+
+    def _aggregate_args(self, name, op, table, nodes, edge_types, weight, norm, self_loop, root, alpha, root_scale,
+                        out_dtype):
+        from . import ops
+        if op not in _NB_MODE:
+            raise ValueError("%s: op is add, max or mean" % name)
+        if weight not in _NB_KIND:
+            raise ValueError("%s: weight is None, 'edge' or 'norm'" % name)
+        ops._dt(name, table)
+        od = ops._out_dt(name, table, out_dtype)
+        ops._need_cuda(table)
+        if table.dim() != 2 or table.shape[0] < 1:
+            raise ValueError("%s: table is [rows, D] with at least one row, indexed by node id" % name)
+        if not table.is_contiguous():
+            table = table.contiguous()
+        nodes = _as_i64_cuda(nodes, self.device).reshape(-1)
+        n = nodes.numel()
+        if weight == "norm":
+            if norm is None:
+                norm = (self.neighbor_norm(nodes, edge_types, self_loop),
+                        self.neighbor_norm(torch.arange(table.shape[0], device=self.device), edge_types, self_loop))
+            nd, ns = norm
+            for t, m, side in ((nd, n, "norm_dst"), (ns, table.shape[0], "norm_src")):
+                if t.dtype != torch.float32:
+                    raise TypeError("%s: %s is float32, not %s" % (name, side, t.dtype))
+                if t.dim() != 1 or t.numel() != m:
+                    raise ValueError("%s: %s has %d entries, not %s" % (name, side, m, tuple(t.shape)))
+                ops._need_cuda(t)
+            norm = (nd.detach().contiguous(), ns.detach().contiguous())
+        elif norm is not None:
+            raise ValueError("%s: norm comes with weight='norm'" % name)
+        a, b = 1.0, 1.0
+        if alpha is not None:
+            if root is None:
+                raise ValueError("%s: alpha needs root" % name)
+            a, b = 1.0 - float(alpha), float(alpha)
+        if root_scale is not None:
+            if root is None:
+                raise ValueError("%s: root_scale needs root" % name)
+            b = float(root_scale)
+        if root is not None:
+            if root.dtype != torch.float32 and root.dtype != table.dtype:
+                raise TypeError("%s: root is float32 or the dtype of table (%s), not %s"
+                                % (name, table.dtype, root.dtype))
+            if root.dim() != 2 or tuple(root.shape) != (n, table.shape[1]):
+                raise ValueError("%s: root is [n, D] = %s, not %s" % (name, (n, table.shape[1]), tuple(root.shape)))
+            ops._need_cuda(root)
+            root = root.contiguous()
+            # the scales as the fp32 numbers the kernel multiplies by
+            a, b = float(np.float32(a)), float(np.float32(b))
+        return table, nodes, norm, root, a, b, od
+
+    def neighbor_aggregate(self, op, table, nodes, edge_types, weight=None, norm=None, self_loop=False, root=None,
+                           alpha=None, root_scale=None, out_dtype=None):
+        """[n, D]: every node's reduce (op "add" / "max" / "mean") of the table rows of its stored
+        (full) neighbours over the listed edge types, read straight from the graph's rows in one
+        kernel (euler_gpu_neighbor_reduce): SGCN's S^K X, an APPNP step, a GCN layer over full
+        neighbours, the embeddings of all nodes after training.  The bits of get_full_neighbor
+        followed by ops.gather_segment_reduce / ops.gcn_aggregate (neighbor_aggregate_composed),
+        without the [E] list, without a host wait and without the 2^31 limit on E.
+        table is [rows, D] (fp32 / bf16 / fp16), indexed by node id: a neighbour id at or past
+        `rows` reads the last row (and has weight 0 under weight="norm").  weight None: the plain
+        reduce; "edge": every message times its edge's weight; "norm": times norm_dst[i] *
+        norm_src[j], norm = (norm_dst [n], norm_src [rows]) fp32 - None computes them from the
+        listed degrees (neighbor_norm of `nodes` and of the ids 0 .. rows - 1).  self_loop appends
+        the node's own row (weight 1, or its norm product); it counts in a mean.  root [n, D] adds
+        out = agg * a + root * b in the same pass; alpha and root_scale as ops.gcn_aggregate.
+        out_dtype None = the table's dtype, or torch.float32.
+        Gradients flow to table and root only.  The backward pass rebuilds the list with
+        get_full_neighbor and differentiates the composition, re-running its forward: it costs the
+        [E] list and a host wait, and happens only when a gradient is asked for."""
+        table, nodes, norm, root, a, b, od = self._aggregate_args(
+            "neighbor_aggregate", op, table, nodes, edge_types, weight, norm, self_loop, root, alpha, root_scale,
+            out_dtype)
+        return _NeighborAggregate.apply(table, root, self, nodes, edge_types, op, weight, bool(self_loop), norm,
+                                        a, b, od)
 
     def get_sorted_full_neighbor(self, nodes, edge_types):
         """tf_euler get_sorted_full_neighbor: rows ordered by neighbour id

@@ -1377,6 +1377,47 @@ int euler_gpu_table_topk(void* stream, int32_t metric, const void* table_dev, in
 int euler_gpu_table_rank(void* stream, int32_t metric, const void* table_dev, int32_t table_dtype,
                          int64_t n, int64_t d, const void* queries_dev, int32_t q_dtype, int64_t q,
                          const int64_t* target_dev, const int64_t* exclude_dev, int32_t* rank_out);
+/* neighbor_reduce: the aggregation over every queried node's STORED (full) neighbour list, read
+ * straight from the graph's rows - SGCN's S^K X, APPNP's power iteration (appnp_conv.py:54-60), a
+ * GCN layer over full neighbours (gcn_conv.py:33-51), the embeddings of all nodes after training -
+ * in one pass: what euler_gpu_get_full_neighbor (core/graph/node.cc:175-197) followed by
+ * euler_gpu_gather_segment_reduce_ids[_w]_t or euler_gpu_gather_reduce_norm_t (scatter_op.cc,
+ * gather_op.cc) computes, bit for bit, without the list of the edges (16 bytes per listed edge
+ * written and 12 read back), without the host wait for its total, and without the 2^31 limit on
+ * that total.  euler_amd/csrc/mp_rows.h states the contract:
+ *   out[i][c] = reduce over the updates p of nodes_dev[i], in the enumerated order, of
+ *               fl(table[min((uint32) low word of nbr[p], table_rows - 1)][c] * w(p))
+ * the updates being the entries of the row's listed edge-type groups as get_full_neighbor
+ * enumerates them (groups in listed order, a type listed twice read twice, a type outside [0, T)
+ * skipped, an id without a row: none).  mode 0 add (from +0), 1 max (from -1e9), 2 mean (the sum
+ * divided by length + 1e-7f).  weight_kind 0: w = 1; 1: w = fl(prefix_w[p] - prefix_w[p - 1]) (0
+ * for the row's first entry), the edge weight get_full_neighbor returns; 2: w = fl(norm_dst[i] *
+ * norm_src[g]) for the neighbour's index g = (uint32) low word of its id, norm_src fp32
+ * [table_rows], norm_dst fp32 [n]; 0 when g >= table_rows.  The product and the sum are separate
+ * fp32 roundings (mp_weighted.h).  self_loop != 0 appends the table row of nodes_dev[i] itself
+ * (same clamp; weight 1, or fl(norm_dst[i] * norm_src[nodes[i]]) for kind 2; counted by a mean),
+ * whether or not the node has a row.  root_dev (NULL: no epilogue, root_a / root_b are not read)
+ * is [n, d] in root_dtype (fp32 or table_dtype): out = fl(fl(agg * root_a) + fl(root[i] * root_b))
+ * before the one rounding to out_dtype (fp32 or table_dtype).  table_dev is [table_rows, d] in
+ * fp32 / bf16 / fp16, indexed by node id.  A queried node is one wave-slot's loop: a column's sum
+ * is never split.  EULER_GPU_ENOGRAPH: g NULL.  EULER_GPU_EINVAL, in this order: an unknown dtype,
+ * out_dtype / root_dtype neither fp32 nor table_dtype; mode; weight_kind; a negative n, d or k;
+ * (n == 0 or d == 0 returns EULER_GPU_OK and touches nothing;) a null buffer; k > 32; table_rows
+ * outside [1, 2^31); n >= 2^31; norm tables not exactly with weight_kind 2; a buffer not aligned
+ * to its type.  All of it is host arithmetic in front of the first HIP call.
+ * neighbor_degree: out_dev[i] = the listed degree of nodes_dev[i] (what get_full_neighbor's
+ * offsets differ by; + 1 with self_loop; INT32_MAX past it) as int32 (as_norm == 0) or as
+ * 1 / sqrt((float)deg) in fp32, 0 at degree 0 (euler_gpu_gcn_norm's rule).  No host wait. */
+int euler_gpu_neighbor_reduce(const euler_gpu_graph* g, void* stream, int32_t mode,
+                              const uint64_t* nodes_dev, int64_t n, const int32_t* edge_types_host,
+                              int32_t k, int32_t weight_kind, int32_t self_loop, const void* table_dev,
+                              int32_t table_dtype, int64_t table_rows, int64_t d,
+                              const float* norm_dst_dev, const float* norm_src_dev, const void* root_dev,
+                              int32_t root_dtype, float root_a, float root_b, void* out_dev,
+                              int32_t out_dtype);
+int euler_gpu_neighbor_degree(const euler_gpu_graph* g, void* stream, const uint64_t* nodes_dev,
+                              int64_t n, const int32_t* edge_types_host, int32_t k, int32_t self_loop,
+                              int32_t as_norm, void* out_dev);
 /* supervise_loss: the loss head of the supervised models (GraphSAGE, GCN, GAT, ... and the graph
  * classifiers: SuperviseModel.__call__ after out_fc, tf_euler/python/mp_utils/base.py:24-47,
  * SuperviseSolution of solution/base_supervise.py, GraphModel of mp_utils/base_graph.py:24-47,
