@@ -188,6 +188,8 @@ struct AliasEntry {
 };
 static_assert(sizeof(AliasEntry) == 32, "AliasEntry must be 32 bytes");
 
+struct NbAliasEntry;                  // nb_alias.h: the neighbour draw's alias entry (32 bytes per edge)
+
 struct NodeSamplerView {
   const AliasEntry* entries;          // all types, concatenated
   int32_t n_types;
@@ -308,6 +310,12 @@ struct euler_gpu_graph {
   int32_t hw_format = 0;       // ... the lines it holds: 1 = wb_hw.h, 2 = wb_hw2.h (tuning key 76 when it was built)
   std::vector<uint32_t> wb_overflow_rows;   // rows with a bucket that overflows its block (the first 4 096 found)
   mutable std::atomic<int> blk_ready{0};    // EnsureBlockedIndex built the EdgeBlocks (view.blk / skip1 / bpiv)
+  // Neighbour alias tables (nb_alias.h; nb_alias_kernels.hip): one 32-byte entry per edge at the
+  // edge's flat index, built by euler_gpu_graph_build_neighbor_alias or the first alias call,
+  // under nb_alias_mu.  Kept here, not in the view: the exact mode's kernels take the view by value.
+  mutable std::mutex nb_alias_mu;
+  mutable std::atomic<const euler_gpu::NbAliasEntry*> nb_alias{nullptr};
+  mutable int64_t nb_alias_bytes = 0;
   // Block construction (dataflow_kernels.hip): first-occurrence unique of a hop's node list
   // through a table indexed by graph ROW, one per stream, kept across calls: 8 bytes per row
   // {~epoch, smallest position} + 4 bytes {rank}.  Every hop of every call takes a new epoch

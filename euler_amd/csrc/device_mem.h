@@ -119,5 +119,9 @@ inline int64_t FreeBlocks(OwnedBlocks* owner) {
   return bytes;
 }
 
+// graph_build.hip: a finished build's blocks become the graph's (and count in its bytes), under the
+// lock the index builds commit under - for builds that run outside graph_build.hip.
+void AdoptBlocks(euler_gpu_graph* g, AllocList* blocks);
+
 #pragma GCC visibility pop
 }  // namespace euler_gpu

@@ -17,6 +17,7 @@
 
 #include "device_fns.h"
 #include "device_mem.h"
+#include "nb_alias.h"
 #include "wb_index.h"
 #include "wb_hw.h"
 #include "wb_hw2.h"
@@ -218,30 +219,18 @@ void DestroyGraph(euler_gpu_graph* g) {
   delete g;
 }
 
-// AliasMethod::Init (euler/common/alias_method.cc:23-63), restated for the
-// table build: LIFO small/large stacks, `avg` in double, weights updated in
-// float, prob in float.  Element order is the caller's (Q7).
+// AliasMethod::Init (euler/common/alias_method.cc:23-63) for the node / edge samplers' tables: the
+// build of nb_alias.h - one source with the neighbour alias tables - over vectors.
 void AliasBuild(const std::vector<float>& weights, std::vector<float>* prob,
                 std::vector<int64_t>* alias) {
   const size_t n = weights.size();
   prob->assign(n, 0.f);
   alias->assign(n, 0);
-  std::vector<int64_t> small, large;
+  if (n == 0) return;
   std::vector<float> w(weights);
-  const double avg = 1 / static_cast<double>(n);
-  for (size_t i = 0; i < n; ++i) {
-    if (w[i] > avg) large.push_back((int64_t)i); else small.push_back((int64_t)i);
-  }
-  while (!large.empty() && !small.empty()) {
-    const int64_t less = small.back(); small.pop_back();
-    const int64_t more = large.back(); large.pop_back();
-    (*prob)[less] = w[less] * n;
-    (*alias)[less] = more;
-    w[more] = w[more] + w[less] - avg;
-    if (w[more] > avg) large.push_back(more); else small.push_back(more);
-  }
-  while (!small.empty()) { (*prob)[small.back()] = 1.0; small.pop_back(); }
-  while (!large.empty()) { (*prob)[large.back()] = 1.0; large.pop_back(); }
+  std::vector<int64_t> stack(n);
+  AliasArrays<int64_t> tab{w.data(), prob->data(), alias->data()};
+  euler_gpu::AliasBuild(tab, (int64_t)n, stack.data());
 }
 
 // Graph::BuildGlobalSampler (core/graph/graph.cc:333-370) +
@@ -1150,6 +1139,11 @@ int EnsureWbIndex(const euler_gpu_graph* cg) {
   }
   g->wb_tried.store(1, std::memory_order_release);
   return EULER_GPU_OK;
+}
+
+void AdoptBlocks(euler_gpu_graph* g, AllocList* blocks) {
+  std::lock_guard<std::mutex> lk(g_blocked_mu);
+  g->bytes += blocks->HandOver(&g->allocations);
 }
 
 // test hook (euler_gpu_set_tuning key 56): the next N builds of the EdgeBlocks fail as an

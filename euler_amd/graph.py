@@ -341,6 +341,7 @@ class Graph:
         self.seed = 0
         self._call_id = 0
         self._lock = threading.Lock()
+        self._nb_method = "exact"   # what method=None of sample_neighbor / sample_fanout resolves to
         self.data_path = None       # the directory of a loaded graph (feature names)
         self.node_type_names = (meta or {}).get("node_types", {})
         self.edge_type_names = (meta or {}).get("edge_types", {})
@@ -522,6 +523,53 @@ class Graph:
                                                         C.byref(n)))
         return out[:n.value]
 
+    # ------------------------------------------------- alias neighbour mode
+    NEIGHBOR_METHODS = ("exact", "alias")
+
+    def build_neighbor_alias(self):
+        """Builds the neighbour alias tables (csrc/nb_alias.h: one 32-byte entry per edge) on the
+        current stream and waits for them; idempotent.  `method="alias"` calls build them on
+        first use.  Graphs with negative or NaN weights are refused (EulerGpuError)."""
+        with self._on_device():
+            check(lib().euler_gpu_graph_build_neighbor_alias(self._h, _stream()))
+
+    def neighbor_alias(self):
+        """(bytes, entries) of the neighbour alias tables, (0, 0) when they are not built; the
+        bytes are part of `device_bytes`."""
+        b, n = C.c_int64(0), C.c_int64(0)
+        check(lib().euler_gpu_graph_neighbor_alias_info(self._h, C.byref(b), C.byref(n)))
+        return b.value, n.value
+
+    def neighbor_alias_rows(self, ids):
+        """The alias entries of the rows of `ids`, in the row order of `export_rows`, as host
+        arrays: (row_ptr, id_self, id_alias, prob, w_self, w_alias).  The tables must be built."""
+        ids = _np(ids, np.uint64)
+        n = len(ids)
+        row_ptr = np.zeros(n + 1, np.int64)
+        args = (self._h, ids.ctypes.data_as(_lib.u64p), n, row_ptr.ctypes.data_as(_lib.i64p))
+        check(lib().euler_gpu_graph_export_neighbor_alias(*args, None, None, None, None, None))
+        tot = int(row_ptr[-1])
+        id_self, id_alias = np.zeros(max(tot, 1), np.uint64), np.zeros(max(tot, 1), np.uint64)
+        prob, w_self, w_alias = (np.zeros(max(tot, 1), np.float32) for _ in range(3))
+        check(lib().euler_gpu_graph_export_neighbor_alias(
+            *args, id_self.ctypes.data_as(_lib.u64p), id_alias.ctypes.data_as(_lib.u64p),
+            prob.ctypes.data_as(_lib.f32p), w_self.ctypes.data_as(_lib.f32p),
+            w_alias.ctypes.data_as(_lib.f32p)))
+        return row_ptr, id_self[:tot], id_alias[:tot], prob[:tot], w_self[:tot], w_alias[:tot]
+
+    def set_neighbor_method(self, name):
+        """The neighbour draw that `method=None` of `sample_neighbor` / `sample_fanout` resolves
+        to: "exact" (the default: the reference's CDF inversion, its neighbours bit for bit) or
+        "alias" (one alias-table entry per draw: the same distribution, other neighbours)."""
+        self._nb_method = self._neighbor_method(name)
+
+    def _neighbor_method(self, method):
+        if method is None:
+            return self._nb_method
+        if method not in self.NEIGHBOR_METHODS:
+            raise ValueError("method must be one of %s, not %r" % (" / ".join(self.NEIGHBOR_METHODS), method))
+        return method
+
     # ---------------------------------------------------------------- RNG
 
     def _on_device(self):
@@ -548,10 +596,16 @@ class Graph:
 
     # ------------------------------------------------------------ sampling
     def sample_neighbor(self, nodes, edge_types, count, default_node=-1,
-                        layout="tf", call_id=None, return_mask=False, dedup=True):
+                        layout="tf", call_id=None, return_mask=False, dedup=True, method=None,
+                        root_mask=None, root_group=1):
         """tf_euler SampleNeighbor (tf_euler/kernels/sample_neighbor_op.cc):
         nodes [n] int64 -> (neighbors [n,count] int64, weights f32, types
-        int32).  layout='core' gives the API_SAMPLE_NB fill (0, 0.0, 0)."""
+        int32).  layout='core' gives the API_SAMPLE_NB fill (0, 0.0, 0).
+        method: "exact" (the reference's draw), "alias" (the alias tables: same distribution,
+        other neighbours; `dedup` is accepted and ignored) or None = `set_neighbor_method`'s.
+        root_mask: optional uint8 [ceil(n / root_group)]; the roots of a non-zero byte sample as
+        node id 0 (how a fanout chains its hops)."""
+        method = self._neighbor_method(method)
         nodes = _as_i64_cuda(nodes, self.device)
         shape = tuple(nodes.shape) + (int(count),)
         flat = nodes.reshape(-1)
@@ -563,11 +617,18 @@ class Graph:
                 if return_mask else None)
         et, et_p, k = _i32_array(edge_types)
         lay = _lib.LAYOUT_TF if layout == "tf" else _lib.LAYOUT_CORE
+        if root_mask is not None:
+            if method == "exact" and not dedup:
+                raise ValueError("root_mask: not with dedup=False")
+            root_mask = root_mask.to(device=self.device, dtype=torch.uint8).contiguous()
+            if root_group < 1 or root_mask.numel() * int(root_group) < n:
+                raise ValueError("root_mask: needs ceil(n / root_group) bytes")
         with self._on_device():
-            if dedup:
-                check(lib().euler_gpu_sample_neighbor(
+            if method == "alias" or dedup:
+                fn = lib().euler_gpu_sample_neighbor_alias if method == "alias" else lib().euler_gpu_sample_neighbor
+                check(fn(
                     self._h, _stream(), self.seed, self._take_call_ids(1, call_id),
-                    _ptr(flat), n, None, 1, et_p, k, int(count), lay,
+                    _ptr(flat), n, _ptr(root_mask), int(root_group), et_p, k, int(count), lay,
                     int(default_node), _ptr(out_n), _ptr(out_w), _ptr(out_t),
                     _ptr(mask)))
             else:       # roots known to be distinct (sharded sampler)
@@ -658,10 +719,11 @@ class Graph:
         return out
 
     def sample_fanout(self, nodes, edge_types, counts, default_node=-1,
-                      call_id=None):
+                      call_id=None, method=None):
         """tf_euler sample_fanout (euler_ops/neighbor_ops.py:122-158 over
         tf_euler/kernels/sample_fanout_op.cc): returns (neighbors_list,
-        weights_list, types_list) with flattened per-hop tensors."""
+        weights_list, types_list) with flattened per-hop tensors.  method: as `sample_neighbor`."""
+        method = self._neighbor_method(method)
         nodes = _as_i64_cuda(nodes, self.device).reshape(-1)
         layers = len(counts)
         et, et_p, k, cnt, cnt_p = _fanout_plan(edge_types, counts)
@@ -683,8 +745,10 @@ class Graph:
         pn = (C.c_void_p * layers)(*[t.data_ptr() for t in outs_n])
         pw = (C.c_void_p * layers)(*[t.data_ptr() for t in outs_w])
         pt = (C.c_void_p * layers)(*[t.data_ptr() for t in outs_t])
+        # (the alias mode's workspace has the exact mode's size: euler_gpu_sample_fanout_alias_workspace)
+        fn = lib().euler_gpu_sample_fanout_alias if method == "alias" else lib().euler_gpu_sample_fanout
         with self._on_device():
-            check(lib().euler_gpu_sample_fanout(
+            check(fn(
                 self._h, _stream(), self.seed,
                 self._take_call_ids(layers, call_id), _ptr(nodes), n, et_p, k,
                 cnt_p, layers, int(default_node), pn, pw, pt, _ptr(ws)))

@@ -363,6 +363,66 @@ int euler_gpu_sample_fanout(const euler_gpu_graph* g, void* stream,
                             float* const* out_w_dev, int32_t* const* out_t_dev,
                             void* workspace_dev);
 
+/* ---- SampleNeighbor, alias mode (opt-in) -----------------------------------
+ * The calls above invert the row's running sums exactly as the reference does
+ * (RandomSelect): that is the default and the only mode that reproduces the reference's
+ * neighbours.  The calls below draw from the SAME distribution through one alias table per
+ * (row, edge-type group) - AliasMethod (common/alias_method.cc:23-78) over the group's
+ * normalised weights (FastWeightedCollection::Init, common/fast_weighted_collection.h:55-75),
+ * the structure the reference itself uses for SampleNode: one 32-byte entry read per draw,
+ * whatever the degree and the weight distribution.  For the same seed they pick DIFFERENT
+ * neighbours than the exact mode; the mode is validated statistically.  One departure from
+ * alias_method.cc:52-62: an edge of weight 0 is never drawn (csrc/nb_alias.h).
+ *
+ * The tables: 32 bytes per edge, counted in euler_gpu_graph_bytes; built by the call below or by
+ * the first alias call, on `stream`, under a per-graph lock (concurrent callers wait; the call
+ * returns when the build has finished).  Idempotent.  EULER_GPU_EINVAL for a graph with negative
+ * or NaN weights; a failed build leaves the graph as it was and returns the HIP error.  Builds
+ * none of the exact mode's indexes. */
+int euler_gpu_graph_build_neighbor_alias(euler_gpu_graph* g, void* stream);
+/* Bytes and entries of the tables; 0 / 0 when they are not built. */
+int euler_gpu_graph_neighbor_alias_info(const euler_gpu_graph* g, int64_t* bytes_host,
+                                        int64_t* entries_host);
+/* The entries of the listed rows in the row order of euler_gpu_graph_export_rows (spot checks):
+ * entry x of row i at row_ptr_host[i] + x holds AliasMethod's prob_ (alias_method.cc:43,55,61),
+ * the ids of the edge itself and of its alias_ edge, and the weights the exact mode returns for
+ * the two.  Call with id_self_host == NULL to obtain row_ptr_host (n + 1) first.
+ * EULER_GPU_EINVAL when the tables are not built. */
+int euler_gpu_graph_export_neighbor_alias(const euler_gpu_graph* g, const uint64_t* ids_host,
+                                          int64_t n, int64_t* row_ptr_host,
+                                          uint64_t* id_self_host, uint64_t* id_alias_host,
+                                          float* prob_host, float* w_self_host,
+                                          float* w_alias_host);
+/* euler_gpu_sample_neighbor with the alias draw: the same parameters, row lookup, type modes
+ * (Node::__SampleNeighbor, core/graph/node.cc:98-161; the type of a sample is drawn as the exact
+ * mode draws it), layouts, fills, first-id-0 rule, root mask and row mask.  The neighbour is
+ * AliasMethod::Next (alias_method.cc:66-78): column = floor(d * u), one entry, coin < prob ? the
+ * edge : its alias.  Domain 0, stream = the root's node id; sample j uses draw indices 4 j (type,
+ * when one is drawn), 4 j + 2 (column), 4 j + 3 (coin).  Duplicate roots get identical rows. */
+int euler_gpu_sample_neighbor_alias(const euler_gpu_graph* g, void* stream,
+                                    uint64_t seed, uint32_t call_id,
+                                    const uint64_t* roots_dev, int64_t n,
+                                    const uint8_t* root_mask_dev, int32_t root_group,
+                                    const int32_t* edge_types_host, int32_t k,
+                                    int32_t count, int32_t layout,
+                                    int64_t default_node, uint64_t* out_id_dev,
+                                    float* out_w_dev, int32_t* out_t_dev,
+                                    uint8_t* out_row_mask_dev);
+/* euler_gpu_sample_fanout with the alias draw (AliasMethod::Next per sample, alias_method.cc:
+ * 66-78): `layers` launches in one enqueue, hop h with call_id + h on hop h - 1's TF-layout ids;
+ * the rows under a default row of hop h - 1 sample as node id 0.  Same parameters and workspace
+ * size as the exact calls. */
+size_t euler_gpu_sample_fanout_alias_workspace(int64_t n, const int32_t* counts_host,
+                                               int32_t layers);
+int euler_gpu_sample_fanout_alias(const euler_gpu_graph* g, void* stream,
+                                  uint64_t seed, uint32_t call_id,
+                                  const uint64_t* roots_dev, int64_t n,
+                                  const int32_t* edge_types_host, int32_t k,
+                                  const int32_t* counts_host, int32_t layers,
+                                  int64_t default_node, uint64_t* const* out_id_dev,
+                                  float* const* out_w_dev, int32_t* const* out_t_dev,
+                                  void* workspace_dev);
+
 /* ---- SampleNode -----------------------------------------------------------
  * Replaces euler::SampleNode (core/api/api.cc:32-37) -> Graph::SampleNode
  * (core/graph/graph.cc:221-275) -> AliasMethod::Next (common/alias_method.cc:
