@@ -324,6 +324,7 @@ struct euler_gpu_graph {
   struct FlowTableDense { void* p = nullptr; size_t rows = 0; uint32_t next_epoch = 1; };
   mutable std::map<void*, FlowTableDense> flow_tables;
   int32_t shards = 1;                 // shards of the dataset this graph holds a part of
+  std::vector<float> from_edges_pass_ms;    // a graph built from an edge list: its passes' times (edge_build.h: EbPass)
   // Graph-label index (graph_label_kernels.hip): the nodes of every label in table order (label
   // r owns label_nodes[label_start[r] .. label_start[r + 1]), ascending ids) and the labels'
   // bytes; built from the node binary slot label_slot (binary_graph_label of a loaded dataset)
@@ -351,6 +352,8 @@ int BuildGraphFromHost(const euler_gpu_host_csr* csr, int device,
 int BuildGraphSynthetic(const euler_gpu_synth_params* p, int device,
                         int32_t partitions, int32_t shard_index, int32_t shards,
                         euler_gpu_graph** out);
+// an edge list on the device -> graph (the passes: edge_build.h)
+int BuildGraphFromEdges(const euler_gpu_dev_edges* e, int device, void* stream, euler_gpu_graph** out);
 int EnsureBlockedIndex(const euler_gpu_graph* g);   // EdgeBlocks + block pivots, on first use
 // Graph::BuildGlobalSampler's per-type alias tables + type collection (host work): the view
 // without its entries pointer, the entries, the per-type weight sums

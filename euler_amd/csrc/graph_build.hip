@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cstdlib>
 #include <cmath>
 #include <cstring>
@@ -17,6 +18,7 @@
 
 #include "device_fns.h"
 #include "device_mem.h"
+#include "edge_build.h"
 #include "nb_alias.h"
 #include "wb_index.h"
 #include "wb_hw.h"
@@ -809,6 +811,69 @@ int BuildGraphSynthetic(const euler_gpu_synth_params* sp, int device,
   return EULER_GPU_OK;
 }
 
+// ------------------------------------------------------------------------
+// An edge list on the device -> graph.  The rows, the id map, the flags and the features come from
+// the device passes of edge_build_kernels.hip (edge_build.h states them); the search index and
+// the node sampler are the ones of the two builds above.
+// ------------------------------------------------------------------------
+void LaunchHashInit(hipStream_t st, uint64_t* slots, uint64_t cap) {
+  hipLaunchKernelGGL(HashInitKernel, dim3(GridFor((int64_t)cap, 256)), dim3(256), 0, st, slots, cap);
+}
+
+int BuildGraphFromEdges(const euler_gpu_dev_edges* e, int device, void* stream, euler_gpu_graph** out) {
+  {
+    const int rc = CheckDevEdges(e, out);
+    if (rc != EULER_GPU_OK) return rc;
+  }
+  EG_HIP(hipSetDevice(device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  KeepPoolMemory(device);
+  GraphBuilder b;
+  b.g->device = device;
+  GraphView& v = b.g->view;
+  EdgeBuildFacts facts;
+  int rc = BuildRowsFromEdges(e, st, &b, &v, &facts);
+  if (rc != EULER_GPU_OK) {
+    // (whatever a failed pass left in flight ends before the builder returns the blocks)
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  const int64_t n = v.n_rows;
+  b.g->max_id = facts.max_id;
+  b.g->feat_slot_aligned = facts.feat_slot_aligned;
+  b.g->node_type_dev = facts.node_type_dev;
+  auto t0 = std::chrono::steady_clock::now();
+  auto lap = [&t0, &facts](int pass) {
+    const auto t1 = std::chrono::steady_clock::now();
+    facts.pass_ms[pass] += std::chrono::duration<float, std::milli>(t1 - t0).count();
+    t0 = t1;
+  };
+  rc = BuildSearchIndex(&b);              // (null stream; the passes' stream is drained)
+  if (rc != EULER_GPU_OK) return rc;
+  lap(kEbSearchIndex);
+  b.g->has_sampler = false;
+  b.g->n_node_types = e->n_node_types > 0 ? e->n_node_types : 1;
+  if (e->node_sampler != 0) {
+    // Graph::BuildGlobalSampler over the rows in row order, as BuildGraphFromHost enumerates them
+    std::vector<uint64_t> ids((size_t)n);
+    std::vector<int32_t> types((size_t)n, 0);
+    std::vector<float> weights((size_t)n, 1.0f);
+    if (n > 0) {
+      EG_HIP(hipMemcpy(ids.data(), v.row_id, (size_t)n * 8, hipMemcpyDeviceToHost));
+      if (e->node_type) EG_HIP(hipMemcpy(types.data(), e->node_type, (size_t)n * 4, hipMemcpyDeviceToHost));
+      if (e->node_weight) EG_HIP(hipMemcpy(weights.data(), e->node_weight, (size_t)n * 4, hipMemcpyDeviceToHost));
+    }
+    rc = BuildNodeSampler(&b, ids, types, weights, b.g->n_node_types);
+    if (rc != EULER_GPU_OK) return rc;
+  }
+  lap(kEbNodeSampler);
+  b.g->from_edges_pass_ms.assign(facts.pass_ms, facts.pass_ms + kEbPasses);
+  b.g->shards = 1;
+  b.Commit();
+  *out = b.g.release();
+  return EULER_GPU_OK;
+}
+
 // ---- weight-bucket index (wb_index.h) ------------------------------------------------
 __global__ void WbCountKernel(GraphView g, uint32_t* nbk) {
   const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1245,6 +1310,21 @@ int euler_gpu_graph_create_synthetic(const euler_gpu_synth_params* p, int device
                                      int32_t partitions, int32_t shard_index,
                                      int32_t shards, euler_gpu_graph** out) {
   return BuildGraphSynthetic(p, device, partitions, shard_index, shards, out);
+}
+
+int euler_gpu_graph_create_from_edges(const euler_gpu_dev_edges* edges, int device, void* stream,
+                                      euler_gpu_graph** out) {
+  return BuildGraphFromEdges(edges, device, stream, out);
+}
+
+int euler_gpu_graph_from_edges_pass_ms(const euler_gpu_graph* g, float* ms_host, int32_t cap,
+                                       int32_t* n_host) {
+  if (!g) return Fail(EULER_GPU_ENOGRAPH, "from_edges_pass_ms: null graph");
+  if (!n_host || cap < 0 || (cap > 0 && !ms_host)) return Fail(EULER_GPU_EINVAL, "from_edges_pass_ms: bad arguments");
+  const int32_t n = (int32_t)g->from_edges_pass_ms.size();
+  for (int32_t i = 0; i < n && i < cap; ++i) ms_host[i] = g->from_edges_pass_ms[(size_t)i];
+  *n_host = n;
+  return EULER_GPU_OK;
 }
 
 int euler_gpu_graph_load(const char* data_path, int device, int32_t shard_index,

@@ -420,6 +420,90 @@ class Graph:
         return cls(h, device)
 
     @classmethod
+    def from_edges(cls, src, dst=None, edge_type=None, weight=None, n_edge_types=None, nodes=None,
+                   node_type=None, node_weight=None, n_node_types=None, features=None,
+                   undirected=False, node_sampler=True, device=None):
+        """The graph of an edge list that lives on the device, built there (csrc/edge_build.h): the
+        same graph `from_csr` makes from these edges laid out by the reference's rules.
+
+        src, dst: [E] int64 device tensors (the bits of the u64 ids); a [2, E] edge_index is taken as
+        src with dst=None.  edge_type [E] (None: all 0), weight [E] (None: all 1.0).  n_edge_types None
+        = max(edge_type) + 1.  nodes [N]: the rows, in this order (None: the distinct ids of src and
+        dst, ascending as unsigned numbers).  node_type / node_weight [N] and features - a list of
+        [N, d] fp32 tensors, one per dense feature slot - need nodes.  undirected: the list is the
+        edges followed by all of them reversed.  node_sampler=False leaves the global node sampler to
+        a later set_node_sampler.  Nothing given is written to; the work runs on the current stream
+        and the graph is complete on return."""
+        def dev_tensor(x, dtype):
+            if x is None:
+                return None
+            if not torch.is_tensor(x):
+                x = torch.as_tensor(np.asarray(x))
+            return x.to(device=dev, dtype=dtype).contiguous()
+
+        if dst is None:
+            if not torch.is_tensor(src) or src.dim() != 2 or src.shape[0] != 2:
+                raise ValueError("from_edges: dst=None needs a [2, E] edge_index as src")
+            src, dst = src[0], src[1]
+        if device is None:
+            device = src.device.index if torch.is_tensor(src) and src.is_cuda else torch.cuda.current_device()
+        dev = torch.device("cuda", device)
+        src = dev_tensor(src, torch.int64).reshape(-1)
+        dst = dev_tensor(dst, torch.int64).reshape(-1)
+        n_e = src.numel()
+        if dst.numel() != n_e:
+            raise ValueError("from_edges: src and dst differ in length")
+        edge_type = dev_tensor(edge_type, torch.int32)
+        weight = dev_tensor(weight, torch.float32)
+        for t, what in ((edge_type, "edge_type"), (weight, "weight")):
+            if t is not None and t.numel() != n_e:
+                raise ValueError("from_edges: %s has %d entries for %d edges" % (what, t.numel(), n_e))
+        if n_edge_types is None:
+            n_edge_types = int(edge_type.max()) + 1 if edge_type is not None and n_e else 1
+        nodes = dev_tensor(nodes, torch.int64)
+        n_n = nodes.numel() if nodes is not None else 0
+        if nodes is not None and n_n == 0:
+            nodes = torch.empty(1, dtype=torch.int64, device=dev)      # no rows, but a pointer: "given"
+        node_type = dev_tensor(node_type, torch.int32)
+        node_weight = dev_tensor(node_weight, torch.float32)
+        for t, what in ((node_type, "node_type"), (node_weight, "node_weight")):
+            if t is not None and nodes is not None and t.numel() != n_n:
+                raise ValueError("from_edges: %s has %d entries for %d nodes" % (what, t.numel(), n_n))
+        if n_node_types is None:
+            n_node_types = int(node_type.max()) + 1 if node_type is not None and node_type.numel() else 1
+        feats = [dev_tensor(f, torch.float32) for f in (features or [])]
+        for f in feats:
+            if nodes is not None and (f.dim() != 2 or f.shape[0] != n_n):
+                raise ValueError("from_edges: a feature slot is [N, d], N = len(nodes)")
+        e = _lib.DevEdges()
+        e.n_edges, e.n_nodes = n_e, n_n
+        e.n_edge_types, e.undirected = int(n_edge_types), 1 if undirected else 0
+        e.src, e.dst, e.type, e.weight = _ptr(src), _ptr(dst), _ptr(edge_type), _ptr(weight)
+        e.nodes, e.node_type, e.node_weight = _ptr(nodes), _ptr(node_type), _ptr(node_weight)
+        e.n_node_types, e.node_sampler = int(n_node_types), 1 if node_sampler else 0
+        e.n_features = len(feats)
+        if feats:
+            ptrs = (C.c_void_p * len(feats))(*[f.data_ptr() for f in feats])
+            dims = (C.c_int32 * len(feats))(*[int(f.shape[1]) if f.dim() == 2 else 0 for f in feats])
+            e.features = C.cast(ptrs, C.POINTER(C.c_void_p))
+            e.feature_dims = C.cast(dims, _lib.i32p)
+        h = C.c_void_p()
+        with torch.cuda.device(dev):
+            check(lib().euler_gpu_graph_create_from_edges(C.byref(e), device, _stream(), C.byref(h)))
+        return cls(h, device)
+
+    def from_edges_pass_ms(self):
+        """{pass: milliseconds} of the build of a graph made by from_edges (the stream drained after
+        each pass); {} for any other graph."""
+        names = ("rows", "id_map", "keys", "sort", "segments", "gather", "prefix_short_rows",
+                 "prefix_long_rows", "features", "search_index", "node_sampler")
+        ms = np.zeros(len(names), np.float32)
+        n = C.c_int32(0)
+        check(lib().euler_gpu_graph_from_edges_pass_ms(self._h, ms.ctypes.data_as(_lib.f32p), len(names),
+                                                       C.byref(n)))
+        return {k: float(x) for k, x in zip(names[:n.value], ms)}
+
+    @classmethod
     def load(cls, data_path, device=0, shard_index=0, shards=1, edges=False):
         """Graph::Init over a data directory; edges=True also loads the Edge records the shard
         keeps (edge sampling and edge features)."""

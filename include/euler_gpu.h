@@ -150,6 +150,60 @@ int euler_gpu_graph_create_synthetic(const euler_gpu_synth_params* p,
                                      int device, int32_t partitions,
                                      int32_t shard_index, int32_t shards,
                                      euler_gpu_graph** out);
+/* An edge list in device memory, as OGB, PyG and most pipelines hand a graph over.  Every array is
+ * read only.  features / feature_dims are HOST arrays (of device pointers and of widths). */
+typedef struct euler_gpu_dev_edges {
+  int64_t n_edges;             /* E                                                       */
+  int64_t n_nodes;             /* N, the length of nodes (not looked at when nodes NULL)  */
+  int32_t n_edge_types;        /* T: 1 .. 32                                              */
+  int32_t undirected;          /* != 0: the list is the E edges, then all of them reversed */
+  const uint64_t* src;         /* [E] device                                              */
+  const uint64_t* dst;         /* [E] device                                              */
+  const int32_t* type;         /* [E] device, or NULL (all type 0)                        */
+  const float* weight;         /* [E] device, or NULL (all 1.0f)                          */
+  const uint64_t* nodes;       /* [N] device: the rows, in this order; or NULL            */
+  const int32_t* node_type;    /* [N] device or NULL (all type 0); needs nodes            */
+  const float* node_weight;    /* [N] device or NULL (all 1.0f); needs nodes              */
+  int32_t n_node_types;        /* 0 .. 32; 0 = 1                                          */
+  int32_t node_sampler;        /* != 0: build the global node sampler over the rows       */
+  int32_t n_features;          /* dense feature slots; needs nodes                        */
+  int32_t pad0;
+  const float* const* features;  /* HOST [n_features]: device pointers to [N, dim] fp32   */
+  const int32_t* feature_dims;   /* HOST [n_features]: the widths, each >= 1             */
+} euler_gpu_dev_edges;
+/* The graph of an edge list, built on the device: replaces GraphBuilder::Build + Node::Init
+ * (core/graph/graph_builder.cc:57-158, core/graph/node.cc:46-66) over files the reference's
+ * converters wrote, and the host pass of euler_gpu_graph_create.  The result is the graph
+ * euler_gpu_graph_create makes from the same edges laid out by the reference's rules - the same
+ * bytes in every row array, the same output of every seeded call:
+ *   rows     nodes NULL: one per distinct id of src and dst, ascending as UNSIGNED 64-bit numbers;
+ *            nodes given: exactly those, in that order - an id twice is refused, an edge whose
+ *            src is not among them is refused, a dst that is not among them stays a neighbour
+ *            without a row.  A node without out-edges is a row of degree 0.
+ *   entries  of a row: grouped by type 0 .. T-1, within a (row, type) group in the order of the
+ *            list (the sort is stable); repeated edges are all kept.
+ *   weights  prefix_w is the sequential fp32 sum over the whole row, type_prefix the running sum
+ *            of each group's own sequential fp32 sum (Node::Init); weights are not validated.
+ *   id map   the strided identity when row r has the id base + r * stride, stride > 0; else the
+ *            hash table.  has_zero_nbr / monotone / uniform_w as euler_gpu_graph_create sets them.
+ *   features the uniform layout: a row's slots side by side, feat_stride = the sum of the widths.
+ *   sampler  node_sampler != 0: Graph::BuildGlobalSampler over the rows in row order (the ids,
+ *            types and weights are copied to the host for it); 0: none, as a synthetic graph, for
+ *            a later euler_gpu_graph_set_node_sampler.  node_type is kept either way.
+ * The work runs on `stream` (a hipStream_t; NULL = the null stream) and the call returns when the
+ * graph is complete.  Temporaries peak at 16 bytes per entry of the list (24 when N * T > 2^32)
+ * plus 8 (N * T + 1), or at 32 E while the rows of a nodes == NULL call are found, and are
+ * returned before the search index is built (csrc/edge_build.h has the passes).
+ * E = 0 and N = 0 are graphs.  EULER_GPU_EINVAL, checked in this order before the first HIP call:
+ * a null argument; a negative size; T outside 1 .. 32; n_node_types outside 0 .. 32; a null src
+ * or dst with E > 0; features, node_type or node_weight without nodes; a null features /
+ * feature_dims array or entry, a width < 1, widths summing to 2^31 or more; a buffer not aligned
+ * to its type; E (2 E when undirected) >= 2^31 - a position in the list is a uint32 and type_end an
+ * int32, so no row can reach 2^31 entries either (hipcub's own item counts are 64-bit).  Found on
+ * the device, with the count in the message: a type outside [0, T); a src that is no row; an id
+ * twice in nodes.  On any failure *out is NULL and nothing stays allocated. */
+int euler_gpu_graph_create_from_edges(const euler_gpu_dev_edges* edges, int device, void* stream,
+                                      euler_gpu_graph** out);
 /* Load a directory written by euler/tools (euler.meta + Node/<x>_<partition>.dat), the
  * input of the reference's Graph::Init (core/graph/graph_builder.cc:57-158,
  * core/graph/node.cc:414-526). */

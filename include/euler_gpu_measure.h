@@ -270,6 +270,13 @@ int euler_gpu_random_walk_algo_bytes(const euler_gpu_graph* g, void* stream,
                                      int32_t walk_len, float p, float q,
                                      double* bytes_host);
 
+/* The wall-clock milliseconds of the passes of the build that made g, the stream drained after
+ * each: rows, id map, keys, sort, segments, gather, prefix of the short rows, prefix of the long
+ * rows, features, search index, node sampler (11 floats; up to cap are written, *n_host = 11).
+ * A graph not built from edges: *n_host = 0. */
+int euler_gpu_graph_from_edges_pass_ms(const euler_gpu_graph* g, float* ms_host, int32_t cap,
+                                       int32_t* n_host);
+
 #ifdef __cplusplus
 }
 #endif
