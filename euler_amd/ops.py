@@ -734,6 +734,193 @@ def gather_segment_topk(params, gather_indices, size, k, seg_ptr=None, count=Non
     return (out, sel) if return_indices else out
 
 
+# ---- pooling aggregation (SAGE meanpool / maxpool: utils/aggregators.py:75-114) ----------------
+_POOL_OP = {"max": 0, "mean": 1, "add": 2}
+_POOL_ACT = {"relu": 0, "none": 1}
+# The backward pass recomputes the composed form over chunks of whole destinations; a chunk holds
+# at most this many gathered rows (one destination at least), which bounds its temporaries.
+POOL_GRAD_CHUNK_ROWS = 1 << 20
+
+
+def _pool_raw(op, act, table, weight, bias, gi, sp, count, e, size, od):
+    """euler_gpu_pool_aggregate on prepared tensors -> out [size, F]"""
+    f = int(weight.shape[1])
+    out = (torch.zeros if size == 0 else torch.empty)((size, f), dtype=od, device=table.device)
+    if size == 0:
+        return out
+    with _on(table.device):
+        check(lib().euler_gpu_pool_aggregate(
+            _stream(), _POOL_OP[op], _POOL_ACT[act], _ptr(table), _DT[table.dtype], int(table.shape[0]),
+            _ptr(weight), _ptr(bias), _DT[bias.dtype] if bias is not None else 0, _ptr(gi),
+            int(gi is not None and gi.dtype == torch.int64), _ptr(sp), int(count), e, int(table.shape[1]), f, size,
+            _ptr(out), _DT[od]))
+    return out
+
+
+def _pool_chunks(sp, count, size):
+    """[(r_a, r_b, p_a, p_b)]: runs of whole destinations of at most POOL_GRAD_CHUNK_ROWS positions
+    (a longer destination is a chunk of its own).  With seg_ptr the boundaries come to the host."""
+    cap = max(1, int(POOL_GRAD_CHUNK_ROWS))
+    if sp is None:
+        step = max(1, cap // count)
+        return [(r, min(r + step, size), r * count, min(r + step, size) * count) for r in range(0, size, step)]
+    b = np.maximum.accumulate(sp.cpu().numpy())
+    chunks, r = [], 0
+    while r < size:
+        nxt = max(r + 1, int(np.searchsorted(b, b[r] + cap, side="right")) - 1)
+        nxt = min(nxt, size)
+        chunks.append((r, nxt, int(b[r]), int(b[nxt])))
+        r = nxt
+    return chunks
+
+
+class _PoolAggregate(torch.autograd.Function):
+    """The fused forward; the backward recomputes the composed form chunk by chunk (see
+    pool_aggregate)."""
+
+    @staticmethod
+    def forward(ctx, table, weight, bias, gi, sp, count, e, size, op, act, od):
+        out = _pool_raw(op, act, table, weight, bias, gi, sp, count, e, size, od)
+        ctx.save_for_backward(table, weight, *[t for t in (bias, gi, sp) if t is not None])
+        ctx.conf = (bias is not None, gi is not None, sp is not None, count, e, size, op, act)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        has_bias, has_gi, has_sp, count, e, size, op, act = ctx.conf
+        saved = list(ctx.saved_tensors)
+        table, weight = saved[0], saved[1]
+        rest = saved[2:]
+        bias = rest.pop(0) if has_bias else None
+        gi = rest.pop(0) if has_gi else None
+        sp = rest.pop(0) if has_sp else None
+        rows, d = table.shape
+        dev = table.device
+        w32 = weight.to(_F32)
+        b32 = bias.to(_F32) if has_bias else None
+        grad = grad.to(_F32)
+        want_w, want_b = ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
+        d_table = torch.zeros((rows, d), dtype=_F32, device=dev) if ctx.needs_input_grad[0] else None
+        d_w = torch.zeros_like(w32) if want_w else None
+        d_b = torch.zeros(w32.shape[1], dtype=_F32, device=dev) if want_b else None
+        sp_clamped = torch.cummax(sp.clamp(0, e), 0).values if has_sp else None
+        for r_a, r_b, p_a, p_b in _pool_chunks(sp_clamped, count, size):
+            n = r_b - r_a
+            if p_b == p_a:
+                continue
+            g = gi[p_a:p_b].to(torch.int64) if has_gi else torch.arange(p_a, p_b, device=dev)
+            valid = (g >= 0) & (g < rows)
+            x = _gather_raw(table, torch.where(valid, g, torch.zeros_like(g)), _F32).masked_fill_(~valid.reshape(-1, 1), 0)
+            z = x @ w32
+            if has_bias:
+                z = z + b32
+            h = torch.relu(z) if act == "relu" else z
+            dst = _segment_dst(sp_clamped[r_a:r_b + 1] - p_a if has_sp else None, count, n, dev)
+            g_out = grad[r_a:r_b].contiguous()
+            if op == "max":
+                per_edge = _max_per_edge(h, _scatter_raw(_MAX, h, dst, n), dst, n, g_out)
+            elif op == "mean":      # the forward multiplies by 1 / len, and so does its gradient
+                lens = _scatter_raw(_ADD, torch.ones((p_b - p_a, 1), dtype=_F32, device=dev), dst, n)
+                inv = torch.where(lens > 0, 1.0 / lens, torch.zeros_like(lens))
+                per_edge = _gather_raw(g_out * inv, dst)
+            else:
+                per_edge = _gather_raw(g_out, dst)
+            dz = per_edge * (z > 0).to(_F32) if act == "relu" else per_edge
+            if want_w:
+                d_w += x.t() @ dz
+            if want_b:
+                d_b += dz.sum(0)
+            if d_table is not None:
+                key = torch.where(valid, g, torch.full_like(g, -1))
+                d_table += _scatter_raw(_ADD, dz @ w32.t(), key, rows)
+        return (d_table.to(table.dtype) if d_table is not None else None,
+                d_w.to(weight.dtype) if want_w else None,
+                d_b.to(bias.dtype) if want_b else None) + (None,) * 8
+
+
+def pool_aggregate(op, table, weight, gather_indices, size, bias=None, seg_ptr=None, count=None, activation="relu",
+                   out_dtype=None):
+    """The meanpool / maxpool aggregators of the reference's SageEncoder (utils/aggregators.py:
+    75-114) in one pass on the matrix units:
+
+        out[r] = reduce_{p in segment(r)} act(table[gather_indices[p]] @ weight + bias)
+
+    op "max" / "mean" / "add", activation "relu" / "none" - without the [e, d] gathered block or
+    the [e, F] activation block of gather + matmul + relu + scatter_*.  table [rows, d] fp32 / bf16
+    / fp16; weight [d, F] (a TF Dense kernel's layout) of the table's dtype; bias [F], fp32 or the
+    table's dtype; 1 <= d, F <= 4096.  Segments and indices are those of gather_segment_topk:
+    seg_ptr (int64 [size + 1]) or count; int32 indices, the int64 ids a sampler returned, or None
+    (position p reads row p).  An index outside [0, rows) names no row: it is never dereferenced,
+    reads as a row of +0 and takes part with the term act(bias) - a default_node fill in the
+    reference - and its table gradient is dropped.  Products are accumulated in fp32 in an order
+    that depends only on d; the terms of a segment are folded in increasing p in fp32 (max: NaN
+    greatest; mean: one multiply by 1 / len); one rounding to out_dtype (fp32 or the table's; None:
+    the table's).  An empty segment gives +0.  The same call gives the same bits on every run and
+    for count or the equivalent seg_ptr.  The full contract and the tiling: csrc/mp_pool.h.
+
+    Differentiable in table, weight and bias.  The backward pass is deliberately NOT a fused
+    kernel (that is three more GEMM shapes and a deterministic split-K reduce - a change of its
+    own): it recomputes the composed form in fp32 over chunks of whole destinations of at most
+    POOL_GRAD_CHUNK_ROWS gathered rows - this module's gather, a matmul, the activation and the
+    scatter gradients, so a max gradient is split evenly among maximal positions - and sums dW,
+    db and the table gradient over the chunks in chunk order.  The cap bounds the [rows of a chunk,
+    d | F] temporaries only: when the table needs a gradient, every chunk also makes one fp32
+    [rows, d] scatter result, the size of the table, next to the running sum.  With seg_ptr the chunk boundaries
+    are read on the host (one wait, in the backward pass only); the forward never waits."""
+    name = "pool_aggregate"
+    if op not in _POOL_OP:
+        raise ValueError("%s: op is max, mean or add" % name)
+    if activation not in _POOL_ACT:
+        raise ValueError("%s: activation is relu or none" % name)
+    _dt(name, table)
+    od = _out_dt(name, table, out_dtype)
+    if table.dim() != 2 or table.shape[0] < 1:
+        raise ValueError("%s: table is [rows, d], one row at least" % name)
+    if weight.dim() != 2 or weight.shape[0] != table.shape[1]:
+        raise ValueError("%s: weight is [d, F]" % name)
+    if weight.dtype != table.dtype:
+        raise ValueError("%s: weight has the table's dtype (%s), not %s" % (name, table.dtype, weight.dtype))
+    d, f = int(weight.shape[0]), int(weight.shape[1])
+    if not (1 <= d <= 4096 and 1 <= f <= 4096):
+        raise ValueError("%s: d and F are 1..4096" % name)
+    if bias is not None:
+        if bias.dim() != 1 or bias.numel() != f:
+            raise ValueError("%s: bias is [F]" % name)
+        if bias.dtype not in (_F32, table.dtype):
+            raise ValueError("%s: bias is float32 or of the table's dtype, not %s" % (name, bias.dtype))
+    if (seg_ptr is None) == (count is None):
+        raise ValueError("%s: pass seg_ptr or count" % name)
+    size = int(size)
+    if size < 0 or size >= 2 ** 31:
+        raise ValueError("%s: size is 0 .. 2^31 - 1" % name)
+    table_c, weight_c = table.contiguous(), weight.contiguous()
+    bias_c = bias.contiguous() if bias is not None else None
+    gi = gather_indices
+    if gi is not None:
+        if gi.dtype.is_floating_point or gi.dtype == torch.bool:
+            raise ValueError("%s: gather indices are integers, not %s" % (name, gi.dtype))
+        gi = gi.reshape(-1)
+        gi = gi.contiguous() if gi.dtype == torch.int64 else gi.to(torch.int32).contiguous()
+    sp = None
+    if seg_ptr is not None:
+        sp = seg_ptr.to(torch.int64).contiguous()
+        if sp.numel() != size + 1:
+            raise ValueError("%s: seg_ptr has size + 1 entries" % name)
+        e = gi.numel() if gi is not None else int(table.shape[0])
+        count = 0
+    else:
+        count = int(count)
+        if count < 1:
+            raise ValueError("%s: count >= 1" % name)
+        e = size * count
+        if gi is not None and gi.numel() != e:
+            raise ValueError("%s: size * count gather indices" % name)
+    if e >= 2 ** 31:
+        raise ValueError("%s: fewer than 2^31 positions" % name)
+    _need_cuda(table_c, weight_c, *[t for t in (bias_c, gi, sp) if t is not None])
+    return _PoolAggregate.apply(table_c, weight_c, bias_c, gi, sp, count, e, size, op, activation, od)
+
+
 # ---- edge-weighted aggregation ---------------------------------------------------------------
 def _edge_weight(name, w, e, params):
     """checks an edge_weight argument; -> (the weights as a contiguous [E, H] tensor, H)"""

@@ -1671,6 +1671,28 @@ int euler_gpu_gather_segment_topk(void* stream, const void* params_dev, int32_t 
 int euler_gpu_segment_topk_grad(void* stream, const void* grad_dev, int32_t grad_dtype,
                                 const int32_t* sel_dev, int64_t e, int64_t d, int32_t size,
                                 int32_t k, float* per_edge_dev);
+/* pool_aggregate: the meanpool / maxpool aggregators of the reference's SageEncoder
+ * (tf_euler/python/utils/aggregators.py:75-114) in one pass on the matrix units -
+ * out[r] = reduce_{p in segment(r)} act(table[g[p]] @ W + b), without the [e, d] gathered block
+ * or the [e, f] activation block.  The contract - arguments, the segment forms and the range rule
+ * of gather_segment_topk above, the arithmetic and its order, determinism, the tiling and its LDS
+ * budget - is stated once, in euler_amd/csrc/mp_pool.h.
+ * op: 0 max, 1 mean, 2 add.  act: 0 relu, 1 none.  table_dev [rows, d] and weight_dev [d, f] of
+ * `dtype`, contiguous; bias_dev [f] of bias_dtype (fp32 or dtype) or NULL (+0); gather_dev /
+ * gather_is_ids / seg_ptr_dev / count / e as gather_segment_topk; out_dev [size, f] of out_dtype
+ * (fp32 or dtype).  An empty segment gives +0.  Only enqueues one launch on `stream`: no
+ * allocation, no host wait, no atomics; the same call gives the same bits on every run.
+ * EULER_GPU_EINVAL: an unknown op, activation or dtype, out_dtype or bias_dtype neither fp32 nor
+ * dtype, a negative extent, e or size >= 2^31, d or f outside 1..4096, both or neither of
+ * seg_ptr_dev / count, the count form with e != size * count, a null required buffer, rows < 1, a
+ * buffer not aligned to its element type; every check precedes the first write.  size == 0
+ * returns EULER_GPU_OK and touches nothing. */
+int euler_gpu_pool_aggregate(void* stream, int32_t op, int32_t act, const void* table_dev,
+                             int32_t dtype, int64_t rows, const void* weight_dev,
+                             const void* bias_dev, int32_t bias_dtype, const void* gather_dev,
+                             int32_t gather_is_ids, const int64_t* seg_ptr_dev, int64_t count,
+                             int64_t e, int64_t d, int64_t f, int64_t size, void* out_dev,
+                             int32_t out_dtype);
 
 /* ---- shard ops (multi-GPU) --------------------------------------------------
  * ID_SPLIT (core/kernels/id_split_op.cc:46-99): stable bucket of ids by
