@@ -921,6 +921,245 @@ def pool_aggregate(op, table, weight, gather_indices, size, bias=None, seg_ptr=N
     return _PoolAggregate.apply(table_c, weight_c, bias_c, gi, sp, count, e, size, op, activation, od)
 
 
+# ---- fused mean-aggregator layer: reduce, then dense ---------------------------------------------
+_DENSE_OP = {"mean": 1, "add": 2}
+_DENSE_COMBINE = {None: 0, "add": 1, "concat": 2, "fold": 3}
+
+
+def _dense_raw(op, act, combine, table, weight, bias, gi, sp, count, e, size, root, root_weight, root_scale, od):
+    """euler_gpu_aggregate_dense on prepared tensors -> out [size, F] (concat: [size, Fs + F])"""
+    f = int(weight.shape[1])
+    fs = int(root_weight.shape[1]) if root_weight is not None else 0
+    cols = fs + f if combine == "concat" else f
+    out = (torch.zeros if size == 0 else torch.empty)((size, cols), dtype=od, device=table.device)
+    if size == 0:
+        return out
+    with _on(table.device):
+        check(lib().euler_gpu_aggregate_dense(
+            _stream(), _DENSE_OP[op], _POOL_ACT[act], _DENSE_COMBINE[combine], _ptr(table), _DT[table.dtype],
+            int(table.shape[0]), _ptr(weight), _ptr(bias), _DT[bias.dtype] if bias is not None else 0, _ptr(gi),
+            int(gi is not None and gi.dtype == torch.int64), _ptr(sp), int(count), e, int(table.shape[1]), f, size,
+            _ptr(root), _ptr(root_weight), int(root.shape[1]) if root is not None else 0, fs,
+            int(root_scale is not None), float(root_scale or 0.0), _ptr(out), _DT[od]))
+    return out
+
+
+class _AggregateDense(torch.autograd.Function):
+    """The fused forward; the backward recomputes the composed form chunk by chunk (see
+    aggregate_dense)."""
+
+    @staticmethod
+    def forward(ctx, table, weight, bias, root, root_weight, gi, sp, count, e, size, op, act, combine, root_scale, od):
+        out = _dense_raw(op, act, combine, table, weight, bias, gi, sp, count, e, size, root, root_weight,
+                         root_scale, od)
+        ctx.save_for_backward(table, weight, *[t for t in (bias, root, root_weight, gi, sp) if t is not None])
+        ctx.conf = ([t is not None for t in (bias, root, root_weight, gi, sp)], count, e, size, op, act, combine,
+                    root_scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        has, count, e, size, op, act, combine, root_scale = ctx.conf
+        saved = list(ctx.saved_tensors)
+        table, weight = saved[0], saved[1]
+        rest = saved[2:]
+        bias, root, root_weight, gi, sp = [rest.pop(0) if h else None for h in has]
+        rows, d = table.shape
+        dev, f = table.device, int(weight.shape[1])
+        w32 = weight.to(_F32)
+        ws32 = root_weight.to(_F32) if root_weight is not None else None
+        b32 = bias.to(_F32) if bias is not None else None
+        grad = grad.to(_F32)
+        g_n, g_s = grad, grad               # the gradient of each path's activated value
+        if combine == "concat":
+            g_s, g_n = grad[:, :ws32.shape[1]], grad[:, ws32.shape[1]:]
+        need = ctx.needs_input_grad
+        want_t, want_w, want_b = need[0], need[1], bias is not None and need[2]
+        want_r, want_ws = root is not None and need[3], root_weight is not None and need[4]
+        d_table = torch.zeros((rows, d), dtype=_F32, device=dev) if want_t else None
+        d_w = torch.zeros_like(w32) if want_w else None
+        d_b = torch.zeros(f, dtype=_F32, device=dev) if want_b else None
+        d_root = torch.zeros(root.shape, dtype=_F32, device=dev) if want_r else None
+        d_ws = torch.zeros_like(ws32) if want_ws else None
+        scale = 1.0 if root_scale is None else float(root_scale)
+        sp_clamped = torch.cummax(sp.clamp(0, e), 0).values if sp is not None else None
+        for r_a, r_b, p_a, p_b in _pool_chunks(sp_clamped, count, size):
+            n = r_b - r_a
+            g = gi[p_a:p_b].to(torch.int64) if gi is not None else torch.arange(p_a, p_b, device=dev)
+            valid = (g >= 0) & (g < rows)
+            local = sp_clamped[r_a:r_b + 1] - p_a if sp is not None else None
+            dst = _segment_dst(local, count, n, dev)
+            # A as the forward formed it: this module's segment reduce (a row outside the table has
+            # the weight 0), the root term of fold mode, the mean's denominator, one narrowing
+            s = torch.zeros((n, d), dtype=_F32, device=dev)
+            if p_b > p_a:
+                s = gather_segment_reduce("add", table, torch.where(valid, g, torch.zeros_like(g)).to(torch.int32), n,
+                                          seg_ptr=local, count=count if sp is None else None, out_dtype=_F32,
+                                          edge_weight=valid.to(_F32)).detach()
+            lens = torch.bincount(dst.to(torch.int64), minlength=n).to(_F32).reshape(-1, 1)
+            if combine == "fold":
+                s = s + scale * root[r_a:r_b].to(_F32)
+                lens = lens + 1
+            den = lens + 1e-7 if op == "mean" else torch.ones_like(lens)
+            inv = 1.0 / den
+            a = (s / den).to(table.dtype).to(_F32)
+            z = a @ w32
+            if b32 is not None:
+                z = z + b32
+            dz = g_n[r_a:r_b] * (z > 0).to(_F32) if act == "relu" else g_n[r_a:r_b]
+            if want_w:
+                d_w += a.t() @ dz
+            if want_b:
+                d_b += dz.sum(0)
+            if want_t or (want_r and combine == "fold"):
+                d_a = (dz @ w32.t()) * inv
+                if want_r and combine == "fold":
+                    d_root[r_a:r_b] = scale * d_a
+                if want_t and p_b > p_a:
+                    key = torch.where(valid, g, torch.full_like(g, -1))
+                    d_table += _scatter_raw(_ADD, _gather_raw(d_a.contiguous(), dst), key, rows)
+            if ws32 is not None and (want_r or want_ws):
+                x = root[r_a:r_b].to(_F32)
+                zs = x @ ws32
+                dzs = g_s[r_a:r_b] * (zs > 0).to(_F32) if act == "relu" else g_s[r_a:r_b]
+                if want_ws:
+                    d_ws += x.t() @ dzs
+                if want_r:
+                    d_root[r_a:r_b] = dzs @ ws32.t()
+        return (d_table.to(table.dtype) if want_t else None, d_w.to(weight.dtype) if want_w else None,
+                d_b.to(bias.dtype) if want_b else None, d_root.to(root.dtype) if want_r else None,
+                d_ws.to(root_weight.dtype) if want_ws else None) + (None,) * 10
+
+
+def aggregate_dense(op, table, weight, gather_indices, size, root=None, root_weight=None, combine="add",
+                    root_scale=None, bias=None, activation="relu", seg_ptr=None, count=None, out_dtype=None):
+    """The mean aggregator family of the reference - MeanAggregator (utils/aggregators.py:38-72,
+    SageEncoder's default), GCNAggregator (aggregators.py:25-35), SAGEConv / GraphConv and GINConv -
+    reduce, THEN dense, in one pass on the matrix units.  With A[r] the aggregate of destination r,
+    op "add" / "mean" over table[gather_indices[p]], p in segment(r):
+
+        root=None:          out[r] = act(A[r] @ weight + bias)                  (GCNConv after gcn_norm;
+                            combine stays at its default)
+        combine="add":      out[r] = act(A[r] @ weight + bias) + act(root[r] @ root_weight)
+                            (MeanAggregator; activation="none": SAGEConv, GraphConv)
+        combine="concat":   out[r] = [act(root[r] @ root_weight), act(A[r] @ weight + bias)], [size, Fs + F]
+        combine="fold":     root_scale * root[r] (None: root[r] as it is) joins the reduce as its first
+                            term, mean divides by len + 1; out[r] = act(A'[r] @ weight + bias); no
+                            root_weight, root is [size, d] (GCNAggregator: mean; GINConv: add, 1 + eps)
+
+    without the [size, d] aggregate or the [size, F] results of the two paths that gather_segment_reduce
+    + matmuls + relu + add write.  activation "relu" / "none".  table [rows, d] and weight [d, F] of one
+    dtype, fp32 / bf16 / fp16; root [size, ds] and root_weight [ds, Fs] of that dtype, Fs == F for add;
+    bias [F], fp32 or the table's dtype; 1 <= d, ds <= 1024, 1 <= F, Fs <= 4096.  Segments and indices
+    are those of pool_aggregate: seg_ptr (int64 [size + 1]) or count; int32 indices, the int64 ids a
+    sampler returned, or None (position p reads row p).  An index outside [0, rows) names no row: it is
+    never dereferenced, reads as a row of +0, still counts in the segment's length, and its table
+    gradient is dropped.  The rows are added in increasing p in fp32 from +0; mean divides by
+    fl(len + 1e-7f) as gather_segment_reduce does; A is rounded ONCE to the table's dtype - the bits
+    gather_segment_reduce stores today (for indices inside the table) - then the products are
+    accumulated in fp32 in an order that depends only on d and ds; bias and activation in fp32 per
+    path, the paths combined in fp32, one rounding to out_dtype (fp32 or the table's; None: the
+    table's).  An empty segment has A = +0.  The same call gives the same bits on every run, on every
+    stream and for count or the equivalent seg_ptr.  The full contract and the tiling: csrc/mp_dense.h.
+
+    Differentiable in table, weight, bias, root and root_weight.  As for pool_aggregate the backward
+    pass is deliberately NOT a fused kernel: over chunks of whole destinations of at most
+    POOL_GRAD_CHUNK_ROWS gathered rows it recomputes A through gather_segment_reduce (fp32 sums,
+    narrowed once to the table's dtype and widened), the pre-activations in fp32, and sums the
+    gradients over the chunks in chunk order.  The relu mask is that of the RECOMPUTED pre-activation
+    (fp32 matmuls in the framework's order): where the forward's pre-activation lies within rounding
+    of 0 the two masks may differ.  In fold mode the recomputed sum adds the root term last, not
+    first.  When the table needs a gradient, every chunk also makes one fp32 [rows, d] scatter result.
+    With seg_ptr the chunk boundaries are read on the host (one wait, in the backward pass only); the
+    forward never waits."""
+    name = "aggregate_dense"
+    if op not in _DENSE_OP:
+        raise ValueError("%s: op is mean or add" % name)
+    if activation not in _POOL_ACT:
+        raise ValueError("%s: activation is relu or none" % name)
+    if combine not in ("add", "concat", "fold"):
+        raise ValueError("%s: combine is add, concat or fold" % name)
+    _dt(name, table)
+    od = _out_dt(name, table, out_dtype)
+    if table.dim() != 2 or table.shape[0] < 1:
+        raise ValueError("%s: table is [rows, d], one row at least" % name)
+    if weight.dim() != 2 or weight.shape[0] != table.shape[1]:
+        raise ValueError("%s: weight is [d, F]" % name)
+    if weight.dtype != table.dtype:
+        raise ValueError("%s: weight has the table's dtype (%s), not %s" % (name, table.dtype, weight.dtype))
+    d, f = int(weight.shape[0]), int(weight.shape[1])
+    if not (1 <= d <= 1024 and 1 <= f <= 4096):
+        raise ValueError("%s: d is 1..1024 and F 1..4096" % name)
+    size = int(size)
+    if size < 0 or size >= 2 ** 31:
+        raise ValueError("%s: size is 0 .. 2^31 - 1" % name)
+    if root is None:
+        if combine != "add" or root_weight is not None or root_scale is not None:
+            raise ValueError("%s: combine concat / fold, root_weight and root_scale need root" % name)
+        combine = None
+    else:
+        if root.dim() != 2 or root.shape[0] != size:
+            raise ValueError("%s: root is [size, ds]" % name)
+        if root.dtype != table.dtype:
+            raise ValueError("%s: root has the table's dtype (%s), not %s" % (name, table.dtype, root.dtype))
+        if combine == "fold":
+            if root_weight is not None:
+                raise ValueError("%s: combine fold has no root_weight" % name)
+            if root.shape[1] != d:
+                raise ValueError("%s: combine fold needs root [size, d]" % name)
+        else:
+            if root_scale is not None:
+                raise ValueError("%s: root_scale goes with combine fold" % name)
+            if root_weight is None or root_weight.dim() != 2 or root_weight.shape[0] != root.shape[1]:
+                raise ValueError("%s: root_weight is [ds, Fs]" % name)
+            if root_weight.dtype != table.dtype:
+                raise ValueError("%s: root_weight has the table's dtype (%s), not %s"
+                                 % (name, table.dtype, root_weight.dtype))
+            ds, fs = int(root_weight.shape[0]), int(root_weight.shape[1])
+            if not (1 <= ds <= 1024 and 1 <= fs <= 4096):
+                raise ValueError("%s: ds is 1..1024 and Fs 1..4096" % name)
+            if combine == "add" and fs != f:
+                raise ValueError("%s: combine add needs Fs == F" % name)
+    if root_scale is not None and not math.isfinite(float(root_scale)):
+        raise ValueError("%s: root_scale is a finite number" % name)
+    if bias is not None:
+        if bias.dim() != 1 or bias.numel() != f:
+            raise ValueError("%s: bias is [F]" % name)
+        if bias.dtype not in (_F32, table.dtype):
+            raise ValueError("%s: bias is float32 or of the table's dtype, not %s" % (name, bias.dtype))
+    if (seg_ptr is None) == (count is None):
+        raise ValueError("%s: pass seg_ptr or count" % name)
+    table_c, weight_c = table.contiguous(), weight.contiguous()
+    bias_c = bias.contiguous() if bias is not None else None
+    root_c = root.contiguous() if root is not None else None
+    rw_c = root_weight.contiguous() if root_weight is not None else None
+    gi = gather_indices
+    if gi is not None:
+        if gi.dtype.is_floating_point or gi.dtype == torch.bool:
+            raise ValueError("%s: gather indices are integers, not %s" % (name, gi.dtype))
+        gi = gi.reshape(-1)
+        gi = gi.contiguous() if gi.dtype == torch.int64 else gi.to(torch.int32).contiguous()
+    sp = None
+    if seg_ptr is not None:
+        sp = seg_ptr.to(torch.int64).contiguous()
+        if sp.numel() != size + 1:
+            raise ValueError("%s: seg_ptr has size + 1 entries" % name)
+        e = gi.numel() if gi is not None else int(table.shape[0])
+        count = 0
+    else:
+        count = int(count)
+        if count < 1:
+            raise ValueError("%s: count >= 1" % name)
+        e = size * count
+        if gi is not None and gi.numel() != e:
+            raise ValueError("%s: size * count gather indices" % name)
+    if e >= 2 ** 31:
+        raise ValueError("%s: fewer than 2^31 positions" % name)
+    _need_cuda(table_c, weight_c, *[t for t in (bias_c, root_c, rw_c, gi, sp) if t is not None])
+    return _AggregateDense.apply(table_c, weight_c, bias_c, root_c, rw_c, gi, sp, count, e, size, op, activation,
+                                 combine, None if root_scale is None else float(root_scale), od)
+
+
 # ---- edge-weighted aggregation ---------------------------------------------------------------
 def _edge_weight(name, w, e, params):
     """checks an edge_weight argument; -> (the weights as a contiguous [E, H] tensor, H)"""

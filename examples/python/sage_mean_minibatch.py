@@ -1,0 +1,144 @@
+#!/usr/bin/env python3
+"""GraphSAGE with the mean aggregator (SageEncoder's default) on a sampled 2-hop block, training steps
+on one MI355X.
+
+What the reference's MeanAggregator (tf_euler/python/utils/aggregators.py:38-72) does per layer and hop:
+
+    out = relu(self_dense(self features)) + relu(neigh_dense(mean over the fan-out of neighbour features))
+
+The neighbour ids come from Graph.sample_fanout.  The mean, both dense layers, the activations and the
+add are ONE kernel per hop, ops.aggregate_dense: the [n_dst, d] aggregate and the two [n_dst, F] partial
+results are never written.  --composed runs ops.gather_segment_reduce + two matmuls + relu + add beside
+it, asserts that the two routes' hop-2 layer agree within the rounding bound of both against float64
+(the bound of tests/test_aggregate_dense_gpu.py), and prints ms per step (forward and backward through
+both layers) and peak device bytes of both routes.
+
+    python examples/python/sage_mean_minibatch.py [--steps 5] [--composed] [--batch 4096]
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+import euler_amd                                   # noqa: E402
+from euler_amd import ops                          # noqa: E402
+
+U = 2.0 ** -24
+
+
+class MeanSageLayer(torch.nn.Module):
+    def __init__(self, dim, hidden, dtype, composed):
+        super().__init__()
+        self.composed = composed
+        mk = lambda *s: torch.nn.Parameter((torch.randn(*s, device="cuda") / s[0] ** 0.5).to(dtype))
+        self.self_w, self.neigh_w = mk(dim, hidden), mk(dim, hidden)
+        self.bias = torch.nn.Parameter(torch.zeros(hidden, device="cuda"))
+
+    def forward(self, self_rows, table, ids, count):
+        """[n_dst, hidden]; ids None: neighbour p is row p of table"""
+        n_dst = self_rows.shape[0]
+        if not self.composed:
+            return ops.aggregate_dense("mean", table, self.neigh_w, ids, n_dst, root=self_rows, root_weight=self.self_w,
+                                       bias=self.bias, count=count)
+        if ids is None:
+            ids = torch.arange(table.shape[0], device="cuda", dtype=torch.int32)
+        agg = ops.gather_segment_reduce("mean", table, ids.reshape(-1), n_dst, count=count)
+        return torch.relu(torch.addmm(self.bias.to(agg.dtype), agg, self.neigh_w)) + torch.relu(self_rows @ self.self_w)
+
+
+def encode(layers, table, nodes, fanouts):
+    """two layers over the block nodes[0] (roots), nodes[1], nodes[2]"""
+    h0 = layers[0](ops.gather(table, nodes[0].reshape(-1)), table, nodes[1], fanouts[0])
+    h1 = layers[0](ops.gather(table, nodes[1].reshape(-1)), table, nodes[2], fanouts[1])
+    return layers[1](h0, h1, None, fanouts[0])
+
+
+def check(layer_f, layer_c, table, self_ids, ids, count, n=4096):
+    """the hop-2 layer of both routes, its first n destinations, against float64 on the CPU.  With M the formula
+    on absolute values: the fused route is within (4 (d + ds + 2) + count + 4) 2^-24 M (accumulation with the
+    tests' margin, fold, mean) + 2^-8 M (the one narrowing of the aggregate) + 2^-8 |result| (the bf16 output);
+    the composed route also rounds each path's matmul result and activation sum to bf16: 2 x 2^-8 M more."""
+    n = min(n, self_ids.numel())
+    self_ids, ids = self_ids.reshape(-1)[:n], ids.reshape(-1)[:n * count]
+    with torch.no_grad():
+        rows = ops.gather(table, self_ids)
+        fused = layer_f(rows, table, ids, count).double().cpu()
+        composed = layer_c(rows, table, ids, count).double().cpu()
+    t64 = table.double().cpu()
+    x, r = t64[ids.cpu()].view(n, count, -1), t64[self_ids.cpu()]
+    wn, ws, b = [p.detach().double().cpu() for p in (layer_f.neigh_w, layer_f.self_w, layer_f.bias)]
+    a = x.mean(1).to(torch.bfloat16).double()
+    ref = torch.relu(a @ wn + b) + torch.relu(r @ ws)
+    mag = x.abs().mean(1) @ wn.abs() + b.abs() + r.abs() @ ws.abs()
+    d = table.shape[1]
+    bound_f = ((4 * (2 * d + 2) + count + 4) * U + 2.0 ** -8) * mag + 2.0 ** -8 * ref.abs()
+    bound_c = bound_f + 2 * 2.0 ** -8 * mag
+    print("fused vs float64: largest error / bound %.3f; fused vs composed: %.3f"
+          % (float(((fused - ref).abs() / bound_f).max()), float(((fused - composed).abs() / (bound_f + bound_c)).max())))
+    assert torch.all((fused - ref).abs() <= bound_f) and torch.all((fused - composed).abs() <= bound_f + bound_c)
+    print("routes agree within the bound")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--composed", action="store_true", help="also run gather_segment_reduce + matmuls + relu + add")
+    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--dim", type=int, default=128)
+    ap.add_argument("--hidden", type=int, default=128)
+    ap.add_argument("--nodes", type=int, default=200000)
+    a = ap.parse_args()
+    fanouts = [25, 10]
+    torch.manual_seed(0)
+    G = euler_amd.Graph.synthetic(euler_amd.synth_params(11, a.nodes, 10 * a.nodes, weighted=True))
+    G.set_seed(7)
+    # rows 0 .. nodes are the nodes' features; row nodes + 1 is the default_node fill: zeros on both routes
+    table = torch.randn((a.nodes + 2, a.dim), device="cuda").to(torch.bfloat16)
+    table[a.nodes + 1] = 0
+    routes = {"fused": False, "composed": True} if a.composed else {"fused": False}
+    models = {}
+    for name, composed in routes.items():
+        torch.manual_seed(1)        # the same weights on both routes
+        models[name] = [MeanSageLayer(a.dim, a.hidden, torch.bfloat16, composed),
+                        MeanSageLayer(a.hidden, a.hidden, torch.bfloat16, composed)]
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(9)
+    roots = torch.randint(1, a.nodes + 1, (a.batch,), device="cuda", generator=gen)
+    nodes = G.sample_fanout(roots, [[0], [0]], fanouts, a.nodes + 1, call_id=0)[0]
+    for name, layers in models.items():
+        params = [p for layer in layers for p in layer.parameters()]
+
+        def step():
+            for p in params:
+                p.grad = None
+            out = encode(layers, table, nodes, fanouts)
+            out.float().square().mean().backward()
+            return out
+
+        step()                                                                         # warm-up
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            out = step()
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3 / a.steps
+        assert torch.isfinite(out.float()).all() and all(torch.isfinite(p.grad.float()).all() for p in params)
+        print("%s: %.3f ms per step, peak %d bytes above the inputs" % (name, ms, torch.cuda.max_memory_allocated() - base))
+        with torch.no_grad():
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            encode(layers, table, nodes, fanouts)
+            torch.cuda.synchronize()
+            print("%s: forward alone, peak %d bytes above the inputs" % (name, torch.cuda.max_memory_allocated() - base))
+    if a.composed:
+        check(models["fused"][0], models["composed"][0], table, nodes[1], nodes[2], fanouts[1])
+
+
+if __name__ == "__main__":
+    main()

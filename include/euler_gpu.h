@@ -1693,6 +1693,40 @@ int euler_gpu_pool_aggregate(void* stream, int32_t op, int32_t act, const void* 
                              int32_t gather_is_ids, const int64_t* seg_ptr_dev, int64_t count,
                              int64_t e, int64_t d, int64_t f, int64_t size, void* out_dev,
                              int32_t out_dtype);
+/* aggregate_dense: the mean aggregator family of the reference - MeanAggregator
+ * (tf_euler/python/utils/aggregators.py:38-72, SageEncoder's default), GCNAggregator
+ * (aggregators.py:25-35), SAGEConv / GraphConv (convolution/sage_conv.py) and GINConv
+ * (convolution/gin_conv.py) - reduce, THEN dense, in one pass on the matrix units.  With A[r] =
+ * add | mean over p in segment(r) of table[g[p]], rounded once to `dtype`:
+ *   combine 0 (none):   out[r] = act(A[r] @ W + b)                              root_dev NULL
+ *   combine 1 (add):    out[r] = act(A[r] @ W + b) + act(root[r] @ Ws)          fs == f
+ *   combine 2 (concat): out[r] = [act(root[r] @ Ws), act(A[r] @ W + b)]         out [size, fs + f]
+ *   combine 3 (fold):   the term root_scale * root[r] (has_root_scale 0: root[r] as it is) joins the
+ *                       reduce first, mean divides by len + 1; out[r] = act(A'[r] @ W + b); ds == d,
+ *                       root_weight_dev NULL
+ * without the [size, d] aggregate or the [size, f] results of the two paths.  The contract -
+ * arguments, the segment forms and the range rule of pool_aggregate above, the arithmetic and its
+ * order (mean divides by fl(len + 1e-7f), as gather_segment_reduce), determinism, the tiling and
+ * its LDS budget - is stated once, in euler_amd/csrc/mp_dense.h.
+ * op: 1 mean, 2 add.  act: 0 relu, 1 none.  table_dev [rows, d], weight_dev [d, f], root_dev
+ * [size, ds] and root_weight_dev [ds, fs] of `dtype`, contiguous; bias_dev [f] of bias_dtype (fp32
+ * or dtype) or NULL (+0); out_dev of out_dtype (fp32 or dtype).  Only enqueues one launch on
+ * `stream`: no allocation, no host wait, no atomics; the same call gives the same bits on every run.
+ * EULER_GPU_EINVAL: an unknown op, activation, combine or dtype, out_dtype or bias_dtype neither
+ * fp32 nor dtype, a negative extent, e or size >= 2^31, d or ds outside 1..1024, f or fs outside
+ * 1..4096, fs != f for add, ds != d for fold, both or neither of seg_ptr_dev / count, the count form
+ * with e != size * count, a null required buffer or a root / root_weight that does not go with
+ * `combine`, rows < 1, a buffer not aligned to its element type; every check precedes the first
+ * write.  size == 0 returns EULER_GPU_OK and touches nothing. */
+int euler_gpu_aggregate_dense(void* stream, int32_t op, int32_t act, int32_t combine,
+                              const void* table_dev, int32_t dtype, int64_t rows,
+                              const void* weight_dev, const void* bias_dev, int32_t bias_dtype,
+                              const void* gather_dev, int32_t gather_is_ids,
+                              const int64_t* seg_ptr_dev, int64_t count, int64_t e, int64_t d,
+                              int64_t f, int64_t size, const void* root_dev,
+                              const void* root_weight_dev, int64_t ds, int64_t fs,
+                              int32_t has_root_scale, float root_scale, void* out_dev,
+                              int32_t out_dtype);
 
 /* ---- shard ops (multi-GPU) --------------------------------------------------
  * ID_SPLIT (core/kernels/id_split_op.cc:46-99): stable bucket of ids by
