@@ -1160,6 +1160,209 @@ def aggregate_dense(op, table, weight, gather_indices, size, root=None, root_wei
                                  combine, None if root_scale is None else float(root_scale), od)
 
 
+# ---- fused gated-graph step: neighbour sum, then a TF GRU cell -----------------------------------
+def _gru_raw(op, table, gi, sp, count, e, size, state, gate_w, cand_w, gate_b, cand_b, od):
+    """euler_gpu_aggregate_gru on prepared tensors -> out [size, U]"""
+    out = (torch.zeros if size == 0 else torch.empty)((size, int(cand_w.shape[1])), dtype=od, device=table.device)
+    if size == 0:
+        return out
+    with _on(table.device):
+        check(lib().euler_gpu_aggregate_gru(
+            _stream(), _DENSE_OP[op], _ptr(table), _DT[table.dtype], int(table.shape[0]), _ptr(gi),
+            int(gi is not None and gi.dtype == torch.int64), _ptr(sp), int(count), e, int(table.shape[1]),
+            int(cand_w.shape[1]), size, _ptr(state), _ptr(gate_w), _ptr(cand_w), _ptr(gate_b),
+            _DT[gate_b.dtype] if gate_b is not None else 0, _ptr(cand_b), _DT[cand_b.dtype] if cand_b is not None else 0,
+            _ptr(out), _DT[od]))
+    return out
+
+
+def _gru_cell32(m, h, gate_w, cand_w, gate_b, cand_b, dt):
+    """the cell in fp32 torch on the aggregate m, r * h narrowed once to dt as the forward narrows it"""
+    u_dim = h.shape[1]
+    zg = torch.cat([m, h], 1) @ gate_w
+    if gate_b is not None:
+        zg = zg + gate_b
+    r, u = torch.sigmoid(zg[:, :u_dim]), torch.sigmoid(zg[:, u_dim:])
+    rh = r * h
+    rh = rh + (rh.detach().to(dt).to(_F32) - rh.detach())          # the narrowing, with the gradient of identity
+    zc = torch.cat([m, rh], 1) @ cand_w
+    if cand_b is not None:
+        zc = zc + cand_b
+    return u * h + (1 - u) * torch.tanh(zc)
+
+
+class _AggregateGru(torch.autograd.Function):
+    """The fused forward; the backward recomputes the composed form chunk by chunk (see aggregate_gru)."""
+
+    @staticmethod
+    def forward(ctx, table, state, gate_w, cand_w, gate_b, cand_b, gi, sp, count, e, size, op, od):
+        out = _gru_raw(op, table, gi, sp, count, e, size, state, gate_w, cand_w, gate_b, cand_b, od)
+        ctx.save_for_backward(table, state, gate_w, cand_w, *[t for t in (gate_b, cand_b, gi, sp) if t is not None])
+        ctx.conf = ([t is not None for t in (gate_b, cand_b, gi, sp)], count, e, size, op)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        has, count, e, size, op = ctx.conf
+        saved = list(ctx.saved_tensors)
+        table, state, gate_w, cand_w = saved[:4]
+        rest = saved[4:]
+        gate_b, cand_b, gi, sp = [rest.pop(0) if h else None for h in has]
+        rows, d = table.shape
+        dev = table.device
+        need = ctx.needs_input_grad
+        # fp32 leaves of the recomputed graph: the weights and biases are shared by every chunk
+        leaf = lambda t, want: None if t is None else t.to(_F32).detach().requires_grad_(bool(want))
+        wg, wc = leaf(gate_w, need[2]), leaf(cand_w, need[3])
+        bg, bc = leaf(gate_b, need[4]), leaf(cand_b, need[5])
+        shared = [t for t in (wg, wc, bg, bc) if t is not None and t.requires_grad]
+        sums = [torch.zeros_like(t) for t in shared]
+        d_table = torch.zeros((rows, d), dtype=_F32, device=dev) if need[0] else None
+        d_state = torch.zeros(state.shape, dtype=_F32, device=dev) if need[1] else None
+        grad = grad.to(_F32)
+        sp_clamped = torch.cummax(sp.clamp(0, e), 0).values if sp is not None else None
+        for r_a, r_b, p_a, p_b in _pool_chunks(sp_clamped, count, size):
+            n = r_b - r_a
+            g = gi[p_a:p_b].to(torch.int64) if gi is not None else torch.arange(p_a, p_b, device=dev)
+            valid = (g >= 0) & (g < rows)
+            local = sp_clamped[r_a:r_b + 1] - p_a if sp is not None else None
+            dst = _segment_dst(local, count, n, dev)
+            # m as the forward formed it: this module's segment reduce, the mean's denominator, one narrowing
+            s = torch.zeros((n, d), dtype=_F32, device=dev)
+            if p_b > p_a:
+                s = gather_segment_reduce("add", table, torch.where(valid, g, torch.zeros_like(g)).to(torch.int32), n,
+                                          seg_ptr=local, count=count if sp is None else None, out_dtype=_F32,
+                                          edge_weight=valid.to(_F32)).detach()
+            lens = torch.bincount(dst.to(torch.int64), minlength=n).to(_F32).reshape(-1, 1)
+            den = lens + 1e-7 if op == "mean" else torch.ones_like(lens)
+            inv = 1.0 / den
+            m = (s / den).to(table.dtype).to(_F32).requires_grad_(bool(need[0]))
+            h = leaf(state[r_a:r_b], need[1])
+            wanted = [t for t in [m, h] + shared if t.requires_grad]
+            if not wanted:
+                continue
+            with torch.enable_grad():
+                out = _gru_cell32(m, h, wg, wc, bg, bc, table.dtype)
+            got = dict(zip(map(id, wanted), torch.autograd.grad(out, wanted, grad[r_a:r_b])))
+            for t, acc in zip(shared, sums):
+                acc += got[id(t)]
+            if need[1]:
+                d_state[r_a:r_b] = got[id(h)]
+            if need[0] and p_b > p_a:
+                key = torch.where(valid, g, torch.full_like(g, -1))
+                d_table += _scatter_raw(_ADD, _gather_raw((got[id(m)] * inv).contiguous(), dst), key, rows)
+        by = dict(zip(map(id, shared), sums))
+        cast = lambda t, src: by[id(t)].to(src.dtype) if t is not None and id(t) in by else None
+        return (d_table.to(table.dtype) if need[0] else None, d_state.to(state.dtype) if need[1] else None,
+                cast(wg, gate_w), cast(wc, cand_w), cast(bg, gate_b) if gate_b is not None else None,
+                cast(bc, cand_b) if cand_b is not None else None) + (None,) * 7
+
+
+def aggregate_gru(op, table, gather_indices, size, state, gate_weight, cand_weight, gate_bias=None, cand_bias=None,
+                  seg_ptr=None, count=None, out_dtype=None):
+    """One processing step of the reference's GatedConv (convolution/gated_graph_conv.py:26-57) - the
+    neighbour sum, then ONE tf.nn.rnn_cell.GRUCell seeded with the destination's own row - in one pass
+    on the matrix units.  With m[r] the aggregate of destination r, op "add" (GatedConv's) / "mean" over
+    table[gather_indices[p]], p in segment(r), h = state[r] and U = state.shape[1]:
+
+        [r | u] = sigmoid([m, h] @ gate_weight + gate_bias)      gate_weight [d + U, 2U]
+        c       = tanh([m, r * h] @ cand_weight + cand_bias)     cand_weight [d + U, U]
+        out[r]  = u * h + (1 - u) * c                            [size, U]
+
+    This is GRUCell.call of TF 1.x, not torch.nn.GRUCell: r * h is formed BEFORE the candidate product.
+    The weights are the cell's gates/kernel and candidate/kernel as a checkpoint holds them (rows 0 ..
+    d - 1 multiply the input, the rest the state; r is the first U gate columns); the cell's bias
+    initialiser of 1.0 is the caller's to pass.  Neither the [size, d] sum nor the [size, 2U] and
+    [size, U] pre-activation blocks that gather_segment_reduce + cat + two matmuls + the elementwise
+    steps write exist.  One call is one cell: the second cell of GatedConv's stack is
+    aggregate_gru("add", first, None, size, state, ..., count=1) over the first cell's output.
+
+    table [rows, d], state [size, U] and both weights of one dtype, fp32 / bf16 / fp16; the biases
+    fp32 or that dtype, None = +0; 1 <= d, U <= 256 - wider is refused, not served another way.
+    Segments, indices, the range rule, the fold (fp32, increasing p, mean by fl(len + 1e-7f), m rounded
+    once to the table's dtype) and determinism are those of aggregate_dense.  r * h is one fp32
+    multiply rounded once to the table's dtype; the products accumulate in fp32 in an order that
+    depends only on d and U; gates (1 / (1 + expf(-x)), a true division), candidate (tanhf) and blend
+    in fp32; one rounding to out_dtype (fp32 or the table's; None: the table's).  The full contract and
+    the design: csrc/mp_gru.h.
+
+    Every refusal is a ValueError (an unsupported dtype too, which aggregate_dense reports as a TypeError).
+
+    Which to call: as measured (hop 2 of [25, 10], d = U = 128, bf16) this op is SLOWER than
+    the composed route - 11.2 against 8.2 ms over 131 072 roots, 0.43 against 0.28 ms over 4096 - because
+    it stages all of W again for every 128 destinations.  Call the composed route for speed.  Call this
+    op for what it does not write - it allocates [size, U] and nothing else, a ninth of the composed
+    route's bytes at that shape - and for the reference's cell arithmetic held in fp32 from the products
+    to the blend, which a bf16 composed route rounds at every step.
+    Differentiable in table, state, both weights and both biases, but as for aggregate_dense the
+    backward pass is NOT a fused kernel: over chunks of whole destinations of at most
+    POOL_GRAD_CHUNK_ROWS gathered rows it recomputes m through gather_segment_reduce and the cell in
+    fp32 torch (r * h narrowed as the forward narrows it, with the gradient of the identity) and
+    differentiates that.  A training step's peak memory is therefore the composed route's - the
+    [chunk, d + U], [chunk, 2U] and [chunk, U] blocks, and one fp32 [rows, d] scatter result per chunk
+    when the table needs a gradient - not the forward's.  With seg_ptr the chunk boundaries are read
+    on the host (one wait, in the backward pass only); the forward never waits."""
+    name = "aggregate_gru"
+    if op not in _DENSE_OP:
+        raise ValueError("%s: op is mean or add" % name)
+    try:
+        _dt(name, table)
+        od = _out_dt(name, table, out_dtype)
+    except TypeError as err:            # every refusal of this op is a ValueError
+        raise ValueError(str(err)) from None
+    if table.dim() != 2 or table.shape[0] < 1:
+        raise ValueError("%s: table is [rows, d], one row at least" % name)
+    size = int(size)
+    if size < 0 or size >= 2 ** 31:
+        raise ValueError("%s: size is 0 .. 2^31 - 1" % name)
+    if state.dim() != 2 or state.shape[0] != size:
+        raise ValueError("%s: state is [size, U]" % name)
+    d, u = int(table.shape[1]), int(state.shape[1])
+    if not (1 <= d <= 256 and 1 <= u <= 256):
+        raise ValueError("%s: d and U are 1..256" % name)
+    if gate_weight.dim() != 2 or tuple(gate_weight.shape) != (d + u, 2 * u):
+        raise ValueError("%s: gate_weight is [d + U, 2U]" % name)
+    if cand_weight.dim() != 2 or tuple(cand_weight.shape) != (d + u, u):
+        raise ValueError("%s: cand_weight is [d + U, U]" % name)
+    for what, t in (("state", state), ("gate_weight", gate_weight), ("cand_weight", cand_weight)):
+        if t.dtype != table.dtype:
+            raise ValueError("%s: %s has the table's dtype (%s), not %s" % (name, what, table.dtype, t.dtype))
+    for what, b, n in (("gate_bias", gate_bias, 2 * u), ("cand_bias", cand_bias, u)):
+        if b is not None:
+            if b.dim() != 1 or b.numel() != n:
+                raise ValueError("%s: %s is [%s]" % (name, what, "2U" if n == 2 * u else "U"))
+            if b.dtype not in (_F32, table.dtype):
+                raise ValueError("%s: %s is float32 or of the table's dtype, not %s" % (name, what, b.dtype))
+    if (seg_ptr is None) == (count is None):
+        raise ValueError("%s: pass seg_ptr or count" % name)
+    cont = lambda t: None if t is None else t.contiguous()
+    table_c, state_c, gw_c, cw_c, gb_c, cb_c = map(cont, (table, state, gate_weight, cand_weight, gate_bias, cand_bias))
+    gi = gather_indices
+    if gi is not None:
+        if gi.dtype.is_floating_point or gi.dtype == torch.bool:
+            raise ValueError("%s: gather indices are integers, not %s" % (name, gi.dtype))
+        gi = gi.reshape(-1)
+        gi = gi.contiguous() if gi.dtype == torch.int64 else gi.to(torch.int32).contiguous()
+    sp = None
+    if seg_ptr is not None:
+        sp = seg_ptr.to(torch.int64).contiguous()
+        if sp.numel() != size + 1:
+            raise ValueError("%s: seg_ptr has size + 1 entries" % name)
+        e = gi.numel() if gi is not None else int(table.shape[0])
+        count = 0
+    else:
+        count = int(count)
+        if count < 1:
+            raise ValueError("%s: count >= 1" % name)
+        e = size * count
+        if gi is not None and gi.numel() != e:
+            raise ValueError("%s: size * count gather indices" % name)
+    if e >= 2 ** 31:
+        raise ValueError("%s: fewer than 2^31 positions" % name)
+    _need_cuda(table_c, state_c, gw_c, cw_c, *[t for t in (gb_c, cb_c, gi, sp) if t is not None])
+    return _AggregateGru.apply(table_c, state_c, gw_c, cw_c, gb_c, cb_c, gi, sp, count, e, size, op, od)
+
+
 # ---- edge-weighted aggregation ---------------------------------------------------------------
 def _edge_weight(name, w, e, params):
     """checks an edge_weight argument; -> (the weights as a contiguous [E, H] tensor, H)"""

@@ -1727,6 +1727,35 @@ int euler_gpu_aggregate_dense(void* stream, int32_t op, int32_t act, int32_t com
                               const void* root_weight_dev, int64_t ds, int64_t fs,
                               int32_t has_root_scale, float root_scale, void* out_dev,
                               int32_t out_dtype);
+/* aggregate_gru: one processing step of the reference's GatedConv
+ * (tf_euler/python/convolution/gated_graph_conv.py:26-57) - the neighbour sum, then one TF 1.x
+ * GRUCell seeded with the destination's own row - in one pass on the matrix units.  With m[r] = add |
+ * mean over p in segment(r) of table[g[p]], rounded once to `dtype`, and h = state[r]:
+ *   [r | u] = sigmoid([m, h] @ gate_weight + gate_bias)        gate_weight [d + u, 2 u]
+ *   c       = tanh([m, r * h] @ cand_weight + cand_bias)       cand_weight [d + u, u]
+ *   out[r]  = u * h + (1 - u) * c                              out [size, u]
+ * (r * h BEFORE the candidate product, as TF's cell and unlike torch.nn.GRUCell; the weights are the
+ * cell's gates/kernel and candidate/kernel as they are).  The contract - the segment forms, the
+ * range rule and the fold of aggregate_dense above, the order of the products, the formulas of
+ * sigmoid and tanh, the roundings, determinism, the phases and the LDS budget - is stated once, in
+ * euler_amd/csrc/mp_gru.h.
+ * op: 1 mean, 2 add.  table_dev [rows, d], state_dev [size, u] and both weights of `dtype`,
+ * contiguous; gate_bias_dev [2 u] and cand_bias_dev [u] of their own dtype (fp32 or dtype) or NULL
+ * (+0); out_dev of out_dtype (fp32 or dtype).  Only enqueues one launch on `stream`: no allocation,
+ * no host wait, no atomics; the same call gives the same bits on every run.
+ * EULER_GPU_EINVAL: an unknown op or dtype, out_dtype or a bias dtype neither fp32 nor dtype, a
+ * negative extent, e or size >= 2^31, d or u outside 1..256, both or neither of seg_ptr_dev / count,
+ * the count form with e != size * count, a null required buffer, rows < 1, a buffer not aligned to
+ * its element type; every check precedes the launch.  size == 0 returns EULER_GPU_OK and touches
+ * nothing. */
+int euler_gpu_aggregate_gru(void* stream, int32_t op, const void* table_dev, int32_t dtype,
+                            int64_t rows, const void* gather_dev, int32_t gather_is_ids,
+                            const int64_t* seg_ptr_dev, int64_t count, int64_t e, int64_t d,
+                            int64_t u, int64_t size, const void* state_dev,
+                            const void* gate_weight_dev, const void* cand_weight_dev,
+                            const void* gate_bias_dev, int32_t gate_bias_dtype,
+                            const void* cand_bias_dev, int32_t cand_bias_dtype, void* out_dev,
+                            int32_t out_dtype);
 
 /* ---- shard ops (multi-GPU) --------------------------------------------------
  * ID_SPLIT (core/kernels/id_split_op.cc:46-99): stable bucket of ids by
