@@ -54,21 +54,6 @@ __device__ __forceinline__ void DenseStageW(const void* w, int32_t k_all, int32_
   }
 }
 
-// acc[n] += a (one chunk) x the chunk at byte kb of the NT fragments of wt
-template <int DT, int NT>
-__device__ __forceinline__ void DenseChunkMma(const DenseWords* a, const unsigned char* wt, int32_t stride, int32_t kb,
-                                              int32_t c, DenseAcc* acc) {
-  constexpr int FW = DenseFragWords<DT>();
-#pragma unroll
-  for (int n = 0; n < NT; ++n) {          // (columns from F on are +0 in LDS: no branch here)
-    DenseWords bw[FW];
-#pragma unroll
-    for (int q = 0; q < FW; ++q)
-      bw[q] = *reinterpret_cast<const DenseWords*>(wt + DenseWtByte(n * 16 + c, kb + 16 * q, stride));
-    acc[n] = DenseMma<DT>(a, bw, acc[n]);
-  }
-}
-
 template <int DT>
 __device__ __forceinline__ void DenseStore(const DenseArgs& a, int64_t at, float v) {
   if (DT == kF32 || a.out_f32) static_cast<float*>(a.out)[at] = v;

@@ -71,6 +71,21 @@ __device__ __forceinline__ DenseAcc DenseMma(const DenseWords* a, const DenseWor
   }
 }
 
+// acc[n] += a (one chunk) x the chunk at byte kb of the NT fragments of wt
+template <int DT, int NT>
+__device__ __forceinline__ void DenseChunkMma(const DenseWords* a, const unsigned char* wt, int32_t stride, int32_t kb,
+                                              int32_t c, DenseAcc* acc) {
+  constexpr int FW = DenseFragWords<DT>();
+#pragma unroll
+  for (int n = 0; n < NT; ++n) {          // (columns from F on are +0 in LDS: no branch here)
+    DenseWords bw[FW];
+#pragma unroll
+    for (int q = 0; q < FW; ++q)
+      bw[q] = *reinterpret_cast<const DenseWords*>(wt + DenseWtByte(n * 16 + c, kb + 16 * q, stride));
+    acc[n] = DenseMma<DT>(a, bw, acc[n]);
+  }
+}
+
 // fold[0 .. 8) += the 8 widened elements of w, each add rounded on its own; scale: times s first
 template <int DT>
 __device__ __forceinline__ void DenseFoldAdd(const DenseWords* w, float* fold, bool scale, float s) {

@@ -10,7 +10,8 @@
 //
 // This header: the lane's arithmetic - sixteen codes of one 16-byte load (or one code) to fp32 -
 // and the Ops of WeightedReduceRow (mp_weighted.h) over such rows; the kernels that assign lanes
-// are in fp8_rows_kernels.hip.
+// are in fp8_rows_kernels.hip.  A third reader, the fused mean-aggregator layer over such a table
+// (fp8_dense_kernels.hip, contract in mp_dense_fp8.h), takes x^ from Fp8Value16 / Fp8Value too.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -11,9 +11,14 @@ add are ONE kernel per hop, ops.aggregate_dense: the [n_dst, d] aggregate and th
 results are never written.  --composed runs ops.gather_segment_reduce + two matmuls + relu + add beside
 it, asserts that the two routes' hop-2 layer agree within the rounding bound of both against float64
 (the bound of tests/test_aggregate_dense_gpu.py), and prints ms per step (forward and backward through
-both layers) and peak device bytes of both routes.
+both layers) and peak device bytes of both routes.  --fp8-features also runs layer 0 of the outermost hop
+over the features as an ops.Fp8Rows table (a quarter of their fp32 bytes; the sampler's ids go in as
+gather_indices and root_index), asserts it against float64 on the dequantised table within the bound of
+tests/test_fp8_dense_gpu.py, and prints its relative error against the bf16-feature run.  The synthetic
+graph carries no float features, so the table is quantised from the example's own id-indexed rows; with
+features in the graph it is G.fp8_dense_feature(fid, dim).
 
-    python examples/python/sage_mean_minibatch.py [--steps 5] [--composed] [--batch 4096]
+    python examples/python/sage_mean_minibatch.py [--steps 5] [--composed] [--batch 4096] [--fp8-features]
 """
 import argparse
 import os
@@ -83,6 +88,30 @@ def check(layer_f, layer_c, table, self_ids, ids, count, n=4096):
     print("routes agree within the bound")
 
 
+def check_fp8(layer, table, self_ids, ids, count, n=4096):
+    """layer 0 of the outermost hop over the Fp8Rows table of the same features: its first n destinations
+    against float64 on the dequantised table.  With M the formula on absolute values: (4 (2 d + 2) + count + 4)
+    2^-24 M (accumulation with the tests' margin, fold, mean) + 2^-8 M (the narrowing of the aggregate and of the
+    root rows) + 2^-8 |result| (the bf16 output).  Quantisation adds no term: the reference reads the same x^."""
+    t8 = ops.Fp8Rows.quantize(table.float())
+    n = min(n, self_ids.numel())
+    self_ids, ids = self_ids.reshape(-1)[:n], ids.reshape(-1)[:n * count]
+    with torch.no_grad():
+        out8 = ops.aggregate_dense("mean", t8, layer.neigh_w, ids, n, root_index=self_ids, root_weight=layer.self_w,
+                                   bias=layer.bias, count=count).double().cpu()
+        out16 = layer(ops.gather(table, self_ids), table, ids, count).double().cpu()
+    t64 = t8.dequantize().double().cpu()
+    x, r = t64[ids.cpu()].view(n, count, -1), t64[self_ids.cpu()]
+    wn, ws, b = [p.detach().double().cpu() for p in (layer.neigh_w, layer.self_w, layer.bias)]
+    ref = torch.relu(x.mean(1).to(torch.bfloat16).double() @ wn + b) + torch.relu(r.to(torch.bfloat16).double() @ ws)
+    mag = x.abs().mean(1) @ wn.abs() + b.abs() + r.abs() @ ws.abs()
+    bound = ((4 * (2 * table.shape[1] + 2) + count + 4) * U + 2.0 ** -8) * mag + 2.0 ** -8 * ref.abs()
+    print("fp8 features vs float64 on the dequantised table: largest error / bound %.3f"
+          % float(((out8 - ref).abs() / bound).max()))
+    assert torch.all((out8 - ref).abs() <= bound)
+    print("fp8 features vs bf16 features: relative error %.3e" % float((out8 - out16).norm() / out16.norm()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=5)
@@ -91,6 +120,7 @@ def main():
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--hidden", type=int, default=128)
     ap.add_argument("--nodes", type=int, default=200000)
+    ap.add_argument("--fp8-features", action="store_true", help="also run layer 0 of the outermost hop over an Fp8Rows table")
     a = ap.parse_args()
     fanouts = [25, 10]
     torch.manual_seed(0)
@@ -138,6 +168,8 @@ def main():
             print("%s: forward alone, peak %d bytes above the inputs" % (name, torch.cuda.max_memory_allocated() - base))
     if a.composed:
         check(models["fused"][0], models["composed"][0], table, nodes[1], nodes[2], fanouts[1])
+    if a.fp8_features:
+        check_fp8(models["fused"][0], table, nodes[1], nodes[2], fanouts[1])
 
 
 if __name__ == "__main__":

@@ -1727,6 +1727,29 @@ int euler_gpu_aggregate_dense(void* stream, int32_t op, int32_t act, int32_t com
                               const void* root_weight_dev, int64_t ds, int64_t fs,
                               int32_t has_root_scale, float root_scale, void* out_dev,
                               int32_t out_dtype);
+/* fp8_aggregate_dense: aggregate_dense above over a quantised row table (q_dev [rows, d] e4m3fn
+ * codes, scale_dev [d] fp32: "quantised (FP8) feature row tables").  The gathered rows are x^ =
+ * fl(Dec(code) * scale[c]), folded in fp32 exactly as above; the compute dtype - the one narrowing of
+ * A, both weights, a dense root, the default of bias and out - is weight_dtype.  The root is either
+ * root_dev [size, ds] of weight_dtype, or root_index_dev [size] (int32 indices, or int64 ids with
+ * root_index_is_ids), rows of the SAME table read in place (then ds == d; an index outside [0, rows)
+ * is a row of +0): x^ rounded once to weight_dtype as the self path's operand, or the fold's first
+ * term in fp32.  The K order of the products is the permuted one of euler_amd/csrc/mp_dense_fp8.h,
+ * which states the contract; only the error bound, not the bits, is shared with aggregate_dense on
+ * the dequantised table.  One launch on `stream`, no allocation, no host wait, no atomics.
+ * EULER_GPU_EINVAL: every refusal of aggregate_dense (with "the weight's dtype" for "the table's"),
+ * both or neither of root_dev / root_index_dev where `combine` needs a root, either where it does
+ * not, ds != d with root_index_dev, a null scale_dev, a buffer not aligned to its element type. */
+int euler_gpu_fp8_aggregate_dense(void* stream, int32_t op, int32_t act, int32_t combine,
+                                  const uint8_t* q_dev, const float* scale_dev, int64_t rows,
+                                  int32_t weight_dtype, const void* weight_dev,
+                                  const void* bias_dev, int32_t bias_dtype, const void* gather_dev,
+                                  int32_t gather_is_ids, const int64_t* seg_ptr_dev, int64_t count,
+                                  int64_t e, int64_t d, int64_t f, int64_t size,
+                                  const void* root_dev, const void* root_index_dev,
+                                  int32_t root_index_is_ids, const void* root_weight_dev,
+                                  int64_t ds, int64_t fs, int32_t has_root_scale, float root_scale,
+                                  void* out_dev, int32_t out_dtype);
 /* aggregate_gru: one processing step of the reference's GatedConv
  * (tf_euler/python/convolution/gated_graph_conv.py:26-57) - the neighbour sum, then one TF 1.x
  * GRUCell seeded with the destination's own row - in one pass on the matrix units.  With m[r] = add |

@@ -9,7 +9,12 @@ median / min / max ms per call over the windows and the peak bytes a call alloca
 route the HBM floor.  --route fused --calls N runs N calls and nothing else: the form to put under a
 kernel trace.
 
-    python tools/ubench_aggregate_dense.py [--roots 131072] [--op mean] [--seconds 2] [--repeats 5]
+--table fp8 times layer 0 over an Fp8Rows table of the same values instead, three routes in one
+call: fused_fp8 (aggregate_dense on the Fp8Rows, the roots by root_index), fused_bf16 (the route above,
+unchanged, on the bf16 table) and composed_fp8 (gather_segment_reduce on the Fp8Rows with a bf16 result +
+ops.gather for the roots + the matmuls); the floor is then that of fused_fp8.  --route fused selects fused_fp8.
+
+    python tools/ubench_aggregate_dense.py [--roots 131072] [--op mean] [--seconds 2] [--repeats 5] [--table fp8]
 """
 import argparse
 import json
@@ -38,6 +43,7 @@ def main():
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--calls", type=int, default=0, help="run this many calls of --route and exit")
+    ap.add_argument("--table", default="bf16", choices=["bf16", "fp8"])
     a = ap.parse_args()
     torch.manual_seed(0)
     n_dst, count = a.roots * a.fanout[0], a.fanout[1]
@@ -57,6 +63,19 @@ def main():
         return torch.relu(torch.addmm(b_dt, agg, w)) + torch.relu(root @ ws)
 
     routes = {"fused": fused, "composed": composed}
+    if a.table == "fp8":
+        t8 = ops.Fp8Rows.quantize(table)
+        root_ids = torch.randint(0, a.table_rows, (n_dst,), device="cuda")
+
+        def fused_fp8():
+            return ops.aggregate_dense(a.op, t8, w, ids, n_dst, root_index=root_ids, root_weight=ws, bias=b, count=count)
+
+        def composed_fp8():
+            agg = ops.gather_segment_reduce(a.op, t8, ids, n_dst, count=count, out_dtype=dt)
+            return torch.relu(torch.addmm(b_dt, agg, w)) + torch.relu(ops.gather(t8, root_ids, out_dtype=dt) @ ws)
+
+        routes = {"fused_fp8": fused_fp8, "fused_bf16": fused, "composed_fp8": composed_fp8}
+        a.route = {"fused": "fused_fp8", "composed": "composed_fp8"}.get(a.route, a.route)
     if a.route != "both":
         routes = {a.route: routes[a.route]}
     if a.calls:
@@ -85,7 +104,10 @@ def main():
             ms[name].append((time.perf_counter() - t0) * 1e3 / calls[name])
     # rows + ids in, root in, result out, both W
     bytes_needed = e * (2 * a.dim + 8) + n_dst * a.dim * 2 + n_dst * a.hidden * 2 + 2 * a.dim * a.hidden * 2
-    out = {"shape": {"e": e, "n_dst": n_dst, "d": a.dim, "F": a.hidden, "op": a.op, "dtype": "bf16", "combine": "add"},
+    if a.table == "fp8":        # one byte per code, the roots by id from the same table, the column scales
+        bytes_needed = e * (a.dim + 8) + n_dst * (a.dim + 8) + n_dst * a.hidden * 2 + 2 * a.dim * a.hidden * 2 + 4 * a.dim
+    out = {"shape": {"e": e, "n_dst": n_dst, "d": a.dim, "F": a.hidden, "op": a.op, "dtype": "bf16", "combine": "add",
+                     **({"table": "fp8"} if a.table == "fp8" else {})},
            "calls_per_window": calls, "windows": a.repeats,
            "ms": {n: {"median": statistics.median(v), "min": min(v), "max": max(v)} for n, v in ms.items()},
            "peak_bytes_per_call": peak, "bytes_needed": bytes_needed,
