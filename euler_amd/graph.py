@@ -2033,18 +2033,29 @@ class Graph:
         return ind, val, ([batch, n, m] if nnz.value else [0, 0, 0])
 
     def sample_neighbor_layerwise(self, nodes, edge_types, count, default_node=-1,
-                                  weight_func='', call_id=None):
+                                  weight_func='', call_id=None, adj_format="coo"):
         """tf_euler sample_neighbor_layerwise (euler_ops/neighbor_ops.py:72-77
         over tf_euler/kernels/sample_neighbor_layerwise_with_adj_op.cc):
         nodes [batch, n] -> (neighbors [batch, count] int64, (indices, values,
         dense_shape) of the [batch, n, count] adjacency).  weight_func == ''
         draws a node of the layer by edge weight sum, then one of its
         neighbours; 'sqrt' draws from the layer's distinct neighbours by the
-        square root of their accumulated weight."""
+        square root of their accumulated weight.
+        adj_format="mask" returns (neighbors, mask) instead: the adjacency as the
+        hit mask of sparse_adj_mask, int64 [batch * n, (count + 63) // 64], which
+        ops.mask_aggregate consumes as it is - the COO triple is not sized and
+        the host is not waited for.  The neighbours are those of the default
+        format under the same seed and call id."""
+        if adj_format not in ("coo", "mask"):
+            raise ValueError("sample_neighbor_layerwise: adj_format is coo or mask")
         nodes = _as_i64_cuda(nodes, self.device)
         if nodes.dim() != 2:
             raise ValueError("sample_neighbor_layerwise: nodes must be [batch, n]")
         batch, n = nodes.shape
+        if adj_format == "mask":
+            adj = lambda out: self.sparse_adj_mask(nodes, out, batch, n, int(count), et)
+        else:
+            adj = lambda out: self.sparse_get_adj(nodes, out, et, n, int(count))
         et, et_p, k = _i32_array(edge_types)
         if weight_func:
             # sampleLNB(edge_types, n, m, weight_func, default_node): API_GET_NB_NODE
@@ -2053,14 +2064,14 @@ class Graph:
             out, _w, _t = self.local_sample_layer(idx, ids, w, t, batch, n, int(count),
                                                   weight_func, default_node, call_id)
             out = out.reshape(batch, int(count))
-            return out, self.sparse_get_adj(nodes, out, et, n, int(count))
+            return out, adj(out)
         out = torch.empty((batch, int(count)), dtype=torch.int64, device=self.device)
         with self._on_device():
             check(lib().euler_gpu_sample_neighbor_layerwise(
                 self._h, _stream(), self.seed, self._take_call_ids(1, call_id),
                 _ptr(nodes), batch, n, et_p, k, int(count), int(default_node),
                 _ptr(out)))
-        return out, self.sparse_get_adj(nodes, out, et, n, int(count))
+        return out, adj(out)
 
     def random_walk(self, nodes, edge_types, p=1.0, q=1.0, default_node=-1,
                     call_id=None):

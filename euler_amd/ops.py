@@ -1597,6 +1597,148 @@ def aggregate_gru(op, table, gather_indices, size, state, gate_weight, cand_weig
     return _AggregateGru.apply(table_c, state_c, gw_c, cw_c, gb_c, cb_c, gi, sp, count, e, size, op, od)
 
 
+# ---- layerwise-adjacency aggregation straight from the bit mask ---------------------------------
+_MASK_OP = {"add": 0, "mean": 1, "gcn": 2, "gcn_renorm": 3}
+
+
+def _mask_words(name, mask, rows, cols):
+    """checks a hit mask [rows, (cols + 63) // 64] of 64-bit words; -> it, contiguous"""
+    if mask.dtype not in (torch.int64, torch.uint64):
+        raise ValueError("%s: mask is int64 or uint64 words, not %s" % (name, mask.dtype))
+    if mask.dim() != 2 or tuple(mask.shape) != (rows, (cols + 63) // 64):
+        raise ValueError("%s: mask is [batch * n, (m + 63) // 64] = [%d, %d], not %s"
+                         % (name, rows, (cols + 63) // 64, list(mask.shape)))
+    return mask.contiguous()
+
+
+def _mask_sizes(name, batch, n, m):
+    batch, n, m = int(batch), int(n), int(m)
+    if batch < 0 or n < 0 or m < 0:
+        raise ValueError("%s: batch, n and m are >= 0" % name)
+    if batch * n >= 2 ** 31 or batch * m >= 2 ** 31:
+        raise ValueError("%s: batch * n and batch * m are below 2^31" % name)
+    return batch, n, m
+
+
+def _mask_raw(op, mask, x, root, batch, n, m, od, want_degree):
+    """euler_gpu_mask_aggregate on prepared tensors -> (out [batch * n, d], degree [batch * n] fp32 | None)"""
+    d = int(x.shape[1])
+    out = torch.empty((batch * n, d), dtype=od, device=x.device)
+    deg = torch.empty(batch * n, dtype=_F32, device=x.device) if want_degree else None
+    if batch * n:
+        with _on(x.device):
+            check(lib().euler_gpu_mask_aggregate(_stream(), _MASK_OP[op], _ptr(mask), _ptr(x), _DT[x.dtype],
+                                                 int(x.shape[0]), _ptr(root), batch, n, m, d, _ptr(out), _DT[od],
+                                                 _ptr(deg)))
+    return out, deg
+
+
+def mask_transpose(mask, batch, n, m):
+    """The hit mask [batch * n, (m + 63) // 64] of a [batch, n, m] adjacency as the mask [batch * m,
+    (n + 63) // 64] of its transpose, by 64 x 64 bit blocks on the device (euler_gpu_mask_transpose).  Stray
+    input bits at positions >= m are dropped; output bits >= n are zero.  The result has the mask's dtype."""
+    name = "mask_transpose"
+    batch, n, m = _mask_sizes(name, batch, n, m)
+    mask = _mask_words(name, mask, batch * n, m)
+    _need_cuda(mask)
+    out = torch.empty((batch * m, (n + 63) // 64), dtype=mask.dtype, device=mask.device)
+    if out.numel():
+        with _on(mask.device):
+            check(lib().euler_gpu_mask_transpose(_stream(), _ptr(mask), batch, n, m, _ptr(out)))
+    return out
+
+
+class _MaskAggregate(torch.autograd.Function):
+    """The fused forward; the gradient to x is the SAME kernel, op add, over the transposed mask."""
+
+    @staticmethod
+    def forward(ctx, x, root, mask, batch, n, m, op, od, want_degree):
+        out, deg = _mask_raw(op, mask, x, root, batch, n, m, od, want_degree or any(ctx.needs_input_grad[:2]))
+        ctx.save_for_backward(mask, deg)
+        ctx.conf = (batch, n, m, op, x.shape[0], x.dtype)
+        if deg is not None:
+            ctx.mark_non_differentiable(deg)
+        return out, deg
+
+    @staticmethod
+    def backward(ctx, grad, _grad_degree):
+        mask, deg = ctx.saved_tensors
+        batch, n, m, op, x_rows, x_dt = ctx.conf
+        grad = grad.to(_F32)
+        deg = deg.reshape(-1, 1)
+        # dS = grad / denom in fp32, the denominators as the forward formed them
+        if op == "add":
+            scaled = grad
+        elif op == "gcn_renorm":
+            scaled = grad / (1.0 + deg)
+        else:
+            scaled = grad / deg.clamp_min(1e-7)
+        d_x = d_root = None
+        if ctx.needs_input_grad[0]:
+            d_x, _ = _mask_raw("add", mask_transpose(mask, batch, n, m), scaled.contiguous(), None, batch, m, n, _F32,
+                               False)
+            if x_rows > batch * m:
+                d_x = torch.cat([d_x, d_x.new_zeros((x_rows - batch * m, d_x.shape[1]))])
+            d_x = d_x.to(x_dt)
+        if ctx.needs_input_grad[1]:
+            d_root = (grad if op == "gcn" else scaled).to(x_dt)
+        return (d_x, d_root) + (None,) * 7
+
+
+def mask_aggregate(op, mask, x, batch, n, m, root=None, out_dtype=None, return_degree=False):
+    """The aggregators the reference runs over the SparseTensor of a layerwise sample (utils/
+    sparse_aggregators.py:37-84: tf.sparse_tensor_dense_matmul(adj, x) divided by the degree), read straight
+    from the [batch, n, m] adjacency's bit mask - Graph.sparse_adj_mask, sample_neighbor_layerwise(adj_format=
+    "mask") - in one launch on the matrix units.  With N(b, i) the set bits c < m of mask[b * n + i], deg their
+    count and S = sum of x[b * m + c] over them:
+
+        "add"         out[b * n + i] = S                              sparse_tensor_dense_matmul
+        "mean"                       = S / max(deg, 1e-7)             MeanAggregator
+        "gcn"                        = root + S / max(deg, 1e-7)      GCNAggregator(renorm=False)
+        "gcn_renorm"                 = (root + S) / (1 + deg)         GCNAggregator(renorm=True)
+
+    mask int64 / uint64 [batch * n, (m + 63) // 64]; x [>= batch * m, d] fp32 / bf16 / fp16, 1 <= d <= 1024;
+    root [batch * n, d] of x's dtype, required for the two gcn ops and refused for the others; out_dtype fp32
+    or x's dtype (None: x's).  return_degree: -> (out, deg fp32 [batch * n]), the popcounts, from the same
+    launch.  Bits at positions >= m are ignored.  The bits expand to exact 0 / 1 operands, S accumulates in
+    fp32 in a fixed order of c, the root is added in fp32, there is ONE correctly rounded division and one
+    rounding to out_dtype; the same bits on every run and stream (csrc/mp_mask.h states the contract and the
+    tiling).  There is no COO triple, no nnz and no host wait, forward or backward.
+
+    NON-FINITE x: 0 * inf and 0 * NaN are NaN, so a non-finite x[b * m + c, f] makes column f NaN for the
+    sources of batch row b whether c is their neighbour or not, unlike the reference's sparse product (only
+    a run of 16 sources with no bit at all in c's word of 64 is spared).
+
+    Differentiable in x and root, not in mask.  The gradient to x is Mask^T @ (grad / denom) per batch row:
+    grad is scaled in fp32 by a torch op, the mask is transposed once (mask_transpose) and the SAME kernel
+    runs op "add" with n and m swapped, in fp32.  The gradient to root is grad ("gcn") or grad / (1 + deg)
+    ("gcn_renorm").  Every refusal is a ValueError, raised before the library is touched."""
+    name = "mask_aggregate"
+    if op not in _MASK_OP:
+        raise ValueError("%s: op is add, mean, gcn or gcn_renorm" % name)
+    try:
+        _dt(name, x)
+        od = _out_dt(name, x, out_dtype)
+    except TypeError as err:
+        raise ValueError(str(err)) from None
+    batch, n, m = _mask_sizes(name, batch, n, m)
+    mask_c = _mask_words(name, mask, batch * n, m)
+    if x.dim() != 2 or not 1 <= int(x.shape[1]) <= 1024:
+        raise ValueError("%s: x is [rows, d], d in 1..1024" % name)
+    if x.shape[0] < batch * m:
+        raise ValueError("%s: x has %d rows, fewer than batch * m = %d" % (name, x.shape[0], batch * m))
+    gcn = op in ("gcn", "gcn_renorm")
+    if gcn != (root is not None):
+        raise ValueError("%s: root goes with gcn and gcn_renorm, and only with them" % name)
+    if gcn and (root.dtype != x.dtype or tuple(root.shape) != (batch * n, int(x.shape[1]))):
+        raise ValueError("%s: root is [batch * n, d] of x's dtype" % name)
+    x_c = x.contiguous()
+    root_c = root.contiguous() if gcn else None
+    _need_cuda(mask_c, x_c, *([root_c] if gcn else []))
+    out, deg = _MaskAggregate.apply(x_c, root_c, mask_c, batch, n, m, op, od, return_degree)
+    return (out, deg) if return_degree else out
+
+
 # ---- edge-weighted aggregation ---------------------------------------------------------------
 def _edge_weight(name, w, e, params):
     """checks an edge_weight argument; -> (the weights as a contiguous [E, H] tensor, H)"""

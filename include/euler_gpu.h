@@ -1779,6 +1779,33 @@ int euler_gpu_aggregate_gru(void* stream, int32_t op, const void* table_dev, int
                             const void* gate_bias_dev, int32_t gate_bias_dtype,
                             const void* cand_bias_dev, int32_t cand_bias_dtype, void* out_dev,
                             int32_t out_dtype);
+/* mask_aggregate: the aggregators the reference runs over a layerwise sample's SparseTensor
+ * (tf_euler/python/utils/sparse_aggregators.py:37-84: tf.sparse_tensor_dense_matmul(adj, x) divided
+ * by the degree - GCNAggregator with and without renorm, MeanAggregator) on the matrix units,
+ * read straight from the hit mask of euler_gpu_sparse_adj_mask: no COO triple, no nnz, no host wait.
+ * op: 0 add (S), 1 mean (S / max(deg, 1e-7)), 2 gcn (root + S / max(deg, 1e-7)), 3 gcn_renorm
+ * ((root + S) / (1 + deg)), S[b*n + i] = the sum of x[b*m + c] over the set bits c < m of
+ * mask_dev[b*n + i] (uint64 [batch * n][(m + 63) / 64]; bits >= m are ignored), deg their count.
+ * x_dev [x_rows >= batch * m, d] of `dtype`, contiguous; root_dev [batch * n, d] of `dtype`, read by
+ * the two gcn ops only; out_dev [batch * n, d] of out_dtype (fp32 or dtype); degree_out_dev fp32
+ * [batch * n] or NULL.  The contract - exact 0 / 1 operands, the order of the fp32 accumulation, the
+ * single division, NaN columns from non-finite x, determinism, the tiling and the LDS budget - is
+ * stated once, in euler_amd/csrc/mp_mask.h.  Only enqueues one launch on `stream`.
+ * EULER_GPU_EINVAL: an unknown op or dtype, out_dtype neither fp32 nor dtype, a negative extent,
+ * batch * n or batch * m >= 2^31, d outside 1..1024, x_rows < batch * m, a null required buffer, a
+ * buffer not aligned to its element type; every check precedes the launch.  batch * n == 0 returns
+ * EULER_GPU_OK and touches nothing; m == 0 reads neither mask_dev nor x_dev. */
+int euler_gpu_mask_aggregate(void* stream, int32_t op, const uint64_t* mask_dev, const void* x_dev,
+                             int32_t dtype, int64_t x_rows, const void* root_dev, int64_t batch,
+                             int64_t n, int64_t m, int64_t d, void* out_dev, int32_t out_dtype,
+                             float* degree_out_dev);
+/* mask_transpose: the hit mask [batch * n][(m + 63) / 64] as [batch * m][(n + 63) / 64] - the
+ * adjacency of the gradient of mask_aggregate with respect to x (sparse_aggregators.py:37-84
+ * differentiated: Mask^T @ grad per batch row) - by transposing 64 x 64 bit blocks, one wave each.
+ * Input bits >= m are dropped; output bits >= n are zero.  Every word of out_dev is written.
+ * EULER_GPU_EINVAL: a negative extent, batch * n or batch * m >= 2^31, a null or misaligned buffer. */
+int euler_gpu_mask_transpose(void* stream, const uint64_t* mask_dev, int64_t batch, int64_t n,
+                             int64_t m, uint64_t* out_dev);
 
 /* ---- shard ops (multi-GPU) --------------------------------------------------
  * ID_SPLIT (core/kernels/id_split_op.cc:46-99): stable bucket of ids by
