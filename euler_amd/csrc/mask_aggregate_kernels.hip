@@ -14,8 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
-#include "mp_dense_frag.h"
-#include "mp_mask.h"
+#include "mp_mask_frag.h"
 
 namespace euler_gpu {
 namespace {
@@ -90,25 +89,6 @@ __device__ __forceinline__ void MaskFragment(uint64_t word, int x, int32_t g, De
     for (int p = 0; p < 4; ++p)
       af[0][p] = ((byte >> (2 * p)) & 1u ? kOne : 0u) | ((byte >> (2 * p + 1)) & 1u ? kOne << 16 : 0u);
   }
-}
-
-// The B fragment(s) of column 16 nf + c for the chunk at candidate kc of the block
-template <int DT>
-__device__ __forceinline__ void MaskLoadB(const unsigned char* lds, int32_t stride, int32_t kc, int32_t nf, int32_t c,
-                                          int32_t g, DenseWords* bw) {
-  if constexpr (DT == kF32) {
-    const unsigned char* at = lds + (kc + g) * stride + (16 * nf + c) * 4;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) bw[j / 4][j % 4] = *reinterpret_cast<const uint32_t*>(at + 4 * j * stride);
-  } else {
-    bw[0] = *reinterpret_cast<const DenseWords*>(lds + MaskXtByte(16 * nf + c, (kc + 8 * g) * 2, stride));
-  }
-}
-
-template <int DT>
-__device__ __forceinline__ float MaskRoot(const void* root, int64_t at) {
-  return TkWiden<DT>(DT == kF32 ? static_cast<const uint32_t*>(root)[at]
-                                : (uint32_t)static_cast<const uint16_t*>(root)[at]);
 }
 
 extern __shared__ __align__(16) unsigned char mask_lds[];

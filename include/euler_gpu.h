@@ -1806,6 +1806,36 @@ int euler_gpu_mask_aggregate(void* stream, int32_t op, const uint64_t* mask_dev,
  * EULER_GPU_EINVAL: a negative extent, batch * n or batch * m >= 2^31, a null or misaligned buffer. */
 int euler_gpu_mask_transpose(void* stream, const uint64_t* mask_dev, int64_t batch, int64_t n,
                              int64_t m, uint64_t* out_dev);
+/* mask_attention: the reference's AttentionAggregator over a layerwise sample's SparseTensor
+ * (tf_euler/python/utils/sparse_aggregators.py:87-139: per head leaky_relu(self_layer(from_self) +
+ * neigh_layer(from_all)^T) on the adjacency's entries, tf.sparse_softmax, sparse_tensor_dense_matmul;
+ * renorm=True adds the eye column, renorm=False adds from_self; the heads concatenated) on the matrix
+ * units, read straight from the hit mask of euler_gpu_sparse_adj_mask in one launch: no COO triple, no
+ * nnz, no host wait, no atomics, no [n, m] logits in memory.  With d = heads * dh, for batch row b,
+ * source i, head h and the set bits c < m of mask_dev[b*n + i]:
+ *   e_c = leaky(s_src[b*n+i, h] + s_nb[b*m+c, h]),  e_0 = leaky(s_src[b*n+i, h] + s_root[b*n+i, h])
+ *   alpha = softmax over {e_c} (and e_0 when s_root_dev is given)
+ *   A = sum_c alpha_c * z[b*m+c, h*dh .. (h+1)*dh) (+ alpha_0 * root[b*n+i, the same columns])
+ *   out = A (s_root_dev given, or no root_dev) | root + A (root_dev without s_root_dev)
+ * then relu if activation == 1, one rounding to out_dtype.  z_dev [z_rows >= batch * m, d] of `dtype`
+ * and root_dev [batch * n, d] of `dtype` or NULL, contiguous; s_src_dev [batch * n, heads], s_nb_dev
+ * [s_nb_rows >= batch * m, heads] and s_root_dev [batch * n, heads] (NULL, or with root_dev) fp32;
+ * out_dev [batch * n, d] of out_dtype (fp32 or dtype).  The contract - the shift taken over a source's
+ * own neighbours, the numerators selected by the bit and rounded once to `dtype`, the denominator summed
+ * from the same rounded values in a fixed order, the fp32 self term, the single division, NaN columns
+ * from non-finite z, determinism, the tiling and the LDS budget - is stated once, in
+ * euler_amd/csrc/mp_mask_attention.h.  Only enqueues one launch on `stream`.
+ * EULER_GPU_EINVAL: an unknown dtype or activation, out_dtype neither fp32 nor dtype, negative_slope
+ * negative or not finite, a negative extent, batch * n or batch * m >= 2^31, d outside 1..1024, heads
+ * < 1 or not dividing d, z_rows or s_nb_rows < batch * m, s_root_dev without root_dev, a null required
+ * buffer, a buffer not aligned to its element type; every check precedes the launch.  batch * n == 0
+ * returns EULER_GPU_OK and touches nothing; m == 0 reads none of mask_dev, z_dev and s_nb_dev. */
+int euler_gpu_mask_attention(void* stream, const uint64_t* mask_dev, const void* z_dev, int32_t dtype,
+                             int64_t z_rows, const float* s_src_dev, const float* s_nb_dev,
+                             int64_t s_nb_rows, const void* root_dev, const float* s_root_dev,
+                             int64_t batch, int64_t n, int64_t m, int64_t d, int64_t heads,
+                             float negative_slope, int32_t activation, void* out_dev,
+                             int32_t out_dtype);
 
 /* ---- shard ops (multi-GPU) --------------------------------------------------
  * ID_SPLIT (core/kernels/id_split_op.cc:46-99): stable bucket of ids by
