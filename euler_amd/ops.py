@@ -1776,14 +1776,40 @@ def _mask_attention_composed(bits, z, s_src, s_nb, root, s_root, heads, slope, r
     return torch.relu(out) if relu else out
 
 
+def _mask_attention_fused_backward(mask, z, s_src, s_nb, root, s_root, out, grad, batch, n, m, heads, slope, relu, need):
+    """euler_gpu_mask_attention_backward on prepared tensors -> the five gradients (None where not needed); rows of z
+    and s_nb past batch * m get zeros"""
+    dev, d = z.device, int(z.shape[1])
+
+    def buf(like, rows, dt, want):
+        if like is None or not want:
+            return None
+        new = torch.zeros if like.shape[0] > rows or batch * n == 0 else torch.empty      # (the kernels write rows only)
+        return new(tuple(like.shape), dtype=dt, device=dev)
+    d_z, d_s_src, d_s_nb = buf(z, batch * m, z.dtype, need[0]), buf(s_src, batch * n, _F32, need[1]), buf(s_nb, batch * m, _F32, need[2])
+    d_root, d_s_root = buf(root, batch * n, z.dtype, need[3]), buf(s_root, batch * n, _F32, need[4])
+    if batch * n and any(t is not None for t in (d_z, d_s_src, d_s_nb, d_root, d_s_root)):
+        mask_t = mask_transpose(mask, batch, n, m) if m and (d_z is not None or d_s_nb is not None) else None
+        stats = torch.empty((batch * n, heads, 4), dtype=_F32, device=dev)
+        with _on(dev):
+            check(lib().euler_gpu_mask_attention_backward(
+                _stream(), _ptr(mask), _ptr(mask_t), _ptr(z), _DT[z.dtype], int(z.shape[0]), _ptr(s_src), _ptr(s_nb),
+                int(s_nb.shape[0]), _ptr(root), _ptr(s_root), _ptr(out), _ptr(grad), _DT[grad.dtype], batch, n, m, d, heads,
+                float(slope), int(relu), _ptr(stats), _ptr(d_z), _ptr(d_s_src), _ptr(d_s_nb), _ptr(d_root), _ptr(d_s_root)))
+    return d_z, d_s_src, d_s_nb, d_root, d_s_root
+
+
 class _MaskAttention(torch.autograd.Function):
-    """The fused forward; the backward recomputes the composed form chunk by chunk (see mask_attention)."""
+    """The fused forward; the backward is the two kernels of euler_gpu_mask_attention_backward (fused) or recomputes
+    the composed form chunk by chunk (see mask_attention)."""
 
     @staticmethod
-    def forward(ctx, z, s_src, s_nb, root, s_root, mask, batch, n, m, heads, slope, relu, od):
+    def forward(ctx, z, s_src, s_nb, root, s_root, mask, batch, n, m, heads, slope, relu, od, fused=False):
         out = _mask_attention_raw(mask, z, s_src, s_nb, root, s_root, batch, n, m, heads, slope, relu, od)
-        ctx.save_for_backward(mask, z, s_src, s_nb, *[t for t in (root, s_root) if t is not None])
+        ctx.save_for_backward(mask, z, s_src, s_nb, *[t for t in (root, s_root) if t is not None],
+                              *([out] if fused and relu else []))
         ctx.conf = (root is not None, s_root is not None, batch, n, m, heads, slope, relu)
+        ctx.fused = fused
         return out
 
     @staticmethod
@@ -1793,6 +1819,9 @@ class _MaskAttention(torch.autograd.Function):
         root = rest.pop(0) if has_root else None
         s_root = rest.pop(0) if has_s_root else None
         need = ctx.needs_input_grad[:5]
+        if ctx.fused:
+            return _mask_attention_fused_backward(mask, z, s_src, s_nb, root, s_root, rest.pop(0) if relu else None,
+                                                  grad.contiguous(), batch, n, m, heads, slope, relu, need) + (None,) * 9
         dev = z.device
         zeros = lambda t, want: torch.zeros(t.shape, dtype=_F32, device=dev) if t is not None and want else None
         sums = [zeros(t, w) for t, w in zip((z, s_src, s_nb, root, s_root), need)]
@@ -1822,11 +1851,11 @@ class _MaskAttention(torch.autograd.Function):
                     if t is not None and id(t) in got:
                         acc[at] += got[id(t)]
         cast = lambda acc, src: None if acc is None else acc.to(src.dtype)
-        return tuple(cast(acc, t) for acc, t in zip(sums, (z, s_src, s_nb, root, s_root))) + (None,) * 8
+        return tuple(cast(acc, t) for acc, t in zip(sums, (z, s_src, s_nb, root, s_root))) + (None,) * 9
 
 
 def mask_attention(mask, z, s_src, s_nb, batch, n, m, heads=1, root=None, s_root=None, negative_slope=0.2,
-                   activation=None, out_dtype=None):
+                   activation=None, out_dtype=None, backward="recompute"):
     """The reference's AttentionAggregator over the SparseTensor of a layerwise sample (utils/
     sparse_aggregators.py:87-139, the default aggregator of GenieEncoder), read straight from the [batch, n, m]
     adjacency's bit mask - Graph.sparse_adj_mask, sample_neighbor_layerwise(adj_format="mask") - in one launch
@@ -1859,14 +1888,23 @@ def mask_attention(mask, z, s_src, s_nb, batch, n, m, heads=1, root=None, s_root
     with the density, while the composed route - Graph.adj_from_mask, index arrays, attention_aggregate(
     "additive", indices=...) - pays per edge and a host wait.  As measured (bf16, d = 128, 4 heads) the
     forward is ahead at every density tried - 0.21 against 1.12 ms (1 %) and 3.93 ms (10 %) over 16 384 x 4 096, 0.025
-    against 0.32 and 0.64 ms over 1 024 x 512; densities below 1 % are not measured.  A TRAINING step is another
-    matter: this op's backward (below) is dense torch work and made the example's step 7.1 against 1.6 ms composed -
-    call the composed route when the gradient's time matters more than the forward's.
+    against 0.32 and 0.64 ms over 1 024 x 512; densities below 1 % are not measured.  For TRAINING pass backward="fused":
+    as measured (the same shapes, the backward pass alone) the two gradient kernels take 1.16 ms at 1 % and
+    at 10 % over 16 384 x 4 096 against 1.82 and 7.72 ms for the composed route's autograd and 19.2 ms for
+    backward="recompute", and 0.10 ms over 1 024 x 512 against 0.55 / 0.88 ms composed and 0.9 ms recomputed; their peak
+    is 15 MB against 53 - 393 MB composed and 506 MB recomputed.  Densities below 1 % are not measured; there the composed
+    route, which pays per edge, may be ahead.
 
-    Differentiable in z, s_src, s_nb, root and s_root, not in mask.  The backward pass is NOT a fused kernel: per
-    batch row and chunk of source rows - sized from the shapes alone, at most MASK_ATTENTION_GRAD_BYTES of [rows,
-    m, H] fp32 logits - it unpacks the bits by shifts, recomputes the composed form in fp32 torch ops on the device
-    and differentiates that.  Every refusal is a ValueError, raised before the library is touched."""
+    Differentiable in z, s_src, s_nb, root and s_root, not in mask.  backward="recompute" (the default) is NOT a fused
+    kernel: per batch row and chunk of source rows - sized from the shapes alone, at most MASK_ATTENTION_GRAD_BYTES of
+    [rows, m, H] fp32 logits - it unpacks the bits by shifts, recomputes the composed form in fp32 torch ops on the
+    device and differentiates that.  backward="fused" is euler_gpu_mask_attention_backward: the forward output is saved
+    when relu is on, the mask is transposed once (mask_transpose), and a source-major and a candidate-major kernel on the
+    matrix units write all wanted gradients - every numerator split by the sign of its pre-activation into two fragments
+    and two accumulator sets, no [n, m] block, no atomics, no host wait, the same bits on every run, on every stream and
+    under any split of the batch (csrc/mp_mask_attention_backward.h states the contract); the incoming gradient has
+    out_dtype; where a pre-activation is exactly 0 the kernels take the leaky relu's derivative as 1 (as attention_aggregate's
+    backward does), the recomputation as the slope (torch's choice).  Any other value of backward, like every refusal, is a ValueError raised before the library is touched."""
     name = "mask_attention"
     try:
         _dt(name, z)
@@ -1900,9 +1938,11 @@ def mask_attention(mask, z, s_src, s_nb, batch, n, m, heads=1, root=None, s_root
         raise ValueError("%s: negative_slope is finite and >= 0" % name)
     if activation not in (None, "relu"):
         raise ValueError("%s: activation is None or relu" % name)
+    if backward not in ("recompute", "fused"):
+        raise ValueError("%s: backward is recompute or fused" % name)
     tensors = [t if t is None else t.contiguous() for t in (z, s_src, s_nb, root, s_root)]
     _need_cuda(mask_c, *[t for t in tensors if t is not None])
-    return _MaskAttention.apply(*tensors, mask_c, batch, n, m, heads, slope, activation == "relu", od)
+    return _MaskAttention.apply(*tensors, mask_c, batch, n, m, heads, slope, activation == "relu", od, backward == "fused")
 
 
 # ---- edge-weighted aggregation ---------------------------------------------------------------

@@ -1836,6 +1836,35 @@ int euler_gpu_mask_attention(void* stream, const uint64_t* mask_dev, const void*
                              int64_t batch, int64_t n, int64_t m, int64_t d, int64_t heads,
                              float negative_slope, int32_t activation, void* out_dev,
                              int32_t out_dtype);
+/* mask_attention_backward: the gradients of mask_attention with respect to z, s_src, s_nb, root and
+ * s_root in two launches on the matrix units - a source-major kernel over mask_dev and a
+ * candidate-major kernel over mask_t_dev, the mask of the transposed adjacency as
+ * euler_gpu_mask_transpose writes it ([batch * m][(n + 63) / 64]).  No COO triple, no [n, m] block in
+ * memory, no atomics, no host wait; the same bits on every run, on every stream and under any split of
+ * the batch.  The forward's arguments keep their meaning.  out_dev is the SAVED forward output, read
+ * only with activation 1 (its gradient is zeroed where out <= 0); grad_dev [batch * n, d] is the
+ * incoming gradient; both are of grad_dtype, fp32 or `dtype`.  stats_ws_dev: fp32 [batch * n, heads, 4]
+ * the caller allocates, written by the first kernel and read by the second.  A null gradient pointer
+ * means "not wanted": d_z_dev [batch * m, d] of `dtype`, d_root_dev [batch * n, d] of `dtype`,
+ * d_s_src_dev and d_s_root_dev [batch * n, heads] and d_s_nb_dev [batch * m, heads] fp32; every wanted
+ * element of those extents is written.  The second kernel runs only where d_z_dev or d_s_nb_dev is
+ * wanted and m > 0; nothing runs where nothing is wanted.  The contract - the split of every numerator
+ * by the sign of its pre-activation, the order of every sum, the statistics - is stated once, in
+ * euler_amd/csrc/mp_mask_attention_backward.h.
+ * EULER_GPU_EINVAL: what euler_gpu_mask_attention refuses; grad_dtype neither fp32 nor dtype;
+ * activation 1 without out_dev; d_root_dev without root_dev; d_s_root_dev without s_root_dev; a null
+ * grad_dev, stats_ws_dev or (where the second kernel runs) mask_t_dev; a buffer not aligned to its
+ * element type; every check precedes the launches.  batch * n == 0 returns EULER_GPU_OK and touches
+ * nothing; m == 0 reads no mask and writes d_root (the gated grad) and zero score gradients. */
+int euler_gpu_mask_attention_backward(void* stream, const uint64_t* mask_dev, const uint64_t* mask_t_dev,
+                                      const void* z_dev, int32_t dtype, int64_t z_rows,
+                                      const float* s_src_dev, const float* s_nb_dev, int64_t s_nb_rows,
+                                      const void* root_dev, const float* s_root_dev, const void* out_dev,
+                                      const void* grad_dev, int32_t grad_dtype, int64_t batch, int64_t n,
+                                      int64_t m, int64_t d, int64_t heads, float negative_slope,
+                                      int32_t activation, float* stats_ws_dev, void* d_z_dev,
+                                      float* d_s_src_dev, float* d_s_nb_dev, void* d_root_dev,
+                                      float* d_s_root_dev);
 
 /* ---- shard ops (multi-GPU) --------------------------------------------------
  * ID_SPLIT (core/kernels/id_split_op.cc:46-99): stable bucket of ids by

@@ -8,7 +8,9 @@ over --repeats windows, every shape warmed up first.  Prints one JSON line: per 
 per call over the windows and the peak bytes a call allocates, and for the fused route the numerators it
 evaluates (every source, candidate and head once per column tile of the head, zero words of a run of 16 sources
 skipped) with the rate that makes, beside its matrix instructions and the bytes the shape needs.  --route fused
---calls N runs N calls and nothing else: the form to put under a kernel trace.
+--calls N runs N calls and nothing else: the form to put under a kernel trace.  --backward times the BACKWARD pass
+alone instead (one forward kept, its graph retained): the two kernels of backward="fused", the default
+backward="recompute" in torch ops, and the composed route's own autograd.
 
     python tools/ubench_mask_attention.py [--n 16384] [--m 4096] [--density 0.01] [--heads 4] [--seconds 1]
 """
@@ -39,6 +41,7 @@ def main():
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--calls", type=int, default=0, help="run this many calls of --route and exit")
+    ap.add_argument("--backward", action="store_true", help="time the backward pass of fused / recompute / composed")
     a = ap.parse_args()
     torch.manual_seed(0)
     n, m, d, heads, dt = a.n, a.m, a.dim, a.heads, torch.bfloat16
@@ -51,8 +54,8 @@ def main():
     root = torch.randn((n, d), device="cuda").to(dt) if a.form != "none" else None
     s_root = s_root if a.form == "renorm" else None
 
-    def fused():
-        return ops.mask_attention(mask, z, s_src, s_nb, 1, n, m, heads=heads, root=root, s_root=s_root)
+    def fused(backward="recompute"):
+        return ops.mask_attention(mask, z, s_src, s_nb, 1, n, m, heads=heads, root=root, s_root=s_root, backward=backward)
 
     def composed():
         ind, _val, _shape = Graph.adj_from_mask(mask, 1, n, m)
@@ -66,7 +69,12 @@ def main():
                                        v=torch.cat([z, root]), heads=heads, indices=torch.cat([src, own]))
 
     routes = {"fused": fused, "composed": composed}
-    if a.route != "both":
+    if a.backward:
+        leaves = [t.requires_grad_(True) for t in (z, s_src, s_nb, root, s_root) if t is not None]
+        outs = {"fused": fused("fused"), "recompute": fused(), "composed": composed()}
+        grad = torch.randn((n, d), device="cuda").to(dt)
+        routes = {k: (lambda o=o: torch.autograd.grad(o, leaves, grad, retain_graph=True)) for k, o in outs.items()}
+    elif a.route != "both":
         routes = {a.route: routes[a.route]}
     if a.calls:
         for _ in range(a.calls):
@@ -97,7 +105,7 @@ def main():
            "calls_per_window": calls, "windows": a.repeats,
            "ms": {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in ms.items()},
            "peak_bytes_per_call": peak}
-    if "fused" in ms:
+    if "fused" in ms and not a.backward:
         # pass 2 evaluates 64 numerators per live word and source, for every head and column tile of the head;
         # one v_mfma_f32_16x16x32 per run of 16 sources, chunk of 32 candidates and 16 columns
         dh = d // heads
