@@ -34,26 +34,6 @@ struct DenseArgs {
   DensePlan plan;
 };
 
-// W^T of columns f0 .. f0 + 16 NT and of k_base .. k_base + k_len of w [k_all, f_all] into wt; +0
-// beyond f_all and k_all
-template <int DT, int NT>
-__device__ __forceinline__ void DenseStageW(const void* w, int32_t k_all, int32_t f_all, int32_t f0, int32_t k_base,
-                                            int32_t k_len, int32_t stride, unsigned char* wt) {
-  constexpr int kCols = 16 * NT;
-  constexpr int kEsz = DT == kF32 ? 4 : 2;
-  const int32_t total = kCols * k_len;
-  for (int32_t i = threadIdx.x; i < total; i += blockDim.x) {
-    const int32_t c = i % kCols, k = i / kCols;
-    const bool live = k_base + k < k_all && f0 + c < f_all;
-    const int64_t at = (int64_t)(k_base + k) * f_all + f0 + c;
-    unsigned char* to = wt + DenseWtByte(c, k * kEsz, stride);
-    if constexpr (DT == kF32)
-      *reinterpret_cast<uint32_t*>(to) = live ? static_cast<const uint32_t*>(w)[at] : 0u;
-    else
-      *reinterpret_cast<uint16_t*>(to) = live ? static_cast<const uint16_t*>(w)[at] : (uint16_t)0;
-  }
-}
-
 template <int DT>
 __device__ __forceinline__ void DenseStore(const DenseArgs& a, int64_t at, float v) {
   if (DT == kF32 || a.out_f32) static_cast<float*>(a.out)[at] = v;

@@ -945,17 +945,72 @@ def _dense_raw(op, act, combine, table, weight, bias, gi, sp, count, e, size, ro
     return out
 
 
+DENSE_BWD_MAX_K, DENSE_BWD_MAX_F = 256, 512      # kDenseBwdMaxK, kDenseBwdMaxF of csrc/mp_dense_backward.h
+
+
+def _dense_bwd_slabs(size):
+    """DenseBwdSlabs of csrc/mp_dense_backward.h (the entry checks the workspace against its own)"""
+    rows = max(1024, -(-(-(-size // 256)) // 32) * 32)
+    return -(-size // rows)
+
+
+def _dense_fused_backward(table, weight, bias, root, root_weight, gi, sp, count, e, size, op, act, combine, root_scale,
+                          grad, need):
+    """euler_gpu_aggregate_dense_backward on the saved tensors, then the grouped add of dA' into a zeroed table
+    -> the five gradients (None where not needed)"""
+    (rows, d), f, dev, dt = table.shape, int(weight.shape[1]), table.device, table.dtype
+    two = root_weight is not None
+    ds = int(root.shape[1]) if root is not None else 0
+    fs = int(root_weight.shape[1]) if two else 0
+    want_t, want_w, want_b = need[0], need[1], bias is not None and need[2]
+    want_r, want_ws = root is not None and need[3], two and need[4]
+    new = torch.zeros if size == 0 else torch.empty
+    buf = lambda shape, t, want: new(shape, dtype=t, device=dev) if want else None
+    d_w, d_b = buf((d, f), dt, want_w), buf((f,), bias.dtype if bias is not None else dt, want_b)
+    d_root, d_ws = buf((size, ds), dt, want_r), buf((ds, fs), dt, want_ws)
+    d_table = torch.zeros((rows, d), dtype=dt, device=dev) if want_t else None
+    if size == 0 or not (want_t or want_w or want_b or want_r or want_ws):
+        return d_table, d_w, d_b, d_root, d_ws
+    want_n = want_t or want_w or want_b or (combine == "fold" and want_r)
+    a_ws = buf((size, d), dt, want_w or want_b)
+    dzn, dzs = buf((size, f), dt, want_n), buf((size, fs), dt, two and (want_r or want_ws))
+    floats = _dense_bwd_slabs(size) * max((d * f + f) if (want_w or want_b) else 0, ds * fs if want_ws else 0)
+    partial = buf((floats,), _F32, floats > 0)
+    d_agg = buf((size, d), _F32, want_t)
+    grad = grad.contiguous() if grad.dtype in (_F32, dt) else grad.to(_F32).contiguous()
+    with _on(dev):
+        check(lib().euler_gpu_aggregate_dense_backward(
+            _stream(), _DENSE_OP[op], _POOL_ACT[act], _DENSE_COMBINE[combine], _ptr(table), _DT[dt], int(rows),
+            _ptr(weight), _ptr(bias), _DT[bias.dtype] if bias is not None else 0, _ptr(gi),
+            int(gi is not None and gi.dtype == torch.int64), _ptr(sp), int(count), e, int(d), f, size, _ptr(root),
+            _ptr(root_weight), ds, fs, int(root_scale is not None), float(root_scale or 0.0), _ptr(grad), _DT[grad.dtype],
+            _ptr(a_ws), _ptr(dzn), _ptr(dzs), _ptr(partial), floats, _ptr(d_agg), _ptr(d_w), _ptr(d_b), _ptr(d_root),
+            _ptr(d_ws)))
+        if want_t and e > 0:
+            # d_table[g[p]] += dA'[dst(p)]: the grouped add of embed_store.h, occurrences in increasing p in fp32, one
+            # rounding; an index outside the table, or a position outside every segment, names no row
+            ids = gi.to(torch.int64) if gi is not None else torch.arange(e, device=dev)
+            dst = None
+            if sp is not None:
+                dst = (torch.searchsorted(sp.clamp(0, e), torch.arange(e, device=dev), right=True) - 1).to(torch.int32)
+            check(lib().euler_gpu_store_add(_stream(), _ptr(d_table), _DT[dt], int(rows), int(d), _ptr(ids), e,
+                                            _ptr(d_agg), _DT[_F32], size, _ptr(dst), 0 if sp is not None else int(count)))
+    return d_table, d_w, d_b, d_root, d_ws
+
+
 class _AggregateDense(torch.autograd.Function):
-    """The fused forward; the backward recomputes the composed form chunk by chunk (see
-    aggregate_dense)."""
+    """The fused forward; the backward is euler_gpu_aggregate_dense_backward and one grouped add (fused) or
+    recomputes the composed form chunk by chunk (see aggregate_dense)."""
 
     @staticmethod
-    def forward(ctx, table, weight, bias, root, root_weight, gi, sp, count, e, size, op, act, combine, root_scale, od):
+    def forward(ctx, table, weight, bias, root, root_weight, gi, sp, count, e, size, op, act, combine, root_scale, od,
+                fused=False):
         out = _dense_raw(op, act, combine, table, weight, bias, gi, sp, count, e, size, root, root_weight,
                          root_scale, od)
         ctx.save_for_backward(table, weight, *[t for t in (bias, root, root_weight, gi, sp) if t is not None])
         ctx.conf = ([t is not None for t in (bias, root, root_weight, gi, sp)], count, e, size, op, act, combine,
                     root_scale)
+        ctx.fused = fused
         return out
 
     @staticmethod
@@ -965,6 +1020,9 @@ class _AggregateDense(torch.autograd.Function):
         table, weight = saved[0], saved[1]
         rest = saved[2:]
         bias, root, root_weight, gi, sp = [rest.pop(0) if h else None for h in has]
+        if ctx.fused:
+            return _dense_fused_backward(table, weight, bias, root, root_weight, gi, sp, count, e, size, op, act, combine,
+                                         root_scale, grad, ctx.needs_input_grad[:5]) + (None,) * 11
         rows, d = table.shape
         dev, f = table.device, int(weight.shape[1])
         w32 = weight.to(_F32)
@@ -1029,12 +1087,12 @@ class _AggregateDense(torch.autograd.Function):
                     d_root[r_a:r_b] = dzs @ ws32.t()
         return (d_table.to(table.dtype) if want_t else None, d_w.to(weight.dtype) if want_w else None,
                 d_b.to(bias.dtype) if want_b else None, d_root.to(root.dtype) if want_r else None,
-                d_ws.to(root_weight.dtype) if want_ws else None) + (None,) * 10
+                d_ws.to(root_weight.dtype) if want_ws else None) + (None,) * 11
 
 
 def aggregate_dense(op, table, weight, gather_indices, size, root=None, root_weight=None, combine="add",
                     root_scale=None, bias=None, activation="relu", seg_ptr=None, count=None, out_dtype=None,
-                    root_index=None):
+                    root_index=None, backward="recompute"):
     """The mean aggregator family of the reference - MeanAggregator (utils/aggregators.py:38-72,
     SageEncoder's default), GCNAggregator (aggregators.py:25-35), SAGEConv / GraphConv and GINConv -
     reduce, THEN dense, in one pass on the matrix units.  With A[r] the aggregate of destination r,
@@ -1064,8 +1122,19 @@ def aggregate_dense(op, table, weight, gather_indices, size, root=None, root_wei
     table's).  An empty segment has A = +0.  The same call gives the same bits on every run, on every
     stream and for count or the equivalent seg_ptr.  The full contract and the tiling: csrc/mp_dense.h.
 
-    Differentiable in table, weight, bias, root and root_weight.  As for pool_aggregate the backward
-    pass is deliberately NOT a fused kernel: over chunks of whole destinations of at most
+    Differentiable in table, weight, bias, root and root_weight.  backward="fused" (for TRAINING) is
+    euler_gpu_aggregate_dense_backward (csrc/mp_dense_backward.h): a destination-major MFMA kernel recomputes A and
+    both pre-activations with the forward's own fragment code - the relu mask is the forward's, bit for bit; the
+    derivative at 0 and at NaN is 0 - and stores dZ, narrowed once to the table's dtype; dZ W^T (divided by the mean's
+    denominator: one fp32 division) and the weight and bias gradients (sums over slabs of destinations that depend
+    on `size` alone, added in slab order) are MFMA kernels too; the table gradient is ONE grouped in-place add
+    (embedding_add's: occurrences in increasing p in fp32, one rounding) into a zeroed table-dtype [rows, d].  No
+    Python loop, no host wait with seg_ptr either, no atomics; only the wanted gradients are computed; the same bits
+    on every run, on every stream and for count or the equivalent seg_ptr.  It serves d, ds <= 256 and F, Fs <= 512
+    (kDenseBwdMaxK, kDenseBwdMaxF) and ordinary tables; beyond them, or with an Fp8Rows table, backward="fused" is a
+    ValueError when the op is called, never a fallback.  Its temporaries are A, dZ of each path ([size, d | F | Fs],
+    the table's dtype) and dA' ([size, d] fp32).  Measurements: DESIGN 4.36.
+    backward="recompute" (the default) is deliberately NOT a fused kernel: over chunks of whole destinations of at most
     POOL_GRAD_CHUNK_ROWS gathered rows it recomputes A through gather_segment_reduce (fp32 sums,
     narrowed once to the table's dtype and widened), the pre-activations in fp32, and sums the
     gradients over the chunks in chunk order.  The relu mask is that of the RECOMPUTED pre-activation
@@ -1103,7 +1172,11 @@ def aggregate_dense(op, table, weight, gather_indices, size, root=None, root_wei
         raise ValueError("%s: combine is add, concat or fold" % name)
     if root is not None and root_index is not None:
         raise ValueError("%s: pass root or root_index, not both" % name)
+    if backward not in ("recompute", "fused"):
+        raise ValueError("%s: backward is recompute or fused" % name)
     if isinstance(table, Fp8Rows):
+        if backward == "fused":
+            raise ValueError("%s: backward=\"fused\" does not serve an Fp8Rows table; pass backward=\"recompute\"" % name)
         return _fp8_aggregate_dense(op, table, weight, gather_indices, size, root, root_index, root_weight, combine,
                                     root_scale, bias, activation, seg_ptr, count, out_dtype)
     if root_index is not None:
@@ -1151,6 +1224,12 @@ def aggregate_dense(op, table, weight, gather_indices, size, root=None, root_wei
                 raise ValueError("%s: combine add needs Fs == F" % name)
     if root_scale is not None and not math.isfinite(float(root_scale)):
         raise ValueError("%s: root_scale is a finite number" % name)
+    if backward == "fused":
+        k_max = max(d, int(root.shape[1]) if root is not None else 0)
+        f_max = max(f, int(root_weight.shape[1]) if root_weight is not None else 0)
+        if k_max > DENSE_BWD_MAX_K or f_max > DENSE_BWD_MAX_F:
+            raise ValueError("%s: backward=\"fused\" serves d, ds <= %d (kDenseBwdMaxK) and F, Fs <= %d (kDenseBwdMaxF); "
+                             "pass backward=\"recompute\" beyond them" % (name, DENSE_BWD_MAX_K, DENSE_BWD_MAX_F))
     if bias is not None:
         if bias.dim() != 1 or bias.numel() != f:
             raise ValueError("%s: bias is [F]" % name)
@@ -1186,7 +1265,7 @@ def aggregate_dense(op, table, weight, gather_indices, size, root=None, root_wei
         raise ValueError("%s: fewer than 2^31 positions" % name)
     _need_cuda(table_c, weight_c, *[t for t in (bias_c, root_c, rw_c, gi, sp) if t is not None])
     return _AggregateDense.apply(table_c, weight_c, bias_c, root_c, rw_c, gi, sp, count, e, size, op, activation,
-                                 combine, None if root_scale is None else float(root_scale), od)
+                                 combine, None if root_scale is None else float(root_scale), od, backward == "fused")
 
 
 # ---- the same layer over an Fp8Rows table (csrc/mp_dense_fp8.h) --------------------------------

@@ -16,9 +16,14 @@ over the features as an ops.Fp8Rows table (a quarter of their fp32 bytes; the sa
 gather_indices and root_index), asserts it against float64 on the dequantised table within the bound of
 tests/test_fp8_dense_gpu.py, and prints its relative error against the bf16-feature run.  The synthetic
 graph carries no float features, so the table is quantised from the example's own id-indexed rows; with
-features in the graph it is G.fp8_dense_feature(fid, dim).
+features in the graph it is G.fp8_dense_feature(fid, dim).  --fused-backward adds a third route, the fused op
+with backward="fused" (euler_gpu_aggregate_dense_backward: no Python loop, no fp32 [rows, d] scatter result
+per chunk), prints its step time and peak beside the others, and asserts the hop-2 layer's weight and bias
+gradients of the two backward routes against each other within the bound of
+tests/test_aggregate_dense_backward_gpu.py.
 
-    python examples/python/sage_mean_minibatch.py [--steps 5] [--composed] [--batch 4096] [--fp8-features]
+    python examples/python/sage_mean_minibatch.py [--steps 5] [--composed] [--fused-backward] [--batch 4096]
+                                                  [--fp8-features]
 """
 import argparse
 import os
@@ -36,9 +41,9 @@ U = 2.0 ** -24
 
 
 class MeanSageLayer(torch.nn.Module):
-    def __init__(self, dim, hidden, dtype, composed):
+    def __init__(self, dim, hidden, dtype, composed, backward="recompute"):
         super().__init__()
-        self.composed = composed
+        self.composed, self.backward = composed, backward
         mk = lambda *s: torch.nn.Parameter((torch.randn(*s, device="cuda") / s[0] ** 0.5).to(dtype))
         self.self_w, self.neigh_w = mk(dim, hidden), mk(dim, hidden)
         self.bias = torch.nn.Parameter(torch.zeros(hidden, device="cuda"))
@@ -48,7 +53,7 @@ class MeanSageLayer(torch.nn.Module):
         n_dst = self_rows.shape[0]
         if not self.composed:
             return ops.aggregate_dense("mean", table, self.neigh_w, ids, n_dst, root=self_rows, root_weight=self.self_w,
-                                       bias=self.bias, count=count)
+                                       bias=self.bias, count=count, backward=self.backward)
         if ids is None:
             ids = torch.arange(table.shape[0], device="cuda", dtype=torch.int32)
         agg = ops.gather_segment_reduce("mean", table, ids.reshape(-1), n_dst, count=count)
@@ -88,6 +93,41 @@ def check(layer_f, layer_c, table, self_ids, ids, count, n=4096):
     print("routes agree within the bound")
 
 
+def check_backward(layer_r, layer_f, table, self_ids, ids, count, n=1024):
+    """the hop-2 layer's gradients of both backward routes, over its first n destinations, against each other.  Each
+    is within B of float64 autograd, so they differ by 2 B at most: B = M ((1 + 2^-8)^3 - 1 + 4 (terms + 2) 2^-24) + 2^-8
+    |gradient| for the bf16 bias, M the gradient of the same graph on absolute values with the masks held, terms = n count
+    + 2 d + F, the three narrowings A, dZ and the stored gradient (tests/test_aggregate_dense_backward_gpu.py).  Where a
+    pre-activation lies within the forward's bound of 0 the routes may disagree on its mask: those elements get no
+    incoming gradient."""
+    n = min(n, self_ids.numel())
+    self_ids, ids = self_ids.reshape(-1)[:n], ids.reshape(-1)[:n * count]
+    t64 = table.double().cpu()
+    x, r = t64[ids.cpu()].view(n, count, -1), t64[self_ids.cpu()]
+    names = ("neigh_w", "self_w", "bias")
+    leaves = [getattr(layer_f, k).detach().double().cpu().requires_grad_(True) for k in names]
+    mags = [t.detach().abs().requires_grad_(True) for t in leaves]
+    zn, zs = x.mean(1) @ leaves[0] + leaves[2], r @ leaves[1]
+    mn, ms = x.abs().mean(1) @ mags[0] + mags[2], r.abs() @ mags[1]
+    d, f = table.shape[1], zn.shape[1]
+    far = (zn.abs() > ((4 * (d + 2) + count + 4) * U + 2.0 ** -8) * mn) & (zs.abs() > 4 * (d + 2) * U * ms)
+    g = torch.randn(n, f, generator=torch.Generator().manual_seed(3)) * far
+    (mn * (zn > 0) + ms * (zs > 0)).backward(g.double().abs())
+    got = []
+    for layer in (layer_r, layer_f):
+        for k in names:
+            getattr(layer, k).grad = None
+        layer(ops.gather(table, self_ids), table, ids, count).backward(g.cuda().to(torch.bfloat16))
+        got.append([getattr(layer, k).grad.double().cpu() for k in names])
+    worst = 0.0
+    for k, a, b, m in zip(names, got[0], got[1], mags):
+        bound = 2 * (((1 + 2.0 ** -8) ** 3 - 1 + 4 * (n * count + 2 * d + f + 2) * U) * m.grad + 2.0 ** -8 * m.grad)
+        worst = max(worst, float(((a - b).abs() / bound.clamp(min=1e-300)).max()))
+        assert torch.all((a - b).abs() <= bound), k
+    print("recompute vs fused backward: largest difference / bound %.3f" % worst)
+    print("fused backward agrees within the bound")
+
+
 def check_fp8(layer, table, self_ids, ids, count, n=4096):
     """layer 0 of the outermost hop over the Fp8Rows table of the same features: its first n destinations
     against float64 on the dequantised table.  With M the formula on absolute values: (4 (2 d + 2) + count + 4)
@@ -116,6 +156,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--composed", action="store_true", help="also run gather_segment_reduce + matmuls + relu + add")
+    ap.add_argument("--fused-backward", action="store_true", help="also train through backward=\"fused\"")
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--hidden", type=int, default=128)
@@ -129,12 +170,13 @@ def main():
     # rows 0 .. nodes are the nodes' features; row nodes + 1 is the default_node fill: zeros on both routes
     table = torch.randn((a.nodes + 2, a.dim), device="cuda").to(torch.bfloat16)
     table[a.nodes + 1] = 0
-    routes = {"fused": False, "composed": True} if a.composed else {"fused": False}
+    routes = {"fused": False, **({"composed": True} if a.composed else {}), **({"fused-backward": False} if a.fused_backward else {})}
     models = {}
     for name, composed in routes.items():
-        torch.manual_seed(1)        # the same weights on both routes
-        models[name] = [MeanSageLayer(a.dim, a.hidden, torch.bfloat16, composed),
-                        MeanSageLayer(a.hidden, a.hidden, torch.bfloat16, composed)]
+        torch.manual_seed(1)        # the same weights on every route
+        how = "fused" if name == "fused-backward" else "recompute"
+        models[name] = [MeanSageLayer(a.dim, a.hidden, torch.bfloat16, composed, how),
+                        MeanSageLayer(a.hidden, a.hidden, torch.bfloat16, composed, how)]
     gen = torch.Generator(device="cuda")
     gen.manual_seed(9)
     roots = torch.randint(1, a.nodes + 1, (a.batch,), device="cuda", generator=gen)
@@ -168,6 +210,8 @@ def main():
             print("%s: forward alone, peak %d bytes above the inputs" % (name, torch.cuda.max_memory_allocated() - base))
     if a.composed:
         check(models["fused"][0], models["composed"][0], table, nodes[1], nodes[2], fanouts[1])
+    if a.fused_backward:
+        check_backward(models["fused"][0], models["fused-backward"][0], table, nodes[1], nodes[2], fanouts[1])
     if a.fp8_features:
         check_fp8(models["fused"][0], table, nodes[1], nodes[2], fanouts[1])
 

@@ -1727,6 +1727,42 @@ int euler_gpu_aggregate_dense(void* stream, int32_t op, int32_t act, int32_t com
                               const void* root_weight_dev, int64_t ds, int64_t fs,
                               int32_t has_root_scale, float root_scale, void* out_dev,
                               int32_t out_dtype);
+/* aggregate_dense_backward: the gradients of aggregate_dense above - of the reference's MeanAggregator
+ * and GCNAggregator (tf_euler/python/utils/aggregators.py:25-72), SAGEConv / GraphConv and GINConv - on
+ * the matrix units, in at most seven launches: a destination-major kernel that recomputes A and both
+ * pre-activations with the forward's own fragment code (the relu mask is the forward's bit for bit) and
+ * stores the narrowed A and dZ; one kernel per path for dZ W^T; one slab kernel and its sum per path for
+ * the weight and bias gradients.  The forward's arguments keep their meaning.  grad_dev [size, f] (concat:
+ * [size, fs + f]) of grad_dtype, fp32 or `dtype`.  A null gradient pointer means "not wanted", and what
+ * only it needs does not run: d_weight_dev [d, f], d_root_dev [size, ds] and d_root_weight_dev [ds, fs]
+ * of `dtype`, d_bias_dev [f] of bias_dtype; every element of a wanted one is written.  d_agg_dev, fp32
+ * [size, d], receives dA'[r] = (dZn[r] W^T) / den[r]: the table gradient is the grouped add of these
+ * rows at g[p] (euler_gpu_store_add on a zeroed table: increasing p in fp32, one rounding).
+ * Workspaces the caller allocates: a_ws_dev [size, d] of `dtype`, 16-byte aligned (with d_weight_dev or
+ * d_bias_dev); dzn_ws_dev [size, f] of `dtype` (with any gradient but d_root / d_root_weight of add and
+ * concat); dzs_ws_dev [size, fs] of `dtype` (with d_root or d_root_weight of add / concat);
+ * partial_ws_dev, fp32, partial_ws_floats >= slabs * max(d * f + f, ds * fs) (the terms of the wanted
+ * weight gradients), slabs = ceil(size / max(1024, ceil(size / 256) rounded up to 32)).  The contract -
+ * the mask at 0 and NaN, the one narrowing of dZ, the order of every sum, which depends on the shapes
+ * only - is stated once, in euler_amd/csrc/mp_dense_backward.h.  No atomics, no host wait, no
+ * allocation; the same bits on every run, on every stream and for count or the equivalent seg_ptr.
+ * EULER_GPU_EINVAL: what euler_gpu_aggregate_dense refuses, with the narrower limits d, ds <= 256 and
+ * f, fs <= 512; grad_dtype neither fp32 nor dtype; a null grad_dev; d_bias_dev without bias_dev,
+ * d_root_dev without root_dev, d_root_weight_dev without root_weight_dev; a wanted gradient without its
+ * workspace, or partial_ws_floats too small; a buffer not aligned to its type; every check precedes the
+ * launches.  size == 0, or no gradient wanted, returns EULER_GPU_OK and touches nothing. */
+int euler_gpu_aggregate_dense_backward(void* stream, int32_t op, int32_t act, int32_t combine,
+                                       const void* table_dev, int32_t dtype, int64_t rows,
+                                       const void* weight_dev, const void* bias_dev, int32_t bias_dtype,
+                                       const void* gather_dev, int32_t gather_is_ids,
+                                       const int64_t* seg_ptr_dev, int64_t count, int64_t e, int64_t d,
+                                       int64_t f, int64_t size, const void* root_dev,
+                                       const void* root_weight_dev, int64_t ds, int64_t fs,
+                                       int32_t has_root_scale, float root_scale, const void* grad_dev,
+                                       int32_t grad_dtype, void* a_ws_dev, void* dzn_ws_dev,
+                                       void* dzs_ws_dev, float* partial_ws_dev, int64_t partial_ws_floats,
+                                       float* d_agg_dev, void* d_weight_dev, void* d_bias_dev,
+                                       void* d_root_dev, void* d_root_weight_dev);
 /* fp8_aggregate_dense: aggregate_dense above over a quantised row table (q_dev [rows, d] e4m3fn
  * codes, scale_dev [d] fp32: "quantised (FP8) feature row tables").  The gathered rows are x^ =
  * fl(Dec(code) * scale[c]), folded in fp32 exactly as above; the compute dtype - the one narrowing of

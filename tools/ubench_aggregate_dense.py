@@ -14,7 +14,13 @@ call: fused_fp8 (aggregate_dense on the Fp8Rows, the roots by root_index), fused
 unchanged, on the bf16 table) and composed_fp8 (gather_segment_reduce on the Fp8Rows with a bf16 result +
 ops.gather for the roots + the matmuls); the floor is then that of fused_fp8.  --route fused selects fused_fp8.
 
+--backward times forward + backward per call instead, gradients to the table, both weights, the
+bias and the roots, three routes in one call: recompute (the fused forward, backward="recompute"), fused (the
+fused forward, backward="fused": euler_gpu_aggregate_dense_backward) and composed (torch autograd through the
+composed route).  --route recompute | fused | composed with --calls N is the form for a kernel trace.
+
     python tools/ubench_aggregate_dense.py [--roots 131072] [--op mean] [--seconds 2] [--repeats 5] [--table fp8]
+                                           [--backward]
 """
 import argparse
 import json
@@ -39,11 +45,12 @@ def main():
     ap.add_argument("--hidden", type=int, default=128)
     ap.add_argument("--table-rows", type=int, default=1 << 20)
     ap.add_argument("--op", default="mean", choices=["mean", "add"])
-    ap.add_argument("--route", default="both", choices=["both", "fused", "composed"])
+    ap.add_argument("--route", default="both", choices=["both", "fused", "composed", "recompute"])
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--calls", type=int, default=0, help="run this many calls of --route and exit")
     ap.add_argument("--table", default="bf16", choices=["bf16", "fp8"])
+    ap.add_argument("--backward", action="store_true", help="time forward + backward: recompute, fused, composed")
     a = ap.parse_args()
     torch.manual_seed(0)
     n_dst, count = a.roots * a.fanout[0], a.fanout[1]
@@ -76,6 +83,24 @@ def main():
 
         routes = {"fused_fp8": fused_fp8, "fused_bf16": fused, "composed_fp8": composed_fp8}
         a.route = {"fused": "fused_fp8", "composed": "composed_fp8"}.get(a.route, a.route)
+    if a.backward:
+        leaves = [t.requires_grad_(True) for t in (table, w, ws, b, root)]
+        g_out = torch.randn((n_dst, a.hidden), device="cuda").to(dt)
+
+        def trained(forward):
+            def call():
+                for t in leaves:
+                    t.grad = None
+                forward().backward(g_out)
+            return call
+
+        def composed_fwd():             # (the bias stays an fp32 leaf: its conversion is part of the graph)
+            agg = ops.gather_segment_reduce(a.op, table, ids, n_dst, count=count)
+            return torch.relu(torch.addmm(b.to(dt), agg, w)) + torch.relu(root @ ws)
+
+        fwd = lambda how: lambda: ops.aggregate_dense(a.op, table, w, ids, n_dst, root=root, root_weight=ws, bias=b,
+                                                      count=count, backward=how)
+        routes = {"recompute": trained(fwd("recompute")), "fused": trained(fwd("fused")), "composed": trained(composed_fwd)}
     if a.route != "both":
         routes = {a.route: routes[a.route]}
     if a.calls:
@@ -107,7 +132,7 @@ def main():
     if a.table == "fp8":        # one byte per code, the roots by id from the same table, the column scales
         bytes_needed = e * (a.dim + 8) + n_dst * (a.dim + 8) + n_dst * a.hidden * 2 + 2 * a.dim * a.hidden * 2 + 4 * a.dim
     out = {"shape": {"e": e, "n_dst": n_dst, "d": a.dim, "F": a.hidden, "op": a.op, "dtype": "bf16", "combine": "add",
-                     **({"table": "fp8"} if a.table == "fp8" else {})},
+                     **({"table": "fp8"} if a.table == "fp8" else {}), **({"backward": True} if a.backward else {})},
            "calls_per_window": calls, "windows": a.repeats,
            "ms": {n: {"median": statistics.median(v), "min": min(v), "max": max(v)} for n, v in ms.items()},
            "peak_bytes_per_call": peak, "bytes_needed": bytes_needed,
