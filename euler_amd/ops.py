@@ -775,15 +775,51 @@ def _pool_chunks(sp, count, size):
     return chunks
 
 
+POOL_BWD_MAX_K, POOL_BWD_MAX_F = 256, 512        # kPoolBwdMaxK, kPoolBwdMaxF of csrc/mp_pool_backward.h
+
+
+def _pool_fused_backward(table, weight, bias, gi, sp, count, e, size, op, act, grad, need):
+    """euler_gpu_pool_aggregate_backward on the saved tensors, then the grouped add of dX into a zeroed table
+    -> the three gradients (None where not needed)"""
+    (rows, d), f, dev, dt = table.shape, int(weight.shape[1]), table.device, table.dtype
+    want_t, want_w, want_b = need[0], need[1], bias is not None and need[2]
+    new = torch.zeros if size == 0 else torch.empty
+    buf = lambda shape, t, want: new(shape, dtype=t, device=dev) if want else None
+    d_w, d_b = buf((d, f), dt, want_w), buf((f,), bias.dtype if bias is not None else dt, want_b)
+    d_table = torch.zeros((rows, d), dtype=dt, device=dev) if want_t else None
+    if size == 0 or not (want_t or want_w or want_b):
+        return d_table, d_w, d_b
+    dz = buf((e, f), dt, True)                      # (the entry writes every row, those outside all segments too)
+    m_ws, share_ws = buf((size, f), _F32, op == "max"), buf((size, f), _F32, op == "max")
+    floats = _dense_bwd_slabs(e) * (d * f + f) if (want_w or want_b) and e > 0 else 0
+    partial = buf((floats,), _F32, floats > 0)
+    d_rows = buf((e, d), _F32, want_t)
+    grad = grad.contiguous() if grad.dtype in (_F32, dt) else grad.to(_F32).contiguous()
+    with _on(dev):
+        check(lib().euler_gpu_pool_aggregate_backward(
+            _stream(), _POOL_OP[op], _POOL_ACT[act], _ptr(table), _DT[dt], int(rows), _ptr(weight), _ptr(bias),
+            _DT[bias.dtype] if bias is not None else 0, _ptr(gi), int(gi is not None and gi.dtype == torch.int64),
+            _ptr(sp), int(count), e, int(d), f, size, _ptr(grad), _DT[grad.dtype], _ptr(dz), _ptr(m_ws), _ptr(share_ws),
+            _ptr(partial), floats, _ptr(d_rows), _ptr(d_w), _ptr(d_b)))
+        if want_t and e > 0:
+            # d_table[g[p]] += dX[p]: the grouped add of embed_store.h in its plain form, occurrences in increasing p
+            # in fp32, one rounding; an index outside the table names no row
+            ids = gi.to(torch.int64) if gi is not None else torch.arange(e, device=dev)
+            check(lib().euler_gpu_store_add(_stream(), _ptr(d_table), _DT[dt], int(rows), int(d), _ptr(ids), e,
+                                            _ptr(d_rows), _DT[_F32], e, None, 0))
+    return d_table, d_w, d_b
+
+
 class _PoolAggregate(torch.autograd.Function):
-    """The fused forward; the backward recomputes the composed form chunk by chunk (see
-    pool_aggregate)."""
+    """The fused forward; the backward is euler_gpu_pool_aggregate_backward and one grouped add (fused) or
+    recomputes the composed form chunk by chunk (see pool_aggregate)."""
 
     @staticmethod
-    def forward(ctx, table, weight, bias, gi, sp, count, e, size, op, act, od):
+    def forward(ctx, table, weight, bias, gi, sp, count, e, size, op, act, od, fused=False):
         out = _pool_raw(op, act, table, weight, bias, gi, sp, count, e, size, od)
         ctx.save_for_backward(table, weight, *[t for t in (bias, gi, sp) if t is not None])
         ctx.conf = (bias is not None, gi is not None, sp is not None, count, e, size, op, act)
+        ctx.fused = fused
         return out
 
     @staticmethod
@@ -795,6 +831,9 @@ class _PoolAggregate(torch.autograd.Function):
         bias = rest.pop(0) if has_bias else None
         gi = rest.pop(0) if has_gi else None
         sp = rest.pop(0) if has_sp else None
+        if ctx.fused:
+            return _pool_fused_backward(table, weight, bias, gi, sp, count, e, size, op, act, grad,
+                                        ctx.needs_input_grad[:3]) + (None,) * 9
         rows, d = table.shape
         dev = table.device
         w32 = weight.to(_F32)
@@ -836,11 +875,11 @@ class _PoolAggregate(torch.autograd.Function):
                 d_table += _scatter_raw(_ADD, dz @ w32.t(), key, rows)
         return (d_table.to(table.dtype) if d_table is not None else None,
                 d_w.to(weight.dtype) if want_w else None,
-                d_b.to(bias.dtype) if want_b else None) + (None,) * 8
+                d_b.to(bias.dtype) if want_b else None) + (None,) * 9
 
 
 def pool_aggregate(op, table, weight, gather_indices, size, bias=None, seg_ptr=None, count=None, activation="relu",
-                   out_dtype=None):
+                   out_dtype=None, backward="recompute"):
     """The meanpool / maxpool aggregators of the reference's SageEncoder (utils/aggregators.py:
     75-114) in one pass on the matrix units:
 
@@ -859,9 +898,24 @@ def pool_aggregate(op, table, weight, gather_indices, size, bias=None, seg_ptr=N
     the table's).  An empty segment gives +0.  The same call gives the same bits on every run and
     for count or the equivalent seg_ptr.  The full contract and the tiling: csrc/mp_pool.h.
 
-    Differentiable in table, weight and bias.  The backward pass is deliberately NOT a fused
-    kernel (that is three more GEMM shapes and a deterministic split-K reduce - a change of its
-    own): it recomputes the composed form in fp32 over chunks of whole destinations of at most
+    Differentiable in table, weight and bias.  backward="fused" (for TRAINING) is
+    euler_gpu_pool_aggregate_backward (csrc/mp_pool_backward.h): for max, one MFMA kernel recomputes every
+    position's act(x W + b) with the forward's own fragment code and folds it with a tie counter; the same
+    recompute once more stores dZ per position - the destination's share (add: grad; mean: grad * (1 / len);
+    max: grad / ties, an even split among the positions whose value equals the maximum bit for bit) where the
+    position takes part and its pre-activation is > 0 (relu; the derivative at 0 and at NaN is 0), narrowed once
+    to the table's dtype; dZ W^T and the weight and bias gradients (sums over slabs of positions that depend on
+    e alone, added in slab order) are MFMA kernels too, the weight kernel gathering its rows through the index
+    array; the table gradient is ONE grouped in-place add (embedding_add's: occurrences in increasing p in fp32,
+    one rounding) into a zeroed table-dtype [rows, d].  No Python loop, no host wait with seg_ptr either, no
+    atomics; only the wanted gradients are computed; the same bits on every run, on every stream and for count
+    or the equivalent seg_ptr.  Its temporaries are dZ, [e, F] in the table's dtype (for max also two fp32
+    [size, F]), and dX, fp32 [e, d], ONLY when the table needs a gradient: layer 0 over a model's input
+    features needs none and pays neither the dX kernel nor that block.  The route is not chunked.  It serves
+    d <= 256 and F <= 512 (kPoolBwdMaxK, kPoolBwdMaxF); beyond them backward="fused" is a ValueError when the
+    op is called, never a fallback.  Measurements: DESIGN 4.37.
+    backward="recompute" (the default) is deliberately NOT a fused
+    kernel: it recomputes the composed form in fp32 over chunks of whole destinations of at most
     POOL_GRAD_CHUNK_ROWS gathered rows - this module's gather, a matmul, the activation and the
     scatter gradients, so a max gradient is split evenly among maximal positions - and sums dW,
     db and the table gradient over the chunks in chunk order.  The cap bounds the [rows of a chunk,
@@ -873,6 +927,8 @@ def pool_aggregate(op, table, weight, gather_indices, size, bias=None, seg_ptr=N
         raise ValueError("%s: op is max, mean or add" % name)
     if activation not in _POOL_ACT:
         raise ValueError("%s: activation is relu or none" % name)
+    if backward not in ("recompute", "fused"):
+        raise ValueError("%s: backward is recompute or fused" % name)
     _dt(name, table)
     od = _out_dt(name, table, out_dtype)
     if table.dim() != 2 or table.shape[0] < 1:
@@ -884,6 +940,9 @@ def pool_aggregate(op, table, weight, gather_indices, size, bias=None, seg_ptr=N
     d, f = int(weight.shape[0]), int(weight.shape[1])
     if not (1 <= d <= 4096 and 1 <= f <= 4096):
         raise ValueError("%s: d and F are 1..4096" % name)
+    if backward == "fused" and (d > POOL_BWD_MAX_K or f > POOL_BWD_MAX_F):
+        raise ValueError("%s: backward=\"fused\" serves d <= %d (kPoolBwdMaxK) and F <= %d (kPoolBwdMaxF); "
+                         "pass backward=\"recompute\" beyond them" % (name, POOL_BWD_MAX_K, POOL_BWD_MAX_F))
     if bias is not None:
         if bias.dim() != 1 or bias.numel() != f:
             raise ValueError("%s: bias is [F]" % name)
@@ -919,7 +978,8 @@ def pool_aggregate(op, table, weight, gather_indices, size, bias=None, seg_ptr=N
     if e >= 2 ** 31:
         raise ValueError("%s: fewer than 2^31 positions" % name)
     _need_cuda(table_c, weight_c, *[t for t in (bias_c, gi, sp) if t is not None])
-    return _PoolAggregate.apply(table_c, weight_c, bias_c, gi, sp, count, e, size, op, activation, od)
+    return _PoolAggregate.apply(table_c, weight_c, bias_c, gi, sp, count, e, size, op, activation, od,
+                                backward == "fused")
 
 
 # ---- fused mean-aggregator layer: reduce, then dense ---------------------------------------------

@@ -1763,6 +1763,39 @@ int euler_gpu_aggregate_dense_backward(void* stream, int32_t op, int32_t act, in
                                        void* dzs_ws_dev, float* partial_ws_dev, int64_t partial_ws_floats,
                                        float* d_agg_dev, void* d_weight_dev, void* d_bias_dev,
                                        void* d_root_dev, void* d_root_weight_dev);
+/* pool_aggregate_backward: the gradients of pool_aggregate above - of the reference's meanpool / maxpool
+ * aggregators (tf_euler/python/utils/aggregators.py:75-114) - on the matrix units, in at most eight
+ * launches: for max a destination-major kernel that recomputes every position's act(x W + b) with the
+ * forward's own fragment code and folds it with a tie counter (m and grad / ties per destination); the
+ * same recompute once more, whose walk stores dZ per POSITION - the share of its destination where the
+ * position takes part (max: its value equals m bit for bit) and its pre-activation is > 0 (relu), else +0 -
+ * narrowed once to `dtype`; dZ W^T; one slab kernel over positions, its X rows gathered through the index
+ * array, and its ordered sums for the weight and bias gradients.  The forward's arguments keep their meaning.
+ * grad_dev [size, f] of grad_dtype, fp32 or `dtype`.  A null gradient pointer means "not wanted", and what
+ * only it needs does not run: d_weight_dev [d, f] of `dtype`, d_bias_dev [f] of bias_dtype, d_rows_dev fp32
+ * [e, d] = dZ[p] W^T per position; every element of a wanted one is written.  The table gradient is the
+ * grouped add of d_rows at g[p] (euler_gpu_store_add in its plain form on a zeroed table: ids = g or p,
+ * m = e; increasing p in fp32, one rounding); an index outside the table adds nothing to d_weight, counts in
+ * d_bias, and is left out by store_add.
+ * Workspaces the caller allocates: dz_ws_dev [e, f] of `dtype`, 16-byte aligned (every row is written, a
+ * position outside every segment with +0); for op max m_ws_dev and share_ws_dev, fp32 [size, f];
+ * partial_ws_dev, fp32, partial_ws_floats >= slabs * (d * f + f) with d_weight_dev or d_bias_dev, slabs =
+ * ceil(e / max(1024, ceil(e / 256) rounded up to 32)).  The contract - the tie rule, the masks at 0 and NaN,
+ * the one narrowing of dZ, the order of every sum, which depends on the shapes only - is stated once, in
+ * euler_amd/csrc/mp_pool_backward.h.  No atomics, no host wait, no allocation; the same bits on every run,
+ * on every stream and for count or the equivalent seg_ptr.
+ * EULER_GPU_EINVAL: what euler_gpu_pool_aggregate refuses, with the narrower limits d <= 256 and f <= 512;
+ * grad_dtype neither fp32 nor dtype; a null grad_dev; d_bias_dev without bias_dev; a wanted gradient
+ * without its workspace, or partial_ws_floats too small; a buffer not aligned to its type; every check
+ * precedes the launches.  size == 0, or no gradient wanted, returns EULER_GPU_OK and touches nothing. */
+int euler_gpu_pool_aggregate_backward(void* stream, int32_t op, int32_t act, const void* table_dev,
+                                      int32_t dtype, int64_t rows, const void* weight_dev,
+                                      const void* bias_dev, int32_t bias_dtype, const void* gather_dev,
+                                      int32_t gather_is_ids, const int64_t* seg_ptr_dev, int64_t count,
+                                      int64_t e, int64_t d, int64_t f, int64_t size, const void* grad_dev,
+                                      int32_t grad_dtype, void* dz_ws_dev, float* m_ws_dev,
+                                      float* share_ws_dev, float* partial_ws_dev, int64_t partial_ws_floats,
+                                      float* d_rows_dev, void* d_weight_dev, void* d_bias_dev);
 /* fp8_aggregate_dense: aggregate_dense above over a quantised row table (q_dev [rows, d] e4m3fn
  * codes, scale_dev [d] fp32: "quantised (FP8) feature row tables").  The gathered rows are x^ =
  * fl(Dec(code) * scale[c]), folded in fp32 exactly as above; the compute dtype - the one narrowing of
