@@ -33,21 +33,23 @@ from euler_amd.dataflow import RelationDataFlow    # noqa: E402
 
 
 class RGCNLayer(torch.nn.Module):
-    def __init__(self, in_dim, dim, relations):
+    def __init__(self, in_dim, dim, relations, route="composed"):
         super().__init__()
+        self.route = route                      # "fused": one MFMA pass for the seg_ptr / count forms
         self.matrix = torch.nn.Parameter(torch.randn(relations, dim, in_dim) * (in_dim ** -0.5))
         self.fc = torch.nn.Linear(in_dim, dim, bias=False)
 
     def forward(self, x_dst, x_src, src, edge_type, n_dst, **segments):
         """x_dst [n_dst, F] the destinations' own rows; x_src [*, F] the table `src` indexes"""
-        return self.fc(x_dst) + ops.relation_conv(x_src, self.matrix, src, edge_type, n_dst, **segments)
+        route = "composed" if "indices" in segments else self.route      # (scatter keys: the composed route only)
+        return self.fc(x_dst) + ops.relation_conv(x_src, self.matrix, src, edge_type, n_dst, route=route, **segments)
 
 
 class RGCN(torch.nn.Module):
-    def __init__(self, in_dim, dim, classes, relations):
+    def __init__(self, in_dim, dim, classes, relations, route="composed"):
         super().__init__()
-        self.l1 = RGCNLayer(in_dim, dim, relations)
-        self.l2 = RGCNLayer(dim, classes, relations)
+        self.l1 = RGCNLayer(in_dim, dim, relations, route)
+        self.l2 = RGCNLayer(dim, classes, relations, route)
 
 
 def loss_of(logits, labels):
@@ -90,6 +92,8 @@ def main():
     ap.add_argument("--in-dim", type=int, default=32)
     ap.add_argument("--classes", type=int, default=8)
     ap.add_argument("--nodes", type=int, default=20_000)
+    ap.add_argument("--fused", action="store_true",
+                    help="relation_conv(route=\"fused\") for the sampled blocks (count form)")
     a = ap.parse_args()
     torch.manual_seed(0)
     G = euler_amd.Graph.synthetic(euler_amd.synth_params(20240521, a.nodes, 8 * a.nodes, n_types=a.types,
@@ -101,7 +105,7 @@ def main():
     types = list(range(a.types))
     roots = torch.randint(1, a.nodes + 1, (a.batch,), device="cuda", dtype=torch.int64)
     for name in ("RelationDataFlow blocks", "sampled blocks"):
-        model = RGCN(a.in_dim, a.dim, a.classes, a.types).cuda()
+        model = RGCN(a.in_dim, a.dim, a.classes, a.types, "fused" if a.fused else "composed").cuda()
         opt = torch.optim.SGD(model.parameters(), lr=0.05)
         if name.startswith("Relation"):
             loss = full_neighbour_step(G, model, feats, labels, roots, types)

@@ -1269,6 +1269,34 @@ int euler_gpu_relation_reduce(void* stream, int32_t mode, const void* params_dev
                               const int32_t* indices_dev, const int64_t* seg_ptr_dev, int64_t count,
                               int64_t e, int64_t d, int32_t size,
                               void* out_dev, int32_t out_dtype, int32_t* counts_dev);
+/* relation_dense: RelationConv's aggregation in ONE pass on the matrix units -
+ * out[r] = sum_t bucket(r, t) @ weight[t]^T with bucket(r, t) the relation_reduce of x over the
+ * valid updates of destination r with relation t - without the [size, num_relations, f] block
+ * (csrc/mp_relation_dense.h states the contract and the plan).  x_dev is [rows, f], weight_dev
+ * [num_relations, dim, f], one dtype of fp32 / bf16 / fp16; out_dev is [size, dim], fp32 or x's
+ * dtype.  mode: 0 add, 2 mean over the destination, 3 mean over the bucket (relation_reduce's
+ * codes).  Validity (0 <= edge_type < num_relations; an invalid update's row is never read), the
+ * clamp of gather_dev (NULL: update p is row p and rows >= e; int32; int64 ids by their low
+ * word) to rows - 1 and the clamp of segment boundaries are relation_reduce's.  A bucket is folded
+ * from +0 in input order in fp32, divided (mode 2: by fl(n_valid(r) + 1e-7f), mode 3: by
+ * fl(cnt(r, t) + 1e-7f), a true division) and rounded once to x's dtype - the bits
+ * relation_reduce stores; the matrix instructions then accumulate in fp32, relations in
+ * increasing t and the chunks of 32 k in increasing k, and the result is rounded once to
+ * out_dtype.  An empty bucket contributes nothing: with a non-finite weight[t] the 0 x inf = NaN
+ * of relation_reduce followed by a GEMM is not reproduced.  The destinations come as seg_ptr_dev
+ * (int64 [size + 1]) or count > 0 with e == size * count, exactly one; the call only enqueues.
+ * The same bits on every run, on every stream and for count or the equivalent seg_ptr.
+ * EULER_GPU_EINVAL: mode not 0, 2 or 3, an unknown dtype, out_dtype neither fp32 nor dtype,
+ * f outside 1..256, dim outside 1..256, num_relations outside 1..64, a negative shape, e or
+ * size >= 2^31, not exactly one segment form, count with e != size * count, a mean with e or
+ * count >= 2^24, a null buffer, a table shorter than the rows read, a buffer not aligned to its
+ * type.  size == 0 returns EULER_GPU_OK and touches nothing. */
+int euler_gpu_relation_dense(void* stream, int32_t mode, const void* x_dev, int32_t dtype,
+                             int64_t rows, const void* gather_dev, int32_t gather_is_ids,
+                             const int32_t* edge_type_dev, int32_t num_relations,
+                             const void* weight_dev, const int64_t* seg_ptr_dev, int64_t count,
+                             int64_t e, int64_t f, int64_t dim, int64_t size, void* out_dev,
+                             int32_t out_dtype);
 /* triple_score: the energies of knowledge-graph embedding (calculate_energy of
  * examples/TransX/transX.py:72-79,105-133 and examples/distmult/distmult.py:74-79,99-126) - the
  * lookup of the rows of src, rel_id, dst and the [b, k] negatives, their l2 normalisation
